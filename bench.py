@@ -33,6 +33,8 @@ reported in the extra key `weak_scaling`; `ranks` carries per-rank kernel and ex
 `native_gather` repeats the measurement with the library's own RCCL call (msbwt_rle_allgather_counts).
 
 Prints ONE JSON line (rank 0).  DESIGN.md section 5 defines the roofline figures.
+--dump-outputs DIR writes the counts of the headline's last timed step (rows picked by dump_rows) as .npy files: the inputs depend on
+the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import datetime
@@ -77,6 +79,38 @@ def kernel_stamp():
         text = re.sub(r"//[^\n]*", "", text)          # the sources use // comments only
         h.update(" ".join(text.split()).encode())
     return h.hexdigest()[:16]
+
+
+INDEX_CACHE_ENV = "MSBWT_BENCH_INDEX_CACHE"
+
+
+def index_cache_dir(synth):
+    """Where synth.workload_index keeps the index files it builds: synth/cache/ when the tree can be written, else a directory under
+    the system's temporary directory named after this user and the generators' sources (files built by other generators are never
+    read).  The choice travels to the ranks and child passes in INDEX_CACHE_ENV, so that they all read the files one of them built."""
+    import tempfile
+    chosen = os.environ.get(INDEX_CACHE_ENV)
+    if not chosen:
+        try:
+            os.makedirs(synth.CACHE, exist_ok=True)
+            writable = os.access(synth.CACHE, os.W_OK | os.X_OK)
+        except OSError:
+            writable = False
+        if writable:
+            chosen = synth.CACHE
+        else:
+            here = os.path.dirname(os.path.abspath(synth.__file__))
+            h = hashlib.sha256()
+            for name in sorted(os.listdir(here)):
+                if name.endswith((".py", ".cpp", ".json")):
+                    with open(os.path.join(here, name), "rb") as f:
+                        h.update(name.encode() + b"\0" + f.read())
+            chosen = os.path.join(tempfile.gettempdir(), "msbwt_index_cache_%d_%s" % (os.getuid(), h.hexdigest()[:16]))
+            os.makedirs(chosen, exist_ok=True)
+            if os.stat(chosen).st_uid != os.getuid() or not os.access(chosen, os.W_OK | os.X_OK):
+                chosen = tempfile.mkdtemp(prefix="msbwt_index_cache_")
+        os.environ[INDEX_CACHE_ENV] = chosen
+    return chosen
 
 
 def cpu_model():
@@ -202,7 +236,25 @@ def parse_args(argv=None):
                          "table (`headline_sparse_off`) and their short-k timings (`short_k`)")
     ap.add_argument("--parity-sample", type=int, default=2_000_000)
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the counts of the last step as DIR/counts.npy (float64) and the batch rows they belong to "
+                         "as DIR/count_rows.npy: every row up to %d, a fixed seeded sample of that many on a larger batch" % DUMP_ROWS)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_ROWS = 1 << 21   # --dump-outputs: 2 arrays x 2^21 float64 = 32 MiB
+
+
+def dump_rows(n, cap=DUMP_ROWS, seed=20261015):
+    """The batch rows whose counts --dump-outputs writes, ascending: all n up to `cap`, else a sample of `cap` of them that depends on
+    n alone (the same in every build and run)."""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=cap, replace=False))
 
 
 def self_launch(args):
@@ -213,8 +265,11 @@ def self_launch(args):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
+    argv = sys.argv[1:]
+    if args.dump_outputs:  # (the ranks run from the repository root: a relative DIR is the caller's)
+        argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv
     log("starting %d ranks: %s" % (args.gpus, " ".join(cmd)))
     child = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, cwd=ROOT)
     out, _ = child.communicate()
@@ -561,6 +616,7 @@ def main():
 
     msbwt = importlib.import_module("rust-msbwt_amd")
     import synth
+    synth.CACHE = index_cache_dir(synth)   # (a checkout that cannot be written still runs every line)
 
     # host threads of this rank: the ranks of one node share its cores (generators, oracle)
     nproc = os.cpu_count() or 1
@@ -971,6 +1027,15 @@ def main():
     # what the index looked like when the headline ran (the variant lines further down rebuild its tables)
     headline_shape = index_shape(bwt, k, fused, mine_n if strong else nq)
     d_counts = stitch(d_all, d_out, nq, cap)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the count of each query of the batch, as the last timed step left it
+        rows = dump_rows(nq)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = d_counts[torch.from_numpy(rows).to(dev)].cpu().numpy().view(np.uint64)
+        np.save(os.path.join(args.dump_outputs, "counts.npy"), dumped.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "count_rows.npy"), rows.astype(np.float64))
+        log("counts of %d of the %d queries written to %s" % (len(rows), nq, args.dump_outputs))
+        del dumped
     # the repeat-genome lab line: what a k-mer costs by copy number AT THIS SIZE (human copy numbers: 10^5 and more occurrences)
     main_bins = None
     if exact_bwt and args.genome == "repeats" and not multi and d_q is not None and not args.no_variants:

@@ -111,6 +111,30 @@ def test_bench_default_run_carries_the_real_msbwt_line():
         assert "error" not in again and again["counts_equal_first_run"] and again["ms_per_step"] > 0 and again["ratio_to_the_line"] > 0
 
 
+def test_bench_dump_outputs_are_the_timed_counts_and_repeat(tmp_path):
+    """--dump-outputs: the last timed step's counts (float64, every row of a small batch), the same in two runs with the same
+    arguments; --steps is the number of timed launches."""
+    import numpy as np
+    lean = ["--scale", "0.00003", "--steps", "3", "--warmup", "1", "--no-c5", "--no-variants", "--no-sorted", "--parity-sample", "5000",
+            "--cpu-sample", "2000"]
+    runs = []
+    for i in range(2):
+        out = str(tmp_path / ("dump_%d" % i))
+        r = _run(lean + ["--dump-outputs", out])
+        assert r["steps"] == 3 and r["roofline"]["kernel_launches"] == 3 and r["parity"]["mismatches"] == 0
+        files = sorted(os.listdir(out))
+        assert files == ["count_rows.npy", "counts.npy"]
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10**6
+        arrays = {f: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        nq = r["config"]["queries_per_step"]
+        assert np.array_equal(arrays["count_rows.npy"], np.arange(nq, dtype=np.float64))
+        assert arrays["counts.npy"].shape == (nq,) and arrays["counts.npy"].min() >= 1   # present k-mers (LF walk): each occurs at least once
+        runs.append(arrays)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
 def test_bench_default_is_the_metric_config():
     """The driver runs `python3 bench.py --gpus 1 --steps K --warmup W`: that must be k = 31 on the
     human-scale index (checked on the argument defaults; the full-size run is the driver's)."""

@@ -373,6 +373,47 @@ def test_bench_stdout_line_is_compact():
     assert len(json.dumps(bench.compact_record(full, "e.json"))) < 4096
 
 
+def test_bench_dump_rows_are_fixed_and_small():
+    """--dump-outputs writes the counts of the rows dump_rows picks: every row of a small batch, a sample of a large one that depends on
+    the batch size alone, ascending and distinct, the two float64 arrays within 64 MB; --steps sets the timed steps and cannot be 0."""
+    import bench
+    assert bench.dump_rows(1000).tolist() == list(range(1000))
+    assert bench.dump_rows(bench.DUMP_ROWS).tolist() == list(range(bench.DUMP_ROWS))
+    for n in (bench.DUMP_ROWS + 1, 3 * 10**8):
+        rows = bench.dump_rows(n)
+        assert rows.shape == (bench.DUMP_ROWS,) and rows[0] >= 0 and rows[-1] < n and (np.diff(rows) > 0).all()
+        assert np.array_equal(rows, bench.dump_rows(n))
+    assert 2 * bench.DUMP_ROWS * 8 + 2 * 128 <= 64 * 10**6
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out"
+    assert bench.parse_args([]).dump_outputs == ""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_index_cache_leaves_a_tree_that_cannot_be_written(tmp_path, monkeypatch):
+    """bench.py keeps the index files of the synthetic workloads in synth/cache/ when it can; where the tree cannot be written it uses a
+    directory of the temporary directory, the same for every process of the run (ranks, child passes) and for the same generators."""
+    import tempfile
+    import types
+    import bench
+    import synth
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
+    monkeypatch.delenv(bench.INDEX_CACHE_ENV, raising=False)
+    tree = types.SimpleNamespace(CACHE=str(tmp_path / "tree_cache"), __file__=synth.__file__)
+    assert bench.index_cache_dir(tree) == tree.CACHE and os.environ[bench.INDEX_CACHE_ENV] == tree.CACHE
+    (tmp_path / "a_file").write_text("")
+    blocked = types.SimpleNamespace(CACHE=str(tmp_path / "a_file" / "cache"), __file__=synth.__file__)   # makedirs fails, root or not
+    monkeypatch.delenv(bench.INDEX_CACHE_ENV)
+    first = bench.index_cache_dir(blocked)
+    assert os.path.dirname(first) == str(tmp_path) and os.path.isdir(first) and ("_%d_" % os.getuid()) in first
+    assert os.environ[bench.INDEX_CACHE_ENV] == first
+    assert bench.index_cache_dir(blocked) == first          # a rank or child pass: handed over through the environment
+    monkeypatch.delenv(bench.INDEX_CACHE_ENV)
+    assert bench.index_cache_dir(blocked) == first          # another run of the same generators
+
+
 def test_pipelined_gather_cuts_a_shard_into_at_most_the_pieces_asked_for():
     """msbwt_rle_count_kmers_allgather_device holds pieces + 1 events: its cut (csrc/gather.hpp, allgather_piece_queries) never makes more
     pieces than that for any shard size -- round 5's floor-based cut made 68 of n_mine = 1087, pieces = 64 -- and every piece but the
