@@ -282,7 +282,7 @@ int msbwt_rle_get_table_packed(const msbwt_rle *bwt);
  * started from, [9] buckets a lookup may go beyond its own, [10 + d] DISTINCT d-symbol suffixes that occur (d = 0..31; 0 where the
  * build did not pass: it advances two symbols at a time), [45 + d] of which 255 or more wide, [80 + d] of which exactly 1 wide (suffixes
  * that occur once: on reads with errors, mostly error k-mers), [8] 1 = the table is of the two-tier form, [42] suffixes in its filters,
- * [43] depth of the SECOND, shallower level (0 = none) and [44] its bytes: with k undeclared the table is 23 deep and serves k >= 23; where
+ * [43] depth of the SECOND, shallower level (0 = none), [44] its bytes and [112] 1 = it is of the two-tier form: with k undeclared the table is 23 deep and serves k >= 23; where
  * the deep direct table of an index without a sparse table (packed depth 17) does not fit beside it but a table of the 17-symbol suffixes
  * does, that one is built as well and serves 17 <= k < 23 (MSBWT_SPARSE_SECOND=0: never), so that no k loses to the index without a
  * sparse table.
@@ -293,7 +293,9 @@ int msbwt_rle_get_table_packed(const msbwt_rle *bwt);
  * range is at least 2 wide and sets, for each of the others, four bits of a filter inside its own bucket line (no false negatives):
  * a lookup that finds its tag is served as before, one that finds neither tag nor filter bits is count 0, and one whose filter bits are
  * set continues through the direct table and the search -- the reference's own path (src/rle_bwt.rs:202-287) -- so every count stays
- * exact whatever the filter says.  mode: -1 = automatic (default: the two-tier form of a depth where its complete table does not fit
+ * exact whatever the filter says.  A two-tier level is always deeper than the direct table (its depth once packed): where it would not be,
+ * that depth gets the complete table -- or, when both depths were set explicitly and mode is 1, the setter or load fails with
+ * MSBWT_ERR_INVALID_ARG.  mode: -1 = automatic (default: the two-tier form of a depth where its complete table does not fit
  * HBM or the memory budget -- tried before the next shallower depth), 0 = complete tables only, 1 = two-tier only (tests, measurements).
  * MSBWT_SPARSE_TIERS=auto|0|1 sets the initial mode.  Takes effect immediately if an index is loaded.  Results never change.
  * msbwt_rle_get_sparse_tiers: 1 when the table in HBM is of the two-tier form, else 0.

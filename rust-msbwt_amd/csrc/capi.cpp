@@ -205,6 +205,17 @@ double line_rate_of(const void *p, size_t bytes, hipStream_t stream) {
     return double(lines) / (double(ms) * 1e-3);
 }
 
+// the second, shallower sparse level alone
+void release_sparse2(msbwt_rle *h) {
+    if (h->d_sparse2) (void)hipFree(h->d_sparse2);
+    if (h->d_sparse2_side) (void)hipFree(h->d_sparse2_side);
+    h->d_sparse2 = h->d_sparse2_side = nullptr;
+    h->sparse2_bytes = h->sparse2_side_bytes = h->sparse2_entries = 0;
+    h->sparse2_nbuckets = h->sparse2_probe = 0;
+    h->sparse2_depth = 0;
+    h->sparse2_tier = false;
+}
+
 void release_sparse(msbwt_rle *h) {
     if (h->d_sparse) (void)hipFree(h->d_sparse);
     if (h->d_sparse_side) (void)hipFree(h->d_sparse_side);
@@ -214,13 +225,7 @@ void release_sparse(msbwt_rle *h) {
     h->sparse_depth = 0;
     h->sparse_tier = false;
     h->sparse_report = SparseBuildReport{};
-    if (h->d_sparse2) (void)hipFree(h->d_sparse2);
-    if (h->d_sparse2_side) (void)hipFree(h->d_sparse2_side);
-    h->d_sparse2 = h->d_sparse2_side = nullptr;
-    h->sparse2_bytes = h->sparse2_side_bytes = h->sparse2_entries = 0;
-    h->sparse2_nbuckets = h->sparse2_probe = 0;
-    h->sparse2_depth = 0;
-    h->sparse2_tier = false;
+    release_sparse2(h);
 }
 
 void release_index(msbwt_rle *h) {
@@ -292,10 +297,22 @@ IndexView view_of(msbwt_rle *h) {
     return v;  // tile_counter: with_tickets()
 }
 
+// The two-tier form goes on through the direct table (sparse_policy.hpp, sparse_tier_fits_direct): a direct table deeper than a two-tier
+// level would wrap the kernel's count of the symbols between the two, and an escape line without its side entry cannot be followed from
+// the filter's path.  The loader builds neither; whatever path might, every query launch checks the handle here first and is refused
+// (hipErrorInvalidValue) instead of being made.
+bool tier_launch_ok(const msbwt_rle *h) {
+    if (!h->d_table) return true;
+    const bool unfollowable = h->table_packed && h->table_escape_lines > 0 && !h->d_table_side;
+    auto level_ok = [&](bool tier, int depth) { return !tier || (sparse_tier_fits_direct(depth, h->table_depth) && !unfollowable); };
+    return level_ok(h->d_sparse && h->sparse_tier, h->sparse_depth) && level_ok(h->d_sparse2 && h->sparse2_tier, h->sparse2_depth);
+}
+
 // Runs `launch(view)` with a ticket-counter block that no launch still in flight uses, and marks the block busy
 // until everything enqueued on `stream` so far -- the launch included -- has completed.  The caller holds h->mu.
 template <class Launch>
 hipError_t with_slot(msbwt_rle *h, hipStream_t stream, Launch &&launch) {
+    if (!tier_launch_ok(h)) return hipErrorInvalidValue;
     // Launches queued back to back on ONE stream are ordered by the stream itself (the memset of the counters waits for the
     // previous kernel), so they share a block without asking its event: a caller that enqueues N asynchronous launches
     // gets one block, not N allocations inside its launch path.
@@ -417,6 +434,8 @@ int rebuild_filter(msbwt_rle *h) {
 // Optional structure: when nothing fits (or a step fails for want of memory) the handle simply has none -- unless a depth was
 // asked for explicitly, which is then an error.  keep_free: bytes that what is built afterwards (the packed direct table) still
 // needs; allowance: what a memory budget leaves for this table (kNoBudget: none in force).
+// direct_depth: the depth the direct table will have once the sparse table is built (packed: two deeper than the flat one in HBM now; 0 =
+// none) -- a two-tier level may not be shallower (sparse_tier_fits_direct).
 // deep_direct_depth: the flat depth of the DEEP direct table that is kept beside the sparse table when HBM is plentiful (rebuild_table; 0 =
 // not in question) -- where that one fits no second sparse level is built.
 constexpr int kSparseSecondDepth = 17;  // entries of the second, shallower level (what the packed direct table of round 4 reached)
@@ -429,7 +448,7 @@ bool deep_direct_fits(const msbwt_rle *h, int flat_depth_wanted) {
     return hipMemGetInfo(&free_b, &total_b) == hipSuccess && uint64_t(free_b) + h->table_bytes >= need + uint64_t(total_b) / 8;
 }
 
-int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int deep_direct_depth = 0) {
+int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direct_depth, int deep_direct_depth = 0) {
     release_sparse(h);
     const bool verbose = std::getenv("MSBWT_VERBOSE") != nullptr;
     const bool explicit_depth = h->wanted_sparse > 0;
@@ -437,6 +456,11 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int deep_
     const int flat_depth = flat ? h->table_depth : 0;
     const int max_depth = explicit_depth ? h->wanted_sparse : sparse_auto_max_depth(h->query_length);
     if (max_depth <= flat_depth || max_depth < kSparseMinDepth) return explicit_depth ? fail(h, MSBWT_ERR_INVALID_ARG, "sparse table depth must exceed the direct table's") : MSBWT_OK;
+    // (the two-tier form sends the suffixes that occur once down the direct table's path: it needs that table's side array for escape lines)
+    const int tiers = h->wanted_table_side == 0 ? 0 : h->wanted_tiers;
+    if (explicit_depth && tiers == 1 && max_depth <= kTierMaxDepth && !sparse_tier_fits_direct(max_depth, direct_depth))
+        return fail(h, MSBWT_ERR_INVALID_ARG, "a two-tier sparse table of depth " + std::to_string(max_depth) + " needs a direct table shallower than it (the direct table is " +
+                                                  std::to_string(direct_depth) + " deep)");
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return MSBWT_OK;
     struct Temps {
@@ -474,9 +498,7 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int deep_
     // (an explicit depth wins over a memory budget, like the other explicit settings: only the HBM itself limits it)
     const uint64_t avail = std::min<uint64_t>(explicit_depth ? kNoBudget : allowance, uint64_t(free_b) > spare ? uint64_t(free_b) - spare : 0);
     // the depth: a pure function of the counts and the bytes (sparse_policy.hpp, pinned by a CPU test through msbwt_auto_sparse_depth)
-    // (the two-tier form sends the suffixes that occur once down the direct table's path: it needs that table's side array for escape lines)
-    const int tiers = h->wanted_table_side == 0 ? 0 : h->wanted_tiers;
-    const SparseChoice choice = choose_sparse_depth(rep.distinct, rep.escapes, flat_depth, max_depth, avail, explicit_depth ? max_depth : 0, rep.singles, tiers);
+    const SparseChoice choice = choose_sparse_depth(rep.distinct, rep.escapes, flat_depth, max_depth, avail, explicit_depth ? max_depth : 0, rep.singles, tiers, direct_depth);
     const int chosen = choice.depth;
     uint64_t nbuckets = choice.nbuckets;
     if (!chosen && explicit_depth) return fail(h, MSBWT_ERR_HIP, "the sparse table of the requested depth does not fit in HBM");
@@ -536,7 +558,7 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int deep_
         hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         const uint64_t used = h->sparse_bytes + h->sparse_side_bytes;
         const uint64_t avail2 = std::min<uint64_t>(allowance > used ? allowance - used : 0, uint64_t(free_b) > spare ? uint64_t(free_b) - spare : 0);
-        const SparseChoice second = choose_sparse_depth(rep.distinct, rep.escapes, flat_depth, std::min(kSparseSecondDepth, chosen - 1), avail2, 0, rep.singles, tiers);
+        const SparseChoice second = choose_sparse_depth(rep.distinct, rep.escapes, flat_depth, std::min(kSparseSecondDepth, chosen - 1), avail2, 0, rep.singles, tiers, direct_depth);
         if (second.depth) {
             Temps two;  // (its own buffers: the first table's are the handle's by now)
             SparseBuildReport rep2 = rep;
@@ -650,7 +672,7 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
             const uint64_t held = h->nblocks * kBlockBytes + h->pair_bytes + direct;
             allowance = h->memory_budget > held ? h->memory_budget - held : 0;
         }
-        rc = build_sparse(h, (pack && h->d_table) ? packed_table_bytes(depth + 2) : 0, allowance, (capped && pack) ? uncapped_depth : 0);
+        rc = build_sparse(h, (pack && h->d_table) ? packed_table_bytes(depth + 2) : 0, allowance, h->d_table ? depth + (pack ? 2 : 0) : 0, (capped && pack) ? uncapped_depth : 0);
         if (rc) return rc;
         if (!h->d_sparse && capped) {  // no depth fit: the direct table as if there were no sparse one (the distinct counts stay on record)
             const SparseBuildReport counted = h->sparse_report;
@@ -664,8 +686,10 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     // k-mers: k = 17 2.5 x, k = 19 1.8 x, k = 21 1.5 x slower than behind the packed depth-17 table) -- so where HBM is plentiful (a
     // chr20-sized index: 15 GB of 288) the deep direct table is kept AS WELL: nothing is lost for any k.  Not under a memory budget
     // (the plan has sized the table), and not where it would take the eighth of the device left to the caller's batches (deep_direct_fits);
-    // there build_sparse has tried a second, shallower sparse level instead.
-    if (capped && h->d_sparse && !h->d_sparse2 && h->d_table && pack && deep_direct_fits(h, uncapped_depth)) {
+    // there build_sparse has tried a second, shallower sparse level instead.  Nor where a two-tier table would then be no deeper than the
+    // direct table its filter sends queries to (sparse_tier_fits_direct: a declared k = 16 or 17).
+    if (capped && h->d_sparse && !h->d_sparse2 && h->d_table && pack && (!h->sparse_tier || sparse_tier_fits_direct(h->sparse_depth, uncapped_depth + 2)) &&
+        deep_direct_fits(h, uncapped_depth)) {
         if (h->d_filter) (void)hipFree(h->d_filter);
         h->d_filter = nullptr;
         h->filter_depth = 0;
@@ -732,9 +756,15 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     h->table_side_bytes = side ? uint64_t(escapes) * 512 : 0;
     h->table_lines = pbytes / 128;
     h->table_escape_lines = escapes;
-    if (h->d_sparse && h->sparse_tier && escapes > 0 && !side) {
+    if (h->d_sparse2 && h->sparse2_tier && !h->sparse_tier && escapes > 0 && !side) release_sparse2(h);  // (only the second level is two-tier: it alone goes)
+    if (h->d_sparse && (h->sparse_tier || h->sparse2_tier) && escapes > 0 && !side) {
         // the two-tier table sends queries down this table's path, and an escape line without its side entry cannot be followed from
-        // there (the query's first symbols are gone): no room for the side array -> the index as if there were no sparse table
+        // there (the query's first symbols are gone): no room for the side array -> the index as if there were no sparse table -- unless
+        // that very table was asked for, which is then an error (as an explicit depth that does not fit)
+        if (h->wanted_sparse > 0 && h->wanted_tiers == 1 && h->sparse_tier) {
+            release_sparse(h);
+            return fail(h, MSBWT_ERR_HIP, "the two-tier sparse table of the requested depth cannot be kept: no room for the direct table's side array");
+        }
         const SparseBuildReport counted = h->sparse_report;
         const int again = rebuild_table(h, false);
         h->sparse_report = counted;
@@ -828,7 +858,8 @@ int build_sparse_for_runs(msbwt_rle *h) {
         const uint64_t held = run_peak + parent_bytes;
         allowance = h->memory_budget > held ? h->memory_budget - held : 0;
     }
-    rc = build_sparse(h, run_peak, allowance);
+    // (the run blocks' direct table is rebuilt flat afterwards: at most `parent` deep when automatic)
+    rc = build_sparse(h, run_peak, allowance, h->wanted_table_depth >= 0 ? h->wanted_table_depth : parent);
     drop_temps();
     if (rc && h->wanted_sparse <= 0) {
         release_sparse(h);
@@ -1655,6 +1686,7 @@ int msbwt_rle_count_kmers(const msbwt_rle *ch, const uint8_t *kmers, size_t k, s
         if (!rc) rc = ensure_mail(h);
         if (rc) return rc;
         uint64_t *counts = reinterpret_cast<uint64_t *>(h->mail + kMailCounts);
+        if (!tier_launch_ok(h)) return hip_fail(h, hipErrorInvalidValue, "two-tier sparse table beside a direct table it cannot fall back to");
         IndexView v = view_of(h);  // no ticket counters: at most one tile
         // The lanes kernel announces completion in the mailbox itself: poll that word (about 5 us cheaper than a stream
         // synchronisation on this runtime); a single query even travels inside the kernel arguments.
@@ -2354,6 +2386,7 @@ int msbwt_rle_sparse_table_info(const msbwt_rle *ch, uint64_t *out) {
         out[42] = r.filtered;
         out[43] = uint64_t(h->sparse2_depth);
         out[44] = h->sparse2_bytes + h->sparse2_side_bytes;
+        out[112] = h->d_sparse2 && h->sparse2_tier ? 1 : 0;
     }
     out[7] = uint64_t(r.parent_depth);
     for (int d = 0; d <= kSparseMaxDepth; ++d) {

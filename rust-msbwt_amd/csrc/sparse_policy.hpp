@@ -65,17 +65,30 @@ inline uint64_t sparse_tier_buckets(int depth, uint64_t solid, uint64_t singles)
     return std::max(std::max(by_entries, by_filter), sparse_tier_min_buckets(depth));
 }
 
+// May a two-tier table of depth `depth` stand in front of a direct table `direct_depth` deep (its depth once packed; 0 = none)?  A lookup
+// that ends in the filter goes on through the direct table's line, which answers the query's last direct_depth symbols, and one that hits
+// an entry has the depth - direct_depth symbols between the two cut (lanes_kernel.hpp): a direct table deeper than the sparse one would
+// wrap that count.  Nor may the two be equally deep: the kernel searches on after the direct table's range without asking whether any
+// symbol is left, so a k = depth = direct_depth query that ends in the filter would count symbols beyond its own (found by
+// tests/test_gpu_tier_fallback.py).  One rule for both sparse levels -- the loader keeps to it (capi.cpp: build_sparse, and the deep direct
+// table rebuild_table keeps beside a sparse table), and every query launch refuses what breaks it (capi.cpp, tier_launch_ok).
+inline bool sparse_tier_fits_direct(int depth, int direct_depth) { return direct_depth < depth; }
+
 // singles[d]: of distinct[d], the suffixes that occur exactly once (nullptr: not counted -- no two-tier form); tiers: -1 = the complete
 // table where it fits, else the two-tier form of the SAME depth where that fits (reads with errors: the complete table follows the error
 // k-mers, the two-tier one the genome), else the next shallower depth; 0 = complete tables only; 1 = two-tier only.
+// direct_depth: the depth the direct table will have once packed (0 = none) -- a depth it is deeper than has no two-tier form
+// (sparse_tier_fits_direct).
 inline SparseChoice choose_sparse_depth(const uint64_t *distinct, const uint64_t *wide, int parent_depth, int max_depth, uint64_t avail, int explicit_depth,
-                                        const uint64_t *singles = nullptr, int tiers = 0) {
+                                        const uint64_t *singles = nullptr, int tiers = 0, int direct_depth = 0) {
     SparseChoice none;
     for (int d = std::min(max_depth, kSparseMaxDepth); d >= kSparseMinDepth && d > parent_depth; --d) {
         if (explicit_depth ? d != explicit_depth : distinct[d] == 0) continue;  // not a level of the pass (the other parity), or nothing occurs
+        const bool tier_form = singles != nullptr && d <= kTierMaxDepth && sparse_tier_fits_direct(d, direct_depth);
         for (int tier = 0; tier <= 1; ++tier) {
-            // (tiers = 1 asks for the two-tier form wherever it exists: depths 30..31 have none and stay complete)
-            if (tier ? (tiers == 0 || singles == nullptr || d > kTierMaxDepth) : (tiers == 1 && singles != nullptr && d <= kTierMaxDepth)) continue;
+            // (tiers = 1 asks for the two-tier form wherever it exists: depths 30..31 have none and stay complete, and so does a depth the
+            // direct table is deeper than)
+            if (tier ? (tiers == 0 || !tier_form) : (tiers == 1 && tier_form)) continue;
             const uint64_t single = tier ? std::min(singles[d], distinct[d]) : 0, entries = distinct[d] - single;
             const uint64_t needed = uint64_t(double(entries) / (tier ? sparse_tier_load(d) : sparse_load(d))) + 1;
             const uint64_t nb = tier ? sparse_tier_buckets(d, entries, single) : sparse_buckets_for(d, distinct[d]);

@@ -4,6 +4,7 @@ search kernels.  Needs an MI355X and a few minutes (the C4 index alone takes abo
 host time to build)."""
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -275,6 +276,43 @@ def test_human_scale_9e10_symbols_against_the_oracle():
         got = _count_matrix(torch, dev, bwt, short).cpu().numpy().astype(np.uint64)
         assert np.array_equal(got, ref.count_kmers(short.cpu().numpy(), nthreads=NCPU)), kk
         assert got[:1_000_000].min() >= 1
+    # the metric's own configuration (bench.py declares k = 31): the complete depth-31 table with 40-bit tags, more than 4e8 buckets;
+    # a quarter of the present 31-mers have entries with l > 2^36
+    t0 = time.time()
+    bwt.set_query_length(31)
+    info31 = bwt.sparse_table_info()
+    assert bwt.get_sparse_table() == 31 and not bwt.get_sparse_tiers() and not info31["two_tier"] and info31["buckets"] > 4e8, info31
+    got = _count_matrix(torch, dev, bwt, d_q).cpu().numpy().astype(np.uint64)
+    assert np.array_equal(got, exp)
+    rng = np.random.default_rng(31)
+    mut = present[:200_000].clone()
+    mut[torch.arange(len(mut), device=dev), torch.from_numpy(rng.integers(0, k, size=len(mut))).to(dev)] = \
+        torch.from_numpy(np.array([1, 2, 3, 5], dtype=np.uint8)[rng.integers(0, 4, size=len(mut))]).to(dev)
+    got = _count_matrix(torch, dev, bwt, mut).cpu().numpy().astype(np.uint64)
+    assert np.array_equal(got, ref.count_kmers(mut.cpu().numpy(), nthreads=NCPU))
+    sub = rng.choice(len(q), size=500_000, replace=False)
+    packed_q = msbwt.rle_bwt.pack_2bit(np.ascontiguousarray(q[sub]))
+    assert np.array_equal(bwt.count_kmers_packed(packed_q, k), exp[sub])
+    long_q = bench.walk_kmers(torch, np, bwt, dev, total, 200_000, 59, 31)
+    got = _count_matrix(torch, dev, bwt, long_q).cpu().numpy().astype(np.uint64)
+    assert np.array_equal(got, ref.count_kmers(long_q.cpu().numpy(), nthreads=NCPU)) and got.min() >= 1
+    # two-tier asked for: depths 30 / 31 have no such form -- the declared k keeps the complete table
+    bwt.set_sparse_tiers(1)
+    assert bwt.get_sparse_table() == 31 and not bwt.get_sparse_tiers()
+    # k undeclared, two-tier: depth 23 in front of the packed depth-15 direct table (the second level beside it, where it fits, is two-tier too)
+    bwt.set_query_length(0)
+    tinfo = bwt.sparse_table_info()
+    assert bwt.get_sparse_table() == 23 and bwt.get_sparse_tiers() and bwt.get_table_depth() == 15 <= 23, tinfo
+    assert tinfo["second_depth"] == 0 or tinfo["second_tier"], tinfo
+    bwt.set_search_counters(True)
+    got = _count_matrix(torch, dev, bwt, d_q).cpu().numpy().astype(np.uint64)
+    bwt.set_search_counters(False)
+    assert np.array_equal(got, exp)
+    # back to the defaults
+    bwt.set_sparse_tiers(-1)
+    assert bwt.get_sparse_table() == 23 and not bwt.get_sparse_tiers() and bwt.get_table_depth() == 15
+    assert bwt.sparse_table_info()["second_depth"] == 17
+    print("k = 31 and two-tier checks at human scale: %.1f s" % (time.time() - t0))
     # without the sparse table the loader builds what rounds 2-4 measured: the depth-17 packed direct table (73 GB, 238 GB in all)
     bwt.set_sparse_table(0)
     assert bwt.get_sparse_table() == 0 and bwt.get_table_depth() == 17 and bwt.device_bytes() > 230e9

@@ -353,7 +353,7 @@ def tier_slots_in_use(lines, info):
     return int((raw[:, 81:90] != 0).sum()) if info["depth"] >= 25 else int(((lines[:, :10] >> 24) != 0).sum())
 
 
-@pytest.mark.parametrize("depth", [16, 17, 20, 24, 25, 27, 28])
+@pytest.mark.parametrize("depth", [16, 17, 20, 24, 25, 27, 28, 29])
 def test_two_tier_table_holds_the_solid_suffixes_and_filters_the_ones_that_occur_once(depth, monkeypatch):
     """MSBWT_SPARSE_TIERS=1: every suffix that occurs at least twice has an entry with the oracle's range; every suffix that occurs once has
     NO entry and its four filter bits set in its own bucket; an absent suffix is a miss or (rarely) a filter false positive; the slots
@@ -394,11 +394,11 @@ def test_two_tier_table_holds_the_solid_suffixes_and_filters_the_ones_that_occur
 
 @pytest.mark.parametrize("direct", ["packed", "flat", "none", "deep"])
 @pytest.mark.parametrize("stride", [96, 128])
-@pytest.mark.parametrize("depth", [16, 19, 23, 25, 28])
+@pytest.mark.parametrize("depth", [16, 19, 23, 25, 28, 29])
 def test_counts_with_the_two_tier_table_equal_the_oracle(depth, stride, direct, monkeypatch):
     """Solid, once-only, absent and mutated k-mers (counts n / 1 / 0 exact) through the two-tier table: a lookup that ends in the filter goes
     on through the direct table -- packed, flat, or none at all (from [0, total)) -- and the search."""
-    if direct != "packed" and (stride == 128 or depth in (19, 28)):
+    if direct != "packed" and (stride == 128 or depth in (19, 28, 29)):
         pytest.skip("the direct-table variants are covered at stride 96, depths 16 / 23 / 25")
     if direct == "deep" and depth != 23:
         pytest.skip("the deep direct table (73 GB) once")
