@@ -100,6 +100,34 @@ int msbwt_rle_constrain_ranges_device(const msbwt_rle *bwt, const void *d_syms, 
                                       void *hip_stream);
 int msbwt_rle_device_status(const msbwt_rle *bwt, void *hip_stream);
 
+/* ---- k-mer ranges and left-extension counts (no reference counterpart: the trait keeps the range inside count_kmer,
+ * src/msbwt_core.rs:124-161) ----
+ * Queries as for msbwt_rle_count_kmers: n x k row-major symbol codes ($ A C G N T = 0..5), any k including 0.
+ * Error codes, the device forms' asynchrony (msbwt_rle_device_status), unaligned d_kmers and the host forms' pinned pipeline are
+ * those of msbwt_rle_count_kmers[_device]; a row holding a code >= 6 comes back all-ones (MSBWT_ERR_INVALID_SYMBOL), every other
+ * row stays exact.  Results never depend on a knob (MSBWT_* or msbwt_rle_set_*), and batch ordering (MSBWT_ORDER,
+ * msbwt_rle_set_batch_order) does not apply to these calls: they always search in the caller's order.
+ *
+ * FM range of each k-mer: [l, h) after constrain_range on every symbol, last first, from [0, total)
+ * (src/msbwt_core.rs:128-160).  h - l == count_kmer(row).  A row whose count is 0 gets l = h = 0.  k = 0: [0, total).
+ * With msbwt_rle_constrain_ranges a caller can carry a search on one symbol at a time instead of searching a longer k-mer anew. */
+int msbwt_rle_kmer_ranges(const msbwt_rle *bwt, const uint8_t *kmers, size_t k, size_t n,
+                          uint64_t *out_l, uint64_t *out_h);
+int msbwt_rle_kmer_ranges_device(const msbwt_rle *bwt, const void *d_kmers, size_t k, size_t n,
+                                 void *d_out_l, void *d_out_h, void *hip_stream);
+
+/* Left-extension counts: out[6*i + c] = count_kmer([c] ++ row i) for c = 0..5 ($ A C G N T).
+ * The six sum to count_kmer(row i).  k = 0: the six symbol counts.  One search plus the index line(s) of the range's two bounds,
+ * instead of six searches of k + 1 symbols.
+ * Right extensions: on an index that holds every read AND its reverse complement, count(q . c) = count(rc(c . rc(q))), so
+ *     count(q . c) = ext(rc(q))[COMPLEMENT_INT[c]]    (reverse_complement_i / COMPLEMENT_INT, src/string_util.rs:12,45-50)
+ * -- the right extensions of q are the left extensions of rc(q), one call.  On a single-strand index right extensions are
+ * separate searches of the (k+1)-mers q . c (msbwt_rle_count_kmers). */
+int msbwt_rle_count_kmer_extensions(const msbwt_rle *bwt, const uint8_t *kmers, size_t k, size_t n,
+                                    uint64_t *out_counts /* n x 6 */);
+int msbwt_rle_count_kmer_extensions_device(const msbwt_rle *bwt, const void *d_kmers, size_t k, size_t n,
+                                           void *d_out_counts /* n x 6 u64 */, void *hip_stream);
+
 /* ---- compact queries: two bits per symbol (no reference counterpart; the trait's count_kmer takes one byte per symbol,
  * src/msbwt_core.rs:125, codes as string_util.rs:15-67 makes them) ----
  * A k-mer over ACGT, 1 <= k <= 64, as ceil(k / 32) u64 words: the k-mer read as a base-4 number with A C G T -> 0 1 2 3 and
@@ -217,7 +245,7 @@ int msbwt_kmer_order_keys(const uint8_t *kmers, size_t k, size_t n, uint64_t *ou
  * random batches lost 30 % to 2.7x -- and since round 5 the default index looks its queries up in a HASHED sparse suffix table,
  * whose lookups an order cannot help: the same dense batches now LOSE 6-14 % with the pass forced on (round 5, `library_ordered` beside
  * the c4_* lines of bench.py: 7.5 -> 6.8 and 7.9 -> 7.4 x 10^9 q/s).  MSBWT_ORDER=0|1 in the environment sets the initial mode.
- * Applies to msbwt_rle_count_kmers[_device] and the packed forms.  msbwt_rle_batch_order_for: 1 if a batch of n k-symbol queries
+ * Applies to msbwt_rle_count_kmers[_device] and the packed forms (not to the k-mer range and extension calls).  msbwt_rle_batch_order_for: 1 if a batch of n k-symbol queries
  * would be ordered now.  Results never change. */
 int msbwt_rle_set_batch_order(msbwt_rle *bwt, int mode);
 int msbwt_rle_get_batch_order(const msbwt_rle *bwt);

@@ -106,6 +106,24 @@ class RleBWT final : public BWT {
         check(msbwt_rle_count_kmers(raw_, kmers.data(), k, n, out.data()));
         return out;
     }
+    /// FM range [l, h) of every k-mer of n x k symbol codes ({0, 0} when it does not occur).
+    std::vector<BWTRange> kmer_ranges(const std::vector<std::uint8_t> &kmers, std::size_t k) const {
+        const std::size_t n = k ? kmers.size() / k : 0;
+        if (k && kmers.size() % k) throw std::invalid_argument("kmers.size() is not a multiple of k");
+        std::vector<std::uint64_t> l(n), h(n);
+        check(msbwt_rle_kmer_ranges(raw_, kmers.data(), k, n, l.data(), h.data()));
+        std::vector<BWTRange> out(n);
+        for (std::size_t i = 0; i < n; ++i) out[i] = BWTRange{l[i], h[i]};
+        return out;
+    }
+    /// Left-extension counts, n x 6 row-major: [6 i + c] = count_kmer([c] ++ row i), c = 0..5 ($ A C G N T).
+    std::vector<std::uint64_t> count_kmer_extensions(const std::vector<std::uint8_t> &kmers, std::size_t k) const {
+        const std::size_t n = k ? kmers.size() / k : 0;
+        if (k && kmers.size() % k) throw std::invalid_argument("kmers.size() is not a multiple of k");
+        std::vector<std::uint64_t> out(6 * n);
+        check(msbwt_rle_count_kmer_extensions(raw_, kmers.data(), k, n, out.data()));
+        return out;
+    }
     std::vector<BWTRange> constrain_ranges(const std::vector<std::uint8_t> &syms, const std::vector<BWTRange> &ranges) const {
         if (syms.size() != ranges.size()) throw std::invalid_argument("syms and ranges differ in length");
         std::vector<std::uint64_t> l(ranges.size()), h(ranges.size()), ol(ranges.size()), oh(ranges.size());

@@ -1340,6 +1340,31 @@ int launch_count_2bit(msbwt_rle *h, const uint64_t *d_packed, size_t k, size_t n
     });
 }
 
+// FM ranges of n k-mers (msbwt_rle_kmer_ranges[_device]): l to d_l[i * stride], h to d_h[i * stride].  Never ordered: the search
+// runs in the caller's order, in the kRange form of the kernel launch_count would pick (launch_kmer_ranges).
+int launch_ranges(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_l, uint64_t *d_h, uint32_t stride, hipStream_t stream,
+                  int which) {
+    if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
+    return timed_launch(h, stream, [&] {
+        return with_tickets(h, stream, [&](const IndexView &v) {
+            return launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_l, d_h, stride, h->d_flags + which, stream);
+        });
+    });
+}
+
+// Left-extension counts (msbwt_rle_count_kmer_extensions[_device]) in two launches and no scratch: the range of row i goes into the
+// first 16 bytes of its own 48-byte output row, and extend.hip turns the row into the six counts in place.
+int launch_extensions(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
+    if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
+    return timed_launch(h, stream, [&] {
+        return with_tickets(h, stream, [&](const IndexView &v) {
+            hipError_t e = launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_out, d_out + 1, 6u, h->d_flags + which, stream);
+            if (e == hipSuccess) e = launch_kmer_extensions(v, d_out, n, h->d_flags + which, stream);
+            return e;
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1819,6 +1844,89 @@ int msbwt_rle_constrain_range(const msbwt_rle *h, uint8_t sym, uint64_t l, uint6
 int msbwt_rle_count_kmer(const msbwt_rle *h, const uint8_t *kmer, size_t k, uint64_t *out_count) {
     if (!out_count) return MSBWT_ERR_INVALID_ARG;
     return msbwt_rle_count_kmers(h, kmer, k, 1, out_count);
+}
+
+int msbwt_rle_kmer_ranges_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_l, void *d_out_h, void *hip_stream) {
+    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
+    if (n && (!d_out_l || !d_out_h || (!d_kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    return launch_ranges(h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_l), static_cast<uint64_t *>(d_out_h), 1u,
+                         static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+}
+
+int msbwt_rle_count_kmer_extensions_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_counts, void *hip_stream) {
+    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
+    if (n && (!d_out_counts || (!d_kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    return launch_extensions(h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
+                             kDeviceFlags);
+}
+
+// host forms: pipelined like msbwt_rle_count_kmers (chunks of 2 Mi queries, host_pipeline.hpp), no mailbox
+int msbwt_rle_kmer_ranges(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_l, uint64_t *out_h) {
+    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
+    if (n && (!out_l || !out_h || (!kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (n == 0) return MSBWT_OK;
+    std::vector<HostArray> ins(1), outs(2);
+    ins[0].in = kmers;
+    ins[0].item_bytes = k;
+    outs[0].out = out_l;
+    outs[0].item_bytes = sizeof(uint64_t);
+    outs[1].out = out_h;
+    outs[1].item_bytes = sizeof(uint64_t);
+    int launch_rc = MSBWT_OK;
+    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
+                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
+                                         launch_rc = launch_ranges(h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]),
+                                                                   static_cast<uint64_t *>(d_out[1]), 1u, stream, kHostFlags);
+                                         return launch_rc ? hipErrorUnknown : hipSuccess;
+                                     });
+    if (launch_rc) return launch_rc;
+    if (e != hipSuccess) return hip_fail(h, e, "kmer_ranges pipeline");
+    uint32_t flags = 0;
+    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
+    return rc ? rc : flags_to_code(h, flags);
+}
+
+int msbwt_rle_count_kmer_extensions(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_counts) {
+    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
+    if (n && (!out_counts || (!kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (n == 0) return MSBWT_OK;
+    std::vector<HostArray> ins(1), outs(1);
+    ins[0].in = kmers;
+    ins[0].item_bytes = k;
+    outs[0].out = out_counts;
+    outs[0].item_bytes = 6 * sizeof(uint64_t);
+    int launch_rc = MSBWT_OK;
+    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
+                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
+                                         launch_rc = launch_extensions(h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]),
+                                                                       stream, kHostFlags);
+                                         return launch_rc ? hipErrorUnknown : hipSuccess;
+                                     });
+    if (launch_rc) return launch_rc;
+    if (e != hipSuccess) return hip_fail(h, e, "count_kmer_extensions pipeline");
+    uint32_t flags = 0;
+    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
+    return rc ? rc : flags_to_code(h, flags);
 }
 
 // ---- several devices of one node: replicas of one index, batches sharded over them --------------

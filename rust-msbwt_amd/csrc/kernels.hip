@@ -33,11 +33,13 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 
 // ---- count_kmers, any k: one query per group at a time, symbols read as needed ----------
+// kRange: the range instead of the count -- l to counts[q * stride], h to out_h[q * stride]; (0, 0) when empty, all-ones when invalid
+template <bool kRange>
 __global__ __launch_bounds__(256) void k_count_kmers_generic(const uint4 *__restrict__ blocks, uint32_t format,
                                                              const uint4 *__restrict__ overflow, uint64_t total,
                                                              const uint8_t *__restrict__ kmers, uint32_t k,
                                                              uint64_t n, uint64_t *__restrict__ counts,
-                                                             uint32_t *__restrict__ flags) {
+                                                             uint32_t *__restrict__ flags, uint64_t *__restrict__ out_h, uint32_t stride) {
     const uint32_t sub = threadIdx.x & (kGroup - 1);
     const uint64_t ngroups = (uint64_t(gridDim.x) * blockDim.x) / kGroup;
     for (uint64_t q = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup; q < n; q += ngroups) {
@@ -47,18 +49,26 @@ __global__ __launch_bounds__(256) void k_count_kmers_generic(const uint4 *__rest
         for (uint32_t i = sub; i < k; i += kGroup) bad |= (kmer[i] >= 6u) ? 1u : 0u;
         bad = group_sum(bad);
         uint64_t result;
+        Range r{0, total};
         if (bad) {
             result = ~0ull;
             if (sub == 0) atomicOr(flags, kFlagInvalidSymbol);
         } else {
-            Range r{0, total};
             bool broken = false;  // a range outside the index (never seen on a well-formed one) must not become a block address
             for (uint32_t i = k; i-- > 0 && r.l != r.h && !(broken = r.h > total || r.l > r.h);)
                 r = constrain_any(format, blocks, overflow, kmer[i], r.l, r.h, sub);
             result = broken ? ~0ull : r.h - r.l;
             if (broken && sub == 0) atomicOr(flags, kFlagInternal);
         }
-        if (sub == 0) counts[q] = result;
+        if constexpr (kRange) {
+            if (sub == 0) {
+                const bool invalid = result == ~0ull, empty = result == 0ull;
+                counts[q * stride] = invalid ? ~0ull : (empty ? 0ull : r.l);
+                out_h[q * stride] = invalid ? ~0ull : (empty ? 0ull : r.h);
+            }
+        } else {
+            if (sub == 0) counts[q] = result;
+        }
     }
 }
 
@@ -66,16 +76,20 @@ __global__ __launch_bounds__(256) void k_count_kmers_generic(const uint4 *__rest
 template <int kWords>
 struct WaveScratchT {
     static constexpr int kMaxK = kWords * 32 / 3;  // 32 or 64
+    // range mode: the h of every query beside its l in result[] -- in the first 512 bytes of the staged query bytes, which are free
+    // once the tile's queries are packed (more LDS would cost the k > 32 kernel a wave per SIMD)
+    __device__ uint64_t *result_h() { return reinterpret_cast<uint64_t *>(stage + kStageLead / 16); }
     uint4 stage[kStageLead / 16 + kTile * kMaxK / 16];  // kStageLead free bytes (search_common.hpp), then the tile's query bytes (2 or 4 KiB)
     WorkItemT<kWords> work[kTile];                 // 2 or 3 KiB
     uint64_t result[kTile];                        // 512 B
 };
-
-template <bool kReads, int kWords>
+// kRange (matrix queries): the range of each query instead of its count (QuerySource::range_stride)
+template <bool kReads, int kWords, bool kRange = false>
 __global__ __launch_bounds__(256, kWords == 6 ? 4 : 6) void k_count_kmers_tiled(
     const uint4 *__restrict__ blocks, uint32_t format, const uint4 *__restrict__ overflow, uint64_t total,
     const uint4 *__restrict__ table, uint32_t depth, uint32_t table_packed, const uint32_t *__restrict__ filter,
     uint32_t filter_mask, const uint4 *__restrict__ table_side, const QuerySource src, uint32_t *__restrict__ flags) {
+    static_assert(!(kRange && kReads), "ranges are served for matrix queries");
     constexpr int kLanes = kGroup;
     using Scratch = WaveScratchT<kWords>;
     using WorkItem = WorkItemT<kWords>;
@@ -149,7 +163,15 @@ __global__ __launch_bounds__(256, kWords == 6 ? 4 : 6) void k_count_kmers_tiled(
             uint64_t result = 0;
             pending = prepare_query<kReads, kWords>(src, env, stage_bytes + lane * k, q0 + lane, filter_now, flags, l, h, w, rem,
                                                     result, looked_up, passed);
-            if (!pending) ws.result[lane] = result;
+            if (!pending) {
+                if constexpr (kRange) {  // decided at setup: invalid (all-ones), empty (0, 0) or the table's range; h follows below
+                    const bool invalid = result == ~0ull, empty = result == 0ull;
+                    ws.result[lane] = invalid ? ~0ull : (empty ? 0ull : l);
+                    h = invalid ? ~0ull : (empty ? 0ull : h);
+                } else {
+                    ws.result[lane] = result;
+                }
+            }
         }
         if (filter != nullptr) {
             if (filter_now) {
@@ -173,6 +195,9 @@ __global__ __launch_bounds__(256, kWords == 6 ? 4 : 6) void k_count_kmers_tiled(
             ws.work[at] = it;
         }
         wave_lds_sync();
+        if constexpr (kRange) {  // (every staged byte has been read: the line above ordered the wave)
+            if (lane < in_tile && !pending) ws.result_h()[lane] = h;
+        }
         // ---- phase 2: groups pull work items; one backward-search step per iteration ----
         {
             uint32_t next = 0;  // wave-uniform: first unassigned work item
@@ -213,6 +238,7 @@ __global__ __launch_bounds__(256, kWords == 6 ? 4 : 6) void k_count_kmers_tiled(
                     if (sub == 0u) {
                         atomicOr(flags, kFlagInternal);
                         ws.result[slot] = ~0ull;
+                        if constexpr (kRange) ws.result_h()[slot] = ~0ull;
                     }
                     have = false;
                 }
@@ -224,14 +250,25 @@ __global__ __launch_bounds__(256, kWords == 6 ? 4 : 6) void k_count_kmers_tiled(
                     consume_symbols<kWords>(w, 3);
                     --rem;
                     if (rem == 0u || l == h) {
-                        if (sub == 0u) ws.result[slot] = h - l;
+                        if constexpr (kRange) {
+                            if (sub == 0u) {
+                                ws.result[slot] = l == h ? 0ull : l;
+                                ws.result_h()[slot] = l == h ? 0ull : h;
+                            }
+                        } else {
+                            if (sub == 0u) ws.result[slot] = h - l;
+                        }
                         have = false;
                     }
                 }
             }
         }
         wave_lds_sync();
-        if (lane < in_tile) store_count<kReads>(src, q0 + lane, ws.result[lane]);
+        if constexpr (kRange) {
+            if (lane < in_tile) store_range_raw(src, q0 + lane, ws.result[lane], ws.result_h()[lane]);
+        } else {
+            if (lane < in_tile) store_count<kReads>(src, q0 + lane, ws.result[lane]);
+        }
         wave_lds_sync();  // the next tile must not overwrite result[] / stage[] before this
     }
 }
@@ -468,7 +505,7 @@ inline bool use_lanes_kernel(const IndexView &ix, uint32_t k) {
     return ix.search_kernel == kSearchLanes || (ix.search_kernel == kSearchAuto && long_search(ix, k));
 }
 
-template <bool kReads>
+template <bool kReads, bool kRange = false>
 void launch_tiled(bool longk, dim3 grid, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags) {
     const uint4 *blocks = static_cast<const uint4 *>(ix.blocks);
     const uint4 *table = static_cast<const uint4 *>(ix.table.entries);
@@ -479,9 +516,9 @@ void launch_tiled(bool longk, dim3 grid, hipStream_t stream, const IndexView &ix
     const uint4 *overflow = static_cast<const uint4 *>(ix.overflow);
     const uint4 *side = table ? static_cast<const uint4 *>(ix.table.side) : nullptr;
     if (longk)  // 33 <= k <= 64
-        hipLaunchKernelGGL((k_count_kmers_tiled<kReads, 6>), grid, dim3(256), 0, stream, blocks, format, overflow, ix.total, table, depth, packed, filter, filter_mask, side, src, flags);
+        hipLaunchKernelGGL((k_count_kmers_tiled<kReads, 6, kRange>), grid, dim3(256), 0, stream, blocks, format, overflow, ix.total, table, depth, packed, filter, filter_mask, side, src, flags);
     else
-        hipLaunchKernelGGL((k_count_kmers_tiled<kReads, 3>), grid, dim3(256), 0, stream, blocks, format, overflow, ix.total, table, depth, packed, filter, filter_mask, side, src, flags);
+        hipLaunchKernelGGL((k_count_kmers_tiled<kReads, 3, kRange>), grid, dim3(256), 0, stream, blocks, format, overflow, ix.total, table, depth, packed, filter, filter_mask, side, src, flags);
 }
 
 }  // namespace
@@ -513,8 +550,33 @@ hipError_t launch_count_kmers(const IndexView &ix, const uint8_t *kmers, uint32_
         if (use_lanes_kernel(ix, k)) return launch_lanes(ix, src, false, true, flags, stream);
         launch_tiled<false>(k > uint32_t(kMaxShortK), dim3(grid_for(tiles * 64, k > uint32_t(kMaxShortK) ? 4 : 6)), stream, ix, src, flags);
     } else {
-        hipLaunchKernelGGL(k_count_kmers_generic, dim3(grid_for(n * kGroup)), dim3(256), 0, stream, blocks, uint32_t(ix.block_format),
-                           static_cast<const uint4 *>(ix.overflow), ix.total, kmers, k, n, counts, flags);
+        hipLaunchKernelGGL(k_count_kmers_generic<false>, dim3(grid_for(n * kGroup)), dim3(256), 0, stream, blocks, uint32_t(ix.block_format),
+                           static_cast<const uint4 *>(ix.overflow), ix.total, kmers, k, n, counts, flags, nullptr, 1u);
+    }
+    return hipGetLastError();
+}
+
+// The same searches, each ending with its range stored (QuerySource::range_stride): the kernel launch_count_kmers would pick, in its
+// kRange instantiation.
+hipError_t launch_kmer_ranges(const IndexView &ix, const uint8_t *kmers, uint32_t k, uint64_t n, uint64_t *out_l, uint64_t *out_h,
+                              uint32_t stride, uint32_t *flags, hipStream_t stream) {
+    if (stride == 0u) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const bool aligned = (reinterpret_cast<uintptr_t>(kmers) & 15u) == 0;
+    if (k >= 1 && k <= uint32_t(kMaxTiledK) && aligned) {
+        const uint64_t tiles = (n + kTile - 1) / kTile;
+        QuerySource src{};
+        src.data = kmers;
+        src.n = n;
+        src.k = k;
+        src.out_fwd = out_l;
+        src.out_rc = out_h;
+        src.range_stride = stride;
+        if (use_lanes_kernel(ix, k)) return launch_lanes(ix, src, false, true, flags, stream);
+        launch_tiled<false, true>(k > uint32_t(kMaxShortK), dim3(grid_for(tiles * 64, k > uint32_t(kMaxShortK) ? 4 : 6)), stream, ix, src, flags);
+    } else {
+        hipLaunchKernelGGL(k_count_kmers_generic<true>, dim3(grid_for(n * kGroup)), dim3(256), 0, stream, static_cast<const uint4 *>(ix.blocks),
+                           uint32_t(ix.block_format), static_cast<const uint4 *>(ix.overflow), ix.total, kmers, k, n, out_l, flags, out_h, stride);
     }
     return hipGetLastError();
 }

@@ -120,6 +120,15 @@ hipError_t launch_count_kmers(const IndexView &ix, const uint8_t *kmers, uint32_
 // the place of its count (low 32 bits) instead of out_index[] -- the elements the ordering passes produce.
 hipError_t launch_count_packed(const IndexView &ix, const uint64_t *packed, uint32_t k, uint64_t n, uint64_t *counts,
                                const uint32_t *out_index, uint32_t *flags, hipStream_t stream, uint32_t stride_words = 0, bool place_inline = false);
+// FM ranges instead of counts (msbwt_rle_kmer_ranges): the kernel launch_count_kmers picks for the batch, in its range mode.  Query q's
+// [l, h) goes to out_l[q * stride] and out_h[q * stride]: (0, 0) when it does not occur, all-ones (and kFlagInvalidSymbol) when it
+// holds a code >= 6.  Matrix byte queries, any k; never reordered.
+hipError_t launch_kmer_ranges(const IndexView &ix, const uint8_t *kmers, uint32_t k, uint64_t n, uint64_t *out_l, uint64_t *out_h,
+                              uint32_t stride, uint32_t *flags, hipStream_t stream);
+// Left-extension counts (extend.hip), in place: row q = rows[6 q .. 6 q + 6) holds the range of query q in its first two words
+// (launch_kmer_ranges with stride 6) and receives rank_c(h) - rank_c(l) for c = 0..5 -- six zeros for an empty range, six
+// all-ones for an invalid row.
+hipError_t launch_kmer_extensions(const IndexView &ix, uint64_t *rows, uint64_t n, uint32_t *flags, hipStream_t stream);
 // true when a count_kmers launch for k-symbol queries runs the lanes kernel (the only one that knows ix.done / inline queries)
 bool lanes_serves(const IndexView &ix, uint32_t k);
 

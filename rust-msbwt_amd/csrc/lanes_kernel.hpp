@@ -455,7 +455,9 @@ struct SparseScanOut {
 // a lookup that ends in the filter goes on through the DIRECT table (`dtable`: its line is the query's next step, decoded by the lane)
 // and searches from there -- the complete-table kernels (kSparse = 1) carry none of that.
 // kPair = false with kSparse (round 6): run blocks behind a sparse table -- the post-lookup steps are single-symbol steps.
-template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse>
+// kRange (matrix byte queries only): every query ends with its FM range stored instead of its count (QuerySource::range_stride) --
+// (0, 0) for an empty one, all-ones for a query holding a symbol >= 6; the search itself is the same.
+template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse, bool kRange = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_count_kmers_lanes(const uint4 *__restrict__ blocks, uint64_t total,
                                                           const uint4 *__restrict__ table, uint32_t depth, uint32_t table_packed,
                                                           const uint32_t *__restrict__ filter, uint32_t filter_mask,
@@ -468,6 +470,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                                                           uint32_t sparse_probe, const uint4 *__restrict__ dtable, uint32_t dinfo,
                                                           const uint4 *__restrict__ dside) {
     static_assert(!(kReads && kPacked), "packed queries are a matrix-mode input");
+    static_assert(!(kRange && (kReads || kPacked)), "ranges are served for matrix byte queries");
     static_assert(kSparse >= 0 && kSparse <= 4, "0 = direct table; sparse table: 1 = 24-bit tags (depths up to 24), 2 = two-tier form, 3 = 32-bit tags (25..29), 4 = 40-bit tags (30..31)");
     constexpr bool kTier = kSparse == 2, kWideTags = kSparse == 3, kXwide = kSparse == 4;
     constexpr int kReach = kSparse >= 2 ? 32 : 24;  // how deep this kernel's table index may reach (search_common.hpp, pack_row_swar)
@@ -734,7 +737,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
             unpack_words<kWords>(prep_q, skip, prep_w);
             bool pending = prep_kind != 0u;
             if (pending && !lookup && (prep_rem == 0u || pl == ph)) {  // decided by the table (or an empty index)
-                store_count<kReads>(src, place_of(prep_tile * kTile + lane, prep_out), ph - pl);
+                if constexpr (kRange) store_range(src, prep_tile * kTile + lane, pl, ph);
+                else store_count<kReads>(src, place_of(prep_tile * kTile + lane, prep_out), ph - pl);
                 pending = false;
             }
             const uint64_t pend_mask = __ballot(pending);
@@ -813,7 +817,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                 debug[4] = (uint64_t(w[1]) << 32) | w[0];
                 debug[5] = (uint64_t(blockIdx.x) << 32) | lane;
             }
-            store_count<kReads>(src, qid, ~0ull);
+            if constexpr (kRange) store_range_raw(src, qid, ~0ull, ~0ull);
+            else store_count<kReads>(src, qid, ~0ull);
             have = false;
         }
         busy = __ballot(have);
@@ -873,7 +878,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     pack_query<true, kWords, kReach>(src, depth, stage_bytes, q0 + lane, pq);
                 }
                 if (pq.bad) {  // the reference asserts (msbwt_core.rs:127)
-                    store_count<kReads>(src, place_of(q0 + lane, prep_out), ~0ull);
+                    if constexpr (kRange) store_range_raw(src, q0 + lane, ~0ull, ~0ull);
+                    else store_count<kReads>(src, place_of(q0 + lane, prep_out), ~0ull);
                     atomicOr(flags, kFlagInvalidSymbol);
                 } else if (use_table && pq.acgt) {
                     bool maybe = true;
@@ -901,7 +907,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                         }
                         prep_q = pq;
                     } else {
-                        store_count<kReads>(src, place_of(q0 + lane, prep_out), 0ull);
+                        if constexpr (kRange) store_range_raw(src, q0 + lane, 0ull, 0ull);
+                        else store_count<kReads>(src, place_of(q0 + lane, prep_out), 0ull);
                         filtered = true;
                     }
                 } else {
@@ -1056,7 +1063,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     prep_entry.z |= 1u << 8;
                     prep_kind = dd != 0u ? 5u : 2u;  // (no direct table: from [0, total))
                 } else {  // a miss in a complete table: the suffix does not occur (msbwt_core.rs:151-153)
-                    store_count<kReads>(src, place_of(prep_tile * kTile + lane, prep_out), 0ull);
+                    if constexpr (kRange) store_range_raw(src, prep_tile * kTile + lane, 0ull, 0ull);
+                    else store_count<kReads>(src, place_of(prep_tile * kTile + lane, prep_out), 0ull);
                     prep_kind = 0;
                 }
             }
@@ -1098,7 +1106,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     }
                     tmode = false;
                     if (rem == 0u) {  // k == depth: the table's range is the answer
-                        store_count<kReads>(src, qid, h - l);
+                        if constexpr (kRange) store_range(src, qid, l, h);
+                        else store_count<kReads>(src, qid, h - l);
                         have = false;
                     }
                 } else if (header > sparse_nslots && (kTier ? (tdist & 0xFFu) : tdist) < sparse_probe) {  // entries of this bucket were displaced: the next one
@@ -1116,7 +1125,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                         h = total;
                     }
                 } else {  // a miss in a complete table: the suffix does not occur (msbwt_core.rs:151-153)
-                    store_count<kReads>(src, qid, 0ull);
+                    if constexpr (kRange) store_range_raw(src, qid, 0ull, 0ull);
+                    else store_count<kReads>(src, qid, 0ull);
                     have = false;
                 }
                 if (counting) {
@@ -1152,7 +1162,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                 }
                 dmode = false;
                 if (l == h) {  // the filter's false positive (or an absent k-mer that shares its bits): nothing occurs
-                    store_count<kReads>(src, qid, 0ull);
+                    if constexpr (kRange) store_range_raw(src, qid, 0ull, 0ull);
+                    else store_count<kReads>(src, qid, 0ull);
                     have = false;
                 }
                 if (counting) {
@@ -1208,7 +1219,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                 l = nl;
                 h = nh;
                 if (rem == 0u || l == h) {
-                    store_count<kReads>(src, qid, h - l);
+                    if constexpr (kRange) store_range(src, qid, l, h);
+                    else store_count<kReads>(src, qid, h - l);
                     have = false;
                 }
             }
@@ -1235,13 +1247,13 @@ constexpr uint64_t kMaxTiles = 1ull << 32;
 
 // The kernel is persistent: the grid is what the device keeps resident -- workgroups per CU
 // (occupancy API: LDS- and VGPR-bound, capped below) x CUs; tiles are dealt out by atomic tickets.
-template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse>
+template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse, bool kRange>
 uint32_t resident_waves() {
     static const uint32_t cached = [] {
         int device = 0, cus = 0, per_cu = 0;
         if (hipGetDevice(&device) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_count_kmers_lanes<kReads, kPair, kWords, kStride96, kPacked, kSparse>, 64, 0) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_count_kmers_lanes<kReads, kPair, kWords, kStride96, kPacked, kSparse, kRange>, 64, 0) != hipSuccess ||
             cus <= 0 || per_cu <= 0)
             return 7u * 256u;
         // LDS decides (12.1 / 12.9 KiB -> 12 waves); whole multiples of the four SIMDs only: with
@@ -1252,13 +1264,13 @@ uint32_t resident_waves() {
             const int want = std::atoi(env);
             if (want > 0) per_cu = want;
         }
-        if (std::getenv("MSBWT_VERBOSE")) std::fprintf(stderr, "[msbwt] lanes kernel <%d,%d,%d,%d,%d,%d>: %d workgroups per CU x %d CUs\n", int(kReads), int(kPair), kWords, int(kStride96), int(kPacked), int(kSparse), per_cu, cus);
+        if (std::getenv("MSBWT_VERBOSE")) std::fprintf(stderr, "[msbwt] lanes kernel <%d,%d,%d,%d,%d,%d,%d>: %d workgroups per CU x %d CUs\n", int(kReads), int(kPair), kWords, int(kStride96), int(kPacked), int(kSparse), int(kRange), per_cu, cus);
         return uint32_t(cus) * uint32_t(per_cu);
     }();
     return cached;
 }
 
-template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse>
+template <bool kReads, bool kPair, int kWords, bool kStride96, bool kPacked, int kSparse, bool kRange = false>
 hipError_t launch_variant(hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags) {
     // (kSparse: the sparse table's lines, depth and side array travel in the direct table's arguments; `sp`: the one of the two that serves this k)
     const SparseView none{};
@@ -1267,7 +1279,7 @@ hipError_t launch_variant(hipStream_t stream, const IndexView &ix, const QuerySo
     const uint32_t *filter = ix.table.entries ? ix.table.filter : nullptr;
     const uint32_t filter_mask = filter ? uint32_t((1ull << (2 * ix.table.filter_depth)) - 1ull) : 0u;
     const uint64_t tiles = (src.n + kTile - 1) / kTile;
-    const uint64_t waves = std::min<uint64_t>(tiles, resident_waves<kReads, kPair, kWords, kStride96, kPacked, kSparse>());
+    const uint64_t waves = std::min<uint64_t>(tiles, resident_waves<kReads, kPair, kWords, kStride96, kPacked, kSparse, kRange>());
     if (tiles > kMaxTiles) return hipErrorInvalidValue;
     // Ticket counters are only needed when there are more tiles than waves; without them (small batches, the
     // single-query path: no memset, no atomics) the kernel strides statically.
@@ -1279,7 +1291,7 @@ hipError_t launch_variant(hipStream_t stream, const IndexView &ix, const QuerySo
     // tiles per ticket: about eight tickets per wave at least, sixteen tiles at most
     const uint32_t grain = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(16, tiles / (waves * 8))));
     const uint4 *side = static_cast<const uint4 *>(kSparse ? sp.side : (table ? ix.table.side : nullptr));
-    hipLaunchKernelGGL((k_count_kmers_lanes<kReads, kPair, kWords, kStride96, kPacked, kSparse>), dim3(uint32_t(waves)), dim3(64), 0, stream,
+    hipLaunchKernelGGL((k_count_kmers_lanes<kReads, kPair, kWords, kStride96, kPacked, kSparse, kRange>), dim3(uint32_t(waves)), dim3(64), 0, stream,
                        static_cast<const uint4 *>(ix.blocks), ix.total, table, kSparse ? sp.depth : uint32_t(ix.table.depth), ((!kSparse && ix.table.packed) ? 1u : 0u) | (ix.stream_lines ? 2u : 0u),
                        filter, filter_mask, side, static_cast<const uint4 *>(ix.pair_blocks), ix.pair_super, src, flags, ix.debug,
                        tickets ? static_cast<unsigned long long *>(ix.tile_counter) : nullptr, grain, waves == 1 ? ix.done : nullptr, ix.done_seq, ix.counters,
@@ -1291,26 +1303,29 @@ hipError_t launch_variant(hipStream_t stream, const IndexView &ix, const QuerySo
     return hipGetLastError();
 }
 
-template <bool kReads, bool kPacked, int kSparse>
+template <bool kReads, bool kPacked, int kSparse, bool kRange = false>
 hipError_t launch_sparse_shape(bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags) {
     if (!pair) {  // run blocks behind a sparse table: single-symbol steps after the lookup (packed queries never reach run blocks)
         if constexpr (kPacked) return hipErrorInvalidValue;
-        else return longk ? launch_variant<kReads, false, 6, false, false, kSparse>(stream, ix, src, flags) : launch_variant<kReads, false, 3, false, false, kSparse>(stream, ix, src, flags);
+        else return longk ? launch_variant<kReads, false, 6, false, false, kSparse, kRange>(stream, ix, src, flags) : launch_variant<kReads, false, 3, false, false, kSparse, kRange>(stream, ix, src, flags);
     }
-    if (ix.pair_stride96) return longk ? launch_variant<kReads, true, 6, true, kPacked, kSparse>(stream, ix, src, flags) : launch_variant<kReads, true, 3, true, kPacked, kSparse>(stream, ix, src, flags);
-    return longk ? launch_variant<kReads, true, 6, false, kPacked, kSparse>(stream, ix, src, flags) : launch_variant<kReads, true, 3, false, kPacked, kSparse>(stream, ix, src, flags);
+    if (ix.pair_stride96) return longk ? launch_variant<kReads, true, 6, true, kPacked, kSparse, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, true, kPacked, kSparse, kRange>(stream, ix, src, flags);
+    return longk ? launch_variant<kReads, true, 6, false, kPacked, kSparse, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, false, kPacked, kSparse, kRange>(stream, ix, src, flags);
 }
 
 }  // namespace
 
-// the sparse-table launches of the other translation units (kSparse: 2 = two-tier, 3 = 32-bit tags, 4 = 40-bit tags)
-hipError_t launch_lanes_sparse_tier(bool reads, bool packed, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
-hipError_t launch_lanes_sparse_wide(bool reads, bool packed, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
-hipError_t launch_lanes_sparse_xwide(bool reads, bool packed, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
+// the sparse-table launches of the other translation units (kSparse: 2 = two-tier, 3 = 32-bit tags, 4 = 40-bit tags); range: the
+// kRange instantiations (matrix byte queries)
+hipError_t launch_lanes_sparse_tier(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
+hipError_t launch_lanes_sparse_wide(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
+hipError_t launch_lanes_sparse_xwide(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
 
 #define MSBWT_DEFINE_SPARSE_LAUNCH(NAME, LAYOUT)                                                                                                          \
-    hipError_t NAME(bool reads, bool packed, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags) { \
-        if (reads) return packed ? hipErrorInvalidValue : launch_sparse_shape<true, false, LAYOUT>(pair, longk, stream, ix, src, flags);                \
+    hipError_t NAME(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src,       \
+                    uint32_t *flags) {                                                                                                                   \
+        if (reads) return (packed || range) ? hipErrorInvalidValue : launch_sparse_shape<true, false, LAYOUT>(pair, longk, stream, ix, src, flags);     \
+        if (range) return packed ? hipErrorInvalidValue : launch_sparse_shape<false, false, LAYOUT, true>(pair, longk, stream, ix, src, flags);         \
         return packed ? launch_sparse_shape<false, true, LAYOUT>(pair, longk, stream, ix, src, flags)                                                   \
                       : launch_sparse_shape<false, false, LAYOUT>(pair, longk, stream, ix, src, flags);                                                 \
     }

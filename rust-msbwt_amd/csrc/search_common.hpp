@@ -47,7 +47,13 @@ struct QuerySource {
     // after the query's own holds the place its count goes to (low 32 bits) -- one 16-byte load per 31-mer brings both
     // (what the ordering passes of order.hip hand over: one store per element instead of two)
     uint32_t packed_stride, place_inline;
+    // RANGE mode (matrix byte queries, the kRange instantiations; 0 = counts): query v's FM range [l, h) goes to
+    // out_fwd[v * range_stride] (l) and out_rc[v * range_stride] (h) instead of its count -- two arrays with stride 1
+    // (msbwt_rle_kmer_ranges), or the first 16 bytes of a 48-byte row with stride 6 (the extension calls, extend.hip).
+    // (It sits in the struct's tail padding: the layout the count kernels see is unchanged.)
+    uint32_t range_stride;
 };
+static_assert(sizeof(QuerySource) == 192, "QuerySource's layout is shared by every search kernel's arguments");
 
 namespace {
 
@@ -167,6 +173,17 @@ __device__ __forceinline__ void store_count(const QuerySource &src, uint64_t v, 
     } else {
         (src.strands == 2u ? src.out_rc : src.out_fwd)[v] = value;
     }
+}
+
+// range mode: an empty range is stored as (0, 0) -- what the count 0 stands for, whichever step found it empty
+__device__ __forceinline__ void store_range_raw(const QuerySource &src, uint64_t v, uint64_t l, uint64_t h) {
+    const uint64_t at = v * src.range_stride;
+    src.out_fwd[at] = l;
+    src.out_rc[at] = h;
+}
+__device__ __forceinline__ void store_range(const QuerySource &src, uint64_t v, uint64_t l, uint64_t h) {
+    const bool empty = l == h;
+    store_range_raw(src, v, empty ? 0ull : l, empty ? 0ull : h);
 }
 
 // ---- one lane = one query: setup in three pieces -----------------------------------------------

@@ -105,6 +105,34 @@ class RleBWT(BWT):
             _raise(rc, self._h)
         return out
 
+    def kmer_ranges(self, kmers):
+        """kmers: (n, k) uint8 symbol codes -> (l, h), two uint64[n]: the FM range [l, h) of every k-mer
+        (h - l == its count; (0, 0) when it does not occur; k = 0: [0, total))."""
+        a = np.ascontiguousarray(kmers, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("kmers must be (n, k)")
+        n, k = a.shape
+        ol = np.empty(n, dtype=np.uint64)
+        oh = np.empty(n, dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_kmer_ranges(self._h, a.ctypes.data_as(C.c_void_p), k, n,
+                                              ol.ctypes.data_as(C.c_void_p), oh.ctypes.data_as(C.c_void_p))
+        if rc:
+            _raise(rc, self._h)
+        return ol, oh
+
+    def count_kmer_extensions(self, kmers):
+        """kmers: (n, k) uint8 symbol codes -> uint64[n, 6]: out[i, c] = count_kmer([c] + row i), c = 0..5 ($ A C G N T)."""
+        a = np.ascontiguousarray(kmers, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("kmers must be (n, k)")
+        n, k = a.shape
+        out = np.empty((n, 6), dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_count_kmer_extensions(self._h, a.ctypes.data_as(C.c_void_p), k, n,
+                                                        out.ctypes.data_as(C.c_void_p))
+        if rc:
+            _raise(rc, self._h)
+        return out
+
     def constrain_ranges(self, syms, l, h):
         s = np.ascontiguousarray(syms, dtype=np.uint8)
         l = np.ascontiguousarray(l, dtype=np.uint64)
@@ -180,6 +208,18 @@ class RleBWT(BWT):
     def count_kmers_device(self, d_kmers, k, n, d_out, stream=0):
         """Device pointers (ints); asynchronous on `stream` (a hipStream_t as int)."""
         rc = _lib.lib().msbwt_rle_count_kmers_device(self._h, d_kmers, k, n, d_out, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def kmer_ranges_device(self, d_kmers, k, n, d_out_l, d_out_h, stream=0):
+        """Device pointers (ints): n x k symbol codes -> l, h (n u64 each); asynchronous on `stream`."""
+        rc = _lib.lib().msbwt_rle_kmer_ranges_device(self._h, d_kmers, k, n, d_out_l, d_out_h, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def count_kmer_extensions_device(self, d_kmers, k, n, d_out, stream=0):
+        """Device pointers (ints): n x k symbol codes -> n x 6 u64 left-extension counts; asynchronous on `stream`."""
+        rc = _lib.lib().msbwt_rle_count_kmer_extensions_device(self._h, d_kmers, k, n, d_out, stream)
         if rc:
             _raise(rc, self._h)
 

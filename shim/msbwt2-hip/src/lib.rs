@@ -38,6 +38,15 @@ extern "C" {
     fn msbwt_rle_count_kmers_device(bwt: *const MsbwtRle, d_kmers: *const c_void, k: usize, n: usize,
                                     d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn msbwt_rle_device_status(bwt: *const MsbwtRle, hip_stream: *mut c_void) -> c_int;
+    // k-mer ranges and left-extension counts (n x 6)
+    fn msbwt_rle_kmer_ranges(bwt: *const MsbwtRle, kmers: *const u8, k: usize, n: usize,
+                             out_l: *mut u64, out_h: *mut u64) -> c_int;
+    fn msbwt_rle_kmer_ranges_device(bwt: *const MsbwtRle, d_kmers: *const c_void, k: usize, n: usize,
+                                    d_out_l: *mut c_void, d_out_h: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_count_kmer_extensions(bwt: *const MsbwtRle, kmers: *const u8, k: usize, n: usize,
+                                       out_counts: *mut u64) -> c_int;
+    fn msbwt_rle_count_kmer_extensions_device(bwt: *const MsbwtRle, d_kmers: *const c_void, k: usize, n: usize,
+                                              d_out_counts: *mut c_void, hip_stream: *mut c_void) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -113,6 +122,27 @@ impl GpuRleBWT {
         let mut out = vec![0u64; n];
         let rc = unsafe { msbwt_rle_count_kmers(self.raw, kmers.as_ptr(), k, n, out.as_mut_ptr()) };
         if rc != MSBWT_OK { panic!("count_kmers: {}", self.last_error()); } // reference: assert!/panic
+        out
+    }
+
+    /// FM range of every k-mer (row-major, k symbol codes each): `h - l` is its count, `{0, 0}` when it does not occur.
+    pub fn kmer_ranges(&self, kmers: &[u8], k: usize) -> Vec<BWTRange> {
+        assert!(k == 0 || kmers.len() % k == 0);
+        let n = if k == 0 { 0 } else { kmers.len() / k };
+        let (mut l, mut h) = (vec![0u64; n], vec![0u64; n]);
+        let rc = unsafe { msbwt_rle_kmer_ranges(self.raw, kmers.as_ptr(), k, n, l.as_mut_ptr(), h.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("kmer_ranges: {}", self.last_error()); }
+        l.into_iter().zip(h).map(|(l, h)| BWTRange { l, h }).collect()
+    }
+
+    /// Left-extension counts: `out[i][c]` = `count_kmer([c] ++ row i)` for c = 0..5 ($ A C G N T), one search per row.
+    /// On an index of reads and their reverse complements, `count(q ++ [c])` = `ext(rc(q))[COMPLEMENT_INT[c]]`.
+    pub fn count_kmer_extensions(&self, kmers: &[u8], k: usize) -> Vec<[u64; 6]> {
+        assert!(k == 0 || kmers.len() % k == 0);
+        let n = if k == 0 { 0 } else { kmers.len() / k };
+        let mut out = vec![[0u64; 6]; n];
+        let rc = unsafe { msbwt_rle_count_kmer_extensions(self.raw, kmers.as_ptr(), k, n, out.as_mut_ptr() as *mut u64) };
+        if rc != MSBWT_OK { panic!("count_kmer_extensions: {}", self.last_error()); }
         out
     }
 
