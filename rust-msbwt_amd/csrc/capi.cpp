@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,7 +32,92 @@
 
 using namespace msbwt;
 
-struct msbwt_rle {
+namespace {
+
+// The parts of a loaded index beyond its blocks own their device buffers: release() frees them and resets the part.
+// Direct table (kernels.hpp, TableView) of the index in HBM, with the side array of its escape lines and the presence filter made from it
+struct DirectTable {
+    void *entries = nullptr;
+    int depth = 0;               // symbols a table entry stands for
+    bool packed = false;         // packed lines (two levels deeper than the flat table it was made from)
+    size_t bytes = 0;
+    void *side = nullptr;        // packed table: flat entries of its escape lines (512 bytes per line), or nullptr
+    uint64_t side_bytes = 0;
+    uint64_t lines = 0, escape_lines = 0;  // of the packed table
+    uint32_t *filter = nullptr;  // presence bits over the low 2*filter_depth index bits of the table
+    int filter_depth = 0;
+    void release_filter() {
+        if (filter) (void)hipFree(filter);
+        filter = nullptr;
+        filter_depth = 0;
+    }
+    void release() {
+        if (entries) (void)hipFree(entries);
+        if (side) (void)hipFree(side);
+        release_filter();
+        *this = DirectTable{};
+    }
+    TableView view() const {  // (without a table: the filter depth alone)
+        return entries ? TableView{entries, depth, packed, filter, filter_depth, packed ? side : nullptr} : TableView{nullptr, 0, false, nullptr, filter_depth};
+    }
+};
+
+// One level of the sparse suffix table (sparse_table.hpp): ranges of the suffixes that occur, deeper than the direct table reaches
+struct SparseLevel {
+    void *lines = nullptr;       // (nbuckets + probe) lines of 128 bytes
+    void *side = nullptr;        // 16-byte {l, h} entries of its ESCAPE entries
+    uint64_t bytes = 0, side_bytes = 0, entries = 0;  // (entries: the second level's; the first level's are in the handle's sparse_report)
+    uint32_t nbuckets = 0, probe = 0;
+    int depth = 0;
+    bool tier = false;           // of the two-tier form (entries for the suffixes at least 2 wide, filter bits for the rest)
+    void release() {
+        if (lines) (void)hipFree(lines);
+        if (side) (void)hipFree(side);
+        *this = SparseLevel{};
+    }
+    SparseView view() const { return lines ? SparseView{lines, nbuckets, uint32_t(depth), probe, side, tier ? 1u : 0u} : SparseView{}; }
+};
+
+// Pair index (two symbols per step, rank_ops.hpp)
+struct PairIndex {
+    void *blocks = nullptr;
+    void *super = nullptr;
+    uint64_t bytes = 0;
+    uint64_t overlap_bytes = 0;  // what overlapping pair blocks take beyond disjoint ones (0 unless the data-driven policy chose them)
+    int stride = 128;            // spacing of the pair blocks in HBM: 128, or 96 (overlapping); read only beside pair blocks
+    void release() {  // (the stride stays: it describes the last pair index built)
+        if (blocks) (void)hipFree(blocks);
+        if (super) (void)hipFree(super);
+        blocks = super = nullptr;
+        bytes = overlap_bytes = 0;
+    }
+};
+
+// What the caller has asked for: the settings the index is built by.  A replica copies them whole (msbwt_rle_replicate).
+struct Settings {
+    int wanted_block_format = kBlocksPlanes;  // takes effect at the next load
+    int wanted_pair = -1;           // -1 = on when it fits comfortably, 0 = off, 1 = on
+    int wanted_pair_stride = 0;     // 0 = automatic (table_policy.hpp: cheap -> 96; else 96 when the data keep ranges wide and it fits)
+    int wanted_table_side = 1;      // 0 = no side array (queries of escape lines search from scratch, as until round 3)
+    int wanted_second = -1;         // second sparse level: -1 = automatic (k undeclared, the deep direct table does not fit, this one does), 0 = never
+    int wanted_tiers = -1;          // -1 = two-tier where the complete table of a depth does not fit, 0 = complete tables only, 1 = two-tier only
+    int wanted_streaming = -1;      // index lines fetched non-temporally: -1 = when the random-access arrays dwarf the caches, 0 = never, 1 = always
+    int wanted_sparse = -1;         // -1 = automatic (beside a pair index, as deep as the data and HBM allow, at most 23 -- or what query_length says), 0 = off, 16..28 = that depth
+    int query_length = 0;           // the k the index will mostly be asked about (msbwt_rle_set_query_length), 0 = unknown
+    int wanted_table_packed = -1;   // -1 = pack when the data warrants it and it fits, 0 = never, 1 = whenever a pair index exists
+    int wanted_filter = -1;         // -1 = keep it when it can reject something, 0 = off
+    int wanted_table_depth = -1;    // -1 = pick from the index size
+    int search_kernel = kSearchAuto;
+    int wanted_order = -1;          // batch order: 1 = whenever the passes apply; 0 and -1 (automatic: see order_pays) = never
+    int order_bits = 22;            // key bits the bucket passes order by (11 in the global pass + 11 inside each bucket)
+    uint64_t memory_budget = 0;     // bytes of HBM the index may hold (0 = no budget): msbwt_rle_set_memory_budget
+    bool planned = false;           // a budget is in force: `plan` (table_policy.hpp, plan_index) decides the optional structures
+    IndexPlan plan{};
+};
+
+}  // namespace
+
+struct msbwt_rle : Settings {
     int device = 0;
     uint8_t bin_power = 8;
     bool loaded = false;
@@ -39,52 +125,17 @@ struct msbwt_rle {
     void *d_blocks = nullptr;
     uint64_t nblocks = 0;
     int block_format = kBlocksPlanes;         // format of d_blocks
-    int wanted_block_format = kBlocksPlanes;  // takes effect at the next load
     void *d_overflow = nullptr;               // run blocks: plane-shaped lines of the overflowing blocks
     uint64_t overflow_bytes = 0;
-    void *d_pair_blocks = nullptr;  // optional pair index (two symbols per step)
-    void *d_pair_super = nullptr;
-    uint64_t pair_bytes = 0;
-    uint64_t pair_overlap_bytes = 0;  // what overlapping pair blocks take beyond disjoint ones (0 unless the data-driven policy chose them)
-    int wanted_pair = -1;           // -1 = on when it fits comfortably, 0 = off, 1 = on
-    int pair_stride = 128;          // spacing of the pair blocks in HBM: 128, or 96 (overlapping)
-    int wanted_pair_stride = 0;     // 0 = automatic (table_policy.hpp: cheap -> 96; else 96 when the data keep ranges wide and it fits)
+    PairIndex pair;                 // optional
     double typical_width = -1.0;    // median occurrence count of a present 24-mer, probed at load time (-1: not probed)
-    void *d_table = nullptr;
-    int table_depth = 0;         // symbols a table entry stands for (of the table currently in HBM)
-    bool table_packed = false;   // packed lines (two levels deeper than the flat table it was made from)
-    size_t table_bytes = 0;
-    void *d_table_side = nullptr;    // packed table: flat entries of its escape lines (512 bytes per line), or nullptr
-    uint64_t table_side_bytes = 0;
-    uint64_t table_lines = 0, table_escape_lines = 0;  // of the packed table in HBM
-    int wanted_table_side = 1;       // 0 = no side array (queries of escape lines search from scratch, as until round 3)
-    // sparse suffix table (sparse_table.hpp): ranges of the suffixes that occur, deeper than the direct table reaches
-    void *d_sparse = nullptr;        // (nbuckets + probe) lines of 128 bytes
-    void *d_sparse_side = nullptr;   // 16-byte {l, h} entries of its ESCAPE entries
-    uint64_t sparse_bytes = 0, sparse_side_bytes = 0;
-    uint32_t sparse_nbuckets = 0, sparse_probe = 0;
-    int sparse_depth = 0;
-    bool sparse_tier = false;        // the table in HBM is of the two-tier form (entries for the suffixes at least 2 wide, filter bits for the rest)
-    // second, shallower sparse table (round 6; k undeclared): serves the queries shorter than the first one's entries (17 <= k < 23), which would
-    // otherwise fall to the direct table -- shallow beside a sparse table -- and lose 1.5-2.5 x against the index without one
-    void *d_sparse2 = nullptr, *d_sparse2_side = nullptr;
-    uint64_t sparse2_bytes = 0, sparse2_side_bytes = 0, sparse2_entries = 0;
-    uint32_t sparse2_nbuckets = 0, sparse2_probe = 0;
-    int sparse2_depth = 0;
-    bool sparse2_tier = false;
-    int wanted_second = -1;          // -1 = automatic (k undeclared, the deep direct table does not fit, this one does), 0 = never
-    int wanted_tiers = -1;           // -1 = two-tier where the complete table of a depth does not fit, 0 = complete tables only, 1 = two-tier only
-    int wanted_streaming = -1;       // index lines fetched non-temporally: -1 = when the random-access arrays dwarf the caches, 0 = never, 1 = always
-    int wanted_sparse = -1;          // -1 = automatic (beside a pair index, as deep as the data and HBM allow, at most 23 -- or what query_length says), 0 = off, 16..28 = that depth
-    int query_length = 0;            // the k the index will mostly be asked about (msbwt_rle_set_query_length), 0 = unknown
+    DirectTable table;
+    // sparse suffix table: `sparse`, and a second, shallower level (round 6; k undeclared) that serves the queries shorter than the first
+    // one's entries (17 <= k < 23), which would otherwise fall to the direct table -- shallow beside a sparse table -- and lose 1.5-2.5 x
+    // against the index without one
+    SparseLevel sparse, sparse2;
     SparseBuildReport sparse_report{};
     bool counting = false;           // search counters wanted (msbwt_rle_set_search_counters)
-    int wanted_table_packed = -1; // -1 = pack when the data warrants it and it fits, 0 = never, 1 = whenever a pair index exists
-    uint32_t *d_filter = nullptr;   // presence bits over the low 2*filter_depth index bits of the table
-    int filter_depth = 0;
-    int wanted_filter = -1;         // -1 = keep it when it can reject something, 0 = off
-    int wanted_table_depth = -1; // -1 = pick from the index size
-    int search_kernel = kSearchAuto;
     // Tile-ticket counter blocks of the lanes kernel (kernels.hpp, kTicketBytes each): a launch takes a block whose
     // previous launch has COMPLETED (its event says so) or a new one, so two launches in flight on different
     // streams never share counters however many there are.
@@ -96,11 +147,6 @@ struct msbwt_rle {
         void *order_scratch = nullptr;      // scratch of the batch-ordering pass (order.hip) of the launch that holds the slot
         size_t order_bytes = 0;
     };
-    uint64_t memory_budget = 0;  // bytes of HBM the index may hold (0 = no budget): msbwt_rle_set_memory_budget
-    bool planned = false;        // a budget is in force: `plan` (table_policy.hpp, plan_index) decides the optional structures
-    IndexPlan plan{};
-    int wanted_order = -1;   // batch order: 1 = whenever the passes apply; 0 and -1 (automatic: see order_pays) = never
-    int order_bits = 22;     // key bits the bucket passes order by (11 in the global pass + 11 inside each bucket)
     std::vector<TicketSlot> tickets;
     // device status block (128 bytes): word 0 = flags of the host-pointer entry points (handle
     // stream), word 1 = flags of the *_device entry points (caller streams; read and cleared only by
@@ -205,50 +251,22 @@ double line_rate_of(const void *p, size_t bytes, hipStream_t stream) {
     return double(lines) / (double(ms) * 1e-3);
 }
 
-// the second, shallower sparse level alone
-void release_sparse2(msbwt_rle *h) {
-    if (h->d_sparse2) (void)hipFree(h->d_sparse2);
-    if (h->d_sparse2_side) (void)hipFree(h->d_sparse2_side);
-    h->d_sparse2 = h->d_sparse2_side = nullptr;
-    h->sparse2_bytes = h->sparse2_side_bytes = h->sparse2_entries = 0;
-    h->sparse2_nbuckets = h->sparse2_probe = 0;
-    h->sparse2_depth = 0;
-    h->sparse2_tier = false;
-}
-
+// both sparse levels and what the sizing pass counted
 void release_sparse(msbwt_rle *h) {
-    if (h->d_sparse) (void)hipFree(h->d_sparse);
-    if (h->d_sparse_side) (void)hipFree(h->d_sparse_side);
-    h->d_sparse = h->d_sparse_side = nullptr;
-    h->sparse_bytes = h->sparse_side_bytes = 0;
-    h->sparse_nbuckets = h->sparse_probe = 0;
-    h->sparse_depth = 0;
-    h->sparse_tier = false;
+    h->sparse.release();
     h->sparse_report = SparseBuildReport{};
-    release_sparse2(h);
+    h->sparse2.release();
 }
 
 void release_index(msbwt_rle *h) {
     if (h->d_blocks) (void)hipFree(h->d_blocks);
     if (h->d_overflow) (void)hipFree(h->d_overflow);
-    h->d_overflow = nullptr;
+    h->d_blocks = h->d_overflow = nullptr;
     h->overflow_bytes = 0;
-    if (h->d_table) (void)hipFree(h->d_table);
-    if (h->d_table_side) (void)hipFree(h->d_table_side);
-    h->d_table_side = nullptr;
-    h->table_side_bytes = h->table_lines = h->table_escape_lines = 0;
-    if (h->d_filter) (void)hipFree(h->d_filter);
-    h->d_filter = nullptr;
-    h->filter_depth = 0;
+    h->table.release();
     release_sparse(h);
-    if (h->d_pair_blocks) (void)hipFree(h->d_pair_blocks);
-    if (h->d_pair_super) (void)hipFree(h->d_pair_super);
-    h->d_blocks = h->d_table = h->d_pair_blocks = h->d_pair_super = nullptr;
-    h->pair_bytes = 0;
+    h->pair.release();
     h->nblocks = 0;
-    h->table_depth = 0;
-    h->table_packed = false;
-    h->table_bytes = 0;
     h->typical_width = -1.0;
     h->totals = Totals{};  // an unloaded handle reports 0 symbols, not the previous BWT's
     h->loaded = false;
@@ -261,37 +279,20 @@ IndexView view_of(msbwt_rle *h) {
     v.overflow = h->d_overflow;
     v.nblocks = h->nblocks;
     v.total = h->totals.total;
-    v.table.entries = h->d_table;
-    v.table.depth = h->d_table ? h->table_depth : 0;
-    v.table.packed = h->d_table && h->table_packed;
-    v.table.filter = h->d_table ? h->d_filter : nullptr;
-    v.table.filter_depth = h->filter_depth;
-    v.table.side = (h->d_table && h->table_packed) ? h->d_table_side : nullptr;
+    v.table = h->table.view();
     v.counters = (h->counting && h->d_flags) ? reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(h->d_flags) + kCountersOffset) : nullptr;
-    v.pair_blocks = h->d_pair_blocks;
-    v.pair_super = static_cast<const uint64_t *>(h->d_pair_super);
-    v.pair_stride96 = h->d_pair_blocks && h->pair_stride == 96;
+    v.pair_blocks = h->pair.blocks;
+    v.pair_super = static_cast<const uint64_t *>(h->pair.super);
+    v.pair_stride96 = h->pair.blocks && h->pair.stride == 96;
     v.search_kernel = h->search_kernel;
     {   // lines used once should not evict what is reused -- once the arrays the search reads at random (pair blocks, else the blocks
         // themselves) are far beyond what L2 (8 x 4 MB) and the Infinity Cache (256 MB) hold: 4 GiB and up
-        const uint64_t hot = h->d_pair_blocks ? h->pair_bytes : h->nblocks * kBlockBytes;
+        const uint64_t hot = h->pair.blocks ? h->pair.bytes : h->nblocks * kBlockBytes;
         v.stream_lines = h->wanted_streaming > 0 || (h->wanted_streaming < 0 && hot >= kStreamLinesFrom);
     }
-    if (h->d_sparse && (h->d_pair_blocks || h->block_format == kBlocksRuns)) {  // (run blocks: built from pair blocks that are gone again)
-        v.sparse.lines = h->d_sparse;
-        v.sparse.nbuckets = h->sparse_nbuckets;
-        v.sparse.depth = uint32_t(h->sparse_depth);
-        v.sparse.probe = h->sparse_probe;
-        v.sparse.side = h->d_sparse_side;
-        v.sparse.tier = h->sparse_tier ? 1u : 0u;
-        if (h->d_sparse2) {
-            v.sparse2.lines = h->d_sparse2;
-            v.sparse2.nbuckets = h->sparse2_nbuckets;
-            v.sparse2.depth = uint32_t(h->sparse2_depth);
-            v.sparse2.probe = h->sparse2_probe;
-            v.sparse2.side = h->d_sparse2_side;
-            v.sparse2.tier = h->sparse2_tier ? 1u : 0u;
-        }
+    if (h->sparse.lines && (h->pair.blocks || h->block_format == kBlocksRuns)) {  // (run blocks: built from pair blocks that are gone again)
+        v.sparse = h->sparse.view();
+        v.sparse2 = h->sparse2.view();
     }
     v.debug = h->d_flags ? reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(h->d_flags) + 64) : nullptr;
     return v;  // tile_counter: with_tickets()
@@ -302,10 +303,11 @@ IndexView view_of(msbwt_rle *h) {
 // the filter's path.  The loader builds neither; whatever path might, every query launch checks the handle here first and is refused
 // (hipErrorInvalidValue) instead of being made.
 bool tier_launch_ok(const msbwt_rle *h) {
-    if (!h->d_table) return true;
-    const bool unfollowable = h->table_packed && h->table_escape_lines > 0 && !h->d_table_side;
-    auto level_ok = [&](bool tier, int depth) { return !tier || (sparse_tier_fits_direct(depth, h->table_depth) && !unfollowable); };
-    return level_ok(h->d_sparse && h->sparse_tier, h->sparse_depth) && level_ok(h->d_sparse2 && h->sparse2_tier, h->sparse2_depth);
+    const DirectTable &t = h->table;
+    if (!t.entries) return true;
+    const bool unfollowable = t.packed && t.escape_lines > 0 && !t.side;
+    auto level_ok = [&](const SparseLevel &s) { return !(s.lines && s.tier) || (sparse_tier_fits_direct(s.depth, t.depth) && !unfollowable); };
+    return level_ok(h->sparse) && level_ok(h->sparse2);
 }
 
 // Runs `launch(view)` with a ticket-counter block that no launch still in flight uses, and marks the block busy
@@ -354,6 +356,19 @@ hipError_t with_tickets(msbwt_rle *h, hipStream_t stream, Launch &&launch) {
     return with_slot(h, stream, [&](const IndexView &v, msbwt_rle::TicketSlot &) { return launch(v); });
 }
 
+
+// two u64 in the status block: the table packer's escape-line count and side-array cursor, or the run-block builder's overflow count
+unsigned long long *pack_scratch(const msbwt_rle *h) {
+    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_flags) + kPackScratchOffset);
+}
+
+// overflow blocks the run blocks made from `planes` need (run_build.hip); the count stays in pack_scratch for launch_run_block_write
+hipError_t count_overflow_blocks(msbwt_rle *h, const void *planes, uint64_t nplanes, uint64_t total, unsigned long long *nover) {
+    hipError_t e = launch_run_block_count(planes, nplanes, total, pack_scratch(h), h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(nover, pack_scratch(h), sizeof *nover, hipMemcpyDeviceToHost, h->stream);
+    return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
+}
+
 int ensure_runtime(msbwt_rle *h) {
     if (!h->stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     if (!h->d_flags) {
@@ -371,7 +386,8 @@ constexpr size_t kMailKmers = 64, kMailCounts = kMailKmers + kMailKmerBytes, kMa
                  kMailL = kMailSyms + 64, kMailH = kMailL + 8 * kMailQueries, kMailOutL = kMailH + 8 * kMailQueries,
                  kMailOutH = kMailOutL + 8 * kMailQueries, kMailBytes = kMailOutH + 8 * kMailQueries;
 
-int ensure_mail(msbwt_rle *h) {
+int ensure_mail(msbwt_rle *h) {  // (and the handle's stream and status block: ensure_runtime)
+    if (int rc = ensure_runtime(h)) return rc;
     if (h->mail) return MSBWT_OK;
     void *host = nullptr, *dev = nullptr;
     // coherent explicitly: the host polls a word the kernel writes (HIP_HOST_COHERENT=0 in the environment must not turn every
@@ -385,6 +401,17 @@ int ensure_mail(msbwt_rle *h) {
     std::memset(host, 0, kMailBytes);
     h->mail = static_cast<uint8_t *>(host);
     h->d_mail = static_cast<uint8_t *>(dev);
+    return MSBWT_OK;
+}
+
+// scratch of the all-gathers (hipFree waits for the device: no gather still reads the old buffer)
+int ensure_gather(msbwt_rle *h, size_t need) {
+    if (need <= h->gather_bytes) return MSBWT_OK;
+    if (h->d_gather) (void)hipFree(h->d_gather);
+    h->d_gather = nullptr;
+    h->gather_bytes = 0;
+    HIP_TRY(h, hipMalloc(&h->d_gather, need));
+    h->gather_bytes = need;
     return MSBWT_OK;
 }
 
@@ -402,16 +429,15 @@ int ensure_stage(msbwt_rle *h, size_t bytes) {
 // only if it can reject something (less than 90 % of its bits set) -- on a large genome every
 // 12-mer occurs and the filter would be a wasted lookup.
 int rebuild_filter(msbwt_rle *h) {
-    if (h->d_filter) (void)hipFree(h->d_filter);
-    h->d_filter = nullptr;
-    h->filter_depth = 0;
-    if (!h->d_table || h->wanted_filter == 0 || h->table_depth < 6) return MSBWT_OK;
-    const int fd = std::min(12, h->table_depth);
+    DirectTable &t = h->table;
+    t.release_filter();
+    if (!t.entries || h->wanted_filter == 0 || t.depth < 6) return MSBWT_OK;
+    const int fd = std::min(12, t.depth);
     const size_t words = (size_t(1) << (2 * fd)) / 32;
     uint32_t *filter = nullptr;
     HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&filter), words * sizeof(uint32_t)));
     hipError_t e = hipMemsetAsync(filter, 0, words * sizeof(uint32_t), h->stream);
-    if (e == hipSuccess) e = launch_build_filter(h->d_table, h->table_depth, fd, filter, h->stream);
+    if (e == hipSuccess) e = launch_build_filter(t.entries, t.depth, fd, filter, h->stream);
     std::vector<uint32_t> host(words);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), filter, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -425,8 +451,8 @@ int rebuild_filter(msbwt_rle *h) {
         (void)hipFree(filter);
         return MSBWT_OK;
     }
-    h->d_filter = filter;
-    h->filter_depth = fd;
+    t.filter = filter;
+    t.filter_depth = fd;
     return MSBWT_OK;
 }
 
@@ -445,15 +471,15 @@ bool deep_direct_fits(const msbwt_rle *h, int flat_depth_wanted) {
     size_t free_b = 0, total_b = 0;
     const uint64_t flat_deep = (uint64_t(1) << (2 * flat_depth_wanted)) * 16, packed = packed_table_bytes(flat_depth_wanted + 2);
     const uint64_t need = flat_deep + packed + packed / 8;  // (the packer's side array of escape lines: an eighth at most in practice)
-    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && uint64_t(free_b) + h->table_bytes >= need + uint64_t(total_b) / 8;
+    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && uint64_t(free_b) + h->table.bytes >= need + uint64_t(total_b) / 8;
 }
 
 int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direct_depth, int deep_direct_depth = 0) {
     release_sparse(h);
     const bool verbose = std::getenv("MSBWT_VERBOSE") != nullptr;
     const bool explicit_depth = h->wanted_sparse > 0;
-    const void *flat = (h->d_table && !h->table_packed) ? h->d_table : nullptr;
-    const int flat_depth = flat ? h->table_depth : 0;
+    const void *flat = (h->table.entries && !h->table.packed) ? h->table.entries : nullptr;
+    const int flat_depth = flat ? h->table.depth : 0;
     const int max_depth = explicit_depth ? h->wanted_sparse : sparse_auto_max_depth(h->query_length);
     if (max_depth <= flat_depth || max_depth < kSparseMinDepth) return explicit_depth ? fail(h, MSBWT_ERR_INVALID_ARG, "sparse table depth must exceed the direct table's") : MSBWT_OK;
     // (the two-tier form sends the suffixes that occur once down the direct table's path: it needs that table's side array for escape lines)
@@ -521,8 +547,8 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
         if (e != hipSuccess) return optional(e, "bucket lines");
         e = sparse_fill(view_of(h), flat, flat_depth, chosen, choice.tier, tmp.lines, nbuckets, uint32_t(probe), tmp.side, nside, tmp.counts, tmp.work, work_bytes, &rep, h->stream);
         if (e == hipSuccess) {
-            h->sparse_probe = uint32_t(probe);
-            h->sparse_bytes = lines * 128;
+            h->sparse = SparseLevel{tmp.lines, tmp.side, lines * 128, nside * 16, 0, uint32_t(nbuckets), uint32_t(probe), chosen, choice.tier};
+            tmp.lines = tmp.side = nullptr;
             break;
         }
         if (e != hipErrorInvalidValue || attempt == 3) return optional(e, "fill pass");
@@ -534,18 +560,11 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
         const uint64_t again = nbuckets + kSparseMaxProbe;
         if (again > 0xFFFFFFFFull || again * 128 + again * sizeof(uint32_t) + nside * 16 > avail) return optional(hipErrorOutOfMemory, "fill pass (no room for more buckets)");
     }
-    h->d_sparse = tmp.lines;
-    h->d_sparse_side = tmp.side;
-    tmp.lines = tmp.side = nullptr;
-    h->sparse_side_bytes = nside * 16;
-    h->sparse_nbuckets = uint32_t(nbuckets);
-    h->sparse_depth = chosen;
-    h->sparse_tier = choice.tier;
     h->sparse_report = rep;
     if (verbose)
         std::fprintf(stderr, "[msbwt] sparse table: depth %d%s, %llu entries in %u buckets (%.2f per bucket, %llu displaced, %llu in the side array, %llu in the filters), %.2f GB\n", chosen,
-                     choice.tier ? " two-tier" : "", (unsigned long long)rep.entries, h->sparse_nbuckets, double(rep.entries) / double(nbuckets), (unsigned long long)rep.displaced,
-                     (unsigned long long)rep.nescapes, (unsigned long long)rep.filtered, double(h->sparse_bytes + h->sparse_side_bytes) / 1e9);
+                     choice.tier ? " two-tier" : "", (unsigned long long)rep.entries, h->sparse.nbuckets, double(rep.entries) / double(nbuckets), (unsigned long long)rep.displaced,
+                     (unsigned long long)rep.nescapes, (unsigned long long)rep.filtered, double(h->sparse.bytes + h->sparse.side_bytes) / 1e9);
     // ---- a second, shallower level for the queries this table is too deep for (sparse_for, kernels.hpp) ----------------------------------
     // With k undeclared the table above is 23 deep and k = 17..22 fall to the direct table, which stays at packed depth 15 beside a sparse
     // table: measured at human scale (round 6, present k-mers), k = 17 / 19 / 21 run 2.5 / 1.8 / 1.5 x slower than on the index WITHOUT a
@@ -556,7 +575,7 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
     if (!explicit_depth && h->wanted_second != 0 && h->wanted_block_format == kBlocksPlanes && h->query_length == 0 && chosen > kSparseSecondDepth &&
         !deep_direct_fits(h, deep_direct_depth) &&
         hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t used = h->sparse_bytes + h->sparse_side_bytes;
+        const uint64_t used = h->sparse.bytes + h->sparse.side_bytes;
         const uint64_t avail2 = std::min<uint64_t>(allowance > used ? allowance - used : 0, uint64_t(free_b) > spare ? uint64_t(free_b) - spare : 0);
         const SparseChoice second = choose_sparse_depth(rep.distinct, rep.escapes, flat_depth, std::min(kSparseSecondDepth, chosen - 1), avail2, 0, rep.singles, tiers, direct_depth);
         if (second.depth) {
@@ -572,19 +591,12 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
                 e = sparse_fill(view_of(h), flat, flat_depth, second.depth, second.tier, two.lines, second.nbuckets, uint32_t(probe2), two.side, nside2, two.counts, tmp.work, work_bytes, &rep2,
                                 h->stream);
             if (e == hipSuccess) {
-                h->d_sparse2 = two.lines;
-                h->d_sparse2_side = two.side;
+                h->sparse2 = SparseLevel{two.lines, two.side, lines2 * 128, nside2 * 16, rep2.entries, uint32_t(second.nbuckets),
+                                         uint32_t(probe2), second.depth, second.tier};
                 two.lines = two.side = nullptr;
-                h->sparse2_bytes = lines2 * 128;
-                h->sparse2_side_bytes = nside2 * 16;
-                h->sparse2_entries = rep2.entries;
-                h->sparse2_nbuckets = uint32_t(second.nbuckets);
-                h->sparse2_probe = uint32_t(probe2);
-                h->sparse2_depth = second.depth;
-                h->sparse2_tier = second.tier;
                 if (verbose)
                     std::fprintf(stderr, "[msbwt] sparse table, second level: depth %d%s, %llu entries in %u buckets, %.2f GB (serves %d <= k < %d)\n", second.depth,
-                                 second.tier ? " two-tier" : "", (unsigned long long)rep2.entries, h->sparse2_nbuckets, double(h->sparse2_bytes + h->sparse2_side_bytes) / 1e9,
+                                 second.tier ? " two-tier" : "", (unsigned long long)rep2.entries, uint32_t(second.nbuckets), double(lines2 * 128 + nside2 * 16) / 1e9,
                                  second.depth, chosen);
             } else {  // optional: an entry without a slot, no memory -- the index simply has no second level
                 (void)hipGetLastError();
@@ -603,39 +615,30 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     // (run blocks: their sparse table was built at load time from temporary plane and pair blocks -- build_sparse_for_runs -- and does
     // not depend on the direct table rebuilt here; it goes with the index, or by msbwt_rle_set_sparse_table(0))
     if (h->block_format == kBlocksPlanes) release_sparse(h);
-    if (h->d_filter) (void)hipFree(h->d_filter);
-    h->d_filter = nullptr;
-    h->filter_depth = 0;
-    if (h->d_table) (void)hipFree(h->d_table);
-    h->d_table = nullptr;
-    h->table_depth = 0;
-    h->table_packed = false;
-    h->table_bytes = 0;
-    if (h->d_table_side) (void)hipFree(h->d_table_side);
-    h->d_table_side = nullptr;
-    h->table_side_bytes = h->table_lines = h->table_escape_lines = 0;
+    DirectTable &t = h->table;
+    t.release();
     // Automatic depths come from ONE decision (table_policy.hpp, pinned by a CPU test through
     // msbwt_auto_table_depths): beside a pair index the flat table is built as deep as the packed one needs.
     const bool automatic = h->wanted_table_depth < 0;
     int depth = h->wanted_table_depth;
-    bool pack = h->d_pair_blocks != nullptr && h->wanted_table_packed > 0;  // an explicit depth is packed only on request
+    bool pack = h->pair.blocks != nullptr && h->wanted_table_packed > 0;  // an explicit depth is packed only on request
     if (automatic && h->planned) {  // a memory budget is in force: the plan has sized the table (table_policy.hpp, plan_index)
         depth = h->plan.flat;
-        pack = h->plan.packed != 0 && h->d_pair_blocks != nullptr && h->wanted_table_packed != 0;
+        pack = h->plan.packed != 0 && h->pair.blocks != nullptr && h->wanted_table_packed != 0;
     } else if (automatic) {
         size_t free_b = 0, total_b = 0;
         const bool know_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
         // the table budgets against DISJOINT pair blocks: what overlapping ones take on top was checked against the
         // reserve when they were chosen (choose_pair_stride)
-        const TableChoice c = choose_table_depths(h->totals.total, h->nblocks * kBlockBytes, know_free ? uint64_t(free_b) + h->pair_overlap_bytes : 0,
-                                                  h->d_pair_blocks != nullptr, h->wanted_table_packed != 0);
+        const TableChoice c = choose_table_depths(h->totals.total, h->nblocks * kBlockBytes, know_free ? uint64_t(free_b) + h->pair.overlap_bytes : 0,
+                                                  h->pair.blocks != nullptr, h->wanted_table_packed != 0);
         depth = c.flat;
-        pack = c.packed != 0 || (h->d_pair_blocks != nullptr && h->wanted_table_packed > 0);  // mode 1: whenever a pair index exists
+        pack = c.packed != 0 || (h->pair.blocks != nullptr && h->wanted_table_packed > 0);  // mode 1: whenever a pair index exists
     }
     // The sparse table (sparse_table.hpp) is tried whenever a pair index exists; the automatic direct table then stays small.
     // Should no sparse depth fit (a read set whose error k-mers outnumber the genome's many times over), the direct table is built
     // again as if there were no such thing.
-    const bool try_sparse = allow_sparse && h->wanted_sparse != 0 && h->d_pair_blocks != nullptr && h->block_format == kBlocksPlanes && h->totals.total > 0;
+    const bool try_sparse = allow_sparse && h->wanted_sparse != 0 && h->pair.blocks != nullptr && h->block_format == kBlocksPlanes && h->totals.total > 0;
     bool capped = false;
     const int uncapped_depth = depth;
     if (try_sparse && automatic && depth > kDirectDepthBesideSparse) {
@@ -644,7 +647,7 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     }
     // (run blocks behind a sparse table -- built at load time, build_sparse_for_runs: the lean format keeps its flat direct table at depth 13,
     // 1 GB instead of 17, for the queries the sparse table does not serve)
-    if (h->block_format == kBlocksRuns && h->d_sparse && automatic && depth > kDirectDepthBesideSparse) depth = kDirectDepthBesideSparse;
+    if (h->block_format == kBlocksRuns && h->sparse.lines && automatic && depth > kDirectDepthBesideSparse) depth = kDirectDepthBesideSparse;
     if (depth <= 0 && !try_sparse) return MSBWT_OK;
     if (depth + 2 > 18) pack = false;
     auto build_flat = [&](int d) -> int {
@@ -658,9 +661,9 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
             if (e == hipErrorNotSupported) return MSBWT_OK;  // kernel set without a table
             return hip_fail(h, e, "build suffix table");
         }
-        h->d_table = tab;
-        h->table_depth = d;
-        h->table_bytes = bytes;
+        t.entries = tab;
+        t.depth = d;
+        t.bytes = bytes;
         return rebuild_filter(h);  // from the flat table, before it may be packed away
     };
     int rc = depth > 0 ? build_flat(depth) : MSBWT_OK;
@@ -668,13 +671,13 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     if (try_sparse) {
         uint64_t allowance = kNoBudget;
         if (h->planned) {  // what the budget leaves once blocks, pair blocks and the direct table are paid for
-            const uint64_t direct = (pack && h->d_table) ? packed_table_bytes(depth + 2) : uint64_t(h->table_bytes);
-            const uint64_t held = h->nblocks * kBlockBytes + h->pair_bytes + direct;
+            const uint64_t direct = (pack && t.entries) ? packed_table_bytes(depth + 2) : uint64_t(t.bytes);
+            const uint64_t held = h->nblocks * kBlockBytes + h->pair.bytes + direct;
             allowance = h->memory_budget > held ? h->memory_budget - held : 0;
         }
-        rc = build_sparse(h, (pack && h->d_table) ? packed_table_bytes(depth + 2) : 0, allowance, h->d_table ? depth + (pack ? 2 : 0) : 0, (capped && pack) ? uncapped_depth : 0);
+        rc = build_sparse(h, (pack && t.entries) ? packed_table_bytes(depth + 2) : 0, allowance, t.entries ? depth + (pack ? 2 : 0) : 0, (capped && pack) ? uncapped_depth : 0);
         if (rc) return rc;
-        if (!h->d_sparse && capped) {  // no depth fit: the direct table as if there were no sparse one (the distinct counts stay on record)
+        if (!h->sparse.lines && capped) {  // no depth fit: the direct table as if there were no sparse one (the distinct counts stay on record)
             const SparseBuildReport counted = h->sparse_report;
             const int again = rebuild_table(h, false);
             h->sparse_report = counted;
@@ -688,30 +691,24 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
     // (the plan has sized the table), and not where it would take the eighth of the device left to the caller's batches (deep_direct_fits);
     // there build_sparse has tried a second, shallower sparse level instead.  Nor where a two-tier table would then be no deeper than the
     // direct table its filter sends queries to (sparse_tier_fits_direct: a declared k = 16 or 17).
-    if (capped && h->d_sparse && !h->d_sparse2 && h->d_table && pack && (!h->sparse_tier || sparse_tier_fits_direct(h->sparse_depth, uncapped_depth + 2)) &&
+    if (capped && h->sparse.lines && !h->sparse2.lines && t.entries && pack && (!h->sparse.tier || sparse_tier_fits_direct(h->sparse.depth, uncapped_depth + 2)) &&
         deep_direct_fits(h, uncapped_depth)) {
-        if (h->d_filter) (void)hipFree(h->d_filter);
-        h->d_filter = nullptr;
-        h->filter_depth = 0;
-        (void)hipFree(h->d_table);
-        h->d_table = nullptr;
-        h->table_depth = 0;
-        h->table_bytes = 0;
+        t.release();
         depth = uncapped_depth;
         rc = build_flat(depth);
         if (rc) return rc;
     }
-    if (!h->d_table || !pack) return rc;
+    if (!t.entries || !pack) return rc;
     // Packed form, two levels deeper (kernels.hpp, launch_pack_table): every level removes a line fetch
     // per query, and the first step after a shallow table is the expensive one (wide ranges straddle
     // blocks).  Needs the pair index.
     const uint64_t pbytes = packed_table_bytes(depth + 2);
     void *packed = nullptr;
-    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_flags) + kPackScratchOffset);  // [0] escape lines, [1] side cursor
+    unsigned long long *d_cnt = pack_scratch(h);  // [0] escape lines, [1] side cursor
     unsigned long long escapes = 0;
     hipError_t e = hipMalloc(&packed, pbytes);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 16, h->stream);
-    if (e == hipSuccess) e = launch_pack_table(view_of(h), depth, h->d_table, packed, d_cnt, nullptr, nullptr, h->stream);
+    if (e == hipSuccess) e = launch_pack_table(view_of(h), depth, t.entries, packed, d_cnt, nullptr, nullptr, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&escapes, d_cnt, sizeof escapes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     // Escape lines (some delta beyond 16 bits: the suffixes of high-copy repeats) get their ranges as flat entries in a side
@@ -723,7 +720,7 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
             (void)hipGetLastError();
             side = nullptr;
         } else {
-            e = launch_pack_table(view_of(h), depth, h->d_table, packed, nullptr, side, d_cnt + 1, h->stream);
+            e = launch_pack_table(view_of(h), depth, t.entries, packed, nullptr, side, d_cnt + 1, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
     }
@@ -736,32 +733,26 @@ int rebuild_table(msbwt_rle *h, bool allow_sparse = true) {
         // deeper parent that was only meant to be packed away
         const int own = auto_flat_table_depth(h->totals.total, h->nblocks * kBlockBytes);
         if (own < depth) {
-            if (h->d_filter) (void)hipFree(h->d_filter);
-            h->d_filter = nullptr;
-            h->filter_depth = 0;
-            (void)hipFree(h->d_table);
-            h->d_table = nullptr;
-            h->table_depth = 0;
-            h->table_bytes = 0;
+            t.release();
             return own > 0 ? build_flat(own) : MSBWT_OK;
         }
         return MSBWT_OK;
     }
-    (void)hipFree(h->d_table);
-    h->d_table = packed;
-    h->table_depth = depth + 2;
-    h->table_packed = true;
-    h->table_bytes = pbytes;
-    h->d_table_side = side;
-    h->table_side_bytes = side ? uint64_t(escapes) * 512 : 0;
-    h->table_lines = pbytes / 128;
-    h->table_escape_lines = escapes;
-    if (h->d_sparse2 && h->sparse2_tier && !h->sparse_tier && escapes > 0 && !side) release_sparse2(h);  // (only the second level is two-tier: it alone goes)
-    if (h->d_sparse && (h->sparse_tier || h->sparse2_tier) && escapes > 0 && !side) {
+    (void)hipFree(t.entries);
+    t.entries = packed;
+    t.depth = depth + 2;
+    t.packed = true;
+    t.bytes = pbytes;
+    t.side = side;
+    t.side_bytes = side ? uint64_t(escapes) * 512 : 0;
+    t.lines = pbytes / 128;
+    t.escape_lines = escapes;
+    if (h->sparse2.lines && h->sparse2.tier && !h->sparse.tier && escapes > 0 && !side) h->sparse2.release();  // (only the second level is two-tier: it alone goes)
+    if (h->sparse.lines && (h->sparse.tier || h->sparse2.tier) && escapes > 0 && !side) {
         // the two-tier table sends queries down this table's path, and an escape line without its side entry cannot be followed from
         // there (the query's first symbols are gone): no room for the side array -> the index as if there were no sparse table -- unless
         // that very table was asked for, which is then an error (as an explicit depth that does not fit)
-        if (h->wanted_sparse > 0 && h->wanted_tiers == 1 && h->sparse_tier) {
+        if (h->wanted_sparse > 0 && h->wanted_tiers == 1 && h->sparse.tier) {
             release_sparse(h);
             return fail(h, MSBWT_ERR_HIP, "the two-tier sparse table of the requested depth cannot be kept: no room for the direct table's side array");
         }
@@ -788,46 +779,27 @@ int build_sparse_for_runs(msbwt_rle *h) {
     // what the conversion will need beside the planes: the run blocks and their overflow blocks -- counted from the planes, as the conversion does
     const uint64_t run_bytes = run_block_count(h->totals.total) * kBlockBytes;
     uint64_t run_peak = run_bytes + run_bytes / 8;
-    {
-        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_flags) + kPackScratchOffset), nover = 0;
-        hipError_t e = launch_run_block_count(h->d_blocks, h->nblocks, h->totals.total, d_cnt, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&nover, d_cnt, sizeof nover, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) run_peak = run_bytes + uint64_t(nover) * 256;
-        else (void)hipGetLastError();
-    }
+    unsigned long long nover = 0;
+    if (count_overflow_blocks(h, h->d_blocks, h->nblocks, h->totals.total, &nover) == hipSuccess) run_peak = run_bytes + uint64_t(nover) * 256;
+    else (void)hipGetLastError();
     const int parent = std::min(kDirectDepthBesideSparse, std::max(0, auto_flat_table_depth(h->totals.total, h->nblocks * kBlockBytes)));
     const uint64_t parent_bytes = parent > 0 ? (uint64_t(1) << (2 * parent)) * 16 : 0;
     if (sz.pair_block_bytes + sz.super_bytes + sz.scratch_bytes + parent_bytes + run_peak > uint64_t(free_b) - uint64_t(free_b) / 32) {
         if (verbose) std::fprintf(stderr, "[msbwt] run blocks: no room for the temporary pair blocks of a sparse-table build -- none built\n");
         return h->wanted_sparse > 0 ? fail(h, MSBWT_ERR_HIP, "the sparse table of the requested depth cannot be built: no room for its temporary pair blocks") : MSBWT_OK;
     }
-    const int saved_pair = h->wanted_pair, saved_stride = h->wanted_pair_stride;
-    const bool saved_planned = h->planned;
+    const Settings saved = *h;
     h->wanted_pair = 1;
     h->wanted_pair_stride = 128;
     h->planned = false;
     int rc = rebuild_pair_index(h);
-    h->wanted_pair = saved_pair;
-    h->wanted_pair_stride = saved_stride;
-    h->planned = saved_planned;
+    static_cast<Settings &>(*h) = saved;
     auto drop_temps = [&]() {
-        if (h->d_table) (void)hipFree(h->d_table);
-        h->d_table = nullptr;
-        h->table_depth = 0;
-        h->table_bytes = 0;
-        h->table_packed = false;
-        if (h->d_filter) (void)hipFree(h->d_filter);
-        h->d_filter = nullptr;
-        h->filter_depth = 0;
-        if (h->d_pair_blocks) (void)hipFree(h->d_pair_blocks);
-        if (h->d_pair_super) (void)hipFree(h->d_pair_super);
-        h->d_pair_blocks = h->d_pair_super = nullptr;
-        h->pair_bytes = 0;
-        h->pair_overlap_bytes = 0;
-        h->pair_stride = 128;
+        h->table.release();
+        h->pair.release();
+        h->pair.stride = 128;
     };
-    if (rc || !h->d_pair_blocks) {
+    if (rc || !h->pair.blocks) {
         drop_temps();
         (void)hipGetLastError();
         if (h->wanted_sparse > 0) return rc ? rc : fail(h, MSBWT_ERR_HIP, "the sparse table of the requested depth cannot be built: no pair blocks");
@@ -844,10 +816,10 @@ int build_sparse_for_runs(msbwt_rle *h) {
             (void)hipGetLastError();
             tab = nullptr;
         }
-        h->d_table = tab;
-        h->table_depth = tab ? parent : 0;
-        h->table_bytes = tab ? parent_bytes : 0;
-        h->table_packed = false;
+        h->table.entries = tab;
+        h->table.depth = tab ? parent : 0;
+        h->table.bytes = tab ? parent_bytes : 0;
+        h->table.packed = false;
     }
     // what the budget leaves once the run blocks and their (flat) direct table are paid for; the conversion's peak stays free.  Run blocks
     // are the memory-LEAN format: left to itself the table (with its build scratch) may take twice what the finished blocks take and no more
@@ -908,11 +880,8 @@ double probe_typical_width(msbwt_rle *h) {
 // built on the device from them.  Default policy: build it when it fits in half of what is
 // still free in HBM after the blocks (it is a pure speed-for-memory trade).
 int rebuild_pair_index(msbwt_rle *h) {
-    if (h->d_pair_blocks) (void)hipFree(h->d_pair_blocks);
-    if (h->d_pair_super) (void)hipFree(h->d_pair_super);
-    h->d_pair_blocks = h->d_pair_super = nullptr;
-    h->pair_bytes = 0;
-    h->pair_overlap_bytes = 0;
+    PairIndex &p = h->pair;
+    p.release();
     if (h->wanted_pair == 0 || h->totals.total == 0 || h->block_format != kBlocksPlanes) return MSBWT_OK;  // built from plane blocks
     // Spacing (table_policy.hpp, choose_pair_stride): an explicit wish is taken literally; otherwise overlapping
     // blocks (stride 96, 1.33 bytes per symbol: ranges up to 32 wide from one line) when they are cheap in HBM, and
@@ -933,29 +902,26 @@ int rebuild_pair_index(msbwt_rle *h) {
         const uint64_t table_b = expected_table_bytes(h->totals.total, h->nblocks * kBlockBytes, after128, true, h->wanted_table_packed != 0);
         stride = know_free ? choose_pair_stride(bytes96, table_b, free_b, total_b, h->typical_width) : 128;
         by_data = stride == 96 && bytes96 > uint64_t(free_b) / 4;
-        if (by_data) h->pair_overlap_bytes = wide.pair_block_bytes + wide.super_bytes - bytes128;
+        if (by_data) p.overlap_bytes = wide.pair_block_bytes + wide.super_bytes - bytes128;
     }
     const PairIndexSizes sz = pair_index_sizes(h->nblocks, stride);
     if (h->wanted_pair < 0 && !by_data) {  // (the data-driven choice has checked its own fit)
         if (!know_free || sz.pair_block_bytes + sz.scratch_bytes > free_b / 2) return MSBWT_OK;
     }
     void *scratch = nullptr;
-    hipError_t e = hipMalloc(&h->d_pair_blocks, sz.pair_block_bytes);
-    if (e == hipSuccess) e = hipMalloc(&h->d_pair_super, sz.super_bytes);
+    hipError_t e = hipMalloc(&p.blocks, sz.pair_block_bytes);
+    if (e == hipSuccess) e = hipMalloc(&p.super, sz.super_bytes);
     if (e == hipSuccess) e = hipMalloc(&scratch, sz.scratch_bytes);
-    if (e == hipSuccess) e = build_pair_index(h->d_blocks, h->nblocks, h->totals.start_index, h->d_pair_blocks, h->d_pair_super, scratch, h->stream, stride);
+    if (e == hipSuccess) e = build_pair_index(h->d_blocks, h->nblocks, h->totals.start_index, p.blocks, p.super, scratch, h->stream, stride);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (scratch) (void)hipFree(scratch);
     if (e != hipSuccess) {
-        if (h->d_pair_blocks) (void)hipFree(h->d_pair_blocks);
-        if (h->d_pair_super) (void)hipFree(h->d_pair_super);
-        h->d_pair_blocks = h->d_pair_super = nullptr;
-        h->pair_overlap_bytes = 0;
+        p.release();
         if (h->wanted_pair < 0 && e == hipErrorOutOfMemory) return MSBWT_OK;  // optional structure
         return hip_fail(h, e, "build pair index");
     }
-    h->pair_stride = stride;
-    h->pair_bytes = sz.pair_block_bytes + sz.super_bytes;
+    p.stride = stride;
+    p.bytes = sz.pair_block_bytes + sz.super_bytes;
     return MSBWT_OK;
 }
 
@@ -992,9 +958,8 @@ int build_on_device(msbwt_rle *h, const uint8_t *rle, size_t n, Totals *t_out, b
     struct Temps {
         void *rle = nullptr, *scratch = nullptr, *longs = nullptr;
         ~Temps() {
-            if (rle) (void)hipFree(rle);
-            if (scratch) (void)hipFree(scratch);
-            if (longs) (void)hipFree(longs);
+            for (void *p : {rle, scratch, longs})
+                if (p) (void)hipFree(p);
         }
     } tmp;
     HIP_TRY(h, hipMalloc(&tmp.rle, n + 32));
@@ -1080,17 +1045,14 @@ int build_run_index(msbwt_rle *h, const uint8_t *rle, size_t n, Totals *t_out) {
         void *planes = h->d_blocks;
         h->d_blocks = nullptr;
         const uint64_t nplanes = plane_block_count(t_out->total), nruns = run_block_count(t_out->total);
-        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_flags) + kPackScratchOffset);
         unsigned long long nover = 0;
-        hipError_t e = launch_run_block_count(planes, nplanes, t_out->total, d_cnt, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&nover, d_cnt, sizeof nover, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        hipError_t e = count_overflow_blocks(h, planes, nplanes, t_out->total, &nover);
         if (e == hipSuccess) e = hipMalloc(&h->d_blocks, size_t(nruns) * kBlockBytes);
         if (e == hipSuccess && nover) {
             h->overflow_bytes = uint64_t(nover) * 256;
             e = hipMalloc(&h->d_overflow, h->overflow_bytes);
         }
-        if (e == hipSuccess) e = launch_run_block_write(planes, nplanes, t_out->total, d_cnt, h->d_blocks, h->d_overflow, h->stream);
+        if (e == hipSuccess) e = launch_run_block_write(planes, nplanes, t_out->total, pack_scratch(h), h->d_blocks, h->d_overflow, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         (void)hipFree(planes);
         if (e == hipSuccess) return MSBWT_OK;
@@ -1153,21 +1115,21 @@ int install(msbwt_rle *h, const uint8_t *rle, size_t n) {
     h->typical_width = probe_typical_width(h);
     make_plan(h);
     rc = rebuild_pair_index(h);  // first: the table may be packed with its help
-    if (!rc) stage(h->pair_stride == 96 ? "pair blocks, stride 96" : "pair blocks, stride 128", h->pair_bytes);
+    if (!rc) stage(h->pair.stride == 96 ? "pair blocks, stride 96" : "pair blocks, stride 128", h->pair.bytes);
     if (!rc) rc = rebuild_table(h);
-    if (!rc) stage(h->table_packed ? "suffix table, packed" : "suffix table, flat", h->table_bytes);
-    if (!rc && h->d_sparse) stage("sparse suffix table", h->sparse_bytes + h->sparse_side_bytes);
+    if (!rc) stage(h->table.packed ? "suffix table, packed" : "suffix table, flat", h->table.bytes);
+    if (!rc && h->sparse.lines) stage("sparse suffix table", h->sparse.bytes + h->sparse.side_bytes);
     if (rc) {
         release_index(h);
         return rc;
     }
     if (verbose)
         std::fprintf(stderr, "[msbwt] load: %llu symbols, table depth %d, a present %u-mer occurs %.0f times (median), %.2f GB of HBM in all\n",
-                     (unsigned long long)t.total, h->table_depth, kProbeSteps, h->typical_width,
-                     double(h->nblocks * kBlockBytes + h->overflow_bytes + h->pair_bytes + h->table_bytes + h->sparse_bytes + h->sparse_side_bytes) / 1e9);
+                     (unsigned long long)t.total, h->table.depth, kProbeSteps, h->typical_width,
+                     double(h->nblocks * kBlockBytes + h->overflow_bytes + h->pair.bytes + h->table.bytes + h->sparse.bytes + h->sparse.side_bytes) / 1e9);
     if (verbose)  // where the arrays landed (run-to-run differences of up to 15 % on one box follow the process, not the clocks: profiles/r04_lab)
-        std::fprintf(stderr, "[msbwt] load: blocks %p pair blocks %p pair super %p table %p side %p filter %p\n", h->d_blocks, h->d_pair_blocks,
-                     static_cast<void *>(h->d_pair_super), h->d_table, h->d_table_side, static_cast<void *>(h->d_filter));
+        std::fprintf(stderr, "[msbwt] load: blocks %p pair blocks %p pair super %p table %p side %p filter %p\n", h->d_blocks, h->pair.blocks,
+                     h->pair.super, h->table.entries, h->table.side, static_cast<void *>(h->table.filter));
     h->err.clear();
     return MSBWT_OK;
 }
@@ -1195,6 +1157,13 @@ int flags_to_code(msbwt_rle *h, uint32_t flags) {
     if (flags & kFlagInvalidRange) return fail(h, MSBWT_ERR_INVALID_RANGE, "a range has l > h or h > total size");
     if (flags & kFlagNarrowOverflow) return fail(h, MSBWT_ERR_OVERFLOW, "a count does not fit the wire width of the all-gather: repeat it with 64 bits");
     return MSBWT_OK;
+}
+
+// read_flags, then what the word says
+int status_of(msbwt_rle *h, hipStream_t stream, int which) {
+    uint32_t flags = 0;
+    const int rc = read_flags(h, stream, which, &flags);
+    return rc ? rc : flags_to_code(h, flags);
 }
 
 // Folds the recorded start/stop pairs into the running sum.  wait = true (msbwt_rle_kernel_time_ms): waits for the kernels
@@ -1253,6 +1222,12 @@ int timed_launch(msbwt_rle *h, hipStream_t stream, Launch &&launch) {
     return MSBWT_OK;
 }
 
+// timed_launch of `launch(view)` with ticket counters (with_tickets)
+template <class Launch>
+int timed_with_tickets(msbwt_rle *h, hipStream_t stream, Launch &&launch) {
+    return timed_launch(h, stream, [&] { return with_tickets(h, stream, launch); });
+}
+
 // Batch order (order.hip): is this launch to be put through the ordering passes?  Mode 1: whenever they apply (lanes kernel
 // on a pair index, 12 <= k <= 64, 4096 <= n < 2^32).  Automatic (-1, the default) is NEVER, on the measurements of round 4
 // (profiles/r04_lab/library_batch_order.log, one box, pass off / on): 10^8 read-derived 31-mers over the C4 index 16.8 ->
@@ -1287,23 +1262,29 @@ uint32_t order_reach(const IndexView &v, size_t k) {  // the symbols the bucket 
     return uint32_t(std::min<size_t>(depth, k));
 }
 
+// The batch through the ordering passes (order.hip) when they pay and have scratch: rows (d_kmers, then the exceptions pass) or 2-bit
+// words (d_packed).  false = not ordered, nothing enqueued.
+bool launch_ordered(msbwt_rle *h, const IndexView &v, msbwt_rle::TicketSlot &slot, const uint8_t *d_kmers, const uint64_t *d_packed, size_t k, size_t n,
+                    uint64_t *d_out, hipStream_t stream, int which, hipError_t *e) {
+    if (!order_pays(h, v, k, n)) return false;
+    const OrderPlan plan = plan_order(n, uint32_t(k), order_reach(v, k), uint32_t(h->order_bits), d_kmers != nullptr);
+    if (!ensure_order_scratch(slot, plan.scratch_bytes)) return false;
+    const uint64_t *ordered = nullptr;
+    bool inline_place = false;
+    uint64_t *counts = nullptr;
+    *e = launch_order_batch(plan, d_kmers, d_packed, slot.order_scratch, stream, &ordered, &inline_place, &counts);
+    if (*e == hipSuccess) *e = launch_count_packed(v, ordered, uint32_t(k), n, counts, nullptr, h->d_flags + which, stream, plan.words + 1, inline_place);
+    if (*e == hipSuccess) *e = launch_order_finish(plan, slot.order_scratch, d_out, stream);
+    if (*e == hipSuccess && d_kmers) *e = launch_count_exceptions(plan, v.blocks, v.total, d_kmers, slot.order_scratch, d_out, h->d_flags + which, stream);
+    return true;
+}
+
 int launch_count(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
     if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
     return timed_launch(h, stream, [&] {
         return with_slot(h, stream, [&](const IndexView &v, msbwt_rle::TicketSlot &slot) {
-            if (order_pays(h, v, k, n)) {
-                const OrderPlan plan = plan_order(n, uint32_t(k), order_reach(v, k), uint32_t(h->order_bits), true);
-                if (ensure_order_scratch(slot, plan.scratch_bytes)) {
-                    const uint64_t *ordered = nullptr;
-                    bool inline_place = false;
-                    uint64_t *counts = nullptr;
-                    hipError_t e = launch_order_batch(plan, d_kmers, nullptr, slot.order_scratch, stream, &ordered, &inline_place, &counts);
-                    if (e == hipSuccess) e = launch_count_packed(v, ordered, uint32_t(k), n, counts, nullptr, h->d_flags + which, stream, plan.words + 1, inline_place);
-                    if (e == hipSuccess) e = launch_order_finish(plan, slot.order_scratch, d_out, stream);
-                    if (e == hipSuccess) e = launch_count_exceptions(plan, v.blocks, v.total, d_kmers, slot.order_scratch, d_out, h->d_flags + which, stream);
-                    return e;
-                }
-            }
+            hipError_t e = hipSuccess;
+            if (launch_ordered(h, v, slot, d_kmers, nullptr, k, n, d_out, stream, which, &e)) return e;
             return launch_count_kmers(v, d_kmers, uint32_t(k), n, d_out, h->d_flags + which, stream);
         });
     });
@@ -1323,18 +1304,8 @@ int launch_count_2bit(msbwt_rle *h, const uint64_t *d_packed, size_t k, size_t n
                 if (e == hipSuccess) e = launch_count_kmers(v, rows, uint32_t(k), n, d_out, h->d_flags + which, stream);
                 return e;
             }
-            if (order_pays(h, v, k, n)) {
-                const OrderPlan plan = plan_order(n, uint32_t(k), order_reach(v, k), uint32_t(h->order_bits), false);
-                if (ensure_order_scratch(slot, plan.scratch_bytes)) {
-                    const uint64_t *ordered = nullptr;
-                    bool inline_place = false;
-                    uint64_t *counts = nullptr;
-                    hipError_t e = launch_order_batch(plan, nullptr, d_packed, slot.order_scratch, stream, &ordered, &inline_place, &counts);
-                    if (e == hipSuccess) e = launch_count_packed(v, ordered, uint32_t(k), n, counts, nullptr, h->d_flags + which, stream, plan.words + 1, inline_place);
-                    if (e == hipSuccess) e = launch_order_finish(plan, slot.order_scratch, d_out, stream);
-                    return e;
-                }
-            }
+            hipError_t e = hipSuccess;
+            if (launch_ordered(h, v, slot, nullptr, d_packed, k, n, d_out, stream, which, &e)) return e;
             return launch_count_packed(v, d_packed, uint32_t(k), n, d_out, nullptr, h->d_flags + which, stream);
         });
     });
@@ -1345,10 +1316,8 @@ int launch_count_2bit(msbwt_rle *h, const uint64_t *d_packed, size_t k, size_t n
 int launch_ranges(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_l, uint64_t *d_h, uint32_t stride, hipStream_t stream,
                   int which) {
     if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
-    return timed_launch(h, stream, [&] {
-        return with_tickets(h, stream, [&](const IndexView &v) {
-            return launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_l, d_h, stride, h->d_flags + which, stream);
-        });
+    return timed_with_tickets(h, stream, [&](const IndexView &v) {
+        return launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_l, d_h, stride, h->d_flags + which, stream);
     });
 }
 
@@ -1356,13 +1325,94 @@ int launch_ranges(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint
 // first 16 bytes of its own 48-byte output row, and extend.hip turns the row into the six counts in place.
 int launch_extensions(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
     if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
-    return timed_launch(h, stream, [&] {
-        return with_tickets(h, stream, [&](const IndexView &v) {
-            hipError_t e = launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_out, d_out + 1, 6u, h->d_flags + which, stream);
-            if (e == hipSuccess) e = launch_kmer_extensions(v, d_out, n, h->d_flags + which, stream);
-            return e;
-        });
+    return timed_with_tickets(h, stream, [&](const IndexView &v) {
+        hipError_t e = launch_kmer_ranges(v, d_kmers, uint32_t(k), n, d_out, d_out + 1, 6u, h->d_flags + which, stream);
+        if (e == hipSuccess) e = launch_kmer_extensions(v, d_out, n, h->d_flags + which, stream);
+        return e;
     });
+}
+
+// An entry point's prologue: the handle locked for the call, its index checked (loaded), its device made current (bind; open: both).
+class Call {
+  public:
+    msbwt_rle *const h;
+    explicit Call(const msbwt_rle *ch) : h(const_cast<msbwt_rle *>(ch)) {
+        if (h) lock_ = std::unique_lock<std::mutex>(h->mu);
+    }
+    int loaded() const { return h->loaded ? MSBWT_OK : fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded"); }
+    int bind() {
+        scope_.emplace(h->device);
+        return scope_->ok() ? MSBWT_OK : fail(h, MSBWT_ERR_HIP, scope_->why());
+    }
+    // null handle, no index, then the caller's own arguments (`bad_args`: refused with `why`), then bind()
+    int open(bool bad_args = false, const char *why = nullptr) {
+        if (!h) return MSBWT_ERR_INVALID_ARG;
+        if (int rc = loaded()) return rc;
+        if (bad_args) return fail(h, MSBWT_ERR_INVALID_ARG, why);
+        return bind();
+    }
+
+  private:
+    std::unique_lock<std::mutex> lock_;
+    std::optional<DeviceScope> scope_;
+};
+
+// The setters of what a loaded index is built from: `assign()` records the wish under the lock and says whether the index must follow
+// it; if so and an index is loaded, `rebuild()` runs on the handle's device.
+template <class Assign, class Rebuild>
+int set_then_rebuild(msbwt_rle *h, Assign &&assign, Rebuild &&rebuild) {
+    Call c(h);
+    if (!assign() || !h->loaded) return MSBWT_OK;
+    if (int rc = c.bind()) return rc;
+    return rebuild();
+}
+
+// a setting that takes effect at the next launch or load: recorded under the lock
+template <class T, class V>
+int set_locked(msbwt_rle *h, T &setting, V value) {
+    std::lock_guard<std::mutex> lock(h->mu);
+    setting = value;
+    return MSBWT_OK;
+}
+
+HostArray host_in(const void *p, size_t item_bytes) { return HostArray{p, nullptr, item_bytes}; }
+HostArray host_out(void *p, size_t item_bytes) { return HostArray{nullptr, p, item_bytes}; }
+
+// A host-pointer batch through the pinned pipeline (host_pipeline.hpp): `launch` enqueues a chunk of m items; the batch's flags at the end.
+template <class Launch>
+int run_host_batch(msbwt_rle *h, size_t n, size_t chunk, const std::vector<HostArray> &ins, const std::vector<HostArray> &outs, const char *what,
+                   Launch &&launch) {
+    int launch_rc = MSBWT_OK;
+    const hipError_t e = h->pipe.run(n, chunk, ins, outs, h->stream, [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+        launch_rc = launch(m, d_in, d_out, stream);
+        return launch_rc ? hipErrorUnknown : hipSuccess;
+    });
+    if (launch_rc) return launch_rc;
+    if (e != hipSuccess) return hip_fail(h, e, (std::string(what) + " pipeline").c_str());
+    return status_of(h, h->stream, kHostFlags);
+}
+
+// A small host batch through the mailbox (ensure_mail), its queries already there.  With `poll` the host polls the word the kernel writes
+// on completion (v.done: ~5 us cheaper than a stream synchronisation; bounded: a kernel that never reports, a fault, is left to the
+// synchronisation, which says why).  copy_out() says whether a result is the error sentinel u64::MAX: only then is the status word read.
+template <class Launch, class CopyOut>
+int mailbox_call(msbwt_rle *h, IndexView &v, bool poll, Launch &&launch, CopyOut &&copy_out) {
+    volatile uint64_t *done = reinterpret_cast<volatile uint64_t *>(h->mail + kMailDone);
+    const uint64_t seq = ++h->mail_seq;
+    if (poll) {
+        v.done = reinterpret_cast<uint64_t *>(h->d_mail + kMailDone);
+        v.done_seq = seq;
+    }
+    if (int rc = launch()) return rc;
+    bool seen = false;
+    if (poll) {
+        const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
+        for (unsigned spins = 0; !(seen = *done == seq); ++spins)
+            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > give_up) break;
+    }
+    if (!seen) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::atomic_thread_fence(std::memory_order_acquire);  // the results are read after the completion word
+    return copy_out() ? status_of(h, h->stream, kHostFlags) : MSBWT_OK;
 }
 
 }  // namespace
@@ -1453,64 +1503,39 @@ uint64_t msbwt_rle_get_total_size(const msbwt_rle *h) { return h ? h->totals.tot
 
 int msbwt_rle_count_kmers_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n,
                                  void *d_out_counts, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!d_out_counts || (!d_kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return launch_count(h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts),
+    Call c(ch);
+    if (int rc = c.open(n && (!d_out_counts || (!d_kmers && k)), "null device pointer")) return rc;
+    return launch_count(c.h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts),
                         static_cast<hipStream_t>(hip_stream), kDeviceFlags);
 }
 
 int msbwt_rle_count_kmers_packed_device(const msbwt_rle *ch, const void *d_kmers2bit, size_t k, size_t n, void *d_out_counts, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!d_out_counts || !d_kmers2bit)) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!d_out_counts || !d_kmers2bit), "null device pointer")) return rc;
     if (n == 0) return MSBWT_OK;
-    return launch_count_2bit(h, static_cast<const uint64_t *>(d_kmers2bit), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
+    return launch_count_2bit(c.h, static_cast<const uint64_t *>(d_kmers2bit), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
                              kDeviceFlags);
 }
 
 int msbwt_rle_count_kmers_packed(const msbwt_rle *ch, const uint64_t *kmers2bit, size_t k, size_t n, void *out_counts, int count_bits) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (k < 1 || k > 64 || (count_bits != 64 && count_bits != 32)) return fail(h, MSBWT_ERR_INVALID_ARG, "packed queries need 1 <= k <= 64 and 64- or 32-bit counts");
-    if (n && (!out_counts || !kmers2bit)) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    const bool bad_k = k < 1 || k > 64 || (count_bits != 64 && count_bits != 32);
+    if (int rc = c.open(bad_k || (n && (!out_counts || !kmers2bit)), bad_k ? "packed queries need 1 <= k <= 64 and 64- or 32-bit counts" : "null pointer")) return rc;
     if (n == 0) return MSBWT_OK;
-    int rc = ensure_runtime(h);
-    if (rc) return rc;
+    msbwt_rle *h = c.h;
+    if (int rc = ensure_runtime(h)) return rc;
     // pipelined like msbwt_rle_count_kmers: 8 (16) bytes per query in, 8 or 4 out; the 32-bit form counts into a device
     // buffer and narrows on the kernels' stream (a count beyond 32 bits is reported, not truncated silently)
     const size_t words = k > 32 ? 2 : 1, chunk = size_t(1) << 22;
-    if (count_bits == 32 && (rc = ensure_stage(h, std::min(n, chunk) * sizeof(uint64_t))) != MSBWT_OK) return rc;
-    std::vector<HostArray> ins(1), outs(1);
-    ins[0].in = kmers2bit;
-    ins[0].item_bytes = words * sizeof(uint64_t);
-    outs[0].out = out_counts;
-    outs[0].item_bytes = size_t(count_bits / 8);
-    int launch_rc = MSBWT_OK;
-    const hipError_t e = h->pipe.run(n, chunk, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         uint64_t *d_counts = count_bits == 64 ? static_cast<uint64_t *>(d_out[0]) : static_cast<uint64_t *>(h->d_stage);
-                                         launch_rc = launch_count_2bit(h, static_cast<const uint64_t *>(d_in[0]), k, m, d_counts, stream, kHostFlags);
-                                         if (launch_rc) return hipErrorUnknown;
-                                         return count_bits == 64 ? hipSuccess : launch_narrow_counts32(d_counts, static_cast<uint32_t *>(d_out[0]), m, h->d_flags + kHostFlags, stream);
-                                     });
-    if (launch_rc) return launch_rc;
-    if (e != hipSuccess) return hip_fail(h, e, "count_kmers_packed pipeline");
-    uint32_t flags = 0;
-    rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    if (int rc = count_bits == 32 ? ensure_stage(h, std::min(n, chunk) * sizeof(uint64_t)) : MSBWT_OK) return rc;
+    return run_host_batch(h, n, chunk, {host_in(kmers2bit, words * sizeof(uint64_t))}, {host_out(out_counts, size_t(count_bits / 8))}, "count_kmers_packed",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              uint64_t *d_counts = count_bits == 64 ? static_cast<uint64_t *>(d_out[0]) : static_cast<uint64_t *>(h->d_stage);
+                              if (int r = launch_count_2bit(h, static_cast<const uint64_t *>(d_in[0]), k, m, d_counts, stream, kHostFlags)) return r;
+                              if (count_bits == 64) return int(MSBWT_OK);
+                              const hipError_t e = launch_narrow_counts32(d_counts, static_cast<uint32_t *>(d_out[0]), m, h->d_flags + kHostFlags, stream);
+                              return e == hipSuccess ? int(MSBWT_OK) : hip_fail(h, e, "count_kmers_packed pipeline");
+                          });
 }
 
 int msbwt_kmers_pack_2bit(const uint8_t *kmers, size_t k, size_t n, uint64_t *out_words) {
@@ -1530,29 +1555,22 @@ int msbwt_kmers_pack_2bit(const uint8_t *kmers, size_t k, size_t n, uint64_t *ou
 
 int msbwt_rle_set_batch_order(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_order = mode;
-    return MSBWT_OK;
+    return set_locked(h, h->wanted_order, mode);
 }
 
 int msbwt_rle_get_batch_order(const msbwt_rle *h) { return h ? h->wanted_order : 0; }
 
 int msbwt_rle_batch_order_for(const msbwt_rle *ch, size_t k, size_t n) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h || !h->loaded) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    return order_pays(h, view_of(h), k, n) ? 1 : 0;
+    if (!ch || !ch->loaded) return MSBWT_ERR_INVALID_ARG;
+    Call c(ch);
+    return order_pays(c.h, view_of(c.h), k, n) ? 1 : 0;
 }
 
 int msbwt_rle_constrain_ranges_device(const msbwt_rle *ch, const void *d_syms, const void *d_l, const void *d_h,
                                       size_t n, void *d_out_l, void *d_out_h, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!d_syms || !d_l || !d_h || !d_out_l || !d_out_h)) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!d_syms || !d_l || !d_h || !d_out_l || !d_out_h), "null device pointer")) return rc;
+    msbwt_rle *h = c.h;
     HIP_TRY(h, launch_constrain_ranges(view_of(h), static_cast<const uint8_t *>(d_syms),
                                        static_cast<const uint64_t *>(d_l), static_cast<const uint64_t *>(d_h), n,
                                        static_cast<uint64_t *>(d_out_l), static_cast<uint64_t *>(d_out_h),
@@ -1564,66 +1582,48 @@ int msbwt_rle_constrain_ranges_device(const msbwt_rle *ch, const void *d_syms, c
 // handle's device current.
 static int launch_read_kmers_locked(msbwt_rle *h, const void *d_reads, size_t read_len, size_t n_reads, size_t k,
                                     int ascii, void *d_out_fwd, void *d_out_rc, hipStream_t stream, int which) {
-    return timed_launch(h, stream, [&] {
-        return with_tickets(h, stream, [&](const IndexView &v) {
-            return launch_count_read_kmers(v, static_cast<const uint8_t *>(d_reads), uint32_t(read_len), n_reads, uint32_t(k), ascii != 0,
-                                           static_cast<uint64_t *>(d_out_fwd), static_cast<uint64_t *>(d_out_rc), h->d_flags + which, stream);
-        });
+    return timed_with_tickets(h, stream, [&](const IndexView &v) {
+        return launch_count_read_kmers(v, static_cast<const uint8_t *>(d_reads), uint32_t(read_len), n_reads, uint32_t(k), ascii != 0,
+                                       static_cast<uint64_t *>(d_out_fwd), static_cast<uint64_t *>(d_out_rc), h->d_flags + which, stream);
     });
 }
 
 int msbwt_rle_count_read_kmers_device(const msbwt_rle *ch, const void *d_reads, size_t read_len, size_t n_reads,
                                       size_t k, int ascii, void *d_out_fwd, void *d_out_rc, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (k < 1 || k > 64 || k > read_len || read_len > 0xFFFFFFFFull || (!d_out_fwd && !d_out_rc) || (n_reads && !d_reads))
-        return fail(h, MSBWT_ERR_INVALID_ARG, "count_read_kmers needs 1 <= k <= min(64, read_len) and an output");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return launch_read_kmers_locked(h, d_reads, read_len, n_reads, k, ascii, d_out_fwd, d_out_rc,
+    Call c(ch);
+    const bool bad = k < 1 || k > 64 || k > read_len || read_len > 0xFFFFFFFFull || (!d_out_fwd && !d_out_rc) || (n_reads && !d_reads);
+    if (int rc = c.open(bad, "count_read_kmers needs 1 <= k <= min(64, read_len) and an output")) return rc;
+    return launch_read_kmers_locked(c.h, d_reads, read_len, n_reads, k, ascii, d_out_fwd, d_out_rc,
                                     static_cast<hipStream_t>(hip_stream), kDeviceFlags);
 }
 
 int msbwt_rle_count_read_kmers(const msbwt_rle *ch, const uint8_t *reads, size_t read_len, size_t n_reads, size_t k,
                                int ascii, uint64_t *out_fwd, uint64_t *out_rc) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);  // (the lock is held throughout: the staging buffer is per handle)
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);  // held throughout: the staging buffer is per handle
     if (k < 1 || k > 64 || k > read_len || read_len > 0xFFFFFFFFull || (!out_fwd && !out_rc) || (n_reads && !reads))
         return fail(h, MSBWT_ERR_INVALID_ARG, "count_read_kmers needs 1 <= k <= min(64, read_len) and an output");
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (int rc = c.loaded()) return rc;
+    if (int rc = c.bind()) return rc;
     const size_t windows = read_len - k + 1;
     // pipelined: chunks of reads holding ~2 Mi windows travel host -> pinned -> HBM -> pinned -> host
     const size_t chunk = std::max<size_t>(1, (size_t(1) << 21) / windows);
-    std::vector<HostArray> ins(1), outs;
-    ins[0].in = reads;
-    ins[0].item_bytes = read_len;
-    if (out_fwd) { HostArray a; a.out = out_fwd; a.item_bytes = windows * sizeof(uint64_t); outs.push_back(a); }
-    if (out_rc) { HostArray a; a.out = out_rc; a.item_bytes = windows * sizeof(uint64_t); outs.push_back(a); }
-    int launch_rc = MSBWT_OK;
-    const hipError_t e = h->pipe.run(n_reads, chunk, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         void *d_f = out_fwd ? d_out[0] : nullptr, *d_c = out_rc ? d_out[out_fwd ? 1 : 0] : nullptr;
-                                         launch_rc = launch_read_kmers_locked(h, d_in[0], read_len, m, k, ascii, d_f, d_c, stream, kHostFlags);
-                                         return launch_rc ? hipErrorUnknown : hipSuccess;
-                                     });
-    if (launch_rc) return launch_rc;
-    if (e != hipSuccess) return hip_fail(h, e, "count_read_kmers pipeline");
-    uint32_t flags = 0;
-    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    std::vector<HostArray> outs;
+    if (out_fwd) outs.push_back(host_out(out_fwd, windows * sizeof(uint64_t)));
+    if (out_rc) outs.push_back(host_out(out_rc, windows * sizeof(uint64_t)));
+    return run_host_batch(h, n_reads, chunk, {host_in(reads, read_len)}, outs, "count_read_kmers", [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+        void *d_f = out_fwd ? d_out[0] : nullptr, *d_c = out_rc ? d_out[out_fwd ? 1 : 0] : nullptr;
+        return launch_read_kmers_locked(h, d_in[0], read_len, m, k, ascii, d_f, d_c, stream, kHostFlags);
+    });
 }
 
 int msbwt_rle_count_ragged_read_kmers(const msbwt_rle *ch, const uint8_t *reads, const uint64_t *read_offsets,
                                       size_t n_reads, size_t k, int ascii, uint64_t *out_fwd, uint64_t *out_rc,
                                       uint64_t *out_windows) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
     if (k < 1 || k > 64 || (n_reads && (!read_offsets || !reads)))
         return fail(h, MSBWT_ERR_INVALID_ARG, "count_ragged_read_kmers needs 1 <= k <= 64 and offsets");
     // window prefix: read r owns [win[r], win[r+1])
@@ -1636,10 +1636,9 @@ int msbwt_rle_count_ragged_read_kmers(const msbwt_rle *ch, const uint8_t *reads,
     const uint64_t total_windows = win[n_reads];
     if (out_windows) *out_windows = total_windows;
     if (!out_fwd && !out_rc) return MSBWT_OK;
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
+    if (int rc = c.loaded()) return rc;
     if (total_windows == 0) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (int rc = c.bind()) return rc;
     // batches of whole reads holding at most ~4 Mi windows (at least one read)
     uint32_t all_flags = 0;
     for (size_t r0 = 0; r0 < n_reads;) {
@@ -1663,11 +1662,9 @@ int msbwt_rle_count_ragged_read_kmers(const msbwt_rle *ch, const uint8_t *reads,
             HIP_TRY(h, hipMemcpyAsync(d_r, reads + read_offsets[r0], nbytes, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(d_roff, roff.data(), off_bytes, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(d_woff, woff.data(), off_bytes, hipMemcpyHostToDevice, h->stream));
-            rc = timed_launch(h, h->stream, [&] {
-                return with_tickets(h, h->stream, [&](const IndexView &v) {
-                    return launch_count_ragged_read_kmers(v, d_r, d_roff, d_woff, m, nwin, uint32_t(k), ascii != 0, out_fwd ? d_f : nullptr,
-                                                          out_rc ? d_c : nullptr, h->d_flags, h->stream);
-                });
+            rc = timed_with_tickets(h, h->stream, [&](const IndexView &v) {
+                return launch_count_ragged_read_kmers(v, d_r, d_roff, d_woff, m, nwin, uint32_t(k), ascii != 0, out_fwd ? d_f : nullptr,
+                                                      out_rc ? d_c : nullptr, h->d_flags, h->stream);
             });
             if (rc) return rc;
             if (out_fwd) HIP_TRY(h, hipMemcpyAsync(out_fwd + win[r0], d_f, nwin * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1683,156 +1680,90 @@ int msbwt_rle_count_ragged_read_kmers(const msbwt_rle *ch, const uint8_t *reads,
 }
 
 int msbwt_rle_device_status(const msbwt_rle *ch, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
     if (!h->d_flags) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    uint32_t flags = 0;
-    int rc = read_flags(h, static_cast<hipStream_t>(hip_stream), kDeviceFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    if (int rc = c.bind()) return rc;
+    return status_of(h, static_cast<hipStream_t>(hip_stream), kDeviceFlags);
 }
 
 int msbwt_rle_count_kmers(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_counts) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!out_counts || (!kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!out_counts || (!kmers && k)), "null pointer")) return rc;
     if (n == 0) return MSBWT_OK;
+    msbwt_rle *h = c.h;
     if (n <= kMailQueries && n * k <= kMailKmerBytes) {
         // the trait's single-query shape (msbwt_core.rs:124: one k-mer per call) and other tiny batches: through the
         // mailbox.  Every error ends its query with u64::MAX -- no real count is that large -- so the status word is
         // only read back when one shows up.
-        int rc = ensure_runtime(h);
-        if (!rc) rc = ensure_mail(h);
-        if (rc) return rc;
-        uint64_t *counts = reinterpret_cast<uint64_t *>(h->mail + kMailCounts);
+        if (int rc = ensure_mail(h)) return rc;
+        const uint64_t *counts = reinterpret_cast<const uint64_t *>(h->mail + kMailCounts);
         if (!tier_launch_ok(h)) return hip_fail(h, hipErrorInvalidValue, "two-tier sparse table beside a direct table it cannot fall back to");
         IndexView v = view_of(h);  // no ticket counters: at most one tile
-        // The lanes kernel announces completion in the mailbox itself: poll that word (about 5 us cheaper than a stream
-        // synchronisation on this runtime); a single query even travels inside the kernel arguments.
+        // The lanes kernel announces completion in the mailbox itself; a single query even travels inside the kernel arguments.
         const bool poll = k <= 0xFFFFFFFFull && lanes_serves(v, uint32_t(k));
         const bool inlined = poll && n == 1;
         if (k && !inlined) std::memcpy(h->mail + kMailKmers, kmers, n * k);
-        volatile uint64_t *done = reinterpret_cast<volatile uint64_t *>(h->mail + kMailDone);
-        const uint64_t seq = ++h->mail_seq;
-        if (poll) {
-            v.done = reinterpret_cast<uint64_t *>(h->d_mail + kMailDone);
-            v.done_seq = seq;
-        }
-        rc = timed_launch(h, h->stream, [&] {
-            return launch_count_kmers(v, h->d_mail + kMailKmers, uint32_t(k), n, reinterpret_cast<uint64_t *>(h->d_mail + kMailCounts),
-                                      h->d_flags + kHostFlags, h->stream, inlined ? kmers : nullptr);
+        auto launch = [&] {
+            return launch_count_kmers(v, h->d_mail + kMailKmers, uint32_t(k), n, reinterpret_cast<uint64_t *>(h->d_mail + kMailCounts), h->d_flags + kHostFlags,
+                                      h->stream, inlined ? kmers : nullptr);
+        };
+        return mailbox_call(h, v, poll, [&] { return timed_launch(h, h->stream, launch); }, [&] {
+            bool flagged = false;
+            for (size_t i = 0; i < n; ++i) {
+                out_counts[i] = counts[i];
+                flagged |= counts[i] == ~0ull;
+            }
+            return flagged;
         });
-        if (rc) return rc;
-        bool seen = false;
-        if (poll) {  // bounded: a kernel that never reports (a fault) is left to the synchronisation below, which says why
-            const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-            for (unsigned spins = 0; !(seen = *done == seq); ++spins)
-                if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > give_up) break;
-        }
-        if (!seen) HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::atomic_thread_fence(std::memory_order_acquire);  // the counts are read after the completion word
-        bool flagged = false;
-        for (size_t i = 0; i < n; ++i) {
-            out_counts[i] = counts[i];
-            flagged |= counts[i] == ~0ull;
-        }
-        if (!flagged) return MSBWT_OK;
-        uint32_t flags = 0;
-        rc = read_flags(h, h->stream, kHostFlags, &flags);
-        return rc ? rc : flags_to_code(h, flags);
     }
     // pipelined: chunks of 2 Mi queries travel host -> pinned -> HBM -> pinned -> host, copies and
     // kernels overlapping on three streams (host_pipeline.hpp)
-    std::vector<HostArray> ins(1), outs(1);
-    ins[0].in = kmers;
-    ins[0].item_bytes = k;
-    outs[0].out = out_counts;
-    outs[0].item_bytes = sizeof(uint64_t);
-    int launch_rc = MSBWT_OK;
-    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         launch_rc = launch_count(h, static_cast<const uint8_t *>(d_in[0]), k, m,
-                                                                  static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
-                                         return launch_rc ? hipErrorUnknown : hipSuccess;
-                                     });
-    if (launch_rc) return launch_rc;
-    if (e != hipSuccess) return hip_fail(h, e, "count_kmers pipeline");
-    uint32_t flags = 0;
-    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    return run_host_batch(h, n, size_t(1) << 21, {host_in(kmers, k)}, {host_out(out_counts, sizeof(uint64_t))}, "count_kmers",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              return launch_count(h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
+                          });
 }
 
 int msbwt_rle_constrain_ranges(const msbwt_rle *ch, const uint8_t *syms, const uint64_t *l, const uint64_t *hh,
                                size_t n, uint64_t *out_l, uint64_t *out_h) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!syms || !l || !hh || !out_l || !out_h)) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!syms || !l || !hh || !out_l || !out_h), "null pointer")) return rc;
     if (n == 0) return MSBWT_OK;
+    msbwt_rle *h = c.h;
     if (n <= kMailQueries) {  // BWT::constrain_range, one range per call (msbwt_core.rs:99): through the mailbox, as above
-        int rc = ensure_runtime(h);
-        if (!rc) rc = ensure_mail(h);
-        if (rc) return rc;
+        if (int rc = ensure_mail(h)) return rc;
         std::memcpy(h->mail + kMailSyms, syms, n);
         std::memcpy(h->mail + kMailL, l, n * sizeof(uint64_t));
         std::memcpy(h->mail + kMailH, hh, n * sizeof(uint64_t));
         IndexView v = view_of(h);
-        volatile uint64_t *done = reinterpret_cast<volatile uint64_t *>(h->mail + kMailDone);
-        const uint64_t seq = ++h->mail_seq;
         const bool poll = n <= 8;  // one wave of 8-lane groups: the kernel announces completion in the mailbox
-        if (poll) {
-            v.done = reinterpret_cast<uint64_t *>(h->d_mail + kMailDone);
-            v.done_seq = seq;
-        }
-        HIP_TRY(h, launch_constrain_ranges(v, h->d_mail + kMailSyms, reinterpret_cast<const uint64_t *>(h->d_mail + kMailL),
-                                           reinterpret_cast<const uint64_t *>(h->d_mail + kMailH), n, reinterpret_cast<uint64_t *>(h->d_mail + kMailOutL),
-                                           reinterpret_cast<uint64_t *>(h->d_mail + kMailOutH), h->d_flags + kHostFlags, h->stream));
-        bool seen = false;
-        if (poll) {
-            const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-            for (unsigned spins = 0; !(seen = *done == seq); ++spins)
-                if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > give_up) break;
-        }
-        if (!seen) HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const uint64_t *ol = reinterpret_cast<const uint64_t *>(h->mail + kMailOutL), *oh = reinterpret_cast<const uint64_t *>(h->mail + kMailOutH);
-        bool flagged = false;
-        for (size_t i = 0; i < n; ++i) {
-            out_l[i] = ol[i];
-            out_h[i] = oh[i];
-            flagged |= ol[i] == ~0ull;  // an invalid symbol or range ends as {u64::MAX, u64::MAX}
-        }
-        if (!flagged) return MSBWT_OK;
-        uint32_t flags = 0;
-        rc = read_flags(h, h->stream, kHostFlags, &flags);
-        return rc ? rc : flags_to_code(h, flags);
+        auto launch = [&] {
+            HIP_TRY(h, launch_constrain_ranges(v, h->d_mail + kMailSyms, reinterpret_cast<const uint64_t *>(h->d_mail + kMailL),
+                                               reinterpret_cast<const uint64_t *>(h->d_mail + kMailH), n, reinterpret_cast<uint64_t *>(h->d_mail + kMailOutL),
+                                               reinterpret_cast<uint64_t *>(h->d_mail + kMailOutH), h->d_flags + kHostFlags, h->stream));
+            return int(MSBWT_OK);
+        };
+        return mailbox_call(h, v, poll, launch, [&] {
+            const uint64_t *ol = reinterpret_cast<const uint64_t *>(h->mail + kMailOutL), *oh = reinterpret_cast<const uint64_t *>(h->mail + kMailOutH);
+            bool flagged = false;
+            for (size_t i = 0; i < n; ++i) {
+                out_l[i] = ol[i];
+                out_h[i] = oh[i];
+                flagged |= ol[i] == ~0ull;  // an invalid symbol or range ends as {u64::MAX, u64::MAX}
+            }
+            return flagged;
+        });
     }
-    std::vector<HostArray> ins(3), outs(2);
-    ins[0].in = syms; ins[0].item_bytes = 1;
-    ins[1].in = l; ins[1].item_bytes = sizeof(uint64_t);
-    ins[2].in = hh; ins[2].item_bytes = sizeof(uint64_t);
-    outs[0].out = out_l; outs[0].item_bytes = sizeof(uint64_t);
-    outs[1].out = out_h; outs[1].item_bytes = sizeof(uint64_t);
-    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         return launch_constrain_ranges(view_of(h), static_cast<const uint8_t *>(d_in[0]),
-                                                                        static_cast<const uint64_t *>(d_in[1]), static_cast<const uint64_t *>(d_in[2]), m,
-                                                                        static_cast<uint64_t *>(d_out[0]), static_cast<uint64_t *>(d_out[1]),
-                                                                        h->d_flags + kHostFlags, stream);
-                                     });
-    if (e != hipSuccess) return hip_fail(h, e, "constrain_ranges pipeline");
-    uint32_t flags = 0;
-    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    return run_host_batch(h, n, size_t(1) << 21, {host_in(syms, 1), host_in(l, sizeof(uint64_t)), host_in(hh, sizeof(uint64_t))},
+                          {host_out(out_l, sizeof(uint64_t)), host_out(out_h, sizeof(uint64_t))}, "constrain_ranges",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              const hipError_t e = launch_constrain_ranges(view_of(h), static_cast<const uint8_t *>(d_in[0]), static_cast<const uint64_t *>(d_in[1]),
+                                                                           static_cast<const uint64_t *>(d_in[2]), m, static_cast<uint64_t *>(d_out[0]),
+                                                                           static_cast<uint64_t *>(d_out[1]), h->d_flags + kHostFlags, stream);
+                              return e == hipSuccess ? int(MSBWT_OK) : hip_fail(h, e, "constrain_ranges pipeline");
+                          });
 }
 
 int msbwt_rle_constrain_range(const msbwt_rle *h, uint8_t sym, uint64_t l, uint64_t hh, uint64_t *out_l,
@@ -1847,131 +1778,57 @@ int msbwt_rle_count_kmer(const msbwt_rle *h, const uint8_t *kmer, size_t k, uint
 }
 
 int msbwt_rle_kmer_ranges_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_l, void *d_out_h, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!d_out_l || !d_out_h || (!d_kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return launch_ranges(h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_l), static_cast<uint64_t *>(d_out_h), 1u,
+    Call c(ch);
+    if (int rc = c.open(n && (!d_out_l || !d_out_h || (!d_kmers && k)), "null device pointer")) return rc;
+    return launch_ranges(c.h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_l), static_cast<uint64_t *>(d_out_h), 1u,
                          static_cast<hipStream_t>(hip_stream), kDeviceFlags);
 }
 
 int msbwt_rle_count_kmer_extensions_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_counts, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!d_out_counts || (!d_kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null device pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return launch_extensions(h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
+    Call c(ch);
+    if (int rc = c.open(n && (!d_out_counts || (!d_kmers && k)), "null device pointer")) return rc;
+    return launch_extensions(c.h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
                              kDeviceFlags);
 }
 
 // host forms: pipelined like msbwt_rle_count_kmers (chunks of 2 Mi queries, host_pipeline.hpp), no mailbox
 int msbwt_rle_kmer_ranges(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_l, uint64_t *out_h) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!out_l || !out_h || (!kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!out_l || !out_h || (!kmers && k)), "null pointer")) return rc;
     if (n == 0) return MSBWT_OK;
-    std::vector<HostArray> ins(1), outs(2);
-    ins[0].in = kmers;
-    ins[0].item_bytes = k;
-    outs[0].out = out_l;
-    outs[0].item_bytes = sizeof(uint64_t);
-    outs[1].out = out_h;
-    outs[1].item_bytes = sizeof(uint64_t);
-    int launch_rc = MSBWT_OK;
-    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         launch_rc = launch_ranges(h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]),
-                                                                   static_cast<uint64_t *>(d_out[1]), 1u, stream, kHostFlags);
-                                         return launch_rc ? hipErrorUnknown : hipSuccess;
-                                     });
-    if (launch_rc) return launch_rc;
-    if (e != hipSuccess) return hip_fail(h, e, "kmer_ranges pipeline");
-    uint32_t flags = 0;
-    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    return run_host_batch(c.h, n, size_t(1) << 21, {host_in(kmers, k)}, {host_out(out_l, sizeof(uint64_t)), host_out(out_h, sizeof(uint64_t))}, "kmer_ranges",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              return launch_ranges(c.h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]),
+                                                   static_cast<uint64_t *>(d_out[1]), 1u, stream, kHostFlags);
+                          });
 }
 
 int msbwt_rle_count_kmer_extensions(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_counts) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (n && (!out_counts || (!kmers && k))) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Call c(ch);
+    if (int rc = c.open(n && (!out_counts || (!kmers && k)), "null pointer")) return rc;
     if (n == 0) return MSBWT_OK;
-    std::vector<HostArray> ins(1), outs(1);
-    ins[0].in = kmers;
-    ins[0].item_bytes = k;
-    outs[0].out = out_counts;
-    outs[0].item_bytes = 6 * sizeof(uint64_t);
-    int launch_rc = MSBWT_OK;
-    const hipError_t e = h->pipe.run(n, size_t(1) << 21, ins, outs, h->stream,
-                                     [&](size_t, size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) -> hipError_t {
-                                         launch_rc = launch_extensions(h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]),
-                                                                       stream, kHostFlags);
-                                         return launch_rc ? hipErrorUnknown : hipSuccess;
-                                     });
-    if (launch_rc) return launch_rc;
-    if (e != hipSuccess) return hip_fail(h, e, "count_kmer_extensions pipeline");
-    uint32_t flags = 0;
-    const int rc = read_flags(h, h->stream, kHostFlags, &flags);
-    return rc ? rc : flags_to_code(h, flags);
+    return run_host_batch(c.h, n, size_t(1) << 21, {host_in(kmers, k)}, {host_out(out_counts, 6 * sizeof(uint64_t))}, "count_kmer_extensions",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              return launch_extensions(c.h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
+                          });
 }
 
 // ---- several devices of one node: replicas of one index, batches sharded over them --------------
 msbwt_rle *msbwt_rle_replicate(const msbwt_rle *csrc, int device) {
-    msbwt_rle *src = const_cast<msbwt_rle *>(csrc);
-    if (!src) return nullptr;
-    std::lock_guard<std::mutex> lock(src->mu);
-    if (!src->loaded) {
-        fail(src, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-        return nullptr;
-    }
+    Call c(csrc);
+    msbwt_rle *src = c.h;
+    if (!src || c.loaded()) return nullptr;
     msbwt_rle *h = msbwt_rle_new_on_device(src->bin_power, device);
     if (!h) return nullptr;
-    h->wanted_table_depth = src->wanted_table_depth;
-    h->wanted_table_packed = src->wanted_table_packed;
-    h->wanted_table_side = src->wanted_table_side;
-    h->wanted_sparse = src->wanted_sparse;
-    h->wanted_tiers = src->wanted_tiers;
-    h->wanted_second = src->wanted_second;
-    h->query_length = src->query_length;
-    h->wanted_streaming = src->wanted_streaming;
-    h->wanted_block_format = src->wanted_block_format;
+    static_cast<Settings &>(*h) = *src;
     h->block_format = src->block_format;
-    h->wanted_pair = src->wanted_pair;
-    h->wanted_pair_stride = src->wanted_pair_stride;
-    h->pair_stride = src->pair_stride;
-    h->wanted_filter = src->wanted_filter;
-    h->search_kernel = src->search_kernel;
-    h->wanted_order = src->wanted_order;
-    h->order_bits = src->order_bits;
-    h->memory_budget = src->memory_budget;
-    h->planned = src->planned;
-    h->plan = src->plan;
-    auto give_up = [&](hipError_t e, const char *what) -> msbwt_rle * {
-        hip_fail(src, e, what);
+    auto give_up = [&](int /* code: its text is on src */) -> msbwt_rle * {
         msbwt_rle_free(h);
         return nullptr;
     };
     DeviceScope scope(h->device);
-    if (!scope.ok()) {
-        fail(src, MSBWT_ERR_HIP, scope.why());
-        msbwt_rle_free(h);
-        return nullptr;
-    }
-    if (ensure_runtime(h) != MSBWT_OK) return give_up(hipErrorUnknown, "replicate: runtime setup");
+    if (!scope.ok()) return give_up(fail(src, MSBWT_ERR_HIP, scope.why()));
+    if (ensure_runtime(h) != MSBWT_OK) return give_up(hip_fail(src, hipErrorUnknown, "replicate: runtime setup"));
     if (h->device != src->device) {  // direct GPU -> GPU copies (xGMI) when the pair allows it; staged by the runtime otherwise
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, h->device, src->device) == hipSuccess && can) {
@@ -1979,56 +1836,40 @@ msbwt_rle *msbwt_rle_replicate(const msbwt_rle *csrc, int device) {
             if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
         }
     }
-    const PairIndexSizes psz = pair_index_sizes(src->nblocks, src->pair_stride);
-    struct Piece { void *const *from; void **to; size_t bytes; };
+    // the parts by value, then every device buffer re-pointed at its copy on this device (none is this handle's before that)
+    h->pair = src->pair;
+    h->table = src->table;
+    h->sparse = src->sparse;
+    h->sparse2 = src->sparse2;
+    const PairIndexSizes psz = pair_index_sizes(src->nblocks, src->pair.stride);
+    struct Piece { const void *from; void **to; size_t bytes; };
     const Piece pieces[] = {
-        {&src->d_blocks, &h->d_blocks, size_t(src->nblocks) * kBlockBytes},
-        {&src->d_overflow, &h->d_overflow, src->d_overflow ? size_t(src->overflow_bytes) : 0},
-        {&src->d_table, &h->d_table, src->d_table ? src->table_bytes : 0},
-        {&src->d_table_side, &h->d_table_side, src->d_table_side ? size_t(src->table_side_bytes) : 0},
-        {reinterpret_cast<void *const *>(&src->d_filter), reinterpret_cast<void **>(&h->d_filter), src->d_filter ? (size_t(1) << (2 * src->filter_depth)) / 8 : 0},
-        {&src->d_pair_blocks, &h->d_pair_blocks, src->d_pair_blocks ? psz.pair_block_bytes : 0},
-        {&src->d_pair_super, &h->d_pair_super, src->d_pair_super ? psz.super_bytes : 0},
-        {&src->d_sparse, &h->d_sparse, src->d_sparse ? size_t(src->sparse_bytes) : 0},
-        {&src->d_sparse_side, &h->d_sparse_side, src->d_sparse_side ? size_t(src->sparse_side_bytes) : 0},
-        {&src->d_sparse2, &h->d_sparse2, src->d_sparse2 ? size_t(src->sparse2_bytes) : 0},
-        {&src->d_sparse2_side, &h->d_sparse2_side, src->d_sparse2_side ? size_t(src->sparse2_side_bytes) : 0},
+        {src->d_blocks, &h->d_blocks, size_t(src->nblocks) * kBlockBytes},
+        {src->d_overflow, &h->d_overflow, size_t(src->overflow_bytes)},
+        {src->table.entries, &h->table.entries, src->table.bytes},
+        {src->table.side, &h->table.side, size_t(src->table.side_bytes)},
+        {src->table.filter, reinterpret_cast<void **>(&h->table.filter), (size_t(1) << (2 * src->table.filter_depth)) / 8},
+        {src->pair.blocks, &h->pair.blocks, psz.pair_block_bytes},
+        {src->pair.super, &h->pair.super, psz.super_bytes},
+        {src->sparse.lines, &h->sparse.lines, size_t(src->sparse.bytes)},
+        {src->sparse.side, &h->sparse.side, size_t(src->sparse.side_bytes)},
+        {src->sparse2.lines, &h->sparse2.lines, size_t(src->sparse2.bytes)},
+        {src->sparse2.side, &h->sparse2.side, size_t(src->sparse2.side_bytes)},
     };
+    for (const Piece &p : pieces) *p.to = nullptr;
     for (const Piece &p : pieces) {
-        if (!p.bytes || !*p.from) continue;
+        if (!p.bytes || !p.from) continue;
         hipError_t e = hipMalloc(p.to, p.bytes);
-        if (e == hipSuccess) e = hipMemcpyPeerAsync(*p.to, h->device, *p.from, src->device, p.bytes, h->stream);
-        if (e != hipSuccess) return give_up(e, "replicate: copy index to the other device");
+        if (e == hipSuccess) e = hipMemcpyPeerAsync(*p.to, h->device, p.from, src->device, p.bytes, h->stream);
+        if (e != hipSuccess) return give_up(hip_fail(src, e, "replicate: copy index to the other device"));
     }
     const hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return give_up(e, "replicate: copy index to the other device");
+    if (e != hipSuccess) return give_up(hip_fail(src, e, "replicate: copy index to the other device"));
     h->totals = src->totals;
     h->nblocks = src->nblocks;
     h->overflow_bytes = src->overflow_bytes;
-    h->table_depth = src->table_depth;
-    h->table_packed = src->table_packed;
-    h->table_bytes = src->table_bytes;
-    h->table_side_bytes = src->table_side_bytes;
-    h->table_lines = src->table_lines;
-    h->table_escape_lines = src->table_escape_lines;
-    h->sparse_bytes = src->sparse_bytes;
-    h->sparse_side_bytes = src->sparse_side_bytes;
-    h->sparse_nbuckets = src->sparse_nbuckets;
-    h->sparse_probe = src->sparse_probe;
-    h->sparse_depth = src->sparse_depth;
-    h->sparse_tier = src->sparse_tier;
     h->sparse_report = src->sparse_report;
-    h->sparse2_bytes = src->sparse2_bytes;
-    h->sparse2_side_bytes = src->sparse2_side_bytes;
-    h->sparse2_entries = src->sparse2_entries;
-    h->sparse2_nbuckets = src->sparse2_nbuckets;
-    h->sparse2_probe = src->sparse2_probe;
-    h->sparse2_depth = src->sparse2_depth;
-    h->sparse2_tier = src->sparse2_tier;
     h->typical_width = src->typical_width;
-    h->pair_overlap_bytes = src->pair_overlap_bytes;
-    h->filter_depth = src->filter_depth;
-    h->pair_bytes = src->pair_bytes;
     h->loaded = true;
     return h;
 }
@@ -2043,6 +1884,11 @@ void shard_of(size_t n, size_t world, size_t rank, size_t *lo, size_t *hi) {
     const size_t lo_u = rank * base + std::min(rank, extra), hi_u = lo_u + base + (rank < extra ? 1 : 0);
     *lo = std::min(n, lo_u * 16);
     *hi = std::min(n, hi_u * 16);
+}
+
+// a non-empty list of handles, none of them null
+bool all_handles(const msbwt_rle *const *replicas, size_t n) {
+    return replicas && n && std::all_of(replicas, replicas + n, [](const msbwt_rle *r) { return r != nullptr; });
 }
 
 // runs work(r) for every replica on its own host thread; returns the first non-zero code
@@ -2064,10 +1910,7 @@ extern "C" {
 
 int msbwt_rle_count_kmers_multi(const msbwt_rle *const *replicas, size_t n_replicas, const uint8_t *kmers, size_t k, size_t n,
                                 uint64_t *out_counts) {
-    if (!replicas || n_replicas == 0) return MSBWT_ERR_INVALID_ARG;
-    for (size_t r = 0; r < n_replicas; ++r)
-        if (!replicas[r]) return MSBWT_ERR_INVALID_ARG;
-    if (n && (!out_counts || (!kmers && k))) return MSBWT_ERR_INVALID_ARG;
+    if (!all_handles(replicas, n_replicas) || (n && (!out_counts || (!kmers && k)))) return MSBWT_ERR_INVALID_ARG;
     // one host thread and one pinned pipeline per replica; every shard's counts land directly in the
     // caller's buffer -- the "gather" is the D2H copies themselves
     return on_every_replica(n_replicas, [&](size_t r) {
@@ -2079,9 +1922,7 @@ int msbwt_rle_count_kmers_multi(const msbwt_rle *const *replicas, size_t n_repli
 
 int msbwt_rle_count_read_kmers_multi(const msbwt_rle *const *replicas, size_t n_replicas, const uint8_t *reads, size_t read_len,
                                      size_t n_reads, size_t k, int ascii, uint64_t *out_fwd, uint64_t *out_rc) {
-    if (!replicas || n_replicas == 0 || k < 1 || k > read_len) return MSBWT_ERR_INVALID_ARG;
-    for (size_t r = 0; r < n_replicas; ++r)
-        if (!replicas[r]) return MSBWT_ERR_INVALID_ARG;
+    if (!all_handles(replicas, n_replicas) || k < 1 || k > read_len) return MSBWT_ERR_INVALID_ARG;
     const size_t windows = read_len - k + 1;
     return on_every_replica(n_replicas, [&](size_t r) {
         size_t lo, hi;
@@ -2094,10 +1935,7 @@ int msbwt_rle_count_read_kmers_multi(const msbwt_rle *const *replicas, size_t n_
 
 int msbwt_rle_count_kmers_multi_device(const msbwt_rle *const *replicas, size_t n_replicas, const void *d_kmers, size_t k, size_t n,
                                        void *d_out_counts) {
-    if (!replicas || n_replicas == 0) return MSBWT_ERR_INVALID_ARG;
-    for (size_t r = 0; r < n_replicas; ++r)
-        if (!replicas[r]) return MSBWT_ERR_INVALID_ARG;
-    if (n && (!d_out_counts || (!d_kmers && k))) return MSBWT_ERR_INVALID_ARG;
+    if (!all_handles(replicas, n_replicas) || (n && (!d_out_counts || (!d_kmers && k)))) return MSBWT_ERR_INVALID_ARG;
     const int home = replicas[0]->device;
     const uint8_t *src = static_cast<const uint8_t *>(d_kmers);
     uint64_t *dst = static_cast<uint64_t *>(d_out_counts);
@@ -2109,10 +1947,9 @@ int msbwt_rle_count_kmers_multi_device(const msbwt_rle *const *replicas, size_t 
         size_t lo, hi;
         shard_of(n, n_replicas, r, &lo, &hi);
         if (hi <= lo) return MSBWT_OK;
-        std::lock_guard<std::mutex> lock(h->mu);
-        if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-        DeviceScope scope(h->device);
-        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+        Call c(h);
+        if (int rc = c.loaded()) return rc;
+        if (int rc = c.bind()) return rc;
         const size_t m = hi - lo;
         // MSBWT_FORCE_PEER_COPIES=1: take the staging + peer-copy path even on the home device (tests on one GPU)
         static const bool force_peer = [] { const char *e = std::getenv("MSBWT_FORCE_PEER_COPIES"); return e && std::atoi(e) != 0; }();
@@ -2132,13 +1969,10 @@ int msbwt_rle_count_kmers_multi_device(const msbwt_rle *const *replicas, size_t 
     for (size_t r = 0; r < n_replicas && !first; ++r) first = enqueue(r);
     // the counts are complete when every replica's stream has drained
     for (size_t r = 0; r < n_replicas; ++r) {
-        msbwt_rle *h = const_cast<msbwt_rle *>(replicas[r]);
-        std::lock_guard<std::mutex> lock(h->mu);
-        if (!h->stream) continue;
-        DeviceScope scope(h->device);
-        uint32_t flags = 0;
-        int rc = scope.ok() ? read_flags(h, h->stream, kHostFlags, &flags) : fail(h, MSBWT_ERR_HIP, scope.why());
-        if (!rc) rc = flags_to_code(h, flags);
+        Call c(replicas[r]);
+        if (!c.h->stream) continue;
+        int rc = c.bind();
+        if (!rc) rc = status_of(c.h, c.h->stream, kHostFlags);
         if (rc && !first) first = rc;
     }
     return first;
@@ -2169,26 +2003,19 @@ int msbwt_comm_destroy(void *comm) {
 
 int msbwt_rle_allgather_counts(const msbwt_rle *ch, void *comm, const void *d_mine, size_t n_mine, void *d_all, int wire_bits,
                                void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
     if (!comm || (wire_bits != 64 && wire_bits != 32 && wire_bits != 16) || (n_mine && (!d_mine || !d_all)))
         return fail(h, MSBWT_ERR_INVALID_ARG, "allgather_counts needs a communicator, buffers and a wire width of 64, 32 or 16 bits");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    int rc = ensure_runtime(h);
+    int rc = c.bind();
+    if (!rc) rc = ensure_runtime(h);
     if (rc) return rc;
     std::string why;
     const int nranks = comm_ranks(comm, &why);
     if (nranks < 1) return fail(h, MSBWT_ERR_RCCL, why);
     const size_t need = allgather_scratch_bytes(n_mine, nranks, wire_bits);
-    if (need > h->gather_bytes) {  // (hipFree waits for the device: no gather still reads the old buffer)
-        if (h->d_gather) (void)hipFree(h->d_gather);
-        h->d_gather = nullptr;
-        h->gather_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_gather, need));
-        h->gather_bytes = need;
-    }
+    if ((rc = ensure_gather(h, need))) return rc;
     const hipError_t e = allgather_counts(comm, nranks, static_cast<const uint64_t *>(d_mine), n_mine, static_cast<uint64_t *>(d_all), wire_bits,
                                           h->d_gather, h->d_flags + kDeviceFlags, static_cast<hipStream_t>(hip_stream), &why);
     if (e == hipSuccess) return MSBWT_OK;
@@ -2200,18 +2027,14 @@ int msbwt_rle_allgather_counts(const msbwt_rle *ch, void *comm, const void *d_mi
 // ncclAllGather, placed -- on a second stream of the handle.
 int msbwt_rle_count_kmers_allgather_device(const msbwt_rle *ch, void *comm, const void *d_kmers, size_t k, size_t n_mine, void *d_mine_counts, void *d_all,
                                            int wire_bits, int out_bits, int pieces, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    if (!comm || (wire_bits != 64 && wire_bits != 32 && wire_bits != 16) || (out_bits != 64 && out_bits != wire_bits) || pieces < 1 || pieces > 64 || k < 1 ||
-        (n_mine && (!d_kmers || !d_mine_counts || !d_all)))
-        return fail(h, MSBWT_ERR_INVALID_ARG, "count_kmers_allgather needs a communicator, buffers, a wire width of 64 / 32 / 16 bits, counts left at that width or widened to 64, 1..64 pieces");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    int rc = ensure_runtime(h);
+    Call c(ch);
+    int rc = c.open(!comm || (wire_bits != 64 && wire_bits != 32 && wire_bits != 16) || (out_bits != 64 && out_bits != wire_bits) || pieces < 1 || pieces > 64 ||
+                        k < 1 || (n_mine && (!d_kmers || !d_mine_counts || !d_all)),
+                    "count_kmers_allgather needs a communicator, buffers, a wire width of 64 / 32 / 16 bits, counts left at that width or widened to 64, 1..64 pieces");
+    if (!rc) rc = ensure_runtime(c.h);
     if (rc) return rc;
     if (n_mine == 0) return MSBWT_OK;
+    msbwt_rle *h = c.h;
     std::string why;
     const int nranks = comm_ranks(comm, &why);
     if (nranks < 1) return fail(h, MSBWT_ERR_RCCL, why);
@@ -2222,13 +2045,7 @@ int msbwt_rle_count_kmers_allgather_device(const msbwt_rle *ch, void *comm, cons
         h->piece_events.push_back(e);
     }
     const size_t need = allgather_pieces_scratch_bytes(n_mine, nranks, wire_bits);
-    if (need > h->gather_bytes) {  // (hipFree waits for the device: no gather still reads the old buffer)
-        if (h->d_gather) (void)hipFree(h->d_gather);
-        h->d_gather = nullptr;
-        h->gather_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_gather, need));
-        h->gather_bytes = need;
-    }
+    if ((rc = ensure_gather(h, need))) return rc;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     // pieces of whole 16-query units (rows of any k then start 16-byte aligned: the fast kernels), the last one takes what is left
     const size_t per = allgather_piece_queries(n_mine, pieces);  // (gather.hpp: at most `pieces` pieces, whatever n_mine)
@@ -2279,108 +2096,71 @@ int msbwt_kmer_order_keys(const uint8_t *kmers, size_t k, size_t n, uint64_t *ou
 }
 
 int msbwt_rle_kmer_order_keys_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_keys, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
     if (k < 1 || k > 0xFFFFFFFFull || (n && (!d_kmers || !d_out_keys))) return fail(h, MSBWT_ERR_INVALID_ARG, "order keys need 1 <= k and buffers");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (int rc = c.bind()) return rc;
     HIP_TRY(h, launch_order_keys(static_cast<const uint8_t *>(d_kmers), uint32_t(k), n, static_cast<uint64_t *>(d_out_keys), static_cast<hipStream_t>(hip_stream)));
     return MSBWT_OK;
 }
 
 int msbwt_rle_set_table_depth(msbwt_rle *h, int depth) {
     if (!h || depth > kMaxTableDepth) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_table_depth = depth;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_then_rebuild(h, [&] { h->wanted_table_depth = depth; return true; }, [&] { return rebuild_table(h); });
 }
 
-int msbwt_rle_get_table_depth(const msbwt_rle *h) { return h ? h->table_depth : 0; }
+int msbwt_rle_get_table_depth(const msbwt_rle *h) { return h ? h->table.depth : 0; }
 
-int msbwt_rle_set_pair_index(msbwt_rle *h, int mode) {
-    if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_pair = mode;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    const int rc = rebuild_pair_index(h);
-    return rc ? rc : rebuild_table(h);  // the table's packed form exists only beside a pair index
-}
-
-int msbwt_rle_get_pair_index(const msbwt_rle *h) { return (h && h->d_pair_blocks) ? 1 : 0; }
-
-int msbwt_rle_set_pair_stride(msbwt_rle *h, int stride) {
-    if (!h || (stride != 0 && stride != 96 && stride != 128)) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_pair_stride = stride;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+// the table's packed form exists only beside a pair index: both are rebuilt
+static int rebuild_pair_and_table(msbwt_rle *h) {
     const int rc = rebuild_pair_index(h);
     return rc ? rc : rebuild_table(h);
 }
 
-int msbwt_rle_get_pair_stride(const msbwt_rle *h) { return (h && h->d_pair_blocks) ? h->pair_stride : 0; }
+int msbwt_rle_set_pair_index(msbwt_rle *h, int mode) {
+    if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
+    return set_then_rebuild(h, [&] { h->wanted_pair = mode; return true; }, [&] { return rebuild_pair_and_table(h); });
+}
+
+int msbwt_rle_get_pair_index(const msbwt_rle *h) { return (h && h->pair.blocks) ? 1 : 0; }
+
+int msbwt_rle_set_pair_stride(msbwt_rle *h, int stride) {
+    if (!h || (stride != 0 && stride != 96 && stride != 128)) return MSBWT_ERR_INVALID_ARG;
+    return set_then_rebuild(h, [&] { h->wanted_pair_stride = stride; return true; }, [&] { return rebuild_pair_and_table(h); });
+}
+
+int msbwt_rle_get_pair_stride(const msbwt_rle *h) { return (h && h->pair.blocks) ? h->pair.stride : 0; }
 
 int msbwt_rle_set_presence_filter(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_filter = mode == 0 ? 0 : -1;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);  // the filter is made from the flat table, which a packed table no longer holds
+    // (the filter is made from the flat table, which a packed table no longer holds)
+    return set_then_rebuild(h, [&] { h->wanted_filter = mode == 0 ? 0 : -1; return true; }, [&] { return rebuild_table(h); });
 }
 
 int msbwt_rle_set_table_packed(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_table_packed = mode;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_then_rebuild(h, [&] { h->wanted_table_packed = mode; return true; }, [&] { return rebuild_table(h); });
 }
 
-int msbwt_rle_get_table_packed(const msbwt_rle *h) { return (h && h->d_table && h->table_packed) ? 1 : 0; }
+int msbwt_rle_get_table_packed(const msbwt_rle *h) { return (h && h->table.entries && h->table.packed) ? 1 : 0; }
 
 int msbwt_rle_set_memory_budget(msbwt_rle *h, uint64_t bytes) {
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->memory_budget = bytes;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    // the optional structures are rebuilt under the new budget (the plan counts the memory they hold now as free).  Run blocks: their sparse
-    // table was built at load time and cannot be rebuilt (the plane blocks it came from are gone) -- it stays while the index fits the budget
-    if (h->block_format == kBlocksPlanes || (bytes != 0 && msbwt_rle_device_bytes(h) > bytes)) release_sparse(h);
-    if (h->d_table) (void)hipFree(h->d_table);
-    if (h->d_table_side) (void)hipFree(h->d_table_side);
-    if (h->d_filter) (void)hipFree(h->d_filter);
-    if (h->d_pair_blocks) (void)hipFree(h->d_pair_blocks);
-    if (h->d_pair_super) (void)hipFree(h->d_pair_super);
-    h->d_table = h->d_table_side = h->d_pair_blocks = h->d_pair_super = nullptr;
-    h->d_filter = nullptr;
-    h->filter_depth = 0;
-    h->table_depth = 0;
-    h->table_packed = false;
-    h->table_bytes = 0;
-    h->table_side_bytes = h->table_lines = h->table_escape_lines = 0;
-    h->pair_bytes = h->pair_overlap_bytes = 0;
-    make_plan(h);
-    int rc = rebuild_pair_index(h);
-    if (!rc) rc = rebuild_table(h);
-    if (rc) return rc;
-    // a budget that cannot be met is said, not silently exceeded (the call still succeeds: the index works)
-    h->err.clear();
-    if (bytes != 0 && h->block_format != kBlocksPlanes) h->err = "memory budget: the run-block format has no optional structures to plan; the budget is not applied";
-    else if (bytes != 0 && bytes < h->nblocks * kBlockBytes) h->err = "memory budget: below the plane blocks themselves, which are built all the same";
-    return MSBWT_OK;
+    return set_then_rebuild(h, [&] { h->memory_budget = bytes; return true; }, [&] {
+        // the optional structures are rebuilt under the new budget (the plan counts the memory they hold now as free).  Run blocks: their sparse
+        // table was built at load time and cannot be rebuilt (the plane blocks it came from are gone) -- it stays while the index fits the budget
+        if (h->block_format == kBlocksPlanes || (bytes != 0 && msbwt_rle_device_bytes(h) > bytes)) release_sparse(h);
+        h->table.release();
+        h->pair.release();
+        make_plan(h);
+        if (int rc = rebuild_pair_and_table(h)) return rc;
+        // a budget that cannot be met is said, not silently exceeded (the call still succeeds: the index works)
+        h->err.clear();
+        if (bytes != 0 && h->block_format != kBlocksPlanes) h->err = "memory budget: the run-block format has no optional structures to plan; the budget is not applied";
+        else if (bytes != 0 && bytes < h->nblocks * kBlockBytes) h->err = "memory budget: below the plane blocks themselves, which are built all the same";
+        return int(MSBWT_OK);
+    });
 }
 
 uint64_t msbwt_rle_get_memory_budget(const msbwt_rle *h) { return h ? h->memory_budget : 0; }
@@ -2402,73 +2182,61 @@ int msbwt_auto_index_plan(uint64_t total_symbols, uint64_t free_hbm_bytes, uint6
 
 int msbwt_rle_set_table_side(msbwt_rle *h, int mode) {
     if (!h || mode < 0 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_table_side = mode;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_then_rebuild(h, [&] { h->wanted_table_side = mode; return true; }, [&] { return rebuild_table(h); });
 }
 
 int msbwt_rle_table_info(const msbwt_rle *h, uint64_t *lines, uint64_t *escape_lines, uint64_t *side_bytes) {
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    const bool packed = h->d_table && h->table_packed;
-    if (lines) *lines = packed ? h->table_lines : 0;
-    if (escape_lines) *escape_lines = packed ? h->table_escape_lines : 0;
-    if (side_bytes) *side_bytes = packed ? h->table_side_bytes : 0;
+    const DirectTable &t = h->table;
+    const bool packed = t.entries && t.packed;
+    if (lines) *lines = packed ? t.lines : 0;
+    if (escape_lines) *escape_lines = packed ? t.escape_lines : 0;
+    if (side_bytes) *side_bytes = packed ? t.side_bytes : 0;
     return MSBWT_OK;
 }
 
 // ---- sparse suffix table (sparse_table.hpp) ----------------------------------------------------------------------------------
 int msbwt_rle_set_sparse_table(msbwt_rle *h, int depth) {
     if (!h || !(depth == -1 || depth == 0 || (depth >= kSparseMinDepth && depth <= kSparseMaxDepth))) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_sparse = depth;
-    if (!h->loaded) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    if (h->block_format != kBlocksPlanes) {  // run blocks: the table is built at load time only (from plane blocks that are gone); 0 drops it now
-        if (depth == 0) release_sparse(h);
-        return MSBWT_OK;
-    }
-    return rebuild_table(h);
+    return set_then_rebuild(h, [&] { h->wanted_sparse = depth; return true; }, [&] {
+        if (h->block_format != kBlocksPlanes) {  // run blocks: the table is built at load time only (from plane blocks that are gone); 0 drops it now
+            if (depth == 0) release_sparse(h);
+            return int(MSBWT_OK);
+        }
+        return rebuild_table(h);
+    });
 }
 
-int msbwt_rle_get_sparse_table(const msbwt_rle *h) { return (h && h->d_sparse) ? h->sparse_depth : 0; }
+int msbwt_rle_get_sparse_table(const msbwt_rle *h) { return (h && h->sparse.lines) ? h->sparse.depth : 0; }
+
+// A sparse-table setting changes a loaded plane-block index only when it changes what it would be built as (run blocks: at the next load).
+static int set_sparse_wish(msbwt_rle *h, int &wish, int mode) {
+    return set_then_rebuild(h, [&] {
+        const bool changes = mode != wish;
+        wish = mode;
+        return changes && h->wanted_sparse != 0 && h->block_format == kBlocksPlanes;
+    }, [&] { return rebuild_table(h); });
+}
 
 int msbwt_rle_set_sparse_tiers(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    const bool changes = mode != h->wanted_tiers;
-    h->wanted_tiers = mode;
-    if (!h->loaded || !changes || h->wanted_sparse == 0 || h->block_format != kBlocksPlanes) return MSBWT_OK;  // (run blocks: at the next load)
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_sparse_wish(h, h->wanted_tiers, mode);
 }
 
-int msbwt_rle_get_sparse_tiers(const msbwt_rle *h) { return (h && h->d_sparse && h->sparse_tier) ? 1 : 0; }
+int msbwt_rle_get_sparse_tiers(const msbwt_rle *h) { return (h && h->sparse.lines && h->sparse.tier) ? 1 : 0; }
 
 int msbwt_rle_set_sparse_second(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 0) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    const bool changes = mode != h->wanted_second;
-    h->wanted_second = mode;
-    if (!h->loaded || !changes || h->wanted_sparse == 0 || h->block_format != kBlocksPlanes) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_sparse_wish(h, h->wanted_second, mode);
 }
 
 int msbwt_rle_set_query_length(msbwt_rle *h, int k) {
     if (!h || k < 0) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    const bool changes = sparse_auto_max_depth(k) != sparse_auto_max_depth(h->query_length);
-    h->query_length = k;
-    if (!h->loaded || !changes || h->wanted_sparse >= 0 || h->block_format != kBlocksPlanes) return MSBWT_OK;  // (an explicit depth, or none at all, does not follow the hint; run blocks: at the next load)
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    return rebuild_table(h);
+    return set_then_rebuild(h, [&] {
+        const bool changes = sparse_auto_max_depth(k) != sparse_auto_max_depth(h->query_length);
+        h->query_length = k;
+        return changes && h->wanted_sparse < 0 && h->block_format == kBlocksPlanes;  // (an explicit depth, or none at all, does not follow the hint)
+    }, [&] { return rebuild_table(h); });
 }
 
 int msbwt_rle_get_query_length(const msbwt_rle *h) { return h ? h->query_length : 0; }
@@ -2476,25 +2244,25 @@ int msbwt_rle_get_query_length(const msbwt_rle *h) { return h ? h->query_length 
 int msbwt_auto_sparse_max_depth(int query_length) { return sparse_auto_max_depth(query_length); }
 
 int msbwt_rle_sparse_table_info(const msbwt_rle *ch, uint64_t *out) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h || !out) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!ch || !out) return MSBWT_ERR_INVALID_ARG;
+    Call c(ch);
     std::memset(out, 0, MSBWT_SPARSE_INFO_WORDS * sizeof(uint64_t));
-    const SparseBuildReport &r = h->sparse_report;
-    if (h->d_sparse) {
-        out[0] = uint64_t(h->sparse_depth);
+    const SparseBuildReport &r = c.h->sparse_report;
+    const SparseLevel &s = c.h->sparse, &s2 = c.h->sparse2;
+    if (s.lines) {
+        out[0] = uint64_t(s.depth);
         out[1] = r.entries;
-        out[2] = h->sparse_nbuckets;
-        out[3] = h->sparse_bytes;
+        out[2] = s.nbuckets;
+        out[3] = s.bytes;
         out[4] = r.nescapes;
-        out[5] = h->sparse_side_bytes;
+        out[5] = s.side_bytes;
         out[6] = r.displaced;
-        out[8] = h->sparse_tier ? 1 : 0;
-        out[9] = h->sparse_probe;
+        out[8] = s.tier ? 1 : 0;
+        out[9] = s.probe;
         out[42] = r.filtered;
-        out[43] = uint64_t(h->sparse2_depth);
-        out[44] = h->sparse2_bytes + h->sparse2_side_bytes;
-        out[112] = h->d_sparse2 && h->sparse2_tier ? 1 : 0;
+        out[43] = uint64_t(s2.depth);
+        out[44] = s2.bytes + s2.side_bytes;
+        out[112] = s2.lines && s2.tier ? 1 : 0;
     }
     out[7] = uint64_t(r.parent_depth);
     for (int d = 0; d <= kSparseMaxDepth; ++d) {
@@ -2559,40 +2327,34 @@ size_t msbwt_rle_download_sparse_table(const msbwt_rle *ch, void *out_lines, siz
     msbwt_rle *h = const_cast<msbwt_rle *>(ch);
     if (!h) return SIZE_MAX;
     std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded || !h->d_sparse) return SIZE_MAX;
+    const SparseLevel &s = h->sparse;
+    if (!h->loaded || !s.lines) return SIZE_MAX;
     DeviceScope scope(h->device);
     if (!scope.ok()) return SIZE_MAX;
-    if (out_lines && cap_bytes >= h->sparse_bytes && hipMemcpy(out_lines, h->d_sparse, h->sparse_bytes, hipMemcpyDeviceToHost) != hipSuccess) return SIZE_MAX;
-    if (out_side && h->d_sparse_side && cap_side_bytes >= h->sparse_side_bytes &&
-        hipMemcpy(out_side, h->d_sparse_side, h->sparse_side_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return SIZE_MAX;
-    return size_t(h->sparse_bytes);
+    if (out_lines && cap_bytes >= s.bytes && hipMemcpy(out_lines, s.lines, s.bytes, hipMemcpyDeviceToHost) != hipSuccess) return SIZE_MAX;
+    if (out_side && s.side && cap_side_bytes >= s.side_bytes && hipMemcpy(out_side, s.side, s.side_bytes, hipMemcpyDeviceToHost) != hipSuccess) return SIZE_MAX;
+    return size_t(s.bytes);
 }
 
 int msbwt_rle_set_line_streaming(msbwt_rle *h, int mode) {
     if (!h || mode < -1 || mode > 1) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_streaming = mode;
-    return MSBWT_OK;
+    return set_locked(h, h->wanted_streaming, mode);
 }
 
 int msbwt_rle_get_line_streaming(const msbwt_rle *ch) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h || !h->loaded) return 0;
-    std::lock_guard<std::mutex> lock(h->mu);
-    return view_of(h).stream_lines ? 1 : 0;
+    if (!ch || !ch->loaded) return 0;
+    Call c(ch);
+    return view_of(c.h).stream_lines ? 1 : 0;
 }
 
 int msbwt_rle_probe_line_rate(const msbwt_rle *ch, int which, double *lines_per_second) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h || !lines_per_second || which < 0 || which > 3) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->loaded) return fail(h, MSBWT_ERR_NOT_LOADED, "no BWT loaded");
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    const void *p = which == 0 ? h->d_blocks : which == 1 ? h->d_pair_blocks : which == 2 ? h->d_sparse : h->d_table;
-    const uint64_t bytes = which == 0 ? h->nblocks * kBlockBytes : which == 1 ? pair_index_sizes(h->nblocks, h->pair_stride).pair_block_bytes
-                           : which == 2 ? h->sparse_bytes : uint64_t(h->table_bytes);
+    if (!ch || !lines_per_second || which < 0 || which > 3) return MSBWT_ERR_INVALID_ARG;
+    Call c(ch);
+    if (int rc = c.open()) return rc;
+    msbwt_rle *h = c.h;
+    const void *p = which == 0 ? h->d_blocks : which == 1 ? h->pair.blocks : which == 2 ? h->sparse.lines : h->table.entries;
+    const uint64_t bytes = which == 0 ? h->nblocks * kBlockBytes : which == 1 ? pair_index_sizes(h->nblocks, h->pair.stride).pair_block_bytes
+                           : which == 2 ? h->sparse.bytes : uint64_t(h->table.bytes);
     *lines_per_second = 0.0;
     if (!p || bytes < 128) return MSBWT_OK;
     *lines_per_second = line_rate_of(p, bytes, h->stream);
@@ -2600,20 +2362,16 @@ int msbwt_rle_probe_line_rate(const msbwt_rle *ch, int which, double *lines_per_
 }
 
 int msbwt_rle_set_search_counters(msbwt_rle *h, int enabled) {
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->counting = enabled != 0;
-    return MSBWT_OK;
+    return h ? set_locked(h, h->counting, enabled != 0) : MSBWT_ERR_INVALID_ARG;
 }
 
 int msbwt_rle_search_counters(const msbwt_rle *ch, uint64_t *out, void *hip_stream) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
-    if (!h || !out) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!ch || !out) return MSBWT_ERR_INVALID_ARG;
+    Call c(ch);
+    msbwt_rle *h = c.h;
     std::memset(out, 0, MSBWT_SEARCH_COUNTERS * sizeof(uint64_t));
     if (!h->d_flags) return MSBWT_OK;
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (int rc = c.bind()) return rc;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     char *d_counters = reinterpret_cast<char *>(h->d_flags) + kCountersOffset;
     HIP_TRY(h, hipMemcpyAsync(out, d_counters, MSBWT_SEARCH_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
@@ -2622,13 +2380,11 @@ int msbwt_rle_search_counters(const msbwt_rle *ch, uint64_t *out, void *hip_stre
     return MSBWT_OK;
 }
 
-int msbwt_rle_get_presence_filter(const msbwt_rle *h) { return (h && h->d_filter) ? h->filter_depth : 0; }
+int msbwt_rle_get_presence_filter(const msbwt_rle *h) { return (h && h->table.filter) ? h->table.filter_depth : 0; }
 
 int msbwt_rle_set_block_format(msbwt_rle *h, int format) {
     if (!h || (format != kBlocksPlanes && format != kBlocksRuns)) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->wanted_block_format = format;  // the next load builds it
-    return MSBWT_OK;
+    return set_locked(h, h->wanted_block_format, format);  // (the next load builds it)
 }
 
 int msbwt_rle_get_block_format(const msbwt_rle *h) { return h ? (h->loaded ? h->block_format : h->wanted_block_format) : 0; }
@@ -2658,9 +2414,7 @@ double msbwt_rle_get_typical_range_width(const msbwt_rle *h) { return h ? h->typ
 
 int msbwt_rle_set_search_kernel(msbwt_rle *h, int mode) {
     if (!h || mode < kSearchAuto || mode > kSearchLanes) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->search_kernel = mode;
-    return MSBWT_OK;
+    return set_locked(h, h->search_kernel, mode);
 }
 
 int msbwt_rle_get_search_kernel(const msbwt_rle *h) { return h ? h->search_kernel : 0; }
@@ -2668,30 +2422,26 @@ int msbwt_rle_get_search_kernel(const msbwt_rle *h) { return h ? h->search_kerne
 int msbwt_rle_search_kernel_for(const msbwt_rle *h, size_t k) {
     if (!h || !h->loaded) return MSBWT_ERR_INVALID_ARG;
     if (k > 0xFFFFFFFFull) return 0;
-    msbwt_rle *m = const_cast<msbwt_rle *>(h);
-    std::lock_guard<std::mutex> lock(m->mu);
-    return search_kernel_for(view_of(m), uint32_t(k));
+    Call c(h);
+    return search_kernel_for(view_of(c.h), uint32_t(k));
 }
 
 uint64_t msbwt_rle_device_bytes(const msbwt_rle *h) {
     if (!h || !h->loaded) return 0;
-    return h->nblocks * kBlockBytes + h->overflow_bytes + (h->d_table ? uint64_t(h->table_bytes) + h->table_side_bytes : 0) + h->pair_bytes +
-           (h->d_filter ? (uint64_t(1) << (2 * h->filter_depth)) / 8 : 0) + h->sparse_bytes + h->sparse_side_bytes + h->sparse2_bytes + h->sparse2_side_bytes;
+    const DirectTable &t = h->table;
+    return h->nblocks * kBlockBytes + h->overflow_bytes + (t.entries ? uint64_t(t.bytes) + t.side_bytes : 0) + h->pair.bytes +
+           (t.filter ? (uint64_t(1) << (2 * t.filter_depth)) / 8 : 0) + h->sparse.bytes + h->sparse.side_bytes + h->sparse2.bytes + h->sparse2.side_bytes;
 }
 
 int msbwt_rle_set_kernel_timing(msbwt_rle *h, int enabled) {
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->timing = enabled != 0;
-    return MSBWT_OK;
+    return h ? set_locked(h, h->timing, enabled != 0) : MSBWT_ERR_INVALID_ARG;
 }
 
 int msbwt_rle_kernel_time_ms(const msbwt_rle *ch, double *avg_ms, uint64_t *launches) {
-    msbwt_rle *h = const_cast<msbwt_rle *>(ch);
+    Call c(ch);
+    msbwt_rle *h = c.h;
     if (!h) return MSBWT_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    if (int rc = c.bind()) return rc;
     const int rc = drain_timing_events(h);
     if (rc) return rc;
     if (avg_ms) *avg_ms = h->timed_launches ? h->timed_ms / double(h->timed_launches) : 0.0;
