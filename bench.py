@@ -45,6 +45,7 @@ import os
 import socket
 import subprocess
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -158,6 +159,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else this benchmark measures and checks: parity against the CPU oracle, roofline, CPU baseline, "
+                         "the extra lines (c5_random_1e9, c4_*, sorted_batch, the variant lines), live PMC passes, and at N > 1 the weak-scaling, "
+                         "per-rank and native-gather figures.  Off by default: a plain run sets up, warms up, times the steps and prints its line; "
+                         "the --no-* options below choose among the extras of a --full run, and --counters / --c4-lab add to them")
     ap.add_argument("--workload", default="human", choices=["human", "c2", "c3", "c4", "c4r", "c4x3", "c4x3r", "big"])
     ap.add_argument("--big-symbols", type=float, default=2.0**33, help="workload big: BWT length")
     ap.add_argument("--big-mean-run", type=float, default=6.0)
@@ -242,7 +248,15 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the result line -- nothing that takes a pass or a check of its own
+        for skipped in PLAIN_RUN_SKIPS:
+            setattr(args, skipped, True)
+        args.counters = args.c4_lab = False
     return args
+
+
+# what a run without --full leaves out, as the options that switch each of them off in a --full run
+PLAIN_RUN_SKIPS = ("no_oracle", "no_cpu_baseline", "no_c5", "no_c4", "no_sorted", "no_variants", "no_live_pmc", "no_weak", "no_native_gather")
 
 
 DUMP_ROWS = 1 << 21   # --dump-outputs: 2 arrays x 2^21 float64 = 32 MiB
@@ -293,34 +307,45 @@ def walk_kmers(torch, np, bwt, dev, total, n, k, seed, chunk=40_000_000):
     stream = torch.cuda.current_stream(dev).cuda_stream
     out = torch.empty((n, k), dtype=torch.uint8, device=dev)
     have = 0
+    ahead = None   # the next chunk's rows, drawn on a thread of its own while the GPU walks this chunk's -- where the next chunk's size is known already
     while have < n:
         m = min(chunk, int((n - have) * 1.3) + 4096)
-        l = torch.from_numpy(rng.integers(0, total, size=m, dtype=np.int64)).to(dev)
+        if ahead is not None:
+            ahead[0].join()
+            rows, ahead = ahead[1][0], None
+        else:
+            rows = rng.integers(0, total, size=m, dtype=np.int64)
+        drawn = []
+        if m == chunk and int((n - have - m) * 1.3) + 4096 >= chunk:   # (this chunk adds at most m queries: the next one is a whole chunk too)
+            ahead = (threading.Thread(target=lambda box: box.append(rng.integers(0, total, size=chunk, dtype=np.int64)), args=(drawn,), daemon=True), drawn)
+            ahead[0].start()
+        l = torch.from_numpy(rows).to(dev)
         h = l + 1
         kmers = torch.zeros((m, k), dtype=torch.uint8, device=dev)
         ok = torch.ones(m, dtype=torch.bool, device=dev)
         ol = torch.empty_like(l)
         oh = torch.empty_like(l)
+        # (only A, C, G, T are tried: a walk whose row holds '$' or 'N' finds none of them, keeps symbol 0 and the empty range [0, 0), and is dropped)
+        tried = [(s, torch.full((m,), s, dtype=torch.uint8, device=dev)) for s in (1, 2, 3, 5)]
         for step in range(k):
             nl = torch.zeros_like(l)
             nh = torch.zeros_like(l)
             sym_at = torch.zeros(m, dtype=torch.uint8, device=dev)
-            for s in range(6):
-                syms = torch.full((m,), s, dtype=torch.uint8, device=dev)
+            for s, syms in tried:
                 bwt.constrain_ranges_device(syms.data_ptr(), l.data_ptr(), h.data_ptr(), m, ol.data_ptr(), oh.data_ptr(), stream)
                 hit = (oh - ol) == 1
                 nl = torch.where(hit, ol, nl)
                 nh = torch.where(hit, oh, nh)
-                sym_at = torch.where(hit, torch.full_like(sym_at, s), sym_at)
+                sym_at = torch.where(hit, syms, sym_at)
             kmers[:, k - 1 - step] = sym_at
-            ok &= (sym_at != 0) & (sym_at != 4)
+            ok &= sym_at != 0
             l, h = nl, nh
         bwt.device_status(stream)
         good = kmers[ok]
         take = min(n - have, good.shape[0])
         out[have:have + take] = good[:take]
         have += take
-        del l, h, kmers, ok, ol, oh, nl, nh, sym_at, good
+        del l, h, kmers, ok, ol, oh, nl, nh, sym_at, good, tried
     return out
 
 
@@ -721,14 +746,15 @@ def main():
                 rle, _, n_reads_total = bwt_reads.msbwt_rle(genome, cnt, read_len, log=lambda m: log("rank %d: bwt: %s" % (rank, m)))
             del genome, cnt
             torch.cuda.empty_cache()
-            log("rank %d: exact MSBWT of %d error-free %d-bp reads: %d RLE bytes in %.1fs" % (rank, n_reads_total, read_len, len(rle), time.time() - t0))
+            log("rank %d: exact MSBWT of %d error-free %d-bp reads: %d RLE bytes in %.1fs (at most %.1f GB of HBM held)"
+                % (rank, n_reads_total, read_len, len(rle), time.time() - t0, torch.cuda.max_memory_reserved(dev) / 1e9))
         else:
             # structure-equivalent synthetic RLE stream (NOT a real BWT): independent symbols.  Same seed on every rank => identical replicas.
             rle, _ = synth.rle_stream(symbols, args.big_mean_run, 77, histogram=hist_file)
             log("rank %d: synthetic RLE stream of %d bytes in %.1fs (%d host threads)" % (rank, len(rle), time.time() - t0, host_threads))
         t0 = time.time()
         bwt.load_vector(rle)
-        if rank != 0:
+        if rank != 0 or args.no_oracle:
             rle = None  # only rank 0 feeds the oracle
     else:
         # rank 0 builds (and caches) the index file, everyone loads it
@@ -1044,7 +1070,7 @@ def main():
     # per-rank view of the timed region: the count kernel alone (HIP events on the launch stream), and the exchange
     # step alone (the same all_gather + widening, timed without kernels) -- so that a sub-linear curve can be read
     ranks_info = None
-    if multi:
+    if multi and args.full:
         _, _, ex_elapsed, _, _, _ = measure(main_batch, lo, hi, cap, exchange=None)
         per = gather_floats([kernel_ms, ex_elapsed / args.steps * 1e3])
         ranks_info = {"kernel_ms": [p[0] for p in per], "kernel_ms_min": min(p[0] for p in per), "kernel_ms_max": max(p[0] for p in per),

@@ -40,15 +40,19 @@ def _encode_runs(torch, sym, length):
     """runs (symbol code, length > 0, neighbours differ) -> RLE bytes: sym | digit << 3, base-32 digits, least
     significant first, zero digits included (bwt_converter.rs:26-80)."""
     nb = torch.ones_like(length)
+    longest = int(length.max().item()) if length.numel() else 0
     for d in range(1, 9):
+        if longest < (1 << (5 * d)):      # no run has a digit d: none has a higher one either
+            break
         nb += (length >= (1 << (5 * d))).to(length.dtype)
     off = torch.cumsum(nb, 0) - nb
     out = torch.zeros(int(nb.sum().item()), dtype=torch.uint8, device=sym.device)
     sym64 = sym.to(torch.int64)
-    for d in range(0, 9):
-        sel = nb > d
-        if d and not bool(sel.any()):
+    out[off] = (sym64 | ((length & 31) << 3)).to(torch.uint8)          # digit 0: every run has one
+    for d in range(1, 9):
+        if longest < (1 << (5 * d)):
             break
+        sel = nb > d
         out[off[sel] + d] = (sym64[sel] | (((length[sel] >> (5 * d)) & 31) << 3)).to(torch.uint8)
     return out
 
@@ -61,13 +65,30 @@ def _nonzero(torch, x, chunk=1 << 30):
 
 
 class _RunWriter:
-    """Takes runs part by part (in final order), merges equal neighbours across part borders, keeps bytes on the host."""
+    """Takes runs part by part (in final order), merges equal neighbours across part borders.  The encoded parts stay where they were
+    made until finish() gathers them in ONE host array: on a GPU that is page-locked memory written by asynchronous copies (10 GB at
+    human scale: no concatenation on the host, and the index loader's upload reads it at the link's speed)."""
 
     def __init__(self, torch):
         self.torch = torch
         self.parts = []
-        self.pending = None  # (symbol, length) of the last run seen: its successor may still extend it
-        self.totals = np.zeros(6, dtype=np.int64)
+        self.pending = None  # (symbol, length), one-element tensors: the last run seen -- its successor may still extend it
+        self.totals = None   # per symbol code, where the runs are
+        self.reserved = self.reserving = None
+
+    def reserve(self, share_done):
+        """Once a share of the parts is in: page-locked host memory for the whole output, sized from that share, allocated on a thread of
+        its own while the rest is made (locking 10 GB takes a second).  finish() allocates again should the guess prove too small."""
+        torch = self.torch
+        if self.reserving is not None or not self.parts or not self.parts[0].is_cuda:
+            return
+        import threading
+        guess = int(sum(p.numel() for p in self.parts) / share_done * 1.05) + (1 << 26)
+
+        def work():
+            self.reserved = torch.empty(guess, dtype=torch.uint8, pin_memory=True)
+        self.reserving = threading.Thread(target=work, daemon=True)
+        self.reserving.start()
 
     def add(self, sym, length):
         torch = self.torch
@@ -76,27 +97,48 @@ class _RunWriter:
         if sym.numel() == 0:
             return
         if self.pending is not None:
-            sym = torch.cat([torch.tensor([self.pending[0]], dtype=sym.dtype, device=sym.device), sym])
-            length = torch.cat([torch.tensor([self.pending[1]], dtype=length.dtype, device=length.device), length])
+            sym = torch.cat([self.pending[0], sym])
+            length = torch.cat([self.pending[1], length])
         first = torch.ones(sym.numel(), dtype=torch.bool, device=sym.device)
         first[1:] = sym[1:] != sym[:-1]
         gid = torch.cumsum(first.to(torch.int64), 0) - 1
         msym = sym[first]
         mlen = torch.zeros(msym.numel(), dtype=torch.int64, device=sym.device).index_add_(0, gid, length)
-        self.pending = (int(msym[-1].item()), int(mlen[-1].item()))
-        msym, mlen = msym[:-1], mlen[:-1]
+        self.pending = (msym[-1:].clone(), mlen[-1:].clone())
+        self._emit(msym[:-1], mlen[:-1])
+
+    def _emit(self, msym, mlen):
+        torch = self.torch
         if msym.numel():
-            self.totals += torch.zeros(6, dtype=torch.int64, device=sym.device).index_add_(0, msym.to(torch.int64), mlen).cpu().numpy()
-            self.parts.append(_encode_runs(torch, msym, mlen).cpu().numpy())
+            if self.totals is None:
+                self.totals = torch.zeros(6, dtype=torch.int64, device=msym.device)
+            self.totals.index_add_(0, msym.to(torch.int64), mlen)
+            self.parts.append(_encode_runs(torch, msym, mlen))
 
     def finish(self):
         torch = self.torch
         if self.pending is not None:
-            s, n = self.pending
-            self.totals[s] += n
-            self.parts.append(_encode_runs(torch, torch.tensor([s], dtype=torch.uint8), torch.tensor([n], dtype=torch.int64)).numpy())
+            self._emit(*self.pending)
             self.pending = None
-        return (np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=np.uint8)), self.totals
+        totals = np.zeros(6, dtype=np.int64) if self.totals is None else self.totals.cpu().numpy()
+        on_gpu = bool(self.parts) and self.parts[0].is_cuda
+        size = sum(p.numel() for p in self.parts)
+        if self.reserving is not None:
+            self.reserving.join()
+        if self.reserved is not None and self.reserved.numel() >= size:
+            whole = self.reserved[:size]
+        else:
+            whole = torch.empty(size, dtype=torch.uint8, pin_memory=on_gpu)
+        self.reserved = None
+        at = 0
+        while self.parts:
+            part = self.parts.pop(0)
+            whole[at:at + part.numel()].copy_(part, non_blocking=on_gpu)
+            at += part.numel()
+        if on_gpu:
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+        return whole.numpy(), totals     # (the array keeps the tensor, and with it the page-locked memory, alive)
 
 
 def read_set(genome_len, read_len, coverage, seed, device="cpu"):
@@ -128,6 +170,28 @@ def reads_of(genome, cnt, read_len):
     return codes[genome[idx].to(torch.int64)].cpu().numpy()
 
 
+def _keys_of(torch, genome, npos, piece=1 << 28):
+    """key[p] = the 31 bases at p, first base most significant (62 bits), for p < npos: built by doubling -- 1, 2, 4 bases per
+    position in 8 bits, 8 in 32, 16 in 64, and 16 + 15 piece by piece, so that little more than the keys themselves is ever allocated
+    (on a GPU every GB that is allocated and given back costs time: it is cleared on the way)."""
+    assert KEY_BASES == 31 and genome.numel() >= npos + KEY_BASES
+    b = genome[:npos + KEY_BASES]                                   # 1 base
+    b = (b[:-1] << 2) | b[1:]                                       # 2 bases: 4 bits
+    b = (b[:-2] << 4) | b[2:]                                       # 4 bases: 8 bits
+    wide = b[:-4].to(torch.int32) << 8
+    wide |= b[4:]                                                   # 8 bases: 16 bits
+    b = wide
+    wide = b[:-8].to(torch.int64) << 16
+    wide |= b[8:]                                                   # 16 bases: 32 bits
+    del b
+    key = torch.empty(npos, dtype=torch.int64, device=genome.device)
+    for lo in range(0, npos, piece):
+        hi = min(npos, lo + piece)
+        torch.bitwise_left_shift(wide[lo:hi], 30, out=key[lo:hi])
+        key[lo:hi] |= wide[lo + 16:hi + 16] >> 2                    # + the first 15 of the 16 bases that follow
+    return key
+
+
 def msbwt_rle(genome, cnt, read_len, log=None):
     """RLE bytes (numpy uint8) of the multi-string BWT of the read set {genome[s : s + read_len] : cnt[s] times},
     the symbol totals [$ A C G N T], and the number of reads."""
@@ -147,91 +211,104 @@ def msbwt_rle(genome, cnt, read_len, log=None):
     cp = torch.zeros(cntp.numel() + 1, dtype=torch.int32 if n_reads < 2**31 else i64, device=dev)  # cp[i] = sum(cntp[:i])
     torch.cumsum(cntp, 0, dtype=cp.dtype, out=cp[1:])
     # prev[p] = symbol code of genome[p - 1] (prev[0] is never used with a non-zero count)
-    codes = torch.tensor(CODE_OF_BASE, dtype=torch.uint8, device=dev)
+    assert CODE_OF_BASE == (1, 2, 3, 5)
     prev = torch.empty(npos, dtype=torch.uint8, device=dev)
-    prev[0] = codes[0]
-    prev[1:] = codes[genome[:npos - 1].to(i64)]
-    # key[p] = the 31 bases at p, first base most significant (62 bits): built by doubling
-    key = genome[:npos + KEY_BASES].to(i64)
-    have = 1
-    while have < KEY_BASES:            # key holds `have` bases per position; append the next min(have, rest)
-        take = min(have, KEY_BASES - have)
-        nxt = key[have:have + (key.numel() - have)]
-        if take < have:
-            nxt = nxt >> (2 * (have - take))
-        key = (key[:nxt.numel()] << (2 * take)) | nxt
-        have += take
-    key = key[:npos].contiguous()
+    prev[0] = CODE_OF_BASE[0]
+    torch.add(genome[:npos - 1], 1, out=prev[1:])
+    prev[1:] += genome[:npos - 1] == 3            # base b -> code b + 1, T (3) -> 5
+    key = _keys_of(torch, genome, npos)
     say("keys of %d positions ready (%d reads)" % (npos, n_reads))
 
     out = _RunWriter(torch)
     shift_m = lambda m: 2 * (KEY_BASES - m)
 
     def level_rows(m):
-        """rows of one shallow level over ALL positions, in genome-suffix order: (sorted keys, symbols, copies)"""
+        """rows of one shallow level over ALL positions, in genome-suffix order: (where each m-base prefix begins, symbols, copies)"""
         p = _nonzero(torch, cntp[m:m + npos])
         k, order = torch.sort(key[p], stable=True)
         p = p[order]
-        return k, prev[p], cntp[p + m].to(i64)
+        borders = torch.arange(4 ** m + 1, dtype=i64, device=dev) << shift_m(m) if m else None
+        at = torch.searchsorted(k, borders).tolist() if m else [0, k.numel()]
+        return at, prev[p], cntp[p + m]
 
     low = [level_rows(m) for m in range(3)]           # '$', 'x$', 'xy$'
     say("levels 0-2 sorted")
 
     def low_segment(m, prefix):                       # rows of level m whose first m bases are `prefix`
-        k, sym, mult = low[m]
-        lo = int(torch.searchsorted(k, torch.tensor([prefix << shift_m(m)], dtype=i64, device=dev))[0].item()) if m else 0
-        hi = int(torch.searchsorted(k, torch.tensor([(prefix + 1) << shift_m(m)], dtype=i64, device=dev))[0].item()) if m else k.numel()
-        return sym[lo:hi], mult[lo:hi]
+        at, sym, mult = low[m]
+        return sym[at[prefix]:at[prefix + 1]], mult[at[prefix]:at[prefix + 1]].to(i64)
 
-    out.add(*low_segment(0, 0))
-    top3 = (key >> shift_m(3)).to(torch.uint8)    # leading 3-mer of every position: the 64 groups
-    for grp in range(64):
-        if grp % 16 == 0:
-            out.add(*low_segment(1, grp // 16))
-        if grp % 4 == 0:
-            out.add(*low_segment(2, grp // 4))
-        idx = _nonzero(torch, top3 == grp)
-        if idx.numel() == 0:
-            continue
-        ks, order = torch.sort(key[idx], stable=True)
-        sa = idx[order]                                # genome positions of this group in suffix order
-        del idx, order
-        n = sa.numel()
-        wlong = (cp[sa + L] - cp[sa + (M_SHORT + 1)]).to(i64)   # rows with M_SHORT < m < L
-        dollars = cntp[sa + L].to(i64)                          # m = L: reads that start here
-        keys, jl, mu = [], [], []
-        k28 = ks >> shift_m(M_SHORT)
-        for m in range(3, M_SHORT + 1):
-            c = cntp[sa + m]
-            nz = torch.nonzero(c).squeeze(1)
-            if nz.numel() == 0:
+    def emit_groups():
+        out.add(*low_segment(0, 0))
+        top3 = (key >> shift_m(3)).to(torch.uint8)    # leading 3-mer of every position: the 64 groups
+        for grp in range(64):
+            if grp % 16 == 0:
+                out.add(*low_segment(1, grp // 16))
+            if grp % 4 == 0:
+                out.add(*low_segment(2, grp // 4))
+            if grp % 16 == 0:                              # the positions of one leading base, ascending: its 16 groups are picked among them
+                quarter = _nonzero(torch, (top3 >> 4) == grp // 16)
+                top3_quarter = top3[quarter]
+            idx = quarter[_nonzero(torch, top3_quarter == grp)]
+            if idx.numel() == 0:
                 continue
-            pre = (k28[nz] >> (2 * (M_SHORT - m))) << (2 * (M_SHORT - m))   # first m bases, padded with 'A'
-            keys.append((pre << 6) | m)
-            jl.append(nz)
-            mu.append(c[nz].to(i64))
-        if keys:
-            keys, perm = torch.sort(torch.cat(keys), stable=True)   # ties (same string): genome-suffix order, as generated
-            jl, mu = torch.cat(jl)[perm], torch.cat(mu)[perm]
-            ins = torch.searchsorted(k28, keys >> 6, right=False)   # in front of the positions that continue the prefix
-            r = keys.numel()
-        else:
-            jl = mu = ins = torch.zeros(0, dtype=i64, device=dev)
-            r = 0
-        arange_n = torch.arange(n, dtype=i64, device=dev)
-        pile_at = 2 * arange_n + torch.searchsorted(ins, arange_n, right=True)
-        short_at = torch.arange(r, dtype=i64, device=dev) + 2 * ins
-        sym = torch.empty(r + 2 * n, dtype=torch.uint8, device=dev)
-        length = torch.empty(r + 2 * n, dtype=i64, device=dev)
-        sym[short_at] = prev[sa[jl]]
-        length[short_at] = mu
-        sym[pile_at] = prev[sa]
-        length[pile_at] = wlong
-        sym[pile_at + 1] = DOLLAR
-        length[pile_at + 1] = dollars
-        out.add(sym, length)
-        if grp % 8 == 7:
-            say("group %d of 64 done" % (grp + 1))
+            ks, order = torch.sort(key[idx], stable=True)
+            sa = idx[order]                                # genome positions of this group in suffix order
+            del idx, order
+            n = sa.numel()
+            wlong = (cp[sa + L] - cp[sa + (M_SHORT + 1)]).to(i64)   # rows with M_SHORT < m < L
+            dollars = cntp[sa + L].to(i64)                          # m = L: reads that start here
+            k28 = ks >> shift_m(M_SHORT)
+            # the short rows of all levels m = 3 .. M_SHORT at once: one gather of the M_SHORT - 2 neighbouring counts of every position
+            # (row j of `window` = cntp[sa[j] + 3 : sa[j] + M_SHORT + 1]), in pieces that stay below torch.nonzero's 2^31 elements
+            window = cntp.unfold(0, M_SHORT - 2, 1)
+            jl, lv, mu = [], [], []
+            piece = (1 << 30) // (M_SHORT - 2)
+            for lo in range(0, n, piece):
+                c = window[sa[lo:lo + piece] + 3]
+                nz = torch.nonzero(c)
+                jl.append(nz[:, 0] + lo)
+                lv.append(nz[:, 1])
+                mu.append(c[nz[:, 0], nz[:, 1]].to(i64))
+                del c, nz
+            jl, lv, mu = (x[0] if len(x) == 1 else torch.cat(x) for x in (jl, lv, mu))
+            if jl.numel():
+                pad = 2 * (M_SHORT - 3 - lv)
+                keys = (((k28[jl] >> pad) << pad) << 6) | (lv + 3)      # first m bases, padded with 'A'; then m
+                del pad, lv
+                keys, perm = torch.sort(keys, stable=True)   # ties (same string, so same m): genome-suffix order, as generated
+                jl, mu = jl[perm], mu[perm]
+                ins = torch.searchsorted(k28, keys >> 6, right=False)   # in front of the positions that continue the prefix
+                r = keys.numel()
+            else:
+                jl = mu = ins = torch.zeros(0, dtype=i64, device=dev)
+                keys = perm = None
+                r = 0
+            arange_n = torch.arange(n, dtype=i64, device=dev)
+            pile_at = 2 * arange_n + torch.searchsorted(ins, arange_n, right=True)
+            short_at = torch.arange(r, dtype=i64, device=dev) + 2 * ins
+            sym = torch.empty(r + 2 * n, dtype=torch.uint8, device=dev)
+            length = torch.empty(r + 2 * n, dtype=i64, device=dev)
+            sym[short_at] = prev[sa[jl]]
+            length[short_at] = mu
+            sym[pile_at] = prev[sa]
+            length[pile_at] = wlong
+            sym[pile_at + 1] = DOLLAR
+            length[pile_at + 1] = dollars
+            out.add(sym, length)
+            del ks, k28, sa, wlong, dollars, jl, mu, ins, keys, perm, arange_n, pile_at, short_at, sym, length   # (before the next group allocates)
+            if grp % 8 == 7:
+                say("group %d of 64 done" % (grp + 1))
+            if grp == 31:
+                out.reserve(0.5)
+
+    emit_groups()
+    # what the order took is given back before the bytes are gathered: the device clears freed memory at its own pace, and whoever
+    # allocates next (the index loader) waits for that -- less so the earlier it starts
+    del cntp, cp, prev, key
+    low.clear()
+    if dev.type == "cuda":
+        torch.cuda.empty_cache()
     rle, totals = out.finish()
     assert int(totals.sum()) == n_reads * (L + 1) and int(totals[DOLLAR]) == n_reads
     return rle, totals, n_reads

@@ -56,7 +56,7 @@ def _run(args, tmp=[0]):
                                    ["--workload", "c3", "--fused", "--scale", "0.003"],
                                    ["--workload", "big", "--big-symbols", "3000000", "--queries", "20000"]])
 def test_bench_contract(extra):
-    r = _run(extra + ["--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--parity-sample", "5000"])
+    r = _run(extra + ["--full", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--parity-sample", "5000"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity"):
         assert key in r, key
@@ -74,7 +74,7 @@ def test_bench_contract(extra):
 def test_bench_default_run_carries_the_real_msbwt_line():
     """The default run's extra key c4_real_reads (the REAL MSBWT of config C4, read-derived 31-mers), here on a
     shrunk C4 beside a shrunk human-scale index: own value, roofline, parity."""
-    r = _run(["--scale", "0.00003", "--c4-scale", "0.002", "--c4-lab", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--parity-sample", "5000"])
+    r = _run(["--full", "--scale", "0.00003", "--c4-scale", "0.002", "--c4-lab", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--parity-sample", "5000"])
     compact = r["_compact"]
     assert compact["roofline"]["kernel_ms"] > 0 and compact["cpu_baseline"]["value"] > 0 and compact["parity"]["mismatches"] == 0
     for key in ("c4_real_reads_qps", "c4_repeats_qps", "undeclared_k_qps", "headline_sparse_off_qps"):
@@ -115,7 +115,7 @@ def test_bench_dump_outputs_are_the_timed_counts_and_repeat(tmp_path):
     """--dump-outputs: the last timed step's counts (float64, every row of a small batch), the same in two runs with the same
     arguments; --steps is the number of timed launches."""
     import numpy as np
-    lean = ["--scale", "0.00003", "--steps", "3", "--warmup", "1", "--no-c5", "--no-variants", "--no-sorted", "--parity-sample", "5000",
+    lean = ["--full", "--scale", "0.00003", "--steps", "3", "--warmup", "1", "--no-c5", "--no-variants", "--no-sorted", "--parity-sample", "5000",
             "--cpu-sample", "2000"]
     runs = []
     for i in range(2):
@@ -150,7 +150,7 @@ def test_bench_default_is_the_metric_config():
 def test_bench_self_launch_two_ranks(scaling):
     """`python3 bench.py --gpus 2` launched plainly must start its own ranks (child process) and
     print one JSON line with n_gpus = 2."""
-    r = _run(["--gpus", "2", "--dist-backend", "gloo", "--scale", "0.00003", "--steps", "2", "--warmup", "1",
+    r = _run(["--full", "--gpus", "2", "--dist-backend", "gloo", "--scale", "0.00003", "--steps", "2", "--warmup", "1",
               "--parity-sample", "5000", "--scaling", scaling])
     assert r["n_gpus"] == 2 and r["scaling"] == scaling and r["parity"]["mismatches"] == 0 and r["value"] > 0
     assert r["config"]["k"] == 31
@@ -162,7 +162,7 @@ def test_bench_self_launch_two_ranks(scaling):
 def test_bench_two_ranks_sharded_random_line():
     """The literal configs[4] shape at N = 2 (gloo rehearsal on the shared GPU): the device-generated random 31-mers are
     defined chunk by chunk, each rank generates only its shard, all counts are gathered; plus the per-rank timing block."""
-    r = _run(["--gpus", "2", "--dist-backend", "gloo", "--scale", "0.00003", "--steps", "2", "--warmup", "1", "--parity-sample", "5000",
+    r = _run(["--full", "--gpus", "2", "--dist-backend", "gloo", "--scale", "0.00003", "--steps", "2", "--warmup", "1", "--parity-sample", "5000",
               "--c5-queries", "300000", "--no-weak"])
     c5 = r["c5_random_1e9"]
     assert c5["queries"] == 300000 and c5["queries_per_gpu"] in (150000, 150016) and c5["parity"]["mismatches"] == 0 and c5["value"] > 0
@@ -182,7 +182,7 @@ def test_bench_two_ranks_rehearsal(payload):
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo",
            "--workload", "c2", "--scale", "0.003", "--steps", "3", "--warmup", "1", "--parity-sample", "5000", "--payload", payload,
            "--scaling", "weak", "--exchange", "gather" if payload == "auto" else "allgather"]   # (both forms of the step's exchange)
     extras = os.path.join(ROOT, "gpurun_out", "bench_extras_test_ranks_%d_%s.json" % (os.getpid(), payload))
@@ -213,7 +213,7 @@ def test_bench_rccl_calls_on_one_rank(payload):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     extras = os.path.join(ROOT, "gpurun_out", "bench_extras_test_rccl_%d_%s.json" % (os.getpid(), payload))
     os.makedirs(os.path.dirname(extras), exist_ok=True)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--dist-backend", "nccl", "--scale", "0.00003",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--dist-backend", "nccl", "--scale", "0.00003",
                           "--steps", "4", "--warmup", "1", "--parity-sample", "5000", "--payload", payload, "--no-c5", "--extras-file", extras,
                           "--exchange", "gather" if payload == "auto" else "allgather"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)

@@ -22,7 +22,7 @@ wanted() { case " $PASSES " in *" $1 "*) return 0;; *) return 1;; esac; }
 
 if wanted stats; then
 echo "[profile] kernel-trace + stats" >&2
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" "$@" $LEAN --steps 10 --warmup 2 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" --full "$@" $LEAN --steps 10 --warmup 2 \
     > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 fi
 
