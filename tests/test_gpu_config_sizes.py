@@ -17,6 +17,8 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 NCPU = min(os.cpu_count() or 1, 16)
+# device_bytes() of the human-scale index in run blocks with its depth-23 sparse table, as the test prints it (70.25 GB); it wants a quarter more free
+RUN_INDEX_BYTES = 70_250_000_000
 
 
 def _torch():
@@ -37,6 +39,36 @@ def _count_matrix(torch, dev, bwt, d_q):
 def _revcomp(codes):
     comp = np.array([0, 5, 3, 2, 4, 1], dtype=np.uint8)  # string_util.rs:12
     return np.ascontiguousarray(comp[codes[:, ::-1]])
+
+
+def _oracle_ranges_and_extensions(ref, q, suffixes=()):
+    """{k': (l, h, ext)} for k' = k and every suffix length in `suffixes`, by the oracle alone: its constrain_range, last symbol first
+    (the range after t steps is the range of the last t symbols), empty ranges as (0, 0); ext[:, c] = the width of
+    constrain_range(c, l, h), the count of c . row."""
+    n, k = q.shape
+    l = np.zeros(n, dtype=np.uint64)
+    h = np.full(n, ref.get_total_size(), dtype=np.uint64)
+    out = {}
+    for t in range(k + 1):
+        if t == k or t in suffixes:
+            bounds = [ref.constrain_ranges(np.full(n, c, dtype=np.uint8), l, h) for c in range(6)]
+            ext = np.stack([bh - bl for bl, bh in bounds], axis=1)
+            el, eh = l.copy(), h.copy()
+            el[l == h] = 0
+            eh[l == h] = 0
+            out[t] = (el, eh, ext)
+        if t < k:
+            l, h = ref.constrain_ranges(np.ascontiguousarray(q[:, k - 1 - t]), l, h)
+    return out
+
+
+def _check_ranges_and_extensions(bwt, q, expected, what):
+    el, eh, eext = expected
+    l, h = bwt.kmer_ranges(q)
+    ext = bwt.count_kmer_extensions(q)
+    assert np.array_equal(l, el) and np.array_equal(h, eh), what
+    assert np.array_equal(ext, eext), what
+    assert np.array_equal(bwt.count_kmers(q), eh - el) and np.array_equal(ext.sum(axis=1), eh - el), what
 
 
 def test_c3_full_all_read_kmers_fused_both_strands():
@@ -227,7 +259,12 @@ def test_human_scale_9e10_symbols_against_the_oracle():
     beyond 2^36, 40-bit header counts with high bytes up to 20, the full index: sparse suffix table of depth 23 -- and, with it switched off, the 238 GB index of
     rounds 2-4 with its depth-17 packed table --, overlapping pair blocks addressed at human scale): 2e6 present (LF-walk) +
     2e6 random 31-mers under both search kernels, and 1e6 batched constrain_range calls with l, h > 2^36, all
-    against the oracle on the same stream.  Needs ~250 GB of HBM and ~20 GB of host memory; about two minutes."""
+    against the oracle on the same stream.  Then ranges and left-extension counts -- here every symbol's header counts have high bytes of
+    their own -- of 2e5 of these 31-mers, their suffixes of 15 / 16 / 17 / 23 symbols and all ACGT k-mers of k = 1..6, under both kernels, with
+    k undeclared and declared; MSBWT_ERR_OVERFLOW from the packed path's 32-bit counts for k = 1, 2; and the same 31-mers and 1e5 59-mers on
+    the index in run blocks behind a sparse table (70.25 GB; loaded once the plane index is freed, skipped below 88 GB of free HBM).
+    Needs ~250 GB of HBM and ~20 GB of host memory; 142 s on an MI355X, 22 s of them for the ranges, extensions and run blocks (this file:
+    241 s before them, 250 s with them)."""
     import synth
     sys.path.insert(0, ROOT)
     import bench
@@ -337,3 +374,62 @@ def test_human_scale_9e10_symbols_against_the_oracle():
     ol, oh = ref.constrain_ranges(syms, a, b)
     assert np.array_equal(gl, ol) and np.array_equal(gh, oh)
     assert int(gl.max()) > 2**36
+
+    # ---- ranges and left-extension counts at this size.  Here every symbol's header counts have high bytes of their own (A 0..5, C 5..10,
+    # G 10..15, T 15..20): two symbols' bytes mixed up, invisible at 6e9 symbols (tests/test_gpu_beyond_32_bits.py), give wrong bounds here.
+    # 1e5 present + 1e5 absent 31-mers, their suffixes of 15 / 16 / 17 / 23 symbols, and all ACGT k-mers of k = 1..6
+    t0 = time.time()
+    q31 = np.ascontiguousarray(np.concatenate([q[:100_000], q[2_000_000:2_100_000]]))
+    by_depth = _oracle_ranges_and_extensions(ref, q31, suffixes=(15, 16, 17, 23))
+    sets = {kk: (np.ascontiguousarray(q31[:, k - kk:]), by_depth[kk]) for kk in (31, 15, 16, 17, 23)}
+    acgt = np.array([1, 2, 3, 5], dtype=np.uint8)
+    for kk in range(1, 7):
+        every = np.ascontiguousarray(acgt[(np.arange(4 ** kk)[:, None] >> (2 * np.arange(kk - 1, -1, -1))[None, :]) & 3])
+        sets[kk] = (every, _oracle_ranges_and_extensions(ref, every)[kk])
+    l31 = by_depth[31][0][:100_000]
+    assert np.array_equal(by_depth[31][1] - by_depth[31][0], exp[np.r_[0:100_000, 2_000_000:2_100_000]])
+    beyond = float((l31 >= 2**36).mean())
+    print("present 31-mers with l >= 2^36: %.1f %%; oracle ranges and extensions: %.1f s" % (100 * beyond, time.time() - t0))
+    assert beyond >= 0.20, beyond
+    for declared in (0, 31):
+        bwt.set_query_length(declared)
+        assert bwt.get_sparse_table() == (31 if declared else 23)
+        for mode in ("lanes", "groups"):
+            bwt.set_search_kernel(mode)
+            for kk, (qs, expected) in sets.items():
+                _check_ranges_and_extensions(bwt, qs, expected, (declared, mode, kk))
+    # packed queries with 32-bit counts: a 1-mer or 2-mer occurs more than 2^32 times -- reported, not truncated
+    for kk in (1, 2):
+        words = msbwt.rle_bwt.pack_2bit(sets[kk][0])
+        counts = sets[kk][1][1] - sets[kk][1][0]
+        assert counts.min() >= 2**32 and np.array_equal(counts, ref.count_kmers(sets[kk][0], nthreads=NCPU))
+        with pytest.raises(msbwt.rle_bwt.MsbwtError) as err:
+            bwt.count_kmers_packed(words, kk, count_bits=32)
+        assert err.value.code == msbwt._lib.ERR_OVERFLOW, str(err.value)
+        assert np.array_equal(bwt.count_kmers_packed(words, kk), counts)
+    got32 = bwt.count_kmers_packed(msbwt.rle_bwt.pack_2bit(sets[16][0]), 16, count_bits=32)
+    assert got32.dtype == np.uint32 and np.array_equal(got32.astype(np.uint64), sets[16][1][1] - sets[16][1][0])
+    print("ranges, extensions and packed counts at human scale: %.1f s" % (time.time() - t0))
+    # ---- run blocks at this size (MSBWT_BLOCKS=runs: 40-bit header counts with every high byte in use, run blocks behind a sparse table):
+    # the plane index goes first -- the two do not fit side by side
+    t0 = time.time()
+    long_q = np.ascontiguousarray(long_q[:100_000].cpu().numpy())
+    exp59 = _oracle_ranges_and_extensions(ref, long_q)[59]
+    handle, bwt._h = bwt._h, None   # freed now, whoever still refers to the object (pytest.raises keeps the frames of the call that raised)
+    msbwt._lib.lib().msbwt_rle_free(handle)
+    del bwt, d_q, present, absent, mut, err
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info(dev)
+    if free < RUN_INDEX_BYTES + RUN_INDEX_BYTES // 4:
+        pytest.skip("the run-block part needs %.0f GB of free HBM" % (1.25 * RUN_INDEX_BYTES / 1e9))
+    runs = RleBWT(device=0)
+    runs.set_block_format("runs")
+    runs.load_vector(rle)
+    print("run blocks at human scale: device_bytes() = %.2f GB, sparse depth %d, loaded in %.1f s" % (runs.device_bytes() / 1e9, runs.get_sparse_table(), time.time() - t0))
+    assert runs.get_block_format() == "runs" and runs.get_total_size() == total and not runs.get_pair_index()
+    assert runs.get_sparse_table() >= 16
+    for mode in ("lanes", "groups"):
+        runs.set_search_kernel(mode)
+        _check_ranges_and_extensions(runs, sets[31][0], sets[31][1], ("runs", mode, 31))
+        _check_ranges_and_extensions(runs, long_q, exp59, ("runs", mode, 59))
+    print("run blocks at human scale: %.1f s" % (time.time() - t0))
