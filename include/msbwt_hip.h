@@ -163,6 +163,37 @@ int msbwt_rle_count_ragged_read_kmers(const msbwt_rle *bwt, const uint8_t *reads
                                       size_t n_reads, size_t k, int ascii, uint64_t *out_fwd, uint64_t *out_rc,
                                       uint64_t *out_windows);
 
+/* ---- construction: the multi-string BWT of a read set, built on the device ----
+ * DynamicBWT::create_from_fastx (src/dynamic_bwt.rs:453-473) with the semantics of naive_bwt (src/bwt_util.rs:154-171): the
+ * text is every read followed by '$', its suffixes sorted with $ < A < C < G < N < T, suffixes that are equal up to and
+ * including their '$' ordered by the rank of their reads; row i is the symbol before suffix i.  The entry points use the
+ * handle's device, stream, mutex and msbwt_rle_last_error; the handle need not hold an index.
+ *
+ * reads: read r is reads[read_offsets[r] .. read_offsets[r+1]); ascii != 0: bytes as string_util.rs:15-32 maps them
+ * (A/a C/c G/g T/t, anything else N; '$' is an error), ascii == 0: symbol codes 1..5.
+ * out_rle/cap: caller's buffer; read_offsets[n_reads] + n_reads bytes always suffice.  *out_len: bytes written -- or,
+ * with MSBWT_ERR_INVALID_ARG and nothing written, the bytes needed when cap is too small.
+ * Checked on the host before anything is launched: null pointers with n_reads > 0 or decreasing offsets
+ * (MSBWT_ERR_INVALID_ARG), 2^40 symbols or more (MSBWT_ERR_TOO_LARGE), a code 0 or >= 6 / a '$' (MSBWT_ERR_INVALID_SYMBOL).
+ * n_reads == 0 is the empty BWT.  A piece that does not fit HBM: MSBWT_ERR_HIP, the message names the piece size. */
+int msbwt_rle_build_from_reads(msbwt_rle *bwt, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads,
+                               int ascii, uint8_t *out_rle, size_t cap, uint64_t *out_len);
+/* The same build, then the result loaded exactly as msbwt_rle_load_vector would load those bytes (an index the handle
+ * holds is released before the build: its HBM is the builder's to use). */
+int msbwt_rle_load_reads(msbwt_rle *bwt, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii);
+/* Most suffixes sorted at once (0 = automatic, from the free HBM); env MSBWT_BUILD_PIECE.  Results never depend on it. */
+int msbwt_rle_set_build_piece(msbwt_rle *bwt, uint64_t suffixes);
+/* Pure function, no device: HBM bytes the build of `total_symbols` symbols needs with pieces of `piece` suffixes
+ * (0 = the automatic piece), and the automatic piece for `free_hbm_bytes`.  Either output may be NULL. */
+int msbwt_build_reads_plan(uint64_t total_symbols, uint64_t free_hbm_bytes, uint64_t piece, uint64_t *auto_piece,
+                           uint64_t *device_bytes);
+/* Suffixes one workgroup ranks and scatters per radix pass of the builder (tests probe its borders). */
+size_t msbwt_build_reads_sort_tile(void);
+/* Milliseconds the stages of the handle's last build took (host clock, the stream drained at every stage border):
+ * copy in, read order, histogram, collect, sort, emit, encode, copy out; *out_pieces (optional): pieces sorted. */
+#define MSBWT_BUILD_STAGES 8
+int msbwt_rle_build_stage_ms(const msbwt_rle *bwt, double *out_ms, uint64_t *out_pieces);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

@@ -97,6 +97,29 @@ class RleBWT final : public BWT {
         return out;
     }
 
+    // ---- construction from reads (DynamicBWT::create_from_fastx, src/dynamic_bwt.rs:453-473; naive_bwt's semantics) ----
+    /// RLE bytes of the multi-string BWT of the reads: read r is reads[offsets[r] .. offsets[r + 1]), symbol codes 1..5 or, with
+    /// `ascii`, text as string_util::convert_stoi maps it.  Built on the GPU; the handle's own index stays as it is.
+    std::vector<std::uint8_t> build_from_reads(const std::vector<std::uint8_t> &reads, const std::vector<std::uint64_t> &offsets, bool ascii = false) {
+        if (offsets.empty()) return {};
+        const std::size_t n = offsets.size() - 1;
+        std::vector<std::uint8_t> out(static_cast<std::size_t>(offsets[n] - offsets[0]) + n + 1);
+        std::uint64_t len = 0;
+        static const std::uint8_t none = 0;
+        check(msbwt_rle_build_from_reads(raw_, reads.empty() ? &none : reads.data(), offsets.data(), n, ascii ? 1 : 0, out.data(), out.size(), &len));
+        out.resize(static_cast<std::size_t>(len));
+        return out;
+    }
+    /// build_from_reads, then the result loaded as load_vector would load it.
+    void load_reads(const std::vector<std::uint8_t> &reads, const std::vector<std::uint64_t> &offsets, bool ascii = false) {
+        static const std::uint8_t none = 0;
+        static const std::uint64_t zero = 0;
+        check(msbwt_rle_load_reads(raw_, reads.empty() ? &none : reads.data(), offsets.empty() ? &zero : offsets.data(), offsets.empty() ? 0 : offsets.size() - 1,
+                                   ascii ? 1 : 0));
+    }
+    /// Most suffixes the builder sorts at once (0 = automatic, from the free HBM); results never depend on it.
+    void set_build_piece(std::uint64_t suffixes) { check(msbwt_rle_set_build_piece(raw_, suffixes)); }
+
     // ---- batch forms (the GPU entry points proper) ----
     /// kmers: n x k symbol codes, row-major.
     std::vector<std::uint64_t> count_kmers(const std::vector<std::uint8_t> &kmers, std::size_t k) const {

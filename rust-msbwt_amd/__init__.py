@@ -7,15 +7,16 @@ The directory name carries a hyphen (it is fixed by the project layout), so impo
 or through the `rust_msbwt_amd` alias module at the repo root.
 
 Modules mirror the reference crate: msbwt_core (BWTRange, constants, BWT), rle_bwt (RleBWT),
-string_util, bwt_converter.  Everything that computes runs in libmsbwt_hip.so.
+string_util, bwt_converter, dynamic_bwt (create_from_fastx).  Everything that computes runs in libmsbwt_hip.so.
 """
 from . import _lib
 from .msbwt_core import BWT, BWTRange, VC_LEN, LETTER_BITS, NUMBER_BITS, NUM_POWER, MASK, COUNT_MASK
 from .rle_bwt import RleBWT, MsbwtError, RankComm
-from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded
+from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_bwt
+from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -58,3 +59,19 @@ def auto_index_plan(total_symbols, free_hbm_bytes, hbm_total_bytes, typical_widt
         raise MsbwtError(rc, "msbwt_auto_index_plan")
     return {"pair_index": bool(pair.value), "pair_stride": stride.value, "flat_depth": flat.value, "packed_depth": packed.value, "index_bytes": size.value}
 
+
+
+def build_reads_plan(total_symbols, free_hbm_bytes, piece=0):
+    """(automatic piece for that much free HBM, HBM bytes the build of `total_symbols` symbols needs with pieces of `piece` suffixes;
+    0 = the automatic piece).  Pure host logic (csrc/reads_build.hip, plan_reads_build)."""
+    import ctypes
+    auto, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_build_reads_plan(int(total_symbols), int(free_hbm_bytes), int(piece), ctypes.byref(auto), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_build_reads_plan")
+    return auto.value, size.value
+
+
+def build_reads_sort_tile():
+    """Suffixes one workgroup ranks and scatters per radix pass of the builder."""
+    return int(_lib.lib().msbwt_build_reads_sort_tile())

@@ -12,6 +12,7 @@ ERR_INVALID_RANGE, ERR_HIP, ERR_NOT_LOADED, ERR_TOO_LARGE, ERR_INVALID_ARG, ERR_
 ERR_OVERFLOW, ERR_RCCL = -11, -12
 COMM_ID_BYTES = 128
 SPARSE_INFO_WORDS = 120  # MSBWT_SPARSE_INFO_WORDS
+BUILD_STAGES = ("copy_in", "read_order", "histogram", "collect", "sort", "emit", "encode", "copy_out")  # MSBWT_BUILD_STAGES
 
 SIZE_MAX = C.c_size_t(-1).value
 
@@ -40,6 +41,12 @@ SIGNATURES = {
     "msbwt_rle_count_read_kmers": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _vp, _vp]),
     "msbwt_rle_count_ragged_read_kmers": (_int, [_vp, _vp, _vp, _sz, _sz, _int, _vp, _vp, _pu64]),
     "msbwt_rle_count_read_kmers_device": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _vp, _vp, _vp]),
+    "msbwt_rle_build_from_reads": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _sz, _pu64]),
+    "msbwt_rle_load_reads": (_int, [_vp, _vp, _vp, _sz, _int]),
+    "msbwt_rle_set_build_piece": (_int, [_vp, _u64]),
+    "msbwt_build_reads_plan": (_int, [_u64, _u64, _u64, _pu64, _pu64]),
+    "msbwt_build_reads_sort_tile": (_sz, []),
+    "msbwt_rle_build_stage_ms": (_int, [_vp, C.POINTER(C.c_double), _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

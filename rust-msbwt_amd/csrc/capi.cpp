@@ -24,6 +24,7 @@
 #include "order.hpp"
 #include "pair_index.hpp"
 #include "plane_index.hpp"
+#include "reads_build.hpp"
 #include "rle_codec.hpp"
 #include "run_build.hpp"
 #include "run_index.hpp"
@@ -110,6 +111,7 @@ struct Settings {
     int search_kernel = kSearchAuto;
     int wanted_order = -1;          // batch order: 1 = whenever the passes apply; 0 and -1 (automatic: see order_pays) = never
     int order_bits = 22;            // key bits the bucket passes order by (11 in the global pass + 11 inside each bucket)
+    uint64_t build_piece = 0;       // most suffixes the builder from reads sorts at once (0 = automatic, from the free HBM)
     uint64_t memory_budget = 0;     // bytes of HBM the index may hold (0 = no budget): msbwt_rle_set_memory_budget
     bool planned = false;           // a budget is in force: `plan` (table_policy.hpp, plan_index) decides the optional structures
     IndexPlan plan{};
@@ -170,6 +172,8 @@ struct msbwt_rle : Settings {
     std::vector<hipEvent_t> events;  // start/stop pairs not yet read back
     double timed_ms = 0.0;
     uint64_t timed_launches = 0;
+    double build_ms[kReadsBuildStages] = {};  // the stages of the last build from reads
+    uint64_t build_pieces = 0;
     std::mutex mu;
     std::string err;
 };
@@ -182,6 +186,7 @@ constexpr uint64_t kStreamLinesFrom = uint64_t(4) << 30;  // random-access array
 constexpr size_t kStatusBytes = 1024;  // flag words, debug record (bytes 64..128), search counters (bytes 128..256)
 constexpr size_t kCountersOffset = 128;
 static_assert(MSBWT_SEARCH_COUNTERS == kSearchCounters, "the header's counter block is the kernels'");
+static_assert(MSBWT_BUILD_STAGES == kReadsBuildStages, "the header's stage count is the builder's");
 static_assert(10 + kSparseMaxDepth + 1 <= 42 && 45 + kSparseMaxDepth + 1 <= 80 && 80 + kSparseMaxDepth + 1 <= MSBWT_SPARSE_INFO_WORDS,
               "msbwt_rle_sparse_table_info: [10 + d] distinct, [42] filtered, [45 + d] wide, [80 + d] once");
 constexpr size_t kPackScratchOffset = 256;  // two u64 of the table packer (escape-line count, side-array cursor)
@@ -1415,6 +1420,62 @@ int mailbox_call(msbwt_rle *h, IndexView &v, bool poll, Launch &&launch, CopyOut
     return copy_out() ? status_of(h, h->stream, kHostFlags) : MSBWT_OK;
 }
 
+// The host-side checks of a read set (msbwt_rle_build_from_reads): nothing is launched before they pass.  *total = symbols of the
+// text, every read's '$' included.
+int check_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii, uint64_t *total) {
+    *total = 0;
+    if (n_reads == 0) return MSBWT_OK;
+    if (!reads || !read_offsets) return fail(h, MSBWT_ERR_INVALID_ARG, "reads and read_offsets must not be null");
+    for (size_t r = 0; r < n_reads; ++r)
+        if (read_offsets[r + 1] < read_offsets[r]) return fail(h, MSBWT_ERR_INVALID_ARG, "read_offsets decrease at read " + std::to_string(r));
+    const uint64_t lo = read_offsets[0], nbytes = read_offsets[n_reads] - lo;
+    if (nbytes >= (1ull << 40) || nbytes + n_reads >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the read set has 2^40 symbols or more");
+    // ASCII: every byte but '$' has a code (string_util.rs:15-32); codes: 1..5.  Large sets are checked by a few threads.
+    auto bad_in = [&](uint64_t from, uint64_t to) {
+        unsigned bad = 0;
+        if (ascii) for (uint64_t i = from; i < to; ++i) bad |= reads[lo + i] == '$';
+        else for (uint64_t i = from; i < to; ++i) bad |= uint8_t(reads[lo + i] - 1u) > 4u;
+        return bad != 0;
+    };
+    const unsigned workers = unsigned(std::min<uint64_t>(8, nbytes >> 24) + 1);
+    std::atomic<bool> bad{false};
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < workers; ++t)
+        pool.emplace_back([&, t] { if (bad_in(nbytes * t / workers, nbytes * (t + 1) / workers)) bad = true; });
+    if (bad_in(0, nbytes / workers)) bad = true;
+    for (auto &th : pool) th.join();
+    if (bad) return fail(h, MSBWT_ERR_INVALID_SYMBOL, ascii ? "a read holds '$'" : "a read holds a symbol code outside 1..5");
+    *total = nbytes + n_reads;
+    return MSBWT_OK;
+}
+
+// The build itself, on the handle's device and stream: the RLE bytes stay in HBM (out->d_rle, the caller frees them).
+int build_reads_on_device(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii, uint64_t total, ReadsBuildOutput *out) {
+    if (int rc = ensure_runtime(h)) return rc;
+    size_t free_bytes = 0, all_bytes = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+    const uint64_t piece = h->build_piece ? h->build_piece : plan_reads_build(total, free_bytes, 0).auto_piece;
+    const char *wide = std::getenv("MSBWT_BUILD_WIDE");  // 64-bit positions below 2^32 symbols too (tests)
+    const hipError_t e = build_rle_from_reads(reads, read_offsets, n_reads, ascii != 0, piece, wide && std::atoi(wide), h->stream, out);
+    std::copy(out->stage_ms, out->stage_ms + kReadsBuildStages, h->build_ms);
+    h->build_pieces = out->pieces;
+    if (std::getenv("MSBWT_VERBOSE"))
+        std::fprintf(stderr, "[msbwt] build: %llu symbols, %llu pieces of at most %llu suffixes (limit %llu)\n", (unsigned long long)total,
+                     (unsigned long long)out->pieces, (unsigned long long)out->largest_piece, (unsigned long long)piece);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, "build from reads: " + out->what + ": " + hipGetErrorString(e));
+    }
+    return MSBWT_OK;
+}
+
+struct OwnedDevice {  // a build's RLE bytes in HBM, freed at scope exit
+    ReadsBuildOutput out;
+    ~OwnedDevice() {
+        if (out.d_rle) (void)hipFree(out.d_rle);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1444,6 +1505,7 @@ msbwt_rle *msbwt_rle_new_on_device(uint8_t bin_power, int device) {
     if (const char *env = std::getenv("MSBWT_BLOCKS")) h->wanted_block_format = std::strcmp(env, "runs") == 0 ? kBlocksRuns : kBlocksPlanes;
     if (const char *env = std::getenv("MSBWT_MEMORY_BUDGET")) h->memory_budget = std::strtoull(env, nullptr, 10);
     if (const char *env = std::getenv("MSBWT_ORDER")) h->wanted_order = std::strcmp(env, "auto") == 0 ? -1 : (std::atoi(env) ? 1 : 0);
+    if (const char *env = std::getenv("MSBWT_BUILD_PIECE")) h->build_piece = std::strtoull(env, nullptr, 10);
     if (const char *env = std::getenv("MSBWT_ORDER_BITS")) h->order_bits = std::max(1, std::min(std::atoi(env), 36));
     if (const char *env = std::getenv("MSBWT_SEARCH"))
         h->search_kernel = std::strcmp(env, "groups") == 0 ? kSearchGroups : std::strcmp(env, "lanes") == 0 ? kSearchLanes : kSearchAuto;
@@ -1493,6 +1555,74 @@ int msbwt_rle_load_numpy_file(msbwt_rle *h, const char *utf8_path) {
         case NpyStatus::kBadHeader: return fail(h, MSBWT_ERR_BAD_HEADER, msg);
     }
     return install(h, payload.data(), payload.size());
+}
+
+int msbwt_rle_build_from_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii, uint8_t *out_rle, size_t cap,
+                               uint64_t *out_len) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out_len || (!out_rle && cap)) return fail(h, MSBWT_ERR_INVALID_ARG, "out_len must not be null, nor out_rle with a capacity");
+    *out_len = 0;
+    uint64_t total = 0;
+    if (int rc = check_reads(h, reads, read_offsets, n_reads, ascii, &total)) return rc;
+    std::fill(h->build_ms, h->build_ms + kReadsBuildStages, 0.0);
+    h->build_pieces = 0;
+    if (n_reads == 0) return MSBWT_OK;  // the empty BWT
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    OwnedDevice built;
+    if (int rc = build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, &built.out)) return rc;
+    *out_len = built.out.rle_bytes;
+    if (built.out.rle_bytes > cap)
+        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the BWT takes " + std::to_string(built.out.rle_bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(h, hipMemcpyAsync(out_rle, built.out.d_rle, built.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->build_ms[kStageCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->err.clear();
+    return MSBWT_OK;
+}
+
+int msbwt_rle_load_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    uint64_t total = 0;
+    if (int rc = check_reads(h, reads, read_offsets, n_reads, ascii, &total)) return rc;
+    std::vector<uint8_t> rle;
+    if (n_reads) {
+        DeviceScope scope(h->device);
+        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+        release_index(h);  // its HBM is the builder's to use
+        OwnedDevice built;
+        if (int rc = build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, &built.out)) return rc;
+        rle.resize(size_t(built.out.rle_bytes));
+        HIP_TRY(h, hipMemcpyAsync(rle.data(), built.out.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+}
+
+int msbwt_rle_set_build_piece(msbwt_rle *h, uint64_t suffixes) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    return set_locked(h, h->build_piece, suffixes);
+}
+
+int msbwt_build_reads_plan(uint64_t total_symbols, uint64_t free_hbm_bytes, uint64_t piece, uint64_t *auto_piece, uint64_t *device_bytes) {
+    if (total_symbols >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    const ReadsBuildPlan p = plan_reads_build(total_symbols, free_hbm_bytes, piece);
+    if (auto_piece) *auto_piece = p.auto_piece;
+    if (device_bytes) *device_bytes = p.device_bytes;
+    return MSBWT_OK;
+}
+
+size_t msbwt_build_reads_sort_tile(void) { return kReadsSortTile; }
+
+int msbwt_rle_build_stage_ms(const msbwt_rle *ch, double *out_ms, uint64_t *out_pieces) {
+    Call c(ch);
+    if (!c.h || !out_ms) return MSBWT_ERR_INVALID_ARG;
+    std::copy(c.h->build_ms, c.h->build_ms + kReadsBuildStages, out_ms);
+    if (out_pieces) *out_pieces = c.h->build_pieces;
+    return MSBWT_OK;
 }
 
 uint64_t msbwt_rle_get_symbol_count(const msbwt_rle *h, uint8_t symbol) {

@@ -31,6 +31,30 @@ def _raise(code, handle):
     raise MsbwtError(code, msg)
 
 
+def pack_reads(reads, ascii=False):
+    """A read set as the C ABI takes it: (flat uint8 array, uint64 offsets[n + 1]).  `reads`: a sequence of reads -- each a str or
+    bytes of "ACGTN..." (ascii=True) or an array / bytes of symbol codes 1..5 -- or such a (flat, offsets) pair itself."""
+    if isinstance(reads, tuple) and len(reads) == 2 and not isinstance(reads[0], (str, bytes, bytearray)) and np.ndim(reads[1]) == 1 \
+            and np.asarray(reads[1]).dtype.kind in "ui" and np.ndim(reads[0]) == 1 and len(reads[1]) >= 1:
+        flat = np.ascontiguousarray(reads[0], dtype=np.uint8)
+        offsets = np.ascontiguousarray(reads[1], dtype=np.uint64)
+    else:
+        parts = []
+        for r in reads:
+            if isinstance(r, str):
+                if not ascii:
+                    raise TypeError("a str read needs ascii=True; symbol codes come as bytes or arrays")
+                r = r.encode()
+            parts.append(np.frombuffer(bytes(r), dtype=np.uint8) if isinstance(r, (bytes, bytearray)) else np.ascontiguousarray(r, dtype=np.uint8).ravel())
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size for p in parts], out=offsets[1:])
+        flat = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
+    if flat.size == 0:
+        flat = np.zeros(1, dtype=np.uint8)  # (a pointer the library may not be handed as null)
+    return flat, offsets
+
+
 class RleBWT(BWT):
     def __init__(self, bin_power=8, device=-1):
         """RleBWT::new() / with_bin_power (rle_bwt.rs:297-322). `device` = HIP ordinal."""
@@ -87,6 +111,46 @@ class RleBWT(BWT):
         if rc:
             _raise(rc, self._h)
         return int(out.value)
+
+    # ---- construction from reads (DynamicBWT::create_from_fastx, src/dynamic_bwt.rs:453-473, built on the device) ----
+    def build_from_reads(self, reads, ascii=False):
+        """The RLE bytes (np.uint8[]) of the multi-string BWT of `reads` (pack_reads says what a read set may look like), with the
+        semantics of naive_bwt (src/bwt_util.rs:154-171).  The handle's own index, if it has one, stays as it is."""
+        flat, offsets = pack_reads(reads, ascii)
+        n = offsets.size - 1
+        cap = int(offsets[-1] - offsets[0]) + n
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        length = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_build_from_reads(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n,
+                                                   1 if ascii else 0, out.ctypes.data_as(C.c_void_p), cap, C.byref(length))
+        if rc:
+            _raise(rc, self._h)
+        return out[:length.value]
+
+    def load_reads(self, reads, ascii=False):
+        """build_from_reads, then the result loaded as load_vector would load it."""
+        flat, offsets = pack_reads(reads, ascii)
+        rc = _lib.lib().msbwt_rle_load_reads(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), offsets.size - 1,
+                                             1 if ascii else 0)
+        if rc:
+            _raise(rc, self._h)
+
+    def set_build_piece(self, suffixes):
+        """Most suffixes the builder sorts at once (0 = automatic, from the free HBM).  Results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_build_piece(self._h, int(suffixes))
+        if rc:
+            _raise(rc, self._h)
+
+    def build_stage_ms(self):
+        """{stage: milliseconds} of the last build on this handle, and "pieces"."""
+        ms = (C.c_double * len(_lib.BUILD_STAGES))()
+        pieces = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_build_stage_ms(self._h, ms, C.byref(pieces))
+        if rc:
+            _raise(rc, self._h)
+        out = {name: float(ms[i]) for i, name in enumerate(_lib.BUILD_STAGES)}
+        out["pieces"] = int(pieces.value)
+        return out
 
     # ---- batch forms -----------------------------------------------------------------
     def count_kmers(self, kmers, out=None):

@@ -47,6 +47,14 @@ extern "C" {
                                        out_counts: *mut u64) -> c_int;
     fn msbwt_rle_count_kmer_extensions_device(bwt: *const MsbwtRle, d_kmers: *const c_void, k: usize, n: usize,
                                               d_out_counts: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    // construction: the multi-string BWT of a read set, built on the device
+    fn msbwt_rle_build_from_reads(bwt: *mut MsbwtRle, reads: *const u8, read_offsets: *const u64, n_reads: usize,
+                                  ascii: c_int, out_rle: *mut u8, cap: usize, out_len: *mut u64) -> c_int;
+    fn msbwt_rle_load_reads(bwt: *mut MsbwtRle, reads: *const u8, read_offsets: *const u64, n_reads: usize,
+                            ascii: c_int) -> c_int;
+    fn msbwt_rle_set_build_piece(bwt: *mut MsbwtRle, suffixes: u64) -> c_int;
+    fn msbwt_build_reads_plan(total_symbols: u64, free_hbm_bytes: u64, piece: u64, auto_piece: *mut u64,
+                              device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -144,6 +152,54 @@ impl GpuRleBWT {
         let rc = unsafe { msbwt_rle_count_kmer_extensions(self.raw, kmers.as_ptr(), k, n, out.as_mut_ptr() as *mut u64) };
         if rc != MSBWT_OK { panic!("count_kmer_extensions: {}", self.last_error()); }
         out
+    }
+
+    /// The RLE bytes of the multi-string BWT of `reads` (symbol codes 1..5 each), built on the GPU with the semantics of
+    /// `bwt_util::naive_bwt`: what `DynamicBWT::create_from_fastx` + `save_bwt_numpy` produce.  The handle's index is untouched.
+    pub fn build_from_reads(&mut self, reads: &[&[u8]]) -> Vec<u8> {
+        let (flat, offsets) = Self::pack_reads(reads);
+        let cap = flat.len() + reads.len();
+        let mut out = vec![0u8; cap.max(1)];
+        let mut len = 0u64;
+        let rc = unsafe {
+            msbwt_rle_build_from_reads(self.raw, flat.as_ptr(), offsets.as_ptr(), reads.len(), 0, out.as_mut_ptr(), cap, &mut len)
+        };
+        if rc != MSBWT_OK { panic!("build_from_reads: {}", self.last_error()); }
+        out.truncate(len as usize);
+        out
+    }
+
+    /// `build_from_reads`, then the result loaded as `load_vector` would load it.
+    pub fn load_reads(&mut self, reads: &[&[u8]]) {
+        let (flat, offsets) = Self::pack_reads(reads);
+        let rc = unsafe { msbwt_rle_load_reads(self.raw, flat.as_ptr(), offsets.as_ptr(), reads.len(), 0) };
+        if rc != MSBWT_OK { panic!("load_reads: {}", self.last_error()); }
+    }
+
+    /// Most suffixes the builder sorts at once (0 = automatic, from the free HBM); results never depend on it.
+    pub fn set_build_piece(&mut self, suffixes: u64) {
+        let rc = unsafe { msbwt_rle_set_build_piece(self.raw, suffixes) };
+        if rc != MSBWT_OK { panic!("set_build_piece: {}", self.last_error()); }
+    }
+
+    /// (automatic piece for that much free HBM, HBM bytes the build needs with pieces of `piece` suffixes); no device involved.
+    pub fn build_reads_plan(total_symbols: u64, free_hbm_bytes: u64, piece: u64) -> (u64, u64) {
+        let (mut auto_piece, mut bytes) = (0u64, 0u64);
+        let rc = unsafe { msbwt_build_reads_plan(total_symbols, free_hbm_bytes, piece, &mut auto_piece, &mut bytes) };
+        if rc != MSBWT_OK { panic!("build_reads_plan: error {}", rc); }
+        (auto_piece, bytes)
+    }
+
+    fn pack_reads(reads: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+        let mut flat = Vec::with_capacity(reads.iter().map(|r| r.len()).sum::<usize>() + 1);
+        let mut offsets = Vec::with_capacity(reads.len() + 1);
+        offsets.push(0u64);
+        for r in reads {
+            flat.extend_from_slice(r);
+            offsets.push(flat.len() as u64);
+        }
+        if flat.is_empty() { flat.push(0); } // (never a dangling pointer across the ABI)
+        (flat, offsets)
     }
 
     /// Batch form of `constrain_range`.
