@@ -194,6 +194,37 @@ size_t msbwt_build_reads_sort_tile(void);
 #define MSBWT_BUILD_STAGES 8
 int msbwt_rle_build_stage_ms(const msbwt_rle *bwt, double *out_ms, uint64_t *out_pieces);
 
+/* ---- merge: two multi-string BWTs -> the BWT of the union of their read sets, on the device ----
+ * bwt_util::pairwise_bwt_merge (src/bwt_util.rs:21-141), the interleave iteration of Holt & McMillan 2014: no reads and no
+ * suffix sort, the two symbol arrays and a bit per merged row.  The entry points use the handle's device, stream, mutex and
+ * msbwt_rle_last_error; the handle need not hold an index.
+ *
+ * rle0 / rle1: RLE bytes as msbwt_rle_load_vector takes them; a run may span any number of bytes and hold zero digits, the
+ * encoding need not be the canonical one.  Either may be empty (len 0, the pointer may be NULL); two empty inputs give the
+ * empty BWT without touching the device.
+ * out_rle/cap: caller's buffer, the canonical encoding (what convert_to_vec gives); len0 + len1 bytes always suffice for
+ * canonical inputs.  *out_len: bytes written -- or, with MSBWT_ERR_INVALID_ARG and nothing written, the bytes needed when cap
+ * is too small.
+ * out_from_second (optional): ceil(total / 8) bytes; bit i & 7 of byte i >> 3 is set when merged row i came from rle1.  Rows
+ * of equal rotations: those of rle0 first.
+ * Checked on the host before anything is launched: a null input with a length, a null out_len (MSBWT_ERR_INVALID_ARG), a
+ * symbol code >= 6 (MSBWT_ERR_INVALID_SYMBOL), a merged total of 2^40 symbols or more (MSBWT_ERR_TOO_LARGE).  HBM that does
+ * not suffice: MSBWT_ERR_HIP, the message names the bytes needed (msbwt_merge_plan). */
+int msbwt_rle_merge(msbwt_rle *bwt, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1,
+                    uint8_t *out_rle, size_t cap, uint64_t *out_len, uint8_t *out_from_second);
+/* The same merge, then the result loaded exactly as msbwt_rle_load_vector would load those bytes (an index the handle
+ * holds is released before the merge: its HBM is the merge's to use). */
+int msbwt_rle_load_merged(msbwt_rle *bwt, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1);
+/* Pure function, no device: HBM bytes the merge of BWTs of total0 and total1 symbols needs, at most
+ * 2.5 x (total0 + total1) + 64 MiB.  MSBWT_ERR_TOO_LARGE from 2^40 merged symbols on. */
+int msbwt_merge_plan(uint64_t total0, uint64_t total1, uint64_t *device_bytes);
+/* Merged rows one workgroup counts and scatters per iteration (tests probe its borders). */
+size_t msbwt_merge_tile(void);
+/* The handle's last merge: its iterations (the last one found nothing to change) and the milliseconds of its stages (host
+ * clock, the stream drained at every stage border): copy in, decode, iterate, emit, encode, copy out.  Either may be NULL. */
+#define MSBWT_MERGE_STAGES 6
+int msbwt_rle_merge_info(const msbwt_rle *bwt, uint64_t *iterations, double *out_ms);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

@@ -120,6 +120,37 @@ class RleBWT final : public BWT {
     /// Most suffixes the builder sorts at once (0 = automatic, from the free HBM); results never depend on it.
     void set_build_piece(std::uint64_t suffixes) { check(msbwt_rle_set_build_piece(raw_, suffixes)); }
 
+    // ---- merge (bwt_util::pairwise_bwt_merge, src/bwt_util.rs:21-141, iterated on the GPU) ----
+    /// RLE bytes of the BWT of the union of the read sets behind the BWTs rle0 and rle1; rows of equal rotations: those of rle0
+    /// first.  from_second (optional): one bit per merged row, bit i & 7 of byte i >> 3 set = the row came from rle1.
+    std::vector<std::uint8_t> merge(const std::vector<std::uint8_t> &rle0, const std::vector<std::uint8_t> &rle1, std::vector<std::uint8_t> *from_second = nullptr) {
+        std::vector<std::uint8_t> out(rle0.size() + rle1.size() + 1);
+        std::uint64_t len = 0;
+        if (from_second) from_second->assign(static_cast<std::size_t>((symbols_of(rle0) + symbols_of(rle1) + 7) / 8) + 1, 0);
+        int rc = msbwt_rle_merge(raw_, rle0.data(), rle0.size(), rle1.data(), rle1.size(), out.data(), out.size(), &len, from_second ? from_second->data() : nullptr);
+        if (rc == MSBWT_ERR_INVALID_ARG && len > out.size()) {  // inputs that were not canonical
+            out.resize(static_cast<std::size_t>(len));
+            rc = msbwt_rle_merge(raw_, rle0.data(), rle0.size(), rle1.data(), rle1.size(), out.data(), out.size(), &len, from_second ? from_second->data() : nullptr);
+        }
+        check(rc);
+        out.resize(static_cast<std::size_t>(len));
+        return out;
+    }
+    /// merge, then the result loaded as load_vector would load it.
+    void load_merged(const std::vector<std::uint8_t> &rle0, const std::vector<std::uint8_t> &rle1) {
+        check(msbwt_rle_load_merged(raw_, rle0.data(), rle0.size(), rle1.data(), rle1.size()));
+    }
+    /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
+    static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
+        std::uint64_t total = 0;
+        unsigned place = 0;
+        for (std::size_t i = 0; i < rle.size() && total < (std::uint64_t(1) << 40); ++i) {
+            place = i && (rle[i] & MSBWT_MASK) == (rle[i - 1] & MSBWT_MASK) ? place + 1 : 0;
+            if (place < 8) total += std::uint64_t(rle[i] >> MSBWT_LETTER_BITS) << (MSBWT_NUMBER_BITS * place);
+        }
+        return total < (std::uint64_t(1) << 40) ? total : 0;
+    }
+
     // ---- batch forms (the GPU entry points proper) ----
     /// kmers: n x k symbol codes, row-major.
     std::vector<std::uint64_t> count_kmers(const std::vector<std::uint8_t> &kmers, std::size_t k) const {

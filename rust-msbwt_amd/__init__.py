@@ -7,16 +7,16 @@ The directory name carries a hyphen (it is fixed by the project layout), so impo
 or through the `rust_msbwt_amd` alias module at the repo root.
 
 Modules mirror the reference crate: msbwt_core (BWTRange, constants, BWT), rle_bwt (RleBWT),
-string_util, bwt_converter, dynamic_bwt (create_from_fastx).  Everything that computes runs in libmsbwt_hip.so.
+string_util, bwt_converter, dynamic_bwt (create_from_fastx), bwt_util (pairwise_bwt_merge).  Everything that computes runs in libmsbwt_hip.so.
 """
 from . import _lib
 from .msbwt_core import BWT, BWTRange, VC_LEN, LETTER_BITS, NUMBER_BITS, NUM_POWER, MASK, COUNT_MASK
 from .rle_bwt import RleBWT, MsbwtError, RankComm
-from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_bwt
+from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_bwt, bwt_util
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_tile", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -75,3 +75,19 @@ def build_reads_plan(total_symbols, free_hbm_bytes, piece=0):
 def build_reads_sort_tile():
     """Suffixes one workgroup ranks and scatters per radix pass of the builder."""
     return int(_lib.lib().msbwt_build_reads_sort_tile())
+
+
+def merge_plan(total0, total1):
+    """HBM bytes the merge of two BWTs of `total0` and `total1` symbols needs: at most 2.5 bytes per merged symbol + 64 MiB.  Pure host
+    logic (csrc/merge.hip, plan_merge)."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_merge_plan(int(total0), int(total1), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_merge_plan")
+    return size.value
+
+
+def merge_tile():
+    """Merged rows one workgroup counts and scatters per iteration of the merge."""
+    return int(_lib.lib().msbwt_merge_tile())

@@ -24,6 +24,7 @@
 #include "order.hpp"
 #include "pair_index.hpp"
 #include "plane_index.hpp"
+#include "merge.hpp"
 #include "reads_build.hpp"
 #include "rle_codec.hpp"
 #include "run_build.hpp"
@@ -174,6 +175,8 @@ struct msbwt_rle : Settings {
     uint64_t timed_launches = 0;
     double build_ms[kReadsBuildStages] = {};  // the stages of the last build from reads
     uint64_t build_pieces = 0;
+    double merge_ms[kMergeStages] = {};       // the stages of the last merge
+    uint64_t merge_iterations = 0;
     std::mutex mu;
     std::string err;
 };
@@ -187,6 +190,7 @@ constexpr size_t kStatusBytes = 1024;  // flag words, debug record (bytes 64..12
 constexpr size_t kCountersOffset = 128;
 static_assert(MSBWT_SEARCH_COUNTERS == kSearchCounters, "the header's counter block is the kernels'");
 static_assert(MSBWT_BUILD_STAGES == kReadsBuildStages, "the header's stage count is the builder's");
+static_assert(MSBWT_MERGE_STAGES == kMergeStages, "the header's stage count is the merge's");
 static_assert(10 + kSparseMaxDepth + 1 <= 42 && 45 + kSparseMaxDepth + 1 <= 80 && 80 + kSparseMaxDepth + 1 <= MSBWT_SPARSE_INFO_WORDS,
               "msbwt_rle_sparse_table_info: [10 + d] distinct, [42] filtered, [45 + d] wide, [80 + d] once");
 constexpr size_t kPackScratchOffset = 256;  // two u64 of the table packer (escape-line count, side-array cursor)
@@ -1476,6 +1480,47 @@ struct OwnedDevice {  // a build's RLE bytes in HBM, freed at scope exit
     }
 };
 
+// The host-side checks of a merge's inputs (msbwt_rle_merge): nothing is launched before they pass.
+int check_merge_inputs(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1, MergeInput *in0, MergeInput *in1) {
+    if ((!rle0 && len0) || (!rle1 && len1)) return fail(h, MSBWT_ERR_INVALID_ARG, "an input must not be null with a length");
+    const uint8_t *rle[2] = {rle0, rle1};
+    const size_t len[2] = {len0, len1};
+    MergeInput *in[2] = {in0, in1};
+    for (int i = 0; i < 2; ++i) {
+        switch (scan_merge_input(rle[i], len[i], in[i])) {
+            case MergeInputStatus::kOk: break;
+            case MergeInputStatus::kInvalidSymbol: return fail(h, MSBWT_ERR_INVALID_SYMBOL, "input " + std::to_string(i) + " holds a symbol code >= 6");
+            case MergeInputStatus::kTooLarge: return fail(h, MSBWT_ERR_TOO_LARGE, "input " + std::to_string(i) + " has 2^40 symbols or more");
+        }
+    }
+    if (in0->total + in1->total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
+    return MSBWT_OK;
+}
+
+struct OwnedMerge {  // a merge's RLE bytes and vector in HBM, freed at scope exit
+    MergeOutput out;
+    ~OwnedMerge() {
+        if (out.d_rle) (void)hipFree(out.d_rle);
+        if (out.d_from_second) (void)hipFree(out.d_from_second);
+    }
+};
+
+// The merge itself, on the handle's device and stream: the RLE bytes and the vector stay in HBM.
+int merge_on_device(msbwt_rle *h, const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, MergeOutput *out) {
+    if (int rc = ensure_runtime(h)) return rc;
+    const hipError_t e = merge_rle_pair(rle0, len0, in0, rle1, len1, in1, h->stream, out);
+    std::copy(out->stage_ms, out->stage_ms + kMergeStages, h->merge_ms);
+    h->merge_iterations = out->iterations;
+    if (std::getenv("MSBWT_VERBOSE"))
+        std::fprintf(stderr, "[msbwt] merge: %llu + %llu symbols, %llu iterations\n", (unsigned long long)in0.total, (unsigned long long)in1.total,
+                     (unsigned long long)out->iterations);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, "merge: " + out->what + ": " + hipGetErrorString(e));
+    }
+    return MSBWT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1600,6 +1645,69 @@ int msbwt_rle_load_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *rea
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+}
+
+int msbwt_rle_merge(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1, uint8_t *out_rle, size_t cap, uint64_t *out_len,
+                    uint8_t *out_from_second) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out_len || (!out_rle && cap)) return fail(h, MSBWT_ERR_INVALID_ARG, "out_len must not be null, nor out_rle with a capacity");
+    *out_len = 0;
+    MergeInput in0, in1;
+    if (int rc = check_merge_inputs(h, rle0, len0, rle1, len1, &in0, &in1)) return rc;
+    std::fill(h->merge_ms, h->merge_ms + kMergeStages, 0.0);
+    h->merge_iterations = 0;
+    const uint64_t total = in0.total + in1.total;
+    if (total == 0) return MSBWT_OK;  // the empty BWT
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    OwnedMerge merged;
+    if (int rc = merge_on_device(h, rle0, len0, in0, rle1, len1, in1, &merged.out)) return rc;
+    *out_len = merged.out.rle_bytes;
+    if (merged.out.rle_bytes > cap)
+        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the merged BWT takes " + std::to_string(merged.out.rle_bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(h, hipMemcpyAsync(out_rle, merged.out.d_rle, merged.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (out_from_second) HIP_TRY(h, hipMemcpyAsync(out_from_second, merged.out.d_from_second, size_t((total + 7) / 8), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->merge_ms[kMergeCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->err.clear();
+    return MSBWT_OK;
+}
+
+int msbwt_rle_load_merged(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    MergeInput in0, in1;
+    if (int rc = check_merge_inputs(h, rle0, len0, rle1, len1, &in0, &in1)) return rc;
+    std::vector<uint8_t> rle;
+    if (in0.total + in1.total) {
+        DeviceScope scope(h->device);
+        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+        release_index(h);  // its HBM is the merge's to use
+        OwnedMerge merged;
+        if (int rc = merge_on_device(h, rle0, len0, in0, rle1, len1, in1, &merged.out)) return rc;
+        rle.resize(size_t(merged.out.rle_bytes));
+        HIP_TRY(h, hipMemcpyAsync(rle.data(), merged.out.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+}
+
+int msbwt_merge_plan(uint64_t total0, uint64_t total1, uint64_t *device_bytes) {
+    if (total0 >= (1ull << 40) || total1 >= (1ull << 40) || total0 + total1 >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (device_bytes) *device_bytes = plan_merge(total0, total1);
+    return MSBWT_OK;
+}
+
+size_t msbwt_merge_tile(void) { return kMergeTile; }
+
+int msbwt_rle_merge_info(const msbwt_rle *ch, uint64_t *iterations, double *out_ms) {
+    Call c(ch);
+    if (!c.h) return MSBWT_ERR_INVALID_ARG;
+    if (iterations) *iterations = c.h->merge_iterations;
+    if (out_ms) std::copy(c.h->merge_ms, c.h->merge_ms + kMergeStages, out_ms);
+    return MSBWT_OK;
 }
 
 int msbwt_rle_set_build_piece(msbwt_rle *h, uint64_t suffixes) {

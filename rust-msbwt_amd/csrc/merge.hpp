@@ -1,0 +1,51 @@
+// Merge (merge.hip): the RLE bytes of two multi-string BWTs -> the RLE bytes of the BWT of the union of their read sets, by the
+// interleave iteration of Holt & McMillan 2014 (the reference: bwt_util::pairwise_bwt_merge, src/bwt_util.rs:21-141).
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace msbwt {
+
+constexpr uint32_t kMergeTile = 4096;  // merged rows one workgroup counts and scatters per iteration
+
+// stages the merge times (host clock around a stream synchronisation at every stage border)
+enum MergeStage {
+    kMergeCopyIn = 0,  // both RLE streams to HBM
+    kMergeDecode,      // RLE bytes -> one byte per symbol
+    kMergeIterate,     // the interleave iterations
+    kMergeEmit,        // the merged symbols, gathered through the final vector
+    kMergeEncode,      // symbols -> RLE bytes
+    kMergeCopyOut,     // RLE bytes (and the vector) to the caller (timed by the caller)
+    kMergeStages
+};
+
+// What the host learns from one RLE stream before anything is launched.
+enum class MergeInputStatus { kOk, kInvalidSymbol, kTooLarge };
+struct MergeInput {
+    uint64_t total = 0;        // symbols the stream encodes
+    uint64_t long_pieces = 0;  // entries its long sub-runs take in the decoder's list
+};
+// A run may span any number of bytes and hold zero digits.  kTooLarge: 2^40 symbols or more.
+MergeInputStatus scan_merge_input(const uint8_t *rle, size_t n, MergeInput *out);
+
+// Pure host arithmetic: HBM bytes the merge of two BWTs of total0 and total1 symbols needs, whatever their runs are.
+// At most 2.5 x (total0 + total1) + 64 MiB.
+uint64_t plan_merge(uint64_t total0, uint64_t total1);
+
+struct MergeOutput {
+    uint8_t *d_rle = nullptr;    // hipMalloc'ed, the caller frees it
+    uint64_t rle_bytes = 0;
+    uint64_t *d_from_second = nullptr;  // the final vector: bit i & 63 of word i >> 6 set = merged row i is input 1's; the caller frees it
+    uint64_t iterations = 0;
+    double stage_ms[kMergeStages] = {};
+    std::string what;  // on failure: the step that failed
+};
+
+// rle0 / rle1: host memory that scan_merge_input accepted (in0, in1: what it said), in0.total + in1.total in [1, 2^40).
+hipError_t merge_rle_pair(const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, hipStream_t stream,
+                          MergeOutput *out);
+
+}  // namespace msbwt

@@ -1,0 +1,76 @@
+// What the device builders share (run_encode.hip): the workgroup prefix sum, the exclusive scan of u64 in HBM, the arena of a
+// build's allocations, and the encoder symbols -> RLE bytes.  reads_build.hip and merge.hip both call this one copy.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace msbwt {
+
+constexpr uint32_t kScanThreads = 256, kScanWaves = kScanThreads / 64;  // every kernel of the builders runs 256 threads
+
+#if defined(__HIPCC__)
+// exclusive prefix sum of v over the workgroup's threads; *total = the sum.  wave_sums: kScanWaves words of LDS.
+__device__ __forceinline__ uint64_t block_exclusive_sum(uint64_t v, uint64_t *wave_sums, uint64_t *total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    __syncthreads();  // the words are free again
+    if (lane == 63u) wave_sums[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kScanWaves; ++w) {
+        const uint64_t s = wave_sums[w];
+        before += w < wave ? s : 0ull;
+        all += s;
+    }
+    *total = all;
+    return before + incl - v;
+}
+#endif
+
+// words of scratch a scan of n elements needs (the sums of every level)
+uint64_t scan_scratch_words(uint64_t n);
+// exclusive scan of d[0 .. n), in place
+hipError_t exclusive_scan(uint64_t *d, uint64_t n, uint64_t *scratch, hipStream_t stream);
+
+// device allocations of one build: whatever is still held when the build ends, however it ends, is freed
+struct Arena {
+    std::vector<void *> held;
+    ~Arena() {
+        for (void *p : held) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t take(T **p, uint64_t bytes) {
+        void *raw = nullptr;
+        const hipError_t e = hipMalloc(&raw, size_t(std::max<uint64_t>(bytes, 256)));
+        if (e == hipSuccess) held.push_back(raw);
+        *p = static_cast<T *>(raw);
+        return e;
+    }
+    template <class T>
+    void give_back(T *&p) {
+        held.erase(std::remove(held.begin(), held.end(), static_cast<void *>(p)), held.end());
+        (void)hipFree(p);
+        p = nullptr;
+    }
+    template <class T>
+    T *keep(T *p) {  // the caller owns it from here on
+        held.erase(std::remove(held.begin(), held.end(), static_cast<void *>(p)), held.end());
+        return p;
+    }
+};
+
+// symbols[0 .. total) in HBM, total >= 1 -> their RLE bytes (src/msbwt_core.rs:3-14, the canonical encoding convert_to_vec gives)
+// in an allocation of the arena: *d_rle, *rle_bytes.  The stream is drained when it returns.  On failure *what names the step.
+hipError_t encode_symbol_runs(Arena &arena, const uint8_t *d_symbols, uint64_t total, hipStream_t stream, uint8_t **d_rle, uint64_t *rle_bytes,
+                              const char **what);
+
+}  // namespace msbwt

@@ -55,6 +55,31 @@ def pack_reads(reads, ascii=False):
     return flat, offsets
 
 
+def rle_runs(rle):
+    """(symbols, lengths) of the sub-runs of an RLE stream, one per byte: byte i stands for digit << 5 * (its index among the
+    consecutive bytes of its symbol) symbols (src/msbwt_core.rs:3-14).  A digit from the ninth on counts as zero: the library
+    refuses a stream of 2^40 symbols or more before it reads a length."""
+    a = np.ascontiguousarray(rle, dtype=np.uint8).ravel()
+    syms, digits = a & 7, (a >> 3).astype(np.uint64)
+    idx = np.arange(a.size)
+    starts = np.ones(a.size, dtype=bool)
+    starts[1:] = syms[1:] != syms[:-1]
+    place = idx - np.maximum.accumulate(np.where(starts, idx, 0))  # index of the byte inside its run
+    lengths = np.where(place < 8, digits << (5 * np.minimum(place, 7)).astype(np.uint64), np.uint64(0))
+    return syms, lengths.astype(np.uint64)
+
+
+def rle_total(rle):
+    """Symbols an RLE stream encodes."""
+    return int(rle_runs(rle)[1].sum(dtype=np.uint64)) if len(rle) else 0
+
+
+def rle_decode(rle):
+    """The symbol codes (np.uint8[]) an RLE stream encodes."""
+    syms, lengths = rle_runs(rle)
+    return np.repeat(syms, lengths.astype(np.int64))
+
+
 class RleBWT(BWT):
     def __init__(self, bin_power=8, device=-1):
         """RleBWT::new() / with_bin_power (rle_bwt.rs:297-322). `device` = HIP ordinal."""
@@ -150,6 +175,52 @@ class RleBWT(BWT):
             _raise(rc, self._h)
         out = {name: float(ms[i]) for i, name in enumerate(_lib.BUILD_STAGES)}
         out["pieces"] = int(pieces.value)
+        return out
+
+    # ---- merge (bwt_util::pairwise_bwt_merge, src/bwt_util.rs:21-141, iterated on the device) ----
+    def merge(self, rle0, rle1, return_interleave=False):
+        """The RLE bytes (np.uint8[]) of the BWT of the union of the read sets behind the BWTs `rle0` and `rle1` (RLE bytes, either
+        may be empty).  With `return_interleave` a pair: those bytes and an np.uint8 array, one entry per merged row, 1 where the row
+        came from `rle1` (rows of equal rotations: those of `rle0` first).  The handle's own index, if it has one, stays as it is."""
+        a = np.ascontiguousarray(rle0, dtype=np.uint8).ravel()
+        b = np.ascontiguousarray(rle1, dtype=np.uint8).ravel()
+        cap = a.size + b.size
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        bits, total = None, 0
+        if return_interleave:
+            total = rle_total(a) + rle_total(b)
+            bits = np.zeros((total + 7) // 8 + 1 if total < 2 ** 40 else 1, dtype=np.uint8)  # (2^40 and more: the library refuses)
+        length = C.c_uint64(0)
+        args = (a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, b.ctypes.data_as(C.c_void_p) if b.size else None, b.size)
+        rc = _lib.lib().msbwt_rle_merge(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), bits.ctypes.data_as(C.c_void_p) if return_interleave else None)
+        if rc == _lib.ERR_INVALID_ARG and length.value > cap:  # inputs that were not canonical can merge into more bytes than they took
+            cap = int(length.value)
+            out = np.empty(cap, dtype=np.uint8)
+            rc = _lib.lib().msbwt_rle_merge(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), bits.ctypes.data_as(C.c_void_p) if return_interleave else None)
+        if rc:
+            _raise(rc, self._h)
+        if not return_interleave:
+            return out[:length.value]
+        return out[:length.value], np.unpackbits(bits, bitorder="little")[:total]
+
+    def load_merged(self, rle0, rle1):
+        """merge, then the result loaded as load_vector would load it."""
+        a = np.ascontiguousarray(rle0, dtype=np.uint8).ravel()
+        b = np.ascontiguousarray(rle1, dtype=np.uint8).ravel()
+        rc = _lib.lib().msbwt_rle_load_merged(self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size,
+                                              b.ctypes.data_as(C.c_void_p) if b.size else None, b.size)
+        if rc:
+            _raise(rc, self._h)
+
+    def merge_info(self):
+        """{"iterations": those of the last merge on this handle (the last one found nothing to change), stage: milliseconds}."""
+        ms = (C.c_double * len(_lib.MERGE_STAGES))()
+        iterations = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_merge_info(self._h, C.byref(iterations), ms)
+        if rc:
+            _raise(rc, self._h)
+        out = {name: float(ms[i]) for i, name in enumerate(_lib.MERGE_STAGES)}
+        out["iterations"] = int(iterations.value)
         return out
 
     # ---- batch forms -----------------------------------------------------------------

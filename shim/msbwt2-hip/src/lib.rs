@@ -15,6 +15,7 @@ use msbwt2::msbwt_core::{BWTRange, BWT, VC_LEN};
 pub struct MsbwtRle { _private: [u8; 0] }
 
 const MSBWT_OK: c_int = 0;
+const MSBWT_ERR_INVALID_ARG: c_int = -9;
 const MSBWT_ERR_IO: c_int = -1;
 const MSBWT_ERR_UNEXPECTED_EOF: c_int = -2;
 
@@ -55,6 +56,10 @@ extern "C" {
     fn msbwt_rle_set_build_piece(bwt: *mut MsbwtRle, suffixes: u64) -> c_int;
     fn msbwt_build_reads_plan(total_symbols: u64, free_hbm_bytes: u64, piece: u64, auto_piece: *mut u64,
                               device_bytes: *mut u64) -> c_int;
+    // merge: two BWTs in, the BWT of the union of their read sets out (no reads, no suffix sort)
+    fn msbwt_rle_merge(bwt: *mut MsbwtRle, rle0: *const u8, len0: usize, rle1: *const u8, len1: usize,
+                       out_rle: *mut u8, cap: usize, out_len: *mut u64, out_from_second: *mut u8) -> c_int;
+    fn msbwt_rle_load_merged(bwt: *mut MsbwtRle, rle0: *const u8, len0: usize, rle1: *const u8, len1: usize) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -200,6 +205,31 @@ impl GpuRleBWT {
         }
         if flat.is_empty() { flat.push(0); } // (never a dangling pointer across the ABI)
         (flat, offsets)
+    }
+
+    /// The RLE bytes of the BWT of the union of the read sets behind the BWTs `rle0` and `rle1` (`bwt_util::pairwise_bwt_merge`,
+    /// iterated on the GPU); rows of equal rotations: those of `rle0` first.  The handle's index is untouched.
+    pub fn merge(&mut self, rle0: &[u8], rle1: &[u8]) -> Vec<u8> {
+        let mut out = vec![0u8; (rle0.len() + rle1.len()).max(1)];
+        let mut len = 0u64;
+        let mut rc = unsafe {
+            msbwt_rle_merge(self.raw, rle0.as_ptr(), rle0.len(), rle1.as_ptr(), rle1.len(), out.as_mut_ptr(), out.len(), &mut len, std::ptr::null_mut())
+        };
+        if rc == MSBWT_ERR_INVALID_ARG && len as usize > out.len() { // inputs that were not canonical
+            out.resize(len as usize, 0);
+            rc = unsafe {
+                msbwt_rle_merge(self.raw, rle0.as_ptr(), rle0.len(), rle1.as_ptr(), rle1.len(), out.as_mut_ptr(), out.len(), &mut len, std::ptr::null_mut())
+            };
+        }
+        if rc != MSBWT_OK { panic!("merge: {}", self.last_error()); }
+        out.truncate(len as usize);
+        out
+    }
+
+    /// `merge`, then the result loaded as `load_vector` would load it.
+    pub fn load_merged(&mut self, rle0: &[u8], rle1: &[u8]) {
+        let rc = unsafe { msbwt_rle_load_merged(self.raw, rle0.as_ptr(), rle0.len(), rle1.as_ptr(), rle1.len()) };
+        if rc != MSBWT_OK { panic!("load_merged: {}", self.last_error()); }
     }
 
     /// Batch form of `constrain_range`.
