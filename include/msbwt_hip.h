@@ -218,9 +218,35 @@ int msbwt_rle_load_merged(msbwt_rle *bwt, const uint8_t *rle0, size_t len0, cons
 /* Pure function, no device: HBM bytes the merge of BWTs of total0 and total1 symbols needs, at most
  * 2.5 x (total0 + total1) + 64 MiB.  MSBWT_ERR_TOO_LARGE from 2^40 merged symbols on. */
 int msbwt_merge_plan(uint64_t total0, uint64_t total1, uint64_t *device_bytes);
+/* ---- merge of any number of BWTs in one pass ----
+ * The same iteration over a byte per merged row, the index of the input the row came from, in place of a bit: one round whatever
+ * the number of inputs, where a tree of msbwt_rle_merge calls takes ceil(log2 n) rounds over every symbol.
+ *
+ * Input i is rle[rle_offsets[i] .. rle_offsets[i + 1]) (n_inputs + 1 offsets, as msbwt_rle_build_from_reads takes reads): RLE
+ * bytes as msbwt_rle_load_vector takes them; a run may span any number of bytes and hold zero digits; any input may be empty.
+ * out_rle, cap and out_len: as msbwt_rle_merge; the bytes are what a left fold of msbwt_rle_merge over the inputs gives.
+ * out_source (optional): one byte per merged row, the index of the input the row came from.  Rows of equal rotations: lower
+ * input index first, and within one input its own order.  With two inputs it is msbwt_rle_merge's bit vector written as bytes.
+ * One input is re-encoded canonically; no input, or only empty ones, give the empty BWT and nothing touches the device.
+ * Checked on the host before anything is launched: more than MSBWT_MERGE_MAX_INPUTS inputs, a null pointer where a length is
+ * given, decreasing offsets, a null out_len (MSBWT_ERR_INVALID_ARG), a symbol code >= 6 (MSBWT_ERR_INVALID_SYMBOL, the message
+ * names the input), a merged total of 2^40 symbols or more (MSBWT_ERR_TOO_LARGE).  HBM that does not suffice: MSBWT_ERR_HIP,
+ * the message names the bytes needed (msbwt_merge_many_plan).  msbwt_rle_merge_info reports the handle's last merge of either
+ * kind. */
+#define MSBWT_MERGE_MAX_INPUTS 32
+int msbwt_rle_merge_many(msbwt_rle *bwt, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs,
+                         uint8_t *out_rle, size_t cap, uint64_t *out_len, uint8_t *out_source);
+/* The same merge, then the result loaded exactly as msbwt_rle_load_vector would load those bytes (an index the handle
+ * holds is released before the merge: its HBM is the merge's to use). */
+int msbwt_rle_load_merged_many(msbwt_rle *bwt, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs);
+/* Pure function, no device: HBM bytes the one-pass merge of n_inputs BWTs of totals[i] symbols needs: with T their sum, at
+ * least 2 x T and at most 3.25 x T + 64 MiB (a byte per symbol for the decoded inputs, two source arrays of a byte per row,
+ * n_inputs + 6 counts per tile).  It depends on the totals through their sum alone.  MSBWT_ERR_INVALID_ARG beyond
+ * MSBWT_MERGE_MAX_INPUTS inputs, MSBWT_ERR_TOO_LARGE from 2^40 merged symbols on. */
+int msbwt_merge_many_plan(const uint64_t *totals, size_t n_inputs, uint64_t *device_bytes);
 /* Merged rows one workgroup counts and scatters per iteration (tests probe its borders). */
 size_t msbwt_merge_tile(void);
-/* The handle's last merge: its iterations (the last one found nothing to change) and the milliseconds of its stages (host
+/* The handle's last merge, of two inputs or of many: its iterations (the last one found nothing to change) and the milliseconds of its stages (host
  * clock, the stream drained at every stage border): copy in, decode, iterate, emit, encode, copy out.  Either may be NULL. */
 #define MSBWT_MERGE_STAGES 6
 int msbwt_rle_merge_info(const msbwt_rle *bwt, uint64_t *iterations, double *out_ms);

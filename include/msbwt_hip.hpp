@@ -140,6 +140,41 @@ class RleBWT final : public BWT {
     void load_merged(const std::vector<std::uint8_t> &rle0, const std::vector<std::uint8_t> &rle1) {
         check(msbwt_rle_load_merged(raw_, rle0.data(), rle0.size(), rle1.data(), rle1.size()));
     }
+    /// RLE bytes of the BWT of the union of the read sets behind the BWTs rles (at most MSBWT_MERGE_MAX_INPUTS), merged in one
+    /// pass.  sources (optional): one byte per merged row, the index of the BWT the row came from; rows of equal rotations: lower
+    /// index first.
+    std::vector<std::uint8_t> merge_many(const std::vector<std::vector<std::uint8_t>> &rles, std::vector<std::uint8_t> *sources = nullptr) {
+        std::vector<std::uint8_t> flat;
+        std::vector<std::uint64_t> offsets(1, 0);
+        std::uint64_t symbols = 0;
+        for (const auto &r : rles) {
+            flat.insert(flat.end(), r.begin(), r.end());
+            offsets.push_back(flat.size());
+            symbols += symbols_of(r);
+        }
+        std::vector<std::uint8_t> out(flat.size() + 1);
+        std::uint64_t len = 0;
+        if (sources) sources->assign(symbols < (1ull << 40) ? static_cast<std::size_t>(symbols) : 0, 0);  // (2^40 and more: the library refuses)
+        std::uint8_t *where = sources && !sources->empty() ? sources->data() : nullptr;
+        int rc = msbwt_rle_merge_many(raw_, flat.data(), offsets.data(), rles.size(), out.data(), out.size(), &len, where);
+        if (rc == MSBWT_ERR_INVALID_ARG && len > out.size()) {  // inputs that were not canonical
+            out.resize(static_cast<std::size_t>(len));
+            rc = msbwt_rle_merge_many(raw_, flat.data(), offsets.data(), rles.size(), out.data(), out.size(), &len, where);
+        }
+        check(rc);
+        out.resize(static_cast<std::size_t>(len));
+        return out;
+    }
+    /// merge_many, then the result loaded as load_vector would load it.
+    void load_merged_many(const std::vector<std::vector<std::uint8_t>> &rles) {
+        std::vector<std::uint8_t> flat;
+        std::vector<std::uint64_t> offsets(1, 0);
+        for (const auto &r : rles) {
+            flat.insert(flat.end(), r.begin(), r.end());
+            offsets.push_back(flat.size());
+        }
+        check(msbwt_rle_load_merged_many(raw_, flat.data(), offsets.data(), rles.size()));
+    }
     /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
     static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
         std::uint64_t total = 0;

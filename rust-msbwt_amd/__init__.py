@@ -7,16 +7,17 @@ The directory name carries a hyphen (it is fixed by the project layout), so impo
 or through the `rust_msbwt_amd` alias module at the repo root.
 
 Modules mirror the reference crate: msbwt_core (BWTRange, constants, BWT), rle_bwt (RleBWT),
-string_util, bwt_converter, dynamic_bwt (create_from_fastx), bwt_util (pairwise_bwt_merge).  Everything that computes runs in libmsbwt_hip.so.
+string_util, bwt_converter, dynamic_bwt (create_from_fastx), bwt_util (pairwise_bwt_merge, multi_bwt_merge).  Everything that computes runs in libmsbwt_hip.so.
 """
 from . import _lib
+from ._lib import MERGE_MAX_INPUTS
 from .msbwt_core import BWT, BWTRange, VC_LEN, LETTER_BITS, NUMBER_BITS, NUM_POWER, MASK, COUNT_MASK
 from .rle_bwt import RleBWT, MsbwtError, RankComm
 from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_bwt, bwt_util
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_tile", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -85,6 +86,19 @@ def merge_plan(total0, total1):
     rc = _lib.lib().msbwt_merge_plan(int(total0), int(total1), ctypes.byref(size))
     if rc:
         raise MsbwtError(rc, "msbwt_merge_plan")
+    return size.value
+
+
+def merge_many_plan(totals):
+    """HBM bytes the one-pass merge of BWTs of `totals` symbols needs: with T their sum, at least 2 T and at most 3.25 T + 64 MiB.  Pure
+    host logic (csrc/merge_many.hip, plan_merge_many)."""
+    import ctypes
+    import numpy as np
+    a = np.ascontiguousarray([int(t) for t in totals], dtype=np.uint64)
+    size = ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_merge_many_plan(a.ctypes.data_as(ctypes.c_void_p) if a.size else None, a.size, ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_merge_many_plan")
     return size.value
 
 

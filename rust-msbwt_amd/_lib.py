@@ -13,6 +13,7 @@ ERR_OVERFLOW, ERR_RCCL = -11, -12
 COMM_ID_BYTES = 128
 SPARSE_INFO_WORDS = 120  # MSBWT_SPARSE_INFO_WORDS
 BUILD_STAGES = ("copy_in", "read_order", "histogram", "collect", "sort", "emit", "encode", "copy_out")  # MSBWT_BUILD_STAGES
+MERGE_MAX_INPUTS = 32  # MSBWT_MERGE_MAX_INPUTS
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
 SIZE_MAX = C.c_size_t(-1).value
@@ -51,6 +52,9 @@ SIGNATURES = {
     "msbwt_rle_merge": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _pu64, _vp]),
     "msbwt_rle_load_merged": (_int, [_vp, _vp, _sz, _vp, _sz]),
     "msbwt_merge_plan": (_int, [_u64, _u64, _pu64]),
+    "msbwt_rle_merge_many": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _pu64, _vp]),
+    "msbwt_rle_load_merged_many": (_int, [_vp, _vp, _vp, _sz]),
+    "msbwt_merge_many_plan": (_int, [_vp, _sz, _pu64]),
     "msbwt_merge_tile": (_sz, []),
     "msbwt_rle_merge_info": (_int, [_vp, _pu64, C.POINTER(C.c_double)]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),

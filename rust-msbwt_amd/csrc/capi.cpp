@@ -191,6 +191,7 @@ constexpr size_t kCountersOffset = 128;
 static_assert(MSBWT_SEARCH_COUNTERS == kSearchCounters, "the header's counter block is the kernels'");
 static_assert(MSBWT_BUILD_STAGES == kReadsBuildStages, "the header's stage count is the builder's");
 static_assert(MSBWT_MERGE_STAGES == kMergeStages, "the header's stage count is the merge's");
+static_assert(MSBWT_MERGE_MAX_INPUTS == kMergeMaxInputs, "the header's input count is the merge's");
 static_assert(10 + kSparseMaxDepth + 1 <= 42 && 45 + kSparseMaxDepth + 1 <= 80 && 80 + kSparseMaxDepth + 1 <= MSBWT_SPARSE_INFO_WORDS,
               "msbwt_rle_sparse_table_info: [10 + d] distinct, [42] filtered, [45 + d] wide, [80 + d] once");
 constexpr size_t kPackScratchOffset = 256;  // two u64 of the table packer (escape-line count, side-array cursor)
@@ -1521,6 +1522,51 @@ int merge_on_device(msbwt_rle *h, const uint8_t *rle0, size_t len0, const MergeI
     return MSBWT_OK;
 }
 
+// The host-side checks of a one-pass merge's inputs (msbwt_rle_merge_many): nothing is launched before they pass.
+int check_merge_many_inputs(msbwt_rle *h, const uint8_t *rle, const uint64_t *offsets, size_t n, std::vector<MergeInput> *in, uint64_t *total) {
+    *total = 0;
+    if (n > MSBWT_MERGE_MAX_INPUTS) return fail(h, MSBWT_ERR_INVALID_ARG, std::to_string(n) + " inputs, one merge takes at most " + std::to_string(MSBWT_MERGE_MAX_INPUTS));
+    if (n && !offsets) return fail(h, MSBWT_ERR_INVALID_ARG, "rle_offsets must not be null with inputs");
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(h, MSBWT_ERR_INVALID_ARG, "rle_offsets decrease at input " + std::to_string(i));
+    if (n && !rle && offsets[n] > offsets[0]) return fail(h, MSBWT_ERR_INVALID_ARG, "rle must not be null with a length");
+    in->assign(n, MergeInput());
+    for (size_t i = 0; i < n; ++i) {
+        const size_t len = size_t(offsets[i + 1] - offsets[i]);
+        switch (scan_merge_input(len ? rle + offsets[i] : nullptr, len, &(*in)[i])) {
+            case MergeInputStatus::kOk: break;
+            case MergeInputStatus::kInvalidSymbol: return fail(h, MSBWT_ERR_INVALID_SYMBOL, "input " + std::to_string(i) + " holds a symbol code >= 6");
+            case MergeInputStatus::kTooLarge: return fail(h, MSBWT_ERR_TOO_LARGE, "input " + std::to_string(i) + " has 2^40 symbols or more");
+        }
+        *total += (*in)[i].total;  // < 2^45
+        if (*total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
+    }
+    return MSBWT_OK;
+}
+
+struct OwnedMergeMany {  // a one-pass merge's RLE bytes and source array in HBM, freed at scope exit
+    MergeManyOutput out;
+    ~OwnedMergeMany() {
+        if (out.d_rle) (void)hipFree(out.d_rle);
+        if (out.d_source) (void)hipFree(out.d_source);
+    }
+};
+
+// The one-pass merge itself, on the handle's device and stream: the RLE bytes and the source array stay in HBM.
+int merge_many_on_device(msbwt_rle *h, const uint8_t *rle, const uint64_t *offsets, const std::vector<MergeInput> &in, uint64_t total, MergeManyOutput *out) {
+    if (int rc = ensure_runtime(h)) return rc;
+    const hipError_t e = merge_rle_many(rle, offsets, in.data(), in.size(), h->stream, out);
+    std::copy(out->stage_ms, out->stage_ms + kMergeStages, h->merge_ms);
+    h->merge_iterations = out->iterations;
+    if (std::getenv("MSBWT_VERBOSE"))
+        std::fprintf(stderr, "[msbwt] merge: %llu symbols in %zu inputs, %llu iterations\n", (unsigned long long)total, in.size(), (unsigned long long)out->iterations);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, "merge: " + out->what + ": " + hipGetErrorString(e));
+    }
+    return MSBWT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1692,6 +1738,66 @@ int msbwt_rle_load_merged(msbwt_rle *h, const uint8_t *rle0, size_t len0, const 
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+}
+
+int msbwt_rle_merge_many(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs, uint8_t *out_rle, size_t cap, uint64_t *out_len,
+                         uint8_t *out_source) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out_len || (!out_rle && cap)) return fail(h, MSBWT_ERR_INVALID_ARG, "out_len must not be null, nor out_rle with a capacity");
+    *out_len = 0;
+    std::vector<MergeInput> in;
+    uint64_t total = 0;
+    if (int rc = check_merge_many_inputs(h, rle, rle_offsets, n_inputs, &in, &total)) return rc;
+    std::fill(h->merge_ms, h->merge_ms + kMergeStages, 0.0);
+    h->merge_iterations = 0;
+    if (total == 0) return MSBWT_OK;  // the empty BWT
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    OwnedMergeMany merged;
+    if (int rc = merge_many_on_device(h, rle, rle_offsets, in, total, &merged.out)) return rc;
+    *out_len = merged.out.rle_bytes;
+    if (merged.out.rle_bytes > cap)
+        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the merged BWT takes " + std::to_string(merged.out.rle_bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(h, hipMemcpyAsync(out_rle, merged.out.d_rle, merged.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (out_source) HIP_TRY(h, hipMemcpyAsync(out_source, merged.out.d_source, size_t(total), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->merge_ms[kMergeCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->err.clear();
+    return MSBWT_OK;
+}
+
+int msbwt_rle_load_merged_many(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    std::vector<MergeInput> in;
+    uint64_t total = 0;
+    if (int rc = check_merge_many_inputs(h, rle, rle_offsets, n_inputs, &in, &total)) return rc;
+    std::vector<uint8_t> merged_rle;
+    if (total) {
+        DeviceScope scope(h->device);
+        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+        release_index(h);  // its HBM is the merge's to use
+        OwnedMergeMany merged;
+        if (int rc = merge_many_on_device(h, rle, rle_offsets, in, total, &merged.out)) return rc;
+        merged_rle.resize(size_t(merged.out.rle_bytes));
+        HIP_TRY(h, hipMemcpyAsync(merged_rle.data(), merged.out.d_rle, merged_rle.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return install(h, merged_rle.data(), merged_rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+}
+
+int msbwt_merge_many_plan(const uint64_t *totals, size_t n_inputs, uint64_t *device_bytes) {
+    if (n_inputs > MSBWT_MERGE_MAX_INPUTS || (!totals && n_inputs)) return MSBWT_ERR_INVALID_ARG;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_inputs; ++i) {
+        if (totals[i] >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+        total += totals[i];  // < 2^45
+    }
+    if (total >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (device_bytes) *device_bytes = plan_merge_many(total);
+    return MSBWT_OK;
 }
 
 int msbwt_merge_plan(uint64_t total0, uint64_t total1, uint64_t *device_bytes) {

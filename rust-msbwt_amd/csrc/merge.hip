@@ -323,6 +323,8 @@ __global__ __launch_bounds__(256) void k_emit_rows(const uint64_t *__restrict__ 
     *reinterpret_cast<uint4 *>(merged + uint64_t(blockIdx.x) * kMergeTile + uint64_t(threadIdx.x) * kRowsPer) = make_uint4(out[0], out[1], out[2], out[3]);
 }
 
+}  // namespace
+
 // ---- host side ----
 
 hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInput &in, uint8_t *d_symbols, hipStream_t stream, const char **what) {
@@ -355,8 +357,6 @@ hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInp
     arena.give_back(d_cursor);
     return hipSuccess;
 }
-
-}  // namespace
 
 MergeInputStatus scan_merge_input(const uint8_t *rle, size_t n, MergeInput *out) {
     uint64_t total = 0, pieces = 0;

@@ -1,5 +1,6 @@
-// Merge (merge.hip): the RLE bytes of two multi-string BWTs -> the RLE bytes of the BWT of the union of their read sets, by the
-// interleave iteration of Holt & McMillan 2014 (the reference: bwt_util::pairwise_bwt_merge, src/bwt_util.rs:21-141).
+// Merge (merge.hip, merge_many.hip): the RLE bytes of two or more multi-string BWTs -> the RLE bytes of the BWT of the union of
+// their read sets, by the interleave iteration of Holt & McMillan 2014 (the reference: bwt_util::pairwise_bwt_merge,
+// src/bwt_util.rs:21-141).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -47,5 +48,31 @@ struct MergeOutput {
 // rle0 / rle1: host memory that scan_merge_input accepted (in0, in1: what it said), in0.total + in1.total in [1, 2^40).
 hipError_t merge_rle_pair(const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, hipStream_t stream,
                           MergeOutput *out);
+
+// The decoder of merge.hip, which merge_many.hip shares: d_rle[0 .. n) in HBM, a stream scan_merge_input accepted (in: what it
+// said) -> d_symbols[0 .. in.total), a byte per symbol; d_symbols is 16-byte aligned.  The stream is drained when it returns.
+struct Arena;
+hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInput &in, uint8_t *d_symbols, hipStream_t stream, const char **what);
+
+// ---- any number of inputs in one pass (merge_many.hip) ----
+
+constexpr uint32_t kMergeMaxInputs = 32;
+
+// Pure host arithmetic: HBM bytes the one-pass merge of up to kMergeMaxInputs BWTs of `total` symbols in all needs, whatever
+// their number and their runs are.  At least 2 x total, at most 3.25 x total + 64 MiB.
+uint64_t plan_merge_many(uint64_t total);
+
+struct MergeManyOutput {
+    uint8_t *d_rle = nullptr;     // hipMalloc'ed, the caller frees it
+    uint64_t rle_bytes = 0;
+    uint8_t *d_source = nullptr;  // the final array: byte i = the input merged row i came from; the caller frees it
+    uint64_t iterations = 0;
+    double stage_ms[kMergeStages] = {};
+    std::string what;  // on failure: the step that failed
+};
+
+// rle: host memory, input i is rle[offsets[i] .. offsets[i + 1]), a stream scan_merge_input accepted (in[i]: what it said);
+// 1 <= n <= kMergeMaxInputs, the totals sum to [1, 2^40).
+hipError_t merge_rle_many(const uint8_t *rle, const uint64_t *offsets, const MergeInput *in, size_t n, hipStream_t stream, MergeManyOutput *out);
 
 }  // namespace msbwt

@@ -80,6 +80,15 @@ def rle_decode(rle):
     return np.repeat(syms, lengths.astype(np.int64))
 
 
+def _pack_rles(rles):
+    """Several RLE streams as the C ABI takes them: (flat uint8 array, uint64 offsets[n + 1])."""
+    parts = [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in rles]
+    offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        np.cumsum([p.size for p in parts], out=offsets[1:])
+    return (np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)), offsets
+
+
 class RleBWT(BWT):
     def __init__(self, bin_power=8, device=-1):
         """RleBWT::new() / with_bin_power (rle_bwt.rs:297-322). `device` = HIP ordinal."""
@@ -209,6 +218,38 @@ class RleBWT(BWT):
         b = np.ascontiguousarray(rle1, dtype=np.uint8).ravel()
         rc = _lib.lib().msbwt_rle_load_merged(self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size,
                                               b.ctypes.data_as(C.c_void_p) if b.size else None, b.size)
+        if rc:
+            _raise(rc, self._h)
+
+    def merge_many(self, rles, return_sources=False):
+        """The RLE bytes (np.uint8[]) of the BWT of the union of the read sets behind the BWTs `rles` (a sequence of at most
+        MERGE_MAX_INPUTS arrays of RLE bytes, any of them may be empty), merged in one pass.  With `return_sources` a pair: those bytes
+        and an np.uint8 array, one entry per merged row, the index of the input the row came from (rows of equal rotations: lower
+        index first).  The handle's own index, if it has one, stays as it is."""
+        flat, offsets = _pack_rles(rles)
+        n = offsets.size - 1
+        cap = flat.size
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        sources = None
+        if return_sources:
+            total = sum(rle_total(flat[offsets[i]:offsets[i + 1]]) for i in range(n)) if n <= _lib.MERGE_MAX_INPUTS else 0
+            sources = np.zeros(total if total < 2 ** 40 else 0, dtype=np.uint8)  # (2^40 and more, too many inputs: the library refuses)
+        length = C.c_uint64(0)
+        args = (flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), n)
+        where = sources.ctypes.data_as(C.c_void_p) if return_sources and sources.size else None
+        rc = _lib.lib().msbwt_rle_merge_many(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), where)
+        if rc == _lib.ERR_INVALID_ARG and length.value > cap:  # inputs that were not canonical can merge into more bytes than they took
+            cap = int(length.value)
+            out = np.empty(cap, dtype=np.uint8)
+            rc = _lib.lib().msbwt_rle_merge_many(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), where)
+        if rc:
+            _raise(rc, self._h)
+        return (out[:length.value], sources) if return_sources else out[:length.value]
+
+    def load_merged_many(self, rles):
+        """merge_many, then the result loaded as load_vector would load it."""
+        flat, offsets = _pack_rles(rles)
+        rc = _lib.lib().msbwt_rle_load_merged_many(self._h, flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), offsets.size - 1)
         if rc:
             _raise(rc, self._h)
 

@@ -60,6 +60,10 @@ extern "C" {
     fn msbwt_rle_merge(bwt: *mut MsbwtRle, rle0: *const u8, len0: usize, rle1: *const u8, len1: usize,
                        out_rle: *mut u8, cap: usize, out_len: *mut u64, out_from_second: *mut u8) -> c_int;
     fn msbwt_rle_load_merged(bwt: *mut MsbwtRle, rle0: *const u8, len0: usize, rle1: *const u8, len1: usize) -> c_int;
+    // merge of up to 32 BWTs in one pass: input i is rle[rle_offsets[i] .. rle_offsets[i + 1])
+    fn msbwt_rle_merge_many(bwt: *mut MsbwtRle, rle: *const u8, rle_offsets: *const u64, n_inputs: usize,
+                            out_rle: *mut u8, cap: usize, out_len: *mut u64, out_source: *mut u8) -> c_int;
+    fn msbwt_rle_load_merged_many(bwt: *mut MsbwtRle, rle: *const u8, rle_offsets: *const u64, n_inputs: usize) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -232,6 +236,36 @@ impl GpuRleBWT {
         if rc != MSBWT_OK { panic!("load_merged: {}", self.last_error()); }
     }
 
+    /// The RLE bytes of the BWT of the union of the read sets behind the BWTs `rles` (at most 32), merged in one pass, and for
+    /// every merged row the index of the BWT it came from; rows of equal rotations: lower index first.  The handle's index is
+    /// untouched.
+    pub fn merge_many(&mut self, rles: &[&[u8]]) -> (Vec<u8>, Vec<u8>) {
+        let (flat, offsets) = Self::pack_reads(rles);
+        let mut out = vec![0u8; flat.len().max(1)];
+        let mut sources = vec![0u8; rles.iter().map(|r| rle_total(r)).sum::<u64>() as usize];
+        let mut len = 0u64;
+        let where_to = if sources.is_empty() { std::ptr::null_mut() } else { sources.as_mut_ptr() };
+        let mut rc = unsafe {
+            msbwt_rle_merge_many(self.raw, flat.as_ptr(), offsets.as_ptr(), rles.len(), out.as_mut_ptr(), out.len(), &mut len, where_to)
+        };
+        if rc == MSBWT_ERR_INVALID_ARG && len as usize > out.len() { // inputs that were not canonical
+            out.resize(len as usize, 0);
+            rc = unsafe {
+                msbwt_rle_merge_many(self.raw, flat.as_ptr(), offsets.as_ptr(), rles.len(), out.as_mut_ptr(), out.len(), &mut len, where_to)
+            };
+        }
+        if rc != MSBWT_OK { panic!("merge_many: {}", self.last_error()); }
+        out.truncate(len as usize);
+        (out, sources)
+    }
+
+    /// `merge_many`, then the result loaded as `load_vector` would load it.
+    pub fn load_merged_many(&mut self, rles: &[&[u8]]) {
+        let (flat, offsets) = Self::pack_reads(rles);
+        let rc = unsafe { msbwt_rle_load_merged_many(self.raw, flat.as_ptr(), offsets.as_ptr(), rles.len()) };
+        if rc != MSBWT_OK { panic!("load_merged_many: {}", self.last_error()); }
+    }
+
     /// Batch form of `constrain_range`.
     pub fn constrain_ranges(&self, syms: &[u8], ranges: &[BWTRange]) -> Vec<BWTRange> {
         assert_eq!(syms.len(), ranges.len());
@@ -335,6 +369,18 @@ impl GpuRleBWT {
         if rc != MSBWT_OK { panic!("sparse_table_info: {}", self.last_error()); }
         (unsafe { msbwt_rle_get_sparse_table(self.raw) }, info[1])
     }
+}
+
+/// Symbols an RLE stream encodes: byte i stands for digit << 5 * (its index among the consecutive bytes of its symbol); a digit
+/// from the ninth on counts as zero (the library refuses such a stream).
+pub fn rle_total(rle: &[u8]) -> u64 {
+    let (mut total, mut prev, mut place) = (0u64, 8u8, 0u32);
+    for &b in rle {
+        place = if b & 7 == prev { place + 1 } else { 0 };
+        prev = b & 7;
+        if place < 8 { total += ((b >> 3) as u64) << (5 * place); }
+    }
+    total
 }
 
 /// n k-mers of k symbol codes (A C G T = 1 2 3 5) -> 2-bit words: the k-mer as a base-4 number, first symbol most significant.
