@@ -1454,117 +1454,143 @@ int check_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets
     return MSBWT_OK;
 }
 
-// The build itself, on the handle's device and stream: the RLE bytes stay in HBM (out->d_rle, the caller frees them).
-int build_reads_on_device(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii, uint64_t total, ReadsBuildOutput *out) {
+struct Produced {  // what a producer left in HBM: RLE bytes and, after a merge, the final state; freed at scope exit
+    uint8_t *d_rle = nullptr, *d_state = nullptr;
+    uint64_t rle_bytes = 0, state_bytes = 0;
+    Produced() = default;
+    Produced(const Produced &) = delete;
+    Produced &operator=(const Produced &) = delete;
+    ~Produced() {
+        if (d_rle) (void)hipFree(d_rle);
+        if (d_state) (void)hipFree(d_state);
+    }
+};
+
+// The build itself, on the handle's device and stream: the RLE bytes stay in HBM.
+int build_reads_on_device(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii, uint64_t total, Produced *made) {
     if (int rc = ensure_runtime(h)) return rc;
     size_t free_bytes = 0, all_bytes = 0;
     HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
     const uint64_t piece = h->build_piece ? h->build_piece : plan_reads_build(total, free_bytes, 0).auto_piece;
     const char *wide = std::getenv("MSBWT_BUILD_WIDE");  // 64-bit positions below 2^32 symbols too (tests)
-    const hipError_t e = build_rle_from_reads(reads, read_offsets, n_reads, ascii != 0, piece, wide && std::atoi(wide), h->stream, out);
-    std::copy(out->stage_ms, out->stage_ms + kReadsBuildStages, h->build_ms);
-    h->build_pieces = out->pieces;
+    ReadsBuildOutput out;
+    const hipError_t e = build_rle_from_reads(reads, read_offsets, n_reads, ascii != 0, piece, wide && std::atoi(wide), h->stream, &out);
+    made->d_rle = out.d_rle;
+    made->rle_bytes = out.rle_bytes;
+    std::copy(out.stage_ms, out.stage_ms + kReadsBuildStages, h->build_ms);
+    h->build_pieces = out.pieces;
     if (std::getenv("MSBWT_VERBOSE"))
         std::fprintf(stderr, "[msbwt] build: %llu symbols, %llu pieces of at most %llu suffixes (limit %llu)\n", (unsigned long long)total,
-                     (unsigned long long)out->pieces, (unsigned long long)out->largest_piece, (unsigned long long)piece);
+                     (unsigned long long)out.pieces, (unsigned long long)out.largest_piece, (unsigned long long)piece);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, "build from reads: " + out->what + ": " + hipGetErrorString(e));
+        return fail(h, MSBWT_ERR_HIP, "build from reads: " + out.what + ": " + hipGetErrorString(e));
     }
     return MSBWT_OK;
 }
 
-struct OwnedDevice {  // a build's RLE bytes in HBM, freed at scope exit
-    ReadsBuildOutput out;
-    ~OwnedDevice() {
-        if (out.d_rle) (void)hipFree(out.d_rle);
-    }
-};
-
-// The host-side checks of a merge's inputs (msbwt_rle_merge): nothing is launched before they pass.
-int check_merge_inputs(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1, MergeInput *in0, MergeInput *in1) {
-    if ((!rle0 && len0) || (!rle1 && len1)) return fail(h, MSBWT_ERR_INVALID_ARG, "an input must not be null with a length");
-    const uint8_t *rle[2] = {rle0, rle1};
-    const size_t len[2] = {len0, len1};
-    MergeInput *in[2] = {in0, in1};
-    for (int i = 0; i < 2; ++i) {
-        switch (scan_merge_input(rle[i], len[i], in[i])) {
+// The host-side checks of a merge's inputs: nothing is launched before they pass.  Fills every span's `in`; *total = merged rows.
+int check_merge_inputs(msbwt_rle *h, std::vector<MergeSpan> *spans, uint64_t *total) {
+    *total = 0;
+    for (size_t i = 0; i < spans->size(); ++i) {
+        MergeSpan &span = (*spans)[i];
+        switch (scan_merge_input(span.rle, span.len, &span.in)) {
             case MergeInputStatus::kOk: break;
             case MergeInputStatus::kInvalidSymbol: return fail(h, MSBWT_ERR_INVALID_SYMBOL, "input " + std::to_string(i) + " holds a symbol code >= 6");
             case MergeInputStatus::kTooLarge: return fail(h, MSBWT_ERR_TOO_LARGE, "input " + std::to_string(i) + " has 2^40 symbols or more");
         }
-    }
-    if (in0->total + in1->total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
-    return MSBWT_OK;
-}
-
-struct OwnedMerge {  // a merge's RLE bytes and vector in HBM, freed at scope exit
-    MergeOutput out;
-    ~OwnedMerge() {
-        if (out.d_rle) (void)hipFree(out.d_rle);
-        if (out.d_from_second) (void)hipFree(out.d_from_second);
-    }
-};
-
-// The merge itself, on the handle's device and stream: the RLE bytes and the vector stay in HBM.
-int merge_on_device(msbwt_rle *h, const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, MergeOutput *out) {
-    if (int rc = ensure_runtime(h)) return rc;
-    const hipError_t e = merge_rle_pair(rle0, len0, in0, rle1, len1, in1, h->stream, out);
-    std::copy(out->stage_ms, out->stage_ms + kMergeStages, h->merge_ms);
-    h->merge_iterations = out->iterations;
-    if (std::getenv("MSBWT_VERBOSE"))
-        std::fprintf(stderr, "[msbwt] merge: %llu + %llu symbols, %llu iterations\n", (unsigned long long)in0.total, (unsigned long long)in1.total,
-                     (unsigned long long)out->iterations);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, "merge: " + out->what + ": " + hipGetErrorString(e));
+        *total += span.in.total;  // < 2^45
+        if (*total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
     }
     return MSBWT_OK;
 }
 
-// The host-side checks of a one-pass merge's inputs (msbwt_rle_merge_many): nothing is launched before they pass.
-int check_merge_many_inputs(msbwt_rle *h, const uint8_t *rle, const uint64_t *offsets, size_t n, std::vector<MergeInput> *in, uint64_t *total) {
+// msbwt_rle_merge's two inputs as spans, checked
+int check_merge_pair(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1, std::vector<MergeSpan> *spans, uint64_t *total) {
+    if ((!rle0 && len0) || (!rle1 && len1)) return fail(h, MSBWT_ERR_INVALID_ARG, "an input must not be null with a length");
+    *spans = {MergeSpan{rle0, len0, MergeInput()}, MergeSpan{rle1, len1, MergeInput()}};
+    return check_merge_inputs(h, spans, total);
+}
+
+// msbwt_rle_merge_many's packed inputs as spans, checked
+int check_merge_packed(msbwt_rle *h, const uint8_t *rle, const uint64_t *offsets, size_t n, std::vector<MergeSpan> *spans, uint64_t *total) {
     *total = 0;
     if (n > MSBWT_MERGE_MAX_INPUTS) return fail(h, MSBWT_ERR_INVALID_ARG, std::to_string(n) + " inputs, one merge takes at most " + std::to_string(MSBWT_MERGE_MAX_INPUTS));
     if (n && !offsets) return fail(h, MSBWT_ERR_INVALID_ARG, "rle_offsets must not be null with inputs");
     for (size_t i = 0; i < n; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(h, MSBWT_ERR_INVALID_ARG, "rle_offsets decrease at input " + std::to_string(i));
     if (n && !rle && offsets[n] > offsets[0]) return fail(h, MSBWT_ERR_INVALID_ARG, "rle must not be null with a length");
-    in->assign(n, MergeInput());
+    spans->clear();
     for (size_t i = 0; i < n; ++i) {
         const size_t len = size_t(offsets[i + 1] - offsets[i]);
-        switch (scan_merge_input(len ? rle + offsets[i] : nullptr, len, &(*in)[i])) {
-            case MergeInputStatus::kOk: break;
-            case MergeInputStatus::kInvalidSymbol: return fail(h, MSBWT_ERR_INVALID_SYMBOL, "input " + std::to_string(i) + " holds a symbol code >= 6");
-            case MergeInputStatus::kTooLarge: return fail(h, MSBWT_ERR_TOO_LARGE, "input " + std::to_string(i) + " has 2^40 symbols or more");
-        }
-        *total += (*in)[i].total;  // < 2^45
-        if (*total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
+        spans->push_back(MergeSpan{len ? rle + offsets[i] : nullptr, len, MergeInput()});
+    }
+    return check_merge_inputs(h, spans, total);
+}
+
+void reset_merge_info(msbwt_rle *h) {
+    std::fill(h->merge_ms, h->merge_ms + kMergeStages, 0.0);
+    h->merge_iterations = 0;
+}
+
+// The merge itself (`run`: merge_rle_pair or merge_rle_many), on the handle's device and stream: the RLE bytes and the final state
+// stay in HBM.
+int merge_on_device(msbwt_rle *h, decltype(&merge_rle_many) run, const std::vector<MergeSpan> &spans, uint64_t total, Produced *made) {
+    if (int rc = ensure_runtime(h)) return rc;
+    MergeOutput out;
+    const hipError_t e = run(spans.data(), spans.size(), h->stream, &out);
+    made->d_rle = out.d_rle;
+    made->rle_bytes = out.rle_bytes;
+    made->d_state = out.d_state;
+    made->state_bytes = out.state_bytes;
+    std::copy(out.stage_ms, out.stage_ms + kMergeStages, h->merge_ms);
+    h->merge_iterations = out.iterations;
+    if (std::getenv("MSBWT_VERBOSE"))
+        std::fprintf(stderr, "[msbwt] merge: %llu symbols in %zu inputs, %llu iterations\n", (unsigned long long)total, spans.size(), (unsigned long long)out.iterations);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, "merge: " + out.what + ": " + hipGetErrorString(e));
     }
     return MSBWT_OK;
 }
 
-struct OwnedMergeMany {  // a one-pass merge's RLE bytes and source array in HBM, freed at scope exit
-    MergeManyOutput out;
-    ~OwnedMergeMany() {
-        if (out.d_rle) (void)hipFree(out.d_rle);
-        if (out.d_source) (void)hipFree(out.d_source);
-    }
-};
-
-// The one-pass merge itself, on the handle's device and stream: the RLE bytes and the source array stay in HBM.
-int merge_many_on_device(msbwt_rle *h, const uint8_t *rle, const uint64_t *offsets, const std::vector<MergeInput> &in, uint64_t total, MergeManyOutput *out) {
-    if (int rc = ensure_runtime(h)) return rc;
-    const hipError_t e = merge_rle_many(rle, offsets, in.data(), in.size(), h->stream, out);
-    std::copy(out->stage_ms, out->stage_ms + kMergeStages, h->merge_ms);
-    h->merge_iterations = out->iterations;
-    if (std::getenv("MSBWT_VERBOSE"))
-        std::fprintf(stderr, "[msbwt] merge: %llu symbols in %zu inputs, %llu iterations\n", (unsigned long long)total, in.size(), (unsigned long long)out->iterations);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, "merge: " + out->what + ": " + hipGetErrorString(e));
-    }
+// What the producers that hand their bytes to the caller share: `produce` leaves `noun`'s RLE bytes in HBM, they go to out_rle if
+// its capacity allows (*out_len says what they take either way), the final state to out_state where the caller asked for it, and
+// the copy's time to *copy_ms.
+template <class Produce>
+int produce_for_caller(msbwt_rle *h, Produce &&produce, const char *noun, uint8_t *out_rle, size_t cap, uint64_t *out_len, uint8_t *out_state, double *copy_ms) {
+    DeviceScope scope(h->device);
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+    Produced made;
+    if (int rc = produce(&made)) return rc;
+    *out_len = made.rle_bytes;
+    if (made.rle_bytes > cap)
+        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the " + noun + " takes " + std::to_string(made.rle_bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(h, hipMemcpyAsync(out_rle, made.d_rle, made.rle_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (out_state) HIP_TRY(h, hipMemcpyAsync(out_state, made.d_state, size_t(made.state_bytes), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *copy_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->err.clear();
     return MSBWT_OK;
+}
+
+// What the producers that load their result share: unless it is the empty BWT (`any`), the index gives way, `produce` leaves the
+// RLE bytes in HBM, and they come down and are freed; then the loader of msbwt_rle_load_vector, on the same bytes.
+template <class Produce>
+int produce_and_install(msbwt_rle *h, bool any, Produce &&produce) {
+    std::vector<uint8_t> rle;
+    if (any) {
+        DeviceScope scope(h->device);
+        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
+        release_index(h);  // its HBM is the producer's to use
+        Produced made;
+        if (int rc = produce(&made)) return rc;
+        rle.resize(size_t(made.rle_bytes));
+        HIP_TRY(h, hipMemcpyAsync(rle.data(), made.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return install(h, rle.data(), rle.size());
 }
 
 }  // namespace
@@ -1659,19 +1685,8 @@ int msbwt_rle_build_from_reads(msbwt_rle *h, const uint8_t *reads, const uint64_
     std::fill(h->build_ms, h->build_ms + kReadsBuildStages, 0.0);
     h->build_pieces = 0;
     if (n_reads == 0) return MSBWT_OK;  // the empty BWT
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    OwnedDevice built;
-    if (int rc = build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, &built.out)) return rc;
-    *out_len = built.out.rle_bytes;
-    if (built.out.rle_bytes > cap)
-        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the BWT takes " + std::to_string(built.out.rle_bytes));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(h, hipMemcpyAsync(out_rle, built.out.d_rle, built.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->build_ms[kStageCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->err.clear();
-    return MSBWT_OK;
+    auto build = [&](Produced *made) { return build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, made); };
+    return produce_for_caller(h, build, "BWT", out_rle, cap, out_len, nullptr, &h->build_ms[kStageCopyOut]);
 }
 
 int msbwt_rle_load_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets, size_t n_reads, int ascii) {
@@ -1679,18 +1694,7 @@ int msbwt_rle_load_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *rea
     std::lock_guard<std::mutex> lock(h->mu);
     uint64_t total = 0;
     if (int rc = check_reads(h, reads, read_offsets, n_reads, ascii, &total)) return rc;
-    std::vector<uint8_t> rle;
-    if (n_reads) {
-        DeviceScope scope(h->device);
-        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-        release_index(h);  // its HBM is the builder's to use
-        OwnedDevice built;
-        if (int rc = build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, &built.out)) return rc;
-        rle.resize(size_t(built.out.rle_bytes));
-        HIP_TRY(h, hipMemcpyAsync(rle.data(), built.out.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+    return produce_and_install(h, n_reads != 0, [&](Produced *made) { return build_reads_on_device(h, reads, read_offsets, n_reads, ascii, total, made); });
 }
 
 int msbwt_rle_merge(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1, uint8_t *out_rle, size_t cap, uint64_t *out_len,
@@ -1699,45 +1703,22 @@ int msbwt_rle_merge(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_
     std::lock_guard<std::mutex> lock(h->mu);
     if (!out_len || (!out_rle && cap)) return fail(h, MSBWT_ERR_INVALID_ARG, "out_len must not be null, nor out_rle with a capacity");
     *out_len = 0;
-    MergeInput in0, in1;
-    if (int rc = check_merge_inputs(h, rle0, len0, rle1, len1, &in0, &in1)) return rc;
-    std::fill(h->merge_ms, h->merge_ms + kMergeStages, 0.0);
-    h->merge_iterations = 0;
-    const uint64_t total = in0.total + in1.total;
+    std::vector<MergeSpan> spans;
+    uint64_t total = 0;
+    if (int rc = check_merge_pair(h, rle0, len0, rle1, len1, &spans, &total)) return rc;
+    reset_merge_info(h);
     if (total == 0) return MSBWT_OK;  // the empty BWT
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    OwnedMerge merged;
-    if (int rc = merge_on_device(h, rle0, len0, in0, rle1, len1, in1, &merged.out)) return rc;
-    *out_len = merged.out.rle_bytes;
-    if (merged.out.rle_bytes > cap)
-        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the merged BWT takes " + std::to_string(merged.out.rle_bytes));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(h, hipMemcpyAsync(out_rle, merged.out.d_rle, merged.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (out_from_second) HIP_TRY(h, hipMemcpyAsync(out_from_second, merged.out.d_from_second, size_t((total + 7) / 8), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->merge_ms[kMergeCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->err.clear();
-    return MSBWT_OK;
+    auto merge = [&](Produced *made) { return merge_on_device(h, merge_rle_pair, spans, total, made); };
+    return produce_for_caller(h, merge, "merged BWT", out_rle, cap, out_len, out_from_second, &h->merge_ms[kMergeCopyOut]);
 }
 
 int msbwt_rle_load_merged(msbwt_rle *h, const uint8_t *rle0, size_t len0, const uint8_t *rle1, size_t len1) {
     if (!h) return MSBWT_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
-    MergeInput in0, in1;
-    if (int rc = check_merge_inputs(h, rle0, len0, rle1, len1, &in0, &in1)) return rc;
-    std::vector<uint8_t> rle;
-    if (in0.total + in1.total) {
-        DeviceScope scope(h->device);
-        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-        release_index(h);  // its HBM is the merge's to use
-        OwnedMerge merged;
-        if (int rc = merge_on_device(h, rle0, len0, in0, rle1, len1, in1, &merged.out)) return rc;
-        rle.resize(size_t(merged.out.rle_bytes));
-        HIP_TRY(h, hipMemcpyAsync(rle.data(), merged.out.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return install(h, rle.data(), rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+    std::vector<MergeSpan> spans;
+    uint64_t total = 0;
+    if (int rc = check_merge_pair(h, rle0, len0, rle1, len1, &spans, &total)) return rc;
+    return produce_and_install(h, total != 0, [&](Produced *made) { return merge_on_device(h, merge_rle_pair, spans, total, made); });
 }
 
 int msbwt_rle_merge_many(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs, uint8_t *out_rle, size_t cap, uint64_t *out_len,
@@ -1746,46 +1727,22 @@ int msbwt_rle_merge_many(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_o
     std::lock_guard<std::mutex> lock(h->mu);
     if (!out_len || (!out_rle && cap)) return fail(h, MSBWT_ERR_INVALID_ARG, "out_len must not be null, nor out_rle with a capacity");
     *out_len = 0;
-    std::vector<MergeInput> in;
+    std::vector<MergeSpan> spans;
     uint64_t total = 0;
-    if (int rc = check_merge_many_inputs(h, rle, rle_offsets, n_inputs, &in, &total)) return rc;
-    std::fill(h->merge_ms, h->merge_ms + kMergeStages, 0.0);
-    h->merge_iterations = 0;
+    if (int rc = check_merge_packed(h, rle, rle_offsets, n_inputs, &spans, &total)) return rc;
+    reset_merge_info(h);
     if (total == 0) return MSBWT_OK;  // the empty BWT
-    DeviceScope scope(h->device);
-    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-    OwnedMergeMany merged;
-    if (int rc = merge_many_on_device(h, rle, rle_offsets, in, total, &merged.out)) return rc;
-    *out_len = merged.out.rle_bytes;
-    if (merged.out.rle_bytes > cap)
-        return fail(h, MSBWT_ERR_INVALID_ARG, "out_rle holds " + std::to_string(cap) + " bytes, the merged BWT takes " + std::to_string(merged.out.rle_bytes));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(h, hipMemcpyAsync(out_rle, merged.out.d_rle, merged.out.rle_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (out_source) HIP_TRY(h, hipMemcpyAsync(out_source, merged.out.d_source, size_t(total), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->merge_ms[kMergeCopyOut] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->err.clear();
-    return MSBWT_OK;
+    auto merge = [&](Produced *made) { return merge_on_device(h, merge_rle_many, spans, total, made); };
+    return produce_for_caller(h, merge, "merged BWT", out_rle, cap, out_len, out_source, &h->merge_ms[kMergeCopyOut]);
 }
 
 int msbwt_rle_load_merged_many(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs) {
     if (!h) return MSBWT_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
-    std::vector<MergeInput> in;
+    std::vector<MergeSpan> spans;
     uint64_t total = 0;
-    if (int rc = check_merge_many_inputs(h, rle, rle_offsets, n_inputs, &in, &total)) return rc;
-    std::vector<uint8_t> merged_rle;
-    if (total) {
-        DeviceScope scope(h->device);
-        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
-        release_index(h);  // its HBM is the merge's to use
-        OwnedMergeMany merged;
-        if (int rc = merge_many_on_device(h, rle, rle_offsets, in, total, &merged.out)) return rc;
-        merged_rle.resize(size_t(merged.out.rle_bytes));
-        HIP_TRY(h, hipMemcpyAsync(merged_rle.data(), merged.out.d_rle, merged_rle.size(), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return install(h, merged_rle.data(), merged_rle.size());  // the loader of msbwt_rle_load_vector, on the same bytes
+    if (int rc = check_merge_packed(h, rle, rle_offsets, n_inputs, &spans, &total)) return rc;
+    return produce_and_install(h, total != 0, [&](Produced *made) { return merge_on_device(h, merge_rle_many, spans, total, made); });
 }
 
 int msbwt_merge_many_plan(const uint64_t *totals, size_t n_inputs, uint64_t *device_bytes) {

@@ -22,32 +22,20 @@
 //
 // Integer only; every kernel runs without scratch memory.  Every row index, tile offset and bit offset is 64-bit; 32-bit are
 // counts and ranks inside one tile (<= kMergeTile).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cstdint>
-
-#include "merge.hpp"
-#include "run_encode.hpp"
+#include "merge_common.hpp"
 
 namespace msbwt {
 
 namespace {
 
-constexpr uint32_t kThreads = kScanThreads;
-constexpr uint32_t kRowsPer = kMergeTile / kThreads;   // consecutive rows of a tile one thread holds
 constexpr uint32_t kTileWords = kMergeTile / 64;       // words of the vector per tile
 constexpr uint32_t kDecodePer = 16, kDecodeTile = kThreads * kDecodePer;  // decode: RLE bytes per thread / workgroup
 constexpr uint32_t kMaxDigits = 8;                     // 32^8 = 2^40: a non-zero digit further up cannot be (the host has checked)
 constexpr uint64_t kShortRun = 1024;                   // sub-runs below this are written by their thread
 constexpr uint64_t kPiece = 1ull << 20;                // symbols per entry of the long sub-runs' list
-constexpr uint32_t kSymbols = 6, kNoRow = 7;
 constexpr uint32_t kStringWords = kTileWords + 2;      // u64 words of one symbol's bit string: 63 bits of alignment + kMergeTile bits
-constexpr uint64_t kMaxTotal = 1ull << 40;
 static_assert(kRowsPer == 16 && kTileWords == 64, "a thread holds a quarter word of the vector; wave 0 scans the tile's words");
 
-__host__ __device__ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline uint32_t grid_for(uint64_t items, uint64_t per_block, uint32_t cap = 1u << 20) {
     return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(cap, ceil_div(items, per_block))));
 }
@@ -171,7 +159,8 @@ struct Rows {
 
 // symbol k of a tile's rows taken input by input: input 0's slice [start0, start0 + n0), then input 1's from start1 on.  The
 // load itself is unconditional (of element 0 when the index is past the input, which it is not while the vector has exactly t1
-// set bits; an array has at least 256 bytes), so that a thread's loads are all in flight at once.
+// set bits; element 0 of an empty input is a byte of the symbol array or of the slack run_merge allocates past it), so that a
+// thread's loads are all in flight at once.
 __device__ __forceinline__ uint32_t slice_symbol(const Inputs &in, uint64_t start0, uint64_t start1, uint32_t n0, uint32_t k) {
     const bool first = k < n0;
     const uint64_t i = first ? start0 + k : start1 + (k - n0);
@@ -222,14 +211,6 @@ __device__ __forceinline__ Rows load_rows(TileShared &sh, const uint64_t *__rest
     }
     return r;
 }
-
-// one row per symbol, 16 bits each: symbols 0..3 in *a, 4 and 5 in *b (a tile's sum of a field is <= kMergeTile < 2^16)
-__device__ __forceinline__ void count_symbol(uint32_t s, uint64_t *a, uint64_t *b) {
-    *a += s < 4u ? 1ull << (16u * s) : 0ull;
-    *b += s == 4u ? 1ull : s == 5u ? 1ull << 16 : 0ull;
-}
-
-__device__ __forceinline__ uint32_t field(uint64_t a, uint64_t b, uint32_t s) { return uint32_t((s < 4u ? a >> (16u * s) : b >> (16u * (s - 4u))) & 0xFFFFu); }
 
 // hist[symbol * ntiles + tile] = the tile's rows with that symbol.  The counts do not depend on the order of the rows inside
 // the tile, so the two slices are counted as they lie; ones_before (scanned) says where they start and end.
@@ -314,14 +295,49 @@ __global__ __launch_bounds__(256) void k_emit_rows(const uint64_t *__restrict__ 
                                                    uint8_t *__restrict__ merged) {
     __shared__ TileShared sh;
     const Rows r = load_rows(sh, bits, nwords, ones_before, in);
-    uint32_t out[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t j = 0; j < kRowsPer; ++j) {
-        const uint32_t s = uint32_t(r.syms >> (3u * j)) & 7u;
-        out[j >> 2] |= (s == kNoRow ? 0u : s) << (8u * (j & 3u));
-    }
-    *reinterpret_cast<uint4 *>(merged + uint64_t(blockIdx.x) * kMergeTile + uint64_t(threadIdx.x) * kRowsPer) = make_uint4(out[0], out[1], out[2], out[3]);
+    *reinterpret_cast<uint4 *>(merged + uint64_t(blockIdx.x) * kMergeTile + uint64_t(threadIdx.x) * kRowsPer) = merged_symbols(r.syms);
 }
+
+// ---- the bit state under run_merge ----
+
+struct BitState {
+    using Word = uint64_t;
+    static uint64_t plan(const MergeJob &job) { return plan_merge(job.first[1], job.total - job.first[1]); }
+    static uint64_t state_bytes(const MergeJob &job) { return ceil_div(job.total, 64) * 8; }
+    static uint64_t out_bytes(const MergeJob &job) { return ceil_div(job.total, 8); }
+    static uint64_t counts(const MergeJob &) { return 1; }  // the tile's set bits
+
+    const MergeJob &job;
+    const uint64_t nwords;
+    const Inputs inputs;
+    const uint32_t word_grid, tile_grid;
+    explicit BitState(const MergeJob &j)
+        : job(j), nwords(ceil_div(j.total, 64)), inputs{j.d_sym + j.shift[0], j.d_sym + j.first[1] + j.shift[1], j.first[1], j.total - j.first[1]},
+          word_grid(grid_for(nwords, kThreads * 4u)), tile_grid(uint32_t(j.ntiles)) {}
+
+    hipError_t begin(Arena &, uint64_t *cur) const {
+        hipLaunchKernelGGL(k_first_vector, dim3(word_grid), dim3(kThreads), 0, job.stream, cur, nwords, inputs.t0, job.total);
+        return hipSuccess;
+    }
+    // where the tiles of `bits` start in input 1
+    hipError_t tile_starts(const uint64_t *bits) const {
+        hipLaunchKernelGGL(k_tile_ones, dim3(uint32_t(ceil_div(job.ntiles, kScanWaves))), dim3(kThreads), 0, job.stream, bits, nwords, job.ntiles, job.d_counts);
+        return exclusive_scan(job.d_counts, job.ntiles, job.d_counts + job.ntiles, job.stream);
+    }
+    void histogram() const {
+        hipLaunchKernelGGL(k_tile_histogram, dim3(tile_grid), dim3(kThreads), 0, job.stream, job.d_counts, inputs, job.ntiles, job.d_hist);
+    }
+    hipError_t scatter(const uint64_t *cur, uint64_t *next) const {
+        const hipError_t e = hipMemsetAsync(next, 0, nwords * 8, job.stream);  // segments share their first and last word: they are or-ed in
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_scatter, dim3(tile_grid), dim3(kThreads), 0, job.stream, cur, nwords, job.d_counts, inputs, job.ntiles, job.d_hist, next);
+        hipLaunchKernelGGL(k_differs, dim3(word_grid), dim3(kThreads), 0, job.stream, cur, next, nwords, job.d_flag);
+        return hipSuccess;
+    }
+    void emit(const uint64_t *bits, uint8_t *merged) const {
+        hipLaunchKernelGGL(k_emit_rows, dim3(tile_grid), dim3(kThreads), 0, job.stream, bits, nwords, job.d_counts, inputs, merged);
+    }
+};
 
 }  // namespace
 
@@ -386,102 +402,8 @@ uint64_t plan_merge(uint64_t total0, uint64_t total1) {
     return 2 * total + total / 8 + total / 32 + (8ull << 20);
 }
 
-hipError_t merge_rle_pair(const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, hipStream_t stream,
-                          MergeOutput *out) {
-    Arena arena;
-    auto clock = std::chrono::steady_clock::now();
-    hipError_t e = hipSuccess;
-    const uint64_t t0 = in0.total, t1 = in1.total, total = t0 + t1;
-    if (total == 0 || total >= kMaxTotal) return hipErrorInvalidValue;
-    auto failed = [&](const char *what) {
-        out->what = what;
-        if (e == hipErrorOutOfMemory)
-            out->what += ": the merge of " + std::to_string(total) + " symbols needs " + std::to_string(plan_merge(t0, t1)) + " bytes of HBM";
-        return e;
-    };
-    auto lap = [&](MergeStage stage) {
-        const hipError_t s = hipStreamSynchronize(stream);
-        const auto now = std::chrono::steady_clock::now();
-        out->stage_ms[stage] += std::chrono::duration<double, std::milli>(now - clock).count();
-        clock = now;
-        return s;
-    };
-    const uint64_t ntiles = ceil_div(total, kMergeTile), nwords = ceil_div(total, 64);
-
-    // ---- the RLE bytes in HBM
-    uint8_t *d_rle0 = nullptr, *d_rle1 = nullptr, *d_sym0 = nullptr, *d_sym1 = nullptr;
-    if ((e = arena.take(&d_rle0, len0)) != hipSuccess || (e = arena.take(&d_rle1, len1)) != hipSuccess) return failed("the inputs in HBM");
-    if (len0) e = hipMemcpyAsync(d_rle0, rle0, len0, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && len1) e = hipMemcpyAsync(d_rle1, rle1, len1, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = lap(kMergeCopyIn);
-    if (e != hipSuccess) return failed("copying the inputs to HBM");
-
-    // ---- 1. decode
-    const char *step = "";
-    if ((e = arena.take(&d_sym0, t0)) != hipSuccess || (e = arena.take(&d_sym1, t1)) != hipSuccess) return failed("the symbol arrays");
-    if ((e = decode(arena, d_rle0, len0, in0, d_sym0, stream, &step)) != hipSuccess || (e = decode(arena, d_rle1, len1, in1, d_sym1, stream, &step)) != hipSuccess)
-        return failed(step);
-    if ((e = lap(kMergeDecode)) != hipSuccess) return failed("decoding the inputs");
-    arena.give_back(d_rle0);
-    arena.give_back(d_rle1);
-
-    // ---- 2. iterate
-    uint64_t *d_cur = nullptr, *d_next = nullptr, *d_ones = nullptr, *d_hist = nullptr;
-    uint32_t *d_flag = nullptr, changed = 1;
-    if ((e = arena.take(&d_cur, nwords * 8)) != hipSuccess || (e = arena.take(&d_next, nwords * 8)) != hipSuccess ||
-        (e = arena.take(&d_ones, (ntiles + scan_scratch_words(ntiles)) * 8)) != hipSuccess ||
-        (e = arena.take(&d_hist, (kSymbols * ntiles + scan_scratch_words(kSymbols * ntiles)) * 8)) != hipSuccess || (e = arena.take(&d_flag, 4)) != hipSuccess)
-        return failed("the interleave vectors");
-    const Inputs inputs{d_sym0, d_sym1, t0, t1};
-    const uint32_t word_grid = grid_for(nwords, kThreads * 4u), tile_grid = uint32_t(ntiles), ones_grid = uint32_t(ceil_div(ntiles, kScanWaves));
-    // where the tiles of `bits` start in input 1: d_ones, scanned
-    auto tile_starts = [&](const uint64_t *bits) {
-        hipLaunchKernelGGL(k_tile_ones, dim3(ones_grid), dim3(kThreads), 0, stream, bits, nwords, ntiles, d_ones);
-        return exclusive_scan(d_ones, ntiles, d_ones + ntiles, stream);
-    };
-    hipLaunchKernelGGL(k_first_vector, dim3(word_grid), dim3(kThreads), 0, stream, d_cur, nwords, t0, total);
-    while (changed) {
-        if (out->iterations >= total + 2) {  // a bug trap, nothing else: every iteration before the last settles at least one more symbol of context
-            out->what = "the interleave did not settle in " + std::to_string(total + 2) + " iterations (a bug)";
-            return hipErrorUnknown;
-        }
-        if ((e = hipMemsetAsync(d_next, 0, nwords * 8, stream)) != hipSuccess || (e = hipMemsetAsync(d_flag, 0, 4, stream)) != hipSuccess ||
-            (e = tile_starts(d_cur)) != hipSuccess)
-            return failed("an interleave iteration");
-        hipLaunchKernelGGL(k_tile_histogram, dim3(tile_grid), dim3(kThreads), 0, stream, d_ones, inputs, ntiles, d_hist);
-        if ((e = exclusive_scan(d_hist, kSymbols * ntiles, d_hist + kSymbols * ntiles, stream)) != hipSuccess) return failed("an interleave iteration");
-        hipLaunchKernelGGL(k_scatter, dim3(tile_grid), dim3(kThreads), 0, stream, d_cur, nwords, d_ones, inputs, ntiles, d_hist, d_next);
-        hipLaunchKernelGGL(k_differs, dim3(word_grid), dim3(kThreads), 0, stream, d_cur, d_next, nwords, d_flag);
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpyAsync(&changed, d_flag, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess)
-            return failed("an interleave iteration");
-        std::swap(d_cur, d_next);
-        ++out->iterations;
-    }
-    if ((e = lap(kMergeIterate)) != hipSuccess) return failed("the interleave iterations");
-    arena.give_back(d_next);
-    arena.give_back(d_hist);
-    arena.give_back(d_flag);
-
-    // ---- 3. emit
-    uint8_t *d_merged = nullptr;
-    if ((e = arena.take(&d_merged, ntiles * kMergeTile)) != hipSuccess) return failed("the merged symbols");
-    if ((e = tile_starts(d_cur)) != hipSuccess) return failed("emitting the merged symbols");
-    hipLaunchKernelGGL(k_emit_rows, dim3(tile_grid), dim3(kThreads), 0, stream, d_cur, nwords, d_ones, inputs, d_merged);
-    if ((e = hipGetLastError()) != hipSuccess || (e = lap(kMergeEmit)) != hipSuccess) return failed("emitting the merged symbols");
-    arena.give_back(d_sym0);
-    arena.give_back(d_sym1);
-    arena.give_back(d_ones);
-
-    // ---- 4. encode
-    uint8_t *d_rle = nullptr;
-    uint64_t need = 0;
-    if ((e = encode_symbol_runs(arena, d_merged, total, stream, &d_rle, &need, &step)) != hipSuccess) return failed(step);
-    if ((e = lap(kMergeEncode)) != hipSuccess) return failed("writing the runs");
-    out->d_rle = arena.keep(d_rle);
-    out->rle_bytes = need;
-    out->d_from_second = arena.keep(d_cur);
-    return hipSuccess;
+hipError_t merge_rle_pair(const MergeSpan *spans, size_t n, hipStream_t stream, MergeOutput *out) {
+    return n == 2 ? run_merge<BitState>(spans, n, stream, out) : hipErrorInvalidValue;
 }
 
 }  // namespace msbwt

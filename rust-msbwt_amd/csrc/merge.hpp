@@ -36,18 +36,27 @@ MergeInputStatus scan_merge_input(const uint8_t *rle, size_t n, MergeInput *out)
 // At most 2.5 x (total0 + total1) + 64 MiB.
 uint64_t plan_merge(uint64_t total0, uint64_t total1);
 
+// One input: host memory that scan_merge_input accepted (in: what it said).
+struct MergeSpan {
+    const uint8_t *rle;
+    size_t len;
+    MergeInput in;
+};
+
 struct MergeOutput {
     uint8_t *d_rle = nullptr;    // hipMalloc'ed, the caller frees it
     uint64_t rle_bytes = 0;
-    uint64_t *d_from_second = nullptr;  // the final vector: bit i & 63 of word i >> 6 set = merged row i is input 1's; the caller frees it
+    // the final state, hipMalloc'ed, the caller frees it; its first state_bytes bytes describe the merged rows.  merge_rle_pair: bit
+    // i & 7 of byte i >> 3 set = merged row i is input 1's.  merge_rle_many: byte i = the input merged row i came from.
+    uint8_t *d_state = nullptr;
+    uint64_t state_bytes = 0;
     uint64_t iterations = 0;
     double stage_ms[kMergeStages] = {};
     std::string what;  // on failure: the step that failed
 };
 
-// rle0 / rle1: host memory that scan_merge_input accepted (in0, in1: what it said), in0.total + in1.total in [1, 2^40).
-hipError_t merge_rle_pair(const uint8_t *rle0, size_t len0, const MergeInput &in0, const uint8_t *rle1, size_t len1, const MergeInput &in1, hipStream_t stream,
-                          MergeOutput *out);
+// spans: two inputs (n == 2), their totals summing to [1, 2^40).
+hipError_t merge_rle_pair(const MergeSpan *spans, size_t n, hipStream_t stream, MergeOutput *out);
 
 // The decoder of merge.hip, which merge_many.hip shares: d_rle[0 .. n) in HBM, a stream scan_merge_input accepted (in: what it
 // said) -> d_symbols[0 .. in.total), a byte per symbol; d_symbols is 16-byte aligned.  The stream is drained when it returns.
@@ -62,17 +71,7 @@ constexpr uint32_t kMergeMaxInputs = 32;
 // their number and their runs are.  At least 2 x total, at most 3.25 x total + 64 MiB.
 uint64_t plan_merge_many(uint64_t total);
 
-struct MergeManyOutput {
-    uint8_t *d_rle = nullptr;     // hipMalloc'ed, the caller frees it
-    uint64_t rle_bytes = 0;
-    uint8_t *d_source = nullptr;  // the final array: byte i = the input merged row i came from; the caller frees it
-    uint64_t iterations = 0;
-    double stage_ms[kMergeStages] = {};
-    std::string what;  // on failure: the step that failed
-};
-
-// rle: host memory, input i is rle[offsets[i] .. offsets[i + 1]), a stream scan_merge_input accepted (in[i]: what it said);
-// 1 <= n <= kMergeMaxInputs, the totals sum to [1, 2^40).
-hipError_t merge_rle_many(const uint8_t *rle, const uint64_t *offsets, const MergeInput *in, size_t n, hipStream_t stream, MergeManyOutput *out);
+// spans: 1 <= n <= kMergeMaxInputs inputs, their totals summing to [1, 2^40).
+hipError_t merge_rle_many(const MergeSpan *spans, size_t n, hipStream_t stream, MergeOutput *out);
 
 }  // namespace msbwt

@@ -23,29 +23,15 @@
 //
 // Integer only; every kernel runs without scratch memory.  Every row index and offset is 64-bit; 32-bit are counts and ranks
 // inside one tile (<= kMergeTile).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cstdint>
-#include <string>
-
-#include "merge.hpp"
-#include "run_encode.hpp"
+#include "merge_common.hpp"
 
 namespace msbwt {
 
 namespace {
 
-constexpr uint32_t kThreads = kScanThreads;
-constexpr uint32_t kRowsPer = kMergeTile / kThreads;  // consecutive rows of a tile one thread holds: one 16-byte load
-constexpr uint32_t kSymbols = 6, kNoRow = 7;
 constexpr uint32_t kGroups = kMergeMaxInputs / 4;     // words of four 16-bit counts, one count per input
 constexpr uint32_t kStrung = kMergeTile + kSymbols * 32;  // the six strings: each starts at most 15 bytes into a 16-byte line of its own
-constexpr uint64_t kMaxTotal = 1ull << 40;
 static_assert(kRowsPer == 16 && kMergeMaxInputs == 32 && kMergeTile <= 0xFFFFu, "a thread holds 16 bytes of the array; a count of a tile fits 16 bits");
-
-__host__ __device__ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 struct ManyInputs {
     const uint8_t *sym;     // the decoded inputs, one after the other
@@ -149,14 +135,6 @@ __device__ __forceinline__ uint32_t slice_symbol(const TileMap &map, const ManyI
     for (uint32_t step = kMergeMaxInputs / 2; step > 0; step >>= 1) i += map.pre[i + step] <= k ? step : 0u;  // the last slice that starts at or before k
     return in.sym[min(map.from[i] + k, in.sym_bytes - 1u)];
 }
-
-// one row per symbol, 16 bits each: symbols 0..3 in *a, 4 and 5 in *b (a tile's sum of a field is <= kMergeTile < 2^16)
-__device__ __forceinline__ void count_symbol(uint32_t s, uint64_t *a, uint64_t *b) {
-    *a += s < 4u ? 1ull << (16u * s) : 0ull;
-    *b += s == 4u ? 1ull : s == 5u ? 1ull << 16 : 0ull;
-}
-
-__device__ __forceinline__ uint32_t field(uint64_t a, uint64_t b, uint32_t s) { return uint32_t((s < 4u ? a >> (16u * s) : b >> (16u * (s - 4u))) & 0xFFFFu); }
 
 // ---- 2 b. symbols per tile ----
 
@@ -291,14 +269,51 @@ __global__ __launch_bounds__(256) void k_many_emit(const uint8_t *__restrict__ s
                                                    uint8_t *__restrict__ merged) {
     __shared__ TileShared sh;
     const Rows r = load_rows(sh, src, starts, in, ntiles);
-    uint32_t out[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t j = 0; j < kRowsPer; ++j) {
-        const uint32_t s = uint32_t(r.syms >> (3u * j)) & 7u;
-        out[j >> 2] |= (s == kNoRow ? 0u : s) << (8u * (j & 3u));
-    }
-    *reinterpret_cast<uint4 *>(merged + uint64_t(blockIdx.x) * kMergeTile + uint64_t(threadIdx.x) * kRowsPer) = make_uint4(out[0], out[1], out[2], out[3]);
+    *reinterpret_cast<uint4 *>(merged + uint64_t(blockIdx.x) * kMergeTile + uint64_t(threadIdx.x) * kRowsPer) = merged_symbols(r.syms);
 }
+
+// ---- the byte state under run_merge ----
+
+struct ByteState {
+    using Word = uint8_t;
+    static uint64_t plan(const MergeJob &job) { return plan_merge_many(job.total); }
+    static uint64_t state_bytes(const MergeJob &job) { return job.ntiles * kMergeTile; }  // whole tiles: a thread loads 16 bytes
+    static uint64_t out_bytes(const MergeJob &job) { return job.total; }
+    static uint64_t counts(const MergeJob &job) { return job.n; }  // the tile's rows of every input
+
+    const MergeJob &job;
+    const uint32_t tile_grid;
+    ManyInputs inputs;
+    explicit ByteState(const MergeJob &j) : job(j), tile_grid(uint32_t(j.ntiles)), inputs{j.d_sym, nullptr, j.sym_bytes, j.total, j.n} {}
+
+    hipError_t begin(Arena &arena, uint8_t *cur) {
+        uint64_t *d_shift = nullptr;  // (the arena frees it)
+        hipError_t e;
+        if ((e = arena.take(&d_shift, job.n * 8)) != hipSuccess || (e = hipMemcpyAsync(d_shift, job.shift, job.n * 8, hipMemcpyHostToDevice, job.stream)) != hipSuccess) return e;
+        inputs.shift = d_shift;
+        for (uint32_t i = 0; i < job.n; ++i) {
+            const uint64_t rows = job.first[i + 1] - job.first[i];
+            if (rows && (e = hipMemsetAsync(cur + job.first[i], int(i), rows, job.stream)) != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    // where the tiles of `src` start in every input
+    hipError_t tile_starts(const uint8_t *src) const {
+        const uint64_t ncounts = uint64_t(job.n) * job.ntiles;
+        hipLaunchKernelGGL(k_many_input_counts, dim3(tile_grid), dim3(kThreads), 0, job.stream, src, job.total, job.n, job.ntiles, job.d_counts);
+        return exclusive_scan(job.d_counts, ncounts, job.d_counts + ncounts, job.stream);
+    }
+    void histogram() const {
+        hipLaunchKernelGGL(k_many_histogram, dim3(tile_grid), dim3(kThreads), 0, job.stream, job.d_counts, inputs, job.ntiles, job.d_hist);
+    }
+    hipError_t scatter(const uint8_t *cur, uint8_t *next) const {
+        hipLaunchKernelGGL(k_many_scatter, dim3(tile_grid), dim3(kThreads), 0, job.stream, cur, job.d_counts, inputs, job.ntiles, job.d_hist, next, job.d_flag);
+        return hipSuccess;
+    }
+    void emit(const uint8_t *src, uint8_t *merged) const {
+        hipLaunchKernelGGL(k_many_emit, dim3(tile_grid), dim3(kThreads), 0, job.stream, src, job.d_counts, inputs, job.ntiles, merged);
+    }
+};
 
 }  // namespace
 
@@ -313,111 +328,6 @@ uint64_t plan_merge_many(uint64_t total) {
     return 3 * total + total / 8 + (8ull << 20);
 }
 
-hipError_t merge_rle_many(const uint8_t *rle, const uint64_t *offsets, const MergeInput *in, size_t n, hipStream_t stream, MergeManyOutput *out) {
-    Arena arena;
-    auto clock = std::chrono::steady_clock::now();
-    hipError_t e = hipSuccess;
-    if (n == 0 || n > kMergeMaxInputs) return hipErrorInvalidValue;
-    uint64_t first[kMergeMaxInputs + 1], shift[kMergeMaxInputs], total = 0, sym_bytes = 0;  // first: input i's rows in the first array; first + shift: its symbols
-    for (size_t i = 0; i < n; ++i) {
-        first[i] = total;
-        sym_bytes = (sym_bytes + 15u) & ~15ull;
-        shift[i] = sym_bytes - total;
-        sym_bytes += in[i].total;
-        total += in[i].total;
-    }
-    first[n] = total;
-    if (total == 0 || total >= kMaxTotal) return hipErrorInvalidValue;
-    auto failed = [&](const char *what) {
-        out->what = what;
-        if (e == hipErrorOutOfMemory)
-            out->what += ": the merge of " + std::to_string(total) + " symbols in " + std::to_string(n) + " inputs needs " + std::to_string(plan_merge_many(total)) + " bytes of HBM";
-        return e;
-    };
-    auto lap = [&](MergeStage stage) {
-        const hipError_t s = hipStreamSynchronize(stream);
-        const auto now = std::chrono::steady_clock::now();
-        out->stage_ms[stage] += std::chrono::duration<double, std::milli>(now - clock).count();
-        clock = now;
-        return s;
-    };
-    const uint64_t ntiles = ceil_div(total, kMergeTile), rle_bytes = offsets[n] - offsets[0];
-
-    // ---- the RLE bytes in HBM
-    uint8_t *d_rle = nullptr, *d_sym = nullptr;
-    if ((e = arena.take(&d_rle, rle_bytes)) != hipSuccess) return failed("the inputs in HBM");
-    if (rle_bytes) e = hipMemcpyAsync(d_rle, rle + offsets[0], rle_bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = lap(kMergeCopyIn);
-    if (e != hipSuccess) return failed("copying the inputs to HBM");
-
-    // ---- 1. decode
-    const char *step = "";
-    if ((e = arena.take(&d_sym, sym_bytes)) != hipSuccess) return failed("the symbol array");
-    for (size_t i = 0; i < n; ++i)
-        if ((e = decode(arena, d_rle + (offsets[i] - offsets[0]), offsets[i + 1] - offsets[i], in[i], d_sym + first[i] + shift[i], stream, &step)) != hipSuccess)
-            return failed(step);
-    if ((e = lap(kMergeDecode)) != hipSuccess) return failed("decoding the inputs");
-    arena.give_back(d_rle);
-
-    // ---- 2. iterate
-    uint8_t *d_cur = nullptr, *d_next = nullptr;
-    uint64_t *d_counts = nullptr, *d_hist = nullptr, *d_shift = nullptr;
-    uint32_t *d_flag = nullptr, changed = 1;
-    const uint64_t ncounts = uint64_t(n) * ntiles;
-    if ((e = arena.take(&d_cur, ntiles * kMergeTile)) != hipSuccess || (e = arena.take(&d_next, ntiles * kMergeTile)) != hipSuccess ||
-        (e = arena.take(&d_counts, (ncounts + scan_scratch_words(ncounts)) * 8)) != hipSuccess ||
-        (e = arena.take(&d_hist, (kSymbols * ntiles + scan_scratch_words(kSymbols * ntiles)) * 8)) != hipSuccess || (e = arena.take(&d_shift, n * 8)) != hipSuccess ||
-        (e = arena.take(&d_flag, 4)) != hipSuccess)
-        return failed("the interleave arrays");
-    if ((e = hipMemcpyAsync(d_shift, shift, n * 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return failed("the interleave arrays");
-    for (size_t i = 0; i < n; ++i)  // the first array: input 0's rows, then input 1's, and so on
-        if (in[i].total && (e = hipMemsetAsync(d_cur + first[i], int(i), in[i].total, stream)) != hipSuccess) return failed("the first interleave array");
-    const ManyInputs inputs{d_sym, d_shift, sym_bytes, total, uint32_t(n)};
-    const uint32_t tile_grid = uint32_t(ntiles);
-    // where the tiles of `src` start in every input: d_counts, scanned
-    auto tile_starts = [&](const uint8_t *src) {
-        hipLaunchKernelGGL(k_many_input_counts, dim3(tile_grid), dim3(kThreads), 0, stream, src, total, uint32_t(n), ntiles, d_counts);
-        return exclusive_scan(d_counts, ncounts, d_counts + ncounts, stream);
-    };
-    while (changed) {
-        if (out->iterations >= total + 2) {  // a bug trap, nothing else: every iteration before the last settles at least one more symbol of context
-            out->what = "the interleave did not settle in " + std::to_string(total + 2) + " iterations (a bug)";
-            return hipErrorUnknown;
-        }
-        if ((e = hipMemsetAsync(d_flag, 0, 4, stream)) != hipSuccess || (e = tile_starts(d_cur)) != hipSuccess) return failed("an interleave iteration");
-        hipLaunchKernelGGL(k_many_histogram, dim3(tile_grid), dim3(kThreads), 0, stream, d_counts, inputs, ntiles, d_hist);
-        if ((e = exclusive_scan(d_hist, kSymbols * ntiles, d_hist + kSymbols * ntiles, stream)) != hipSuccess) return failed("an interleave iteration");
-        hipLaunchKernelGGL(k_many_scatter, dim3(tile_grid), dim3(kThreads), 0, stream, d_cur, d_counts, inputs, ntiles, d_hist, d_next, d_flag);
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpyAsync(&changed, d_flag, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess)
-            return failed("an interleave iteration");
-        std::swap(d_cur, d_next);
-        ++out->iterations;
-    }
-    if ((e = lap(kMergeIterate)) != hipSuccess) return failed("the interleave iterations");
-    arena.give_back(d_next);
-    arena.give_back(d_hist);
-    arena.give_back(d_flag);
-
-    // ---- 3. emit
-    uint8_t *d_merged = nullptr;
-    if ((e = arena.take(&d_merged, ntiles * kMergeTile)) != hipSuccess) return failed("the merged symbols");
-    if ((e = tile_starts(d_cur)) != hipSuccess) return failed("emitting the merged symbols");
-    hipLaunchKernelGGL(k_many_emit, dim3(tile_grid), dim3(kThreads), 0, stream, d_cur, d_counts, inputs, ntiles, d_merged);
-    if ((e = hipGetLastError()) != hipSuccess || (e = lap(kMergeEmit)) != hipSuccess) return failed("emitting the merged symbols");
-    arena.give_back(d_sym);
-    arena.give_back(d_counts);
-    arena.give_back(d_shift);
-
-    // ---- 4. encode
-    uint8_t *d_out = nullptr;
-    uint64_t need = 0;
-    if ((e = encode_symbol_runs(arena, d_merged, total, stream, &d_out, &need, &step)) != hipSuccess) return failed(step);
-    if ((e = lap(kMergeEncode)) != hipSuccess) return failed("writing the runs");
-    out->d_rle = arena.keep(d_out);
-    out->rle_bytes = need;
-    out->d_source = arena.keep(d_cur);
-    return hipSuccess;
-}
+hipError_t merge_rle_many(const MergeSpan *spans, size_t n, hipStream_t stream, MergeOutput *out) { return run_merge<ByteState>(spans, n, stream, out); }
 
 }  // namespace msbwt

@@ -89,6 +89,19 @@ def _pack_rles(rles):
     return (np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)), offsets
 
 
+def _call_growing(call, cap):
+    """call(out, cap, &length) with an output buffer of `cap` bytes, once more with a larger one if the library says it needs more:
+    (return code, the bytes written)."""
+    length = C.c_uint64(0)
+    for _ in range(2):
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        rc = call(out.ctypes.data_as(C.c_void_p), cap, C.byref(length))
+        if rc != _lib.ERR_INVALID_ARG or length.value <= cap:
+            break
+        cap = int(length.value)
+    return rc, out[:length.value]
+
+
 class RleBWT(BWT):
     def __init__(self, bin_power=8, device=-1):
         """RleBWT::new() / with_bin_power (rle_bwt.rs:297-322). `device` = HIP ordinal."""
@@ -193,24 +206,17 @@ class RleBWT(BWT):
         came from `rle1` (rows of equal rotations: those of `rle0` first).  The handle's own index, if it has one, stays as it is."""
         a = np.ascontiguousarray(rle0, dtype=np.uint8).ravel()
         b = np.ascontiguousarray(rle1, dtype=np.uint8).ravel()
-        cap = a.size + b.size
-        out = np.empty(max(cap, 1), dtype=np.uint8)
         bits, total = None, 0
         if return_interleave:
             total = rle_total(a) + rle_total(b)
             bits = np.zeros((total + 7) // 8 + 1 if total < 2 ** 40 else 1, dtype=np.uint8)  # (2^40 and more: the library refuses)
-        length = C.c_uint64(0)
-        args = (a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, b.ctypes.data_as(C.c_void_p) if b.size else None, b.size)
-        rc = _lib.lib().msbwt_rle_merge(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), bits.ctypes.data_as(C.c_void_p) if return_interleave else None)
-        if rc == _lib.ERR_INVALID_ARG and length.value > cap:  # inputs that were not canonical can merge into more bytes than they took
-            cap = int(length.value)
-            out = np.empty(cap, dtype=np.uint8)
-            rc = _lib.lib().msbwt_rle_merge(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), bits.ctypes.data_as(C.c_void_p) if return_interleave else None)
+        args = (self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, b.ctypes.data_as(C.c_void_p) if b.size else None, b.size)
+        where = bits.ctypes.data_as(C.c_void_p) if return_interleave else None
+        # inputs that were not canonical can merge into more bytes than they took
+        rc, out = _call_growing(lambda *out: _lib.lib().msbwt_rle_merge(*args, *out, where), a.size + b.size)
         if rc:
             _raise(rc, self._h)
-        if not return_interleave:
-            return out[:length.value]
-        return out[:length.value], np.unpackbits(bits, bitorder="little")[:total]
+        return (out, np.unpackbits(bits, bitorder="little")[:total]) if return_interleave else out
 
     def load_merged(self, rle0, rle1):
         """merge, then the result loaded as load_vector would load it."""
@@ -228,23 +234,17 @@ class RleBWT(BWT):
         index first).  The handle's own index, if it has one, stays as it is."""
         flat, offsets = _pack_rles(rles)
         n = offsets.size - 1
-        cap = flat.size
-        out = np.empty(max(cap, 1), dtype=np.uint8)
         sources = None
         if return_sources:
             total = sum(rle_total(flat[offsets[i]:offsets[i + 1]]) for i in range(n)) if n <= _lib.MERGE_MAX_INPUTS else 0
             sources = np.zeros(total if total < 2 ** 40 else 0, dtype=np.uint8)  # (2^40 and more, too many inputs: the library refuses)
-        length = C.c_uint64(0)
-        args = (flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), n)
+        args = (self._h, flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), n)
         where = sources.ctypes.data_as(C.c_void_p) if return_sources and sources.size else None
-        rc = _lib.lib().msbwt_rle_merge_many(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), where)
-        if rc == _lib.ERR_INVALID_ARG and length.value > cap:  # inputs that were not canonical can merge into more bytes than they took
-            cap = int(length.value)
-            out = np.empty(cap, dtype=np.uint8)
-            rc = _lib.lib().msbwt_rle_merge_many(self._h, *args, out.ctypes.data_as(C.c_void_p), cap, C.byref(length), where)
+        # inputs that were not canonical can merge into more bytes than they took
+        rc, out = _call_growing(lambda *out: _lib.lib().msbwt_rle_merge_many(*args, *out, where), flat.size)
         if rc:
             _raise(rc, self._h)
-        return (out[:length.value], sources) if return_sources else out[:length.value]
+        return (out, sources) if return_sources else out
 
     def load_merged_many(self, rles):
         """merge_many, then the result loaded as load_vector would load it."""

@@ -162,6 +162,31 @@ def test_a_single_empty_read_and_an_empty_input(bwt, orc):
     assert np.array_equal(bwt.merge(loose, empty), orc.convert_to_vec("AA$"))
 
 
+# ---- the inputs' places in the one symbol array ----
+
+def tiny_reads(total, seed):
+    """Reads of at most five letters whose symbols and terminators number `total` (none for 0, one empty read for 1)."""
+    rng = np.random.default_rng(seed)
+    sizes = [6] * (total // 6) + [total % 6] * (total % 6 > 0)
+    return ["".join(rng.choice(list("ACGT"), size=n - 1)) for n in sizes]
+
+
+@pytest.mark.parametrize("total1", [0, 1, 16])
+@pytest.mark.parametrize("total0", [15, 16, 17])
+def test_inputs_around_a_16_byte_border(bwt, orc, total0, total1):
+    """Both inputs are decoded into one array, each at a 16-byte border: one symbol short of a border, at it and one past it, then
+    an input that is empty (its first symbol, which the kernels load, is past the array), a single '$' or a whole line."""
+    a, b = tiny_reads(total0, 10 * total0 + total1), tiny_reads(total1, 500 + 10 * total0 + total1)
+    ra, rb = naive_rle(orc, a), naive_rle(orc, b) if b else np.empty(0, dtype=np.uint8)
+    assert rle_total(ra) == total0 and rle_total(rb) == total1
+    want = naive_rle(orc, a + b)
+    for first, second in ((ra, rb), (rb, ra)):
+        merged, bits = bwt.merge(first, second, return_interleave=True)
+        assert np.array_equal(merged, want)
+        check_interleave(bits, merged, first, second)
+        assert bwt.merge_info()["iterations"] >= 1
+
+
 # ---- convergence ----
 
 def test_convergence_takes_longer_than_the_read_length(bwt, orc):
