@@ -2,7 +2,7 @@
 // chunk i's host->pinned copy (CPU threads), chunk i-1's H2D, chunk i-2's kernel and D2H and
 // chunk i-3's pinned->host copy all overlap.  Copies and kernels sit on three HIP streams chained
 // by events; nothing synchronises the device per chunk.  Used by the host-pointer entry points
-// of capi.cpp (the reference's trait surface takes host slices, msbwt_core.rs:124).
+// of query.cpp (the reference's trait surface takes host slices, msbwt_core.rs:124).
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -1,0 +1,18 @@
+// The loader's boundary (index_build.cpp): the six functions through which the rest of the C API decides what sits in HBM.
+// Everything else the loader defines is private to its unit.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/msbwt_hip.h"
+
+namespace msbwt_capi __attribute__((visibility("hidden"))) {
+
+int install(msbwt_rle *h, const uint8_t *rle, size_t n);
+void release_index(msbwt_rle *h);
+void release_sparse(msbwt_rle *h);
+int rebuild_table(msbwt_rle *h, bool allow_sparse = true);
+int rebuild_pair_index(msbwt_rle *h);
+void make_plan(msbwt_rle *h);
+
+}  // namespace msbwt_capi

@@ -63,7 +63,7 @@ struct IndexView {
     // the index -- steps, second lines, escape lines ... (msbwt_rle_search_counters); nullptr = not wanted
     uint64_t *counters = nullptr;
     // The index's random-access arrays are far larger than L2 and Infinity Cache: the lanes kernel fetches their lines with the
-    // non-temporal hint, so that lines used once do not evict what is reused (capi.cpp decides; lanes.hip has the measurements).
+    // non-temporal hint, so that lines used once do not evict what is reused (view_of in handle.hpp decides; lanes.hip has the measurements).
     bool stream_lines = false;
     // optional sparse suffix table (sparse_table.hpp): the ranges of the suffixes that occur, deeper than the direct table
     // reaches; the lanes kernel looks up queries of at least its depth there (beside a pair index), shorter ones in `table`

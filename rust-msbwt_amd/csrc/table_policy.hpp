@@ -95,7 +95,7 @@ inline uint64_t expected_table_bytes(uint64_t total, uint64_t block_bytes, uint6
     return c.packed ? flat_b + packed_table_bytes(c.packed) : flat_b;
 }
 
-// ---- run blocks: does the DEVICE builder fit?  (capi.cpp, build_run_index; pinned by a CPU test through msbwt_run_build_fits_device) ----
+// ---- run blocks: does the DEVICE builder fit?  (index_build.cpp, build_run_index; pinned by a CPU test through msbwt_run_build_fits_device) ----
 // Asked once the RLE bytes are in HBM and the totals are known: the plane blocks (128 bytes per 256 symbols) and the run blocks (128
 // bytes per 512 symbols, + up to an eighth in overflow blocks) must fit the free HBM side by side, with a 32nd of it as slack.  About
 // 0.8 byte per symbol at its peak against 0.3 for the finished index -- an index that loaded in this format only BECAUSE it is lean is
