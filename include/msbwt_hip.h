@@ -251,6 +251,54 @@ size_t msbwt_merge_tile(void);
 #define MSBWT_MERGE_STAGES 6
 int msbwt_rle_merge_info(const msbwt_rle *bwt, uint64_t *iterations, double *out_ms);
 
+/* ---- counts by source: how often a k-mer occurs in each input of a merged BWT (no reference counterpart) ----
+ * The rows of input i inside the merged range of a k-mer are exactly the occurrences of the k-mer in input i.  So with the merge's
+ * source vector attached to the loaded index, one search gives a k-mer's count in every input: column i of a result equals
+ * count_kmer on input i's own BWT, and the columns sum to count_kmer on the merged one.
+ *
+ * msbwt_rle_set_sources: attaches `sources`, a host array of one byte per row -- exactly what out_source of msbwt_rle_merge_many
+ * holds -- to the loaded index: the vector goes to HBM (in pieces through the pinned staging of the host batches) with one checkpoint
+ * of counts per msbwt_source_block_rows rows.  Checked on the host: an index is loaded (MSBWT_ERR_NOT_LOADED), n_rows equals
+ * msbwt_rle_get_total_size and 1 <= n_sources <= MSBWT_MERGE_MAX_INPUTS (MSBWT_ERR_INVALID_ARG); on the device, while the checkpoints
+ * are built: every byte < n_sources (MSBWT_ERR_INVALID_ARG).  Whatever was attached before is gone once the call has found an index,
+ * however it ends.  sources == NULL with n_sources == 0 detaches.  HBM that does not suffice: MSBWT_ERR_HIP, the message names the
+ * bytes needed (msbwt_source_index_plan).
+ * Lifetime: every load (msbwt_rle_load_vector, _load_numpy_file, _load_reads, _load_merged*) drops the attachment; the setters that
+ * rebuild optional structures (msbwt_rle_set_sparse_table, msbwt_rle_set_query_length, ...) keep it, the rows do not move;
+ * msbwt_rle_replicate copies it; msbwt_rle_device_bytes includes it.  It is the caller's explicit request and does NOT count
+ * against the plan of msbwt_rle_set_memory_budget. */
+int msbwt_rle_set_sources(msbwt_rle *bwt, const uint8_t *sources, uint64_t n_rows, size_t n_sources);
+/* msbwt_rle_load_merged_many, then the merge's own source vector attached (n_inputs sources); the vector stays in HBM between the
+ * two.  No inputs at all: nothing is attached. */
+int msbwt_rle_load_merged_many_sources(msbwt_rle *bwt, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs);
+/* Sources attached (0: none), and the rows of each (MSBWT_ERR_NOT_LOADED without an attachment). */
+int msbwt_rle_source_count(const msbwt_rle *bwt);
+int msbwt_rle_source_totals(const msbwt_rle *bwt, uint64_t *out /* n_sources */);
+/* out[n_sources * i + s] = occurrences of row i in input s.  Queries, error codes, the device form's asynchrony, the all-ones row
+ * of a query holding a code >= 6 and "always in the caller's order, whatever the knobs" are those of msbwt_rle_kmer_ranges[_device].
+ * k = 0: the source totals.  A k-mer that does not occur: zeros.  Without sources attached: MSBWT_ERR_NOT_LOADED, the message
+ * "no sources attached". */
+int msbwt_rle_count_kmers_by_source(const msbwt_rle *bwt, const uint8_t *kmers, size_t k, size_t n,
+                                    uint64_t *out_counts /* n x n_sources, row-major */);
+int msbwt_rle_count_kmers_by_source_device(const msbwt_rle *bwt, const void *d_kmers, size_t k, size_t n,
+                                           void *d_out_counts /* n x n_sources u64 */, void *hip_stream);
+/* The second phase on its own, for callers who carry ranges (msbwt_rle_constrain_ranges): out[n_sources * i + s] = rows of source
+ * s in [l[i], h[i]).  l == h: zeros.  l > h or h > total: an all-ones row and MSBWT_ERR_INTERNAL (the device's consistency flag, as
+ * the extension counts raise it); no address is formed from such a range. */
+int msbwt_rle_range_sources(const msbwt_rle *bwt, const uint64_t *l, const uint64_t *h, size_t n,
+                            uint64_t *out_counts /* n x n_sources */);
+int msbwt_rle_range_sources_device(const msbwt_rle *bwt, const void *d_l, const void *d_h, size_t n,
+                                   void *d_out_counts /* n x n_sources u64 */, void *hip_stream);
+/* Pure function, no device: HBM bytes the attachment of n_sources sources to total_rows rows holds -- the vector and the checkpoints,
+ * at most 1.5 x total_rows + MSBWT_SOURCE_INDEX_SLACK at 32 sources (fewer sources: less).  MSBWT_ERR_INVALID_ARG unless
+ * 1 <= n_sources <= MSBWT_MERGE_MAX_INPUTS, MSBWT_ERR_TOO_LARGE from 2^40 rows on. */
+#define MSBWT_SOURCE_INDEX_SLACK 1024
+int msbwt_source_index_plan(uint64_t total_rows, size_t n_sources, uint64_t *device_bytes);
+/* Rows per checkpoint, a power of two; and the widest range that is counted from its own bytes without a checkpoint (tests probe
+ * the borders of both). */
+size_t msbwt_source_block_rows(void);
+size_t msbwt_source_narrow_rows(void);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

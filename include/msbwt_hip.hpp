@@ -8,6 +8,7 @@
 // INTEGRATION.md.  Every query runs on the GPU; there is no CPU fallback.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -175,6 +176,71 @@ class RleBWT final : public BWT {
         }
         check(msbwt_rle_load_merged_many(raw_, flat.data(), offsets.data(), rles.size()));
     }
+
+    // ---- counts by source: how often a k-mer occurs in each input of a merged BWT ----
+    /// Attaches the source vector of a merge (one byte per row of the loaded index: merge_many's `sources`) so that
+    /// count_kmers_by_source can answer; n_sources 0 = the largest entry + 1.  clear_sources detaches; every load drops it.
+    void set_sources(const std::vector<std::uint8_t> &sources, std::size_t n_sources = 0) {
+        static const std::uint8_t none = 0;
+        if (!n_sources) {
+            for (std::uint8_t s : sources) n_sources = std::max<std::size_t>(n_sources, s);
+            n_sources += 1;
+        }
+        check(msbwt_rle_set_sources(raw_, sources.empty() ? &none : sources.data(), sources.size(), n_sources));
+    }
+    void clear_sources() { check(msbwt_rle_set_sources(raw_, nullptr, 0, 0)); }
+    /// load_merged_many with the merge's own source vector attached (rles.size() sources).
+    void load_merged_many_sources(const std::vector<std::vector<std::uint8_t>> &rles) {
+        std::vector<std::uint8_t> flat;
+        std::vector<std::uint64_t> offsets(1, 0);
+        for (const auto &r : rles) {
+            flat.insert(flat.end(), r.begin(), r.end());
+            offsets.push_back(flat.size());
+        }
+        check(msbwt_rle_load_merged_many_sources(raw_, flat.data(), offsets.data(), rles.size()));
+    }
+    std::size_t source_count() const { return static_cast<std::size_t>(msbwt_rle_source_count(raw_)); }
+    std::vector<std::uint64_t> source_totals() const {
+        std::vector<std::uint64_t> out(source_count());
+        if (!out.empty()) check(msbwt_rle_source_totals(raw_, out.data()));
+        return out;
+    }
+    /// n x source_count() row-major: [source_count() i + s] = occurrences of row i (of n x k symbol codes) in input s.
+    std::vector<std::uint64_t> count_kmers_by_source(const std::vector<std::uint8_t> &kmers, std::size_t k) const {
+        const std::size_t n = k ? kmers.size() / k : 0;
+        if (k && kmers.size() % k) throw std::invalid_argument("kmers.size() is not a multiple of k");
+        std::vector<std::uint64_t> out(n * source_count() + 1);
+        check(msbwt_rle_count_kmers_by_source(raw_, kmers.data(), k, n, out.data()));
+        out.resize(n * source_count());
+        return out;
+    }
+    /// The rows of every source inside each range, n x source_count() row-major.
+    std::vector<std::uint64_t> range_sources(const std::vector<BWTRange> &ranges) const {
+        std::vector<std::uint64_t> l(ranges.size() + 1), h(ranges.size() + 1), out(ranges.size() * source_count() + 1);
+        for (std::size_t i = 0; i < ranges.size(); ++i) {
+            l[i] = ranges[i].l;
+            h[i] = ranges[i].h;
+        }
+        check(msbwt_rle_range_sources(raw_, l.data(), h.data(), ranges.size(), out.data()));
+        out.resize(ranges.size() * source_count());
+        return out;
+    }
+    void count_kmers_by_source_device(const void *d_kmers, std::size_t k, std::size_t n, void *d_out, void *hip_stream) const {
+        check(msbwt_rle_count_kmers_by_source_device(raw_, d_kmers, k, n, d_out, hip_stream));
+    }
+    void range_sources_device(const void *d_l, const void *d_h, std::size_t n, void *d_out, void *hip_stream) const {
+        check(msbwt_rle_range_sources_device(raw_, d_l, d_h, n, d_out, hip_stream));
+    }
+    /// HBM bytes the attachment holds; rows per checkpoint.
+    static std::uint64_t source_index_plan(std::uint64_t total_rows, std::size_t n_sources) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_source_index_plan(total_rows, n_sources, &bytes);
+        if (rc) throw Panic(rc, "msbwt_source_index_plan");
+        return bytes;
+    }
+    static std::size_t source_block_rows() { return msbwt_source_block_rows(); }
+    /// The widest range counted from the source bytes alone, without a checkpoint (tests probe its borders).
+    static std::size_t source_narrow_rows() { return msbwt_source_narrow_rows(); }
     /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
     static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
         std::uint64_t total = 0;

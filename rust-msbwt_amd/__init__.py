@@ -17,7 +17,7 @@ from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -105,3 +105,24 @@ def merge_many_plan(totals):
 def merge_tile():
     """Merged rows one workgroup counts and scatters per iteration of the merge."""
     return int(_lib.lib().msbwt_merge_tile())
+
+
+def source_index_plan(total_rows, n_sources):
+    """HBM bytes RleBWT.set_sources holds for `n_sources` sources over `total_rows` rows: the byte per row and the checkpoints, at most
+    1.5 bytes per row + SOURCE_INDEX_SLACK.  Pure host logic (csrc/source_index.hip, source_sizes)."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_source_index_plan(int(total_rows), int(n_sources), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_source_index_plan")
+    return size.value
+
+
+def source_block_rows():
+    """Rows per checkpoint of the source index."""
+    return int(_lib.lib().msbwt_source_block_rows())
+
+
+def source_narrow_rows():
+    """The widest range the by-source count takes from the source bytes alone, without a checkpoint."""
+    return int(_lib.lib().msbwt_source_narrow_rows())

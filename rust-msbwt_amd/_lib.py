@@ -14,6 +14,7 @@ COMM_ID_BYTES = 128
 SPARSE_INFO_WORDS = 120  # MSBWT_SPARSE_INFO_WORDS
 BUILD_STAGES = ("copy_in", "read_order", "histogram", "collect", "sort", "emit", "encode", "copy_out")  # MSBWT_BUILD_STAGES
 MERGE_MAX_INPUTS = 32  # MSBWT_MERGE_MAX_INPUTS
+SOURCE_INDEX_SLACK = 1024  # MSBWT_SOURCE_INDEX_SLACK
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
 SIZE_MAX = C.c_size_t(-1).value
@@ -57,6 +58,17 @@ SIGNATURES = {
     "msbwt_merge_many_plan": (_int, [_vp, _sz, _pu64]),
     "msbwt_merge_tile": (_sz, []),
     "msbwt_rle_merge_info": (_int, [_vp, _pu64, C.POINTER(C.c_double)]),
+    "msbwt_rle_set_sources": (_int, [_vp, _vp, _u64, _sz]),
+    "msbwt_rle_load_merged_many_sources": (_int, [_vp, _vp, _vp, _sz]),
+    "msbwt_rle_source_count": (_int, [_vp]),
+    "msbwt_rle_source_totals": (_int, [_vp, _vp]),
+    "msbwt_rle_count_kmers_by_source": (_int, [_vp, _vp, _sz, _sz, _vp]),
+    "msbwt_rle_count_kmers_by_source_device": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "msbwt_rle_range_sources": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "msbwt_rle_range_sources_device": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "msbwt_source_index_plan": (_int, [_u64, _sz, _pu64]),
+    "msbwt_source_block_rows": (_sz, []),
+    "msbwt_source_narrow_rows": (_sz, []),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

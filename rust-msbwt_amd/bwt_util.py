@@ -64,14 +64,17 @@ def _one_pass_plan(level, device):
     return merge_many_plan([rle_total(r) for r in level]), torch.cuda.mem_get_info(index)[0]
 
 
-def merge_numpy_files(paths, out_path, device=None, method="auto"):
+def merge_numpy_files(paths, out_path, device=None, method="auto", sources_out=None):
     """Merges the BWTs in the .npy files `paths` (RLE bytes, as save_bwt_numpy writes them) into `out_path`.  The file is the same
     whatever the method:
       "tree"      neighbours are merged round by round in a balanced tree, so a symbol takes part in ceil(log2 n) merges, not in
                   up to n - 1;
       "one_pass"  all of them in one merge_many call: at most MERGE_MAX_INPUTS files, and their plan (merge_many_plan) must fit
                   the free HBM;
-      "auto"      one pass from ONE_PASS_MIN_INPUTS files on where it can be taken, else the tree."""
+      "auto"      one pass from ONE_PASS_MIN_INPUTS files on where it can be taken, else the tree.
+    `sources_out`: a path that receives the source vector as a plain .npy of uint8 -- for every merged row the index in `paths` of the
+    file it came from -- so that a later process can load_numpy_file(out_path) and set_sources(np.load(sources_out)).  It takes the one
+    pass (method "auto" or "one_pass"): the tree has no such vector."""
     if method not in ("auto", "tree", "one_pass"):
         raise ValueError("method must be \"auto\", \"tree\" or \"one_pass\"")
     level = [np.load(p, mmap_mode="r") for p in paths]
@@ -81,13 +84,20 @@ def merge_numpy_files(paths, out_path, device=None, method="auto"):
     one_pass = method == "one_pass"
     if one_pass and len(level) > MERGE_MAX_INPUTS:
         raise ValueError("%d BWTs, one pass merges at most %d" % (len(level), MERGE_MAX_INPUTS))
-    if one_pass or (method == "auto" and ONE_PASS_MIN_INPUTS <= len(level) <= MERGE_MAX_INPUTS):
+    if one_pass or (method == "auto" and (ONE_PASS_MIN_INPUTS if sources_out is None else 1) <= len(level) <= MERGE_MAX_INPUTS):
         need, free = _one_pass_plan(level, device)
         if one_pass and need > free:
             raise MemoryError("the one-pass merge needs %d bytes of HBM, %d are free" % (need, free))
         one_pass = need <= free
+    if sources_out is not None and not one_pass:
+        raise ValueError("sources_out needs the one-pass merge: at most %d files whose plan fits the free HBM" % MERGE_MAX_INPUTS)
     if one_pass:
-        level = [handle.merge_many(level)]
+        level = [handle.merge_many(level, return_sources=sources_out is not None)]
+        if sources_out is not None:
+            merged, sources = level[0]
+            level = [merged]
+            with open(sources_out, "wb") as f:  # (the path as given: np.save would append ".npy" to one without it)
+                np.save(f, sources)
     while len(level) > 1:
         merged = [handle.merge(level[i], level[i + 1]) for i in range(0, len(level) - 1, 2)]
         level = merged + ([level[-1]] if len(level) % 2 else [])

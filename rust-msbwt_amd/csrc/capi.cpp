@@ -1,5 +1,5 @@
 // extern "C" boundary (include/msbwt_hip.h): the handle's life, the two plain loads, every setter, getter and info call, the host-only
-// utilities, and the out-of-line helpers that handle.hpp declares.  Loader: index_build.cpp; queries: query.cpp; builders and merges:
+// utilities, and the out-of-line helpers that handle.hpp declares.  Loader: index_build.cpp; queries: query.cpp; source colouring: sources.cpp; builders and merges:
 // produce.cpp; replicas and gathers: multi_device.cpp.
 #include <algorithm>
 #include <cstdint>
@@ -218,6 +218,7 @@ void msbwt_rle_free(msbwt_rle *h) {
             if (t.done) (void)hipEventDestroy(t.done);
             if (t.counters) (void)hipFree(t.counters);
             if (t.order_scratch) (void)hipFree(t.order_scratch);
+            if (t.range_scratch) (void)hipFree(t.range_scratch);
         }
         h->pipe.release();
         if (h->mail) (void)hipHostFree(h->mail);
@@ -567,7 +568,7 @@ uint64_t msbwt_rle_device_bytes(const msbwt_rle *h) {
     if (!h || !h->loaded) return 0;
     const DirectTable &t = h->table;
     return h->nblocks * kBlockBytes + h->overflow_bytes + (t.entries ? uint64_t(t.bytes) + t.side_bytes : 0) + h->pair.bytes +
-           (t.filter ? (uint64_t(1) << (2 * t.filter_depth)) / 8 : 0) + h->sparse.bytes + h->sparse.side_bytes + h->sparse2.bytes + h->sparse2.side_bytes;
+           (t.filter ? (uint64_t(1) << (2 * t.filter_depth)) / 8 : 0) + h->sparse.bytes + h->sparse.side_bytes + h->sparse2.bytes + h->sparse2.side_bytes + h->sources.bytes;
 }
 
 int msbwt_rle_set_kernel_timing(msbwt_rle *h, int enabled) {

@@ -1,6 +1,6 @@
-// What the units of the C API share (capi.cpp, index_build.cpp, query.cpp, produce.cpp, multi_device.cpp; included by those only): the handle,
+// What the units of the C API share (capi.cpp, index_build.cpp, query.cpp, sources.cpp, produce.cpp, multi_device.cpp; included by those only): the handle,
 // the parts of its index, its status block's layout and the plumbing of a call.  Shared names live in msbwt_capi, hidden from the library's
-// symbol table; a unit's own names stay in its anonymous namespace.  The helpers declared here are defined in capi.cpp, launch_count in query.cpp.
+// symbol table; a unit's own names stay in its anonymous namespace.  The helpers declared here are defined in capi.cpp, launch_count in query.cpp, attach_sources in sources.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -19,6 +19,7 @@
 #include "reads_build.hpp"
 #include "rle_codec.hpp"
 #include "sparse_build.hpp"
+#include "source_index.hpp"
 #include "sparse_policy.hpp"
 #include "table_policy.hpp"
 
@@ -85,6 +86,24 @@ struct PairIndex {
     }
 };
 
+// Source colouring of a merged index (source_index.hpp): the input every row came from and the checkpoints over it.  Attached by
+// msbwt_rle_set_sources / msbwt_rle_load_merged_many_sources (sources.cpp), dropped with the index; attached <=> n_sources != 0.
+struct SourceIndex {
+    void *rows = nullptr;
+    void *checkpoints = nullptr;
+    uint32_t n_sources = 0;
+    uint64_t bytes = 0;               // of both arrays: msbwt_source_index_plan
+    uint64_t totals[kSourceMax] = {};  // rows per source
+    void release() {
+        if (rows) (void)hipFree(rows);
+        if (checkpoints) (void)hipFree(checkpoints);
+        *this = SourceIndex{};
+    }
+    SourceView view(uint64_t total) const {
+        return SourceView{static_cast<const uint8_t *>(rows), static_cast<const uint64_t *>(checkpoints), total, n_sources, source_stride(n_sources)};
+    }
+};
+
 // What the caller has asked for: the settings the index is built by.  A replica copies them whole (msbwt_rle_replicate).
 struct Settings {
     int wanted_block_format = kBlocksPlanes;  // takes effect at the next load
@@ -130,6 +149,7 @@ struct msbwt_rle : Settings {
     // against the index without one
     SparseLevel sparse, sparse2;
     SparseBuildReport sparse_report{};
+    SourceIndex sources;             // optional, the caller's explicit request: outside the memory budget's plan
     bool counting = false;           // search counters wanted (msbwt_rle_set_search_counters)
     // Tile-ticket counter blocks of the lanes kernel (kernels.hpp, kTicketBytes each): a launch takes a block whose
     // previous launch has COMPLETED (its event says so) or a new one, so two launches in flight on different
@@ -141,6 +161,8 @@ struct msbwt_rle : Settings {
         hipStream_t last_stream = nullptr;  // the stream of the launch that used it last
         void *order_scratch = nullptr;      // scratch of the batch-ordering pass (order.hip) of the launch that holds the slot
         size_t order_bytes = 0;
+        void *range_scratch = nullptr;      // the dense {l, h} pairs between the two phases of a by-source count (grow-only, as order_scratch)
+        size_t range_bytes = 0;
     };
     std::vector<TicketSlot> tickets;
     // device status block (128 bytes): word 0 = flags of the host-pointer entry points (handle
@@ -179,6 +201,7 @@ constexpr uint64_t kStreamLinesFrom = uint64_t(4) << 30;  // random-access array
 
 constexpr size_t kStatusBytes = 1024;  // flag words, debug record (bytes 64..128), search counters (bytes 128..256)
 constexpr size_t kCountersOffset = 128;
+constexpr size_t kSourceBadOffset = 512;  // one u32 of the source index build: a byte >= n_sources was seen
 constexpr size_t kPackScratchOffset = 256;  // two u64 of the table packer (escape-line count, side-array cursor)
 constexpr size_t kMaxTimedEvents = 256;  // start/stop pairs kept before timed_launch folds them into the running sum
 constexpr int kHostFlags = 0, kDeviceFlags = 1;  // words of the status block
@@ -223,6 +246,9 @@ int flags_to_code(msbwt_rle *h, uint32_t flags);
 int status_of(msbwt_rle *h, hipStream_t stream, int which);
 int drain_timing_events(msbwt_rle *h, bool wait = true);
 int launch_count(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which);
+// sources.cpp: the source vector of n_rows rows (from the host through the pinned pipeline, or already in HBM) attached to the loaded index;
+// the caller holds h->mu and has made the handle's device current.  Whatever was attached before is gone either way.
+int attach_sources(msbwt_rle *h, const uint8_t *host_rows, const uint8_t *device_rows, uint64_t n_rows, size_t n_sources);
 
 inline IndexView view_of(msbwt_rle *h) {
     IndexView v;

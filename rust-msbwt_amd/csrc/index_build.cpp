@@ -487,6 +487,7 @@ void release_index(msbwt_rle *h) {
     h->table.release();
     release_sparse(h);
     h->pair.release();
+    h->sources.release();  // the colouring is of the rows that go
     h->nblocks = 0;
     h->typical_width = -1.0;
     h->totals = Totals{};  // an unloaded handle reports 0 symbols, not the previous BWT's

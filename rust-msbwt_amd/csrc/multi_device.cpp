@@ -83,6 +83,8 @@ msbwt_rle *msbwt_rle_replicate(const msbwt_rle *csrc, int device) {
     h->table = src->table;
     h->sparse = src->sparse;
     h->sparse2 = src->sparse2;
+    h->sources = src->sources;
+    const SourceSizes ssz = source_sizes(src->totals.total, src->sources.n_sources);
     const PairIndexSizes psz = pair_index_sizes(src->nblocks, src->pair.stride);
     struct Piece { const void *from; void **to; size_t bytes; };
     const Piece pieces[] = {
@@ -97,6 +99,8 @@ msbwt_rle *msbwt_rle_replicate(const msbwt_rle *csrc, int device) {
         {src->sparse.side, &h->sparse.side, size_t(src->sparse.side_bytes)},
         {src->sparse2.lines, &h->sparse2.lines, size_t(src->sparse2.bytes)},
         {src->sparse2.side, &h->sparse2.side, size_t(src->sparse2.side_bytes)},
+        {src->sources.rows, &h->sources.rows, size_t(ssz.row_bytes)},
+        {src->sources.checkpoints, &h->sources.checkpoints, size_t(ssz.checkpoint_bytes)},
     };
     for (const Piece &p : pieces) *p.to = nullptr;
     for (const Piece &p : pieces) {

@@ -165,21 +165,29 @@ int produce_for_caller(msbwt_rle *h, Produce &&produce, const char *noun, uint8_
 }
 
 // What the producers that load their result share: unless it is the empty BWT (`any`), the index gives way, `produce` leaves the
-// RLE bytes in HBM, and they come down and are freed; then the loader of msbwt_rle_load_vector, on the same bytes.
+// RLE bytes in HBM, and they come down and are freed; then the loader of msbwt_rle_load_vector, on the same bytes.  With `sources`
+// (msbwt_rle_load_merged_many_sources) the merge's final state, a byte per row, stays in HBM over the load and is attached from there.
 template <class Produce>
-int produce_and_install(msbwt_rle *h, bool any, Produce &&produce) {
+int produce_and_install(msbwt_rle *h, bool any, Produce &&produce, size_t sources = 0) {
+    DeviceScope scope(h->device);  // (install makes the same device current once more; `made` is freed inside this scope however the call ends)
+    if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
     std::vector<uint8_t> rle;
+    Produced made;
     if (any) {
-        DeviceScope scope(h->device);
-        if (!scope.ok()) return fail(h, MSBWT_ERR_HIP, scope.why());
         release_index(h);  // its HBM is the producer's to use
-        Produced made;
         if (int rc = produce(&made)) return rc;
         rle.resize(size_t(made.rle_bytes));
         HIP_TRY(h, hipMemcpyAsync(rle.data(), made.d_rle, rle.size(), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(made.d_rle);  // the loader's to use
+        made.d_rle = nullptr;
+        if (!sources && made.d_state) {
+            (void)hipFree(made.d_state);
+            made.d_state = nullptr;
+        }
     }
-    return install(h, rle.data(), rle.size());
+    if (int rc = install(h, rle.data(), rle.size())) return rc;
+    return sources ? attach_sources(h, nullptr, made.d_state, h->totals.total, sources) : int(MSBWT_OK);
 }
 
 }  // namespace
@@ -255,6 +263,15 @@ int msbwt_rle_load_merged_many(msbwt_rle *h, const uint8_t *rle, const uint64_t 
     uint64_t total = 0;
     if (int rc = check_merge_packed(h, rle, rle_offsets, n_inputs, &spans, &total)) return rc;
     return produce_and_install(h, total != 0, [&](Produced *made) { return merge_on_device(h, merge_rle_many, spans, total, made); });
+}
+
+int msbwt_rle_load_merged_many_sources(msbwt_rle *h, const uint8_t *rle, const uint64_t *rle_offsets, size_t n_inputs) {
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    std::vector<MergeSpan> spans;
+    uint64_t total = 0;
+    if (int rc = check_merge_packed(h, rle, rle_offsets, n_inputs, &spans, &total)) return rc;
+    return produce_and_install(h, total != 0, [&](Produced *made) { return merge_on_device(h, merge_rle_many, spans, total, made); }, n_inputs);
 }
 
 int msbwt_merge_many_plan(const uint64_t *totals, size_t n_inputs, uint64_t *device_bytes) {

@@ -150,6 +150,52 @@ int launch_extensions(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, 
     });
 }
 
+// grows the slot's scratch of range pairs; false = no memory for it
+bool ensure_range_scratch(msbwt_rle::TicketSlot &slot, size_t bytes) {
+    if (bytes <= slot.range_bytes) return true;
+    if (slot.range_scratch) (void)hipFree(slot.range_scratch);  // (waits for the device: nothing still reads it)
+    slot.range_scratch = nullptr;
+    slot.range_bytes = 0;
+    if (hipMalloc(&slot.range_scratch, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    slot.range_bytes = bytes;
+    return true;
+}
+
+constexpr size_t kBySourcePiece = size_t(1) << 23;  // queries whose ranges the scratch holds at once (128 MiB: they stay in the Infinity Cache between the phases)
+
+// Counts by source (msbwt_rle_count_kmers_by_source[_device]) in two launches per piece: the ranges go as dense {l, h} pairs into the slot's
+// scratch -- not into the output rows, which are 8 bytes with one source and strided stores otherwise -- and source_index.hip turns them
+// into the rows.  The scratch grows to the largest piece seen and stays: no allocation in the steady state.
+int launch_by_source(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
+    if (k > 0xFFFFFFFFull) return fail(h, MSBWT_ERR_INVALID_ARG, "k does not fit 32 bits");
+    return timed_launch(h, stream, [&] {
+        return with_slot(h, stream, [&](const IndexView &v, msbwt_rle::TicketSlot &slot) {
+            if (!ensure_range_scratch(slot, std::min(n, kBySourcePiece) * 2 * sizeof(uint64_t))) return hipErrorOutOfMemory;
+            uint64_t *pairs = static_cast<uint64_t *>(slot.range_scratch);
+            const SourceView sv = h->sources.view(v.total);
+            hipError_t e = hipSuccess;
+            for (size_t first = 0; first < n && e == hipSuccess; first += kBySourcePiece) {
+                const size_t m = std::min(kBySourcePiece, n - first);
+                e = launch_kmer_ranges(v, d_kmers + first * k, uint32_t(k), m, pairs, pairs + 1, 2u, h->d_flags + which, stream);
+                if (e == hipSuccess) e = launch_range_sources(sv, pairs, pairs + 1, 2u, m, d_out + first * sv.n_sources, h->d_flags + which, stream);
+            }
+            return e;
+        });
+    });
+}
+
+int launch_sources_of_ranges(msbwt_rle *h, const uint64_t *d_l, const uint64_t *d_h, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
+    return timed_launch(h, stream, [&] { return launch_range_sources(h->sources.view(h->totals.total), d_l, d_h, 1u, n, d_out, h->d_flags + which, stream); });
+}
+
+int need_sources(msbwt_rle *h) { return h->sources.n_sources ? int(MSBWT_OK) : fail(h, MSBWT_ERR_NOT_LOADED, "no sources attached"); }
+
+// queries of a host batch's chunk when a result row holds one u64 per source: 2 Mi as the other batches, fewer once a row passes the extensions' 48 bytes
+size_t by_source_chunk(const msbwt_rle *h) { return std::min(size_t(1) << 21, (size_t(96) << 20) / (h->sources.n_sources * sizeof(uint64_t))); }
+
 // Enqueues the fused read -> k-mer count kernel; the caller holds h->mu and has made the
 // handle's device current.
 int launch_read_kmers_locked(msbwt_rle *h, const void *d_reads, size_t read_len, size_t n_reads, size_t k,
@@ -503,6 +549,52 @@ int msbwt_rle_count_kmer_extensions(const msbwt_rle *ch, const uint8_t *kmers, s
     return run_host_batch(c.h, n, size_t(1) << 21, {host_in(kmers, k)}, {host_out(out_counts, 6 * sizeof(uint64_t))}, "count_kmer_extensions",
                           [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
                               return launch_extensions(c.h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
+                          });
+}
+
+// ---- counts by source (source_index.hip): the rows of every merged input inside a k-mer's range ----
+int msbwt_rle_count_kmers_by_source_device(const msbwt_rle *ch, const void *d_kmers, size_t k, size_t n, void *d_out_counts, void *hip_stream) {
+    Call c(ch);
+    if (int rc = c.open()) return rc;
+    if (int rc = need_sources(c.h)) return rc;
+    if (n && (!d_out_counts || (!d_kmers && k))) return fail(c.h, MSBWT_ERR_INVALID_ARG, "null device pointer");
+    if (n == 0) return MSBWT_OK;
+    return launch_by_source(c.h, static_cast<const uint8_t *>(d_kmers), k, n, static_cast<uint64_t *>(d_out_counts), static_cast<hipStream_t>(hip_stream),
+                            kDeviceFlags);
+}
+
+int msbwt_rle_count_kmers_by_source(const msbwt_rle *ch, const uint8_t *kmers, size_t k, size_t n, uint64_t *out_counts) {
+    Call c(ch);
+    if (int rc = c.open()) return rc;
+    if (int rc = need_sources(c.h)) return rc;
+    if (n && (!out_counts || (!kmers && k))) return fail(c.h, MSBWT_ERR_INVALID_ARG, "null pointer");
+    if (n == 0) return MSBWT_OK;
+    return run_host_batch(c.h, n, by_source_chunk(c.h), {host_in(kmers, k)}, {host_out(out_counts, c.h->sources.n_sources * sizeof(uint64_t))}, "count_kmers_by_source",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              return launch_by_source(c.h, static_cast<const uint8_t *>(d_in[0]), k, m, static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
+                          });
+}
+
+int msbwt_rle_range_sources_device(const msbwt_rle *ch, const void *d_l, const void *d_h, size_t n, void *d_out_counts, void *hip_stream) {
+    Call c(ch);
+    if (int rc = c.open()) return rc;
+    if (int rc = need_sources(c.h)) return rc;
+    if (n && (!d_l || !d_h || !d_out_counts)) return fail(c.h, MSBWT_ERR_INVALID_ARG, "null device pointer");
+    return launch_sources_of_ranges(c.h, static_cast<const uint64_t *>(d_l), static_cast<const uint64_t *>(d_h), n, static_cast<uint64_t *>(d_out_counts),
+                                    static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+}
+
+int msbwt_rle_range_sources(const msbwt_rle *ch, const uint64_t *l, const uint64_t *hh, size_t n, uint64_t *out_counts) {
+    Call c(ch);
+    if (int rc = c.open()) return rc;
+    if (int rc = need_sources(c.h)) return rc;
+    if (n && (!l || !hh || !out_counts)) return fail(c.h, MSBWT_ERR_INVALID_ARG, "null pointer");
+    if (n == 0) return MSBWT_OK;
+    return run_host_batch(c.h, n, by_source_chunk(c.h), {host_in(l, sizeof(uint64_t)), host_in(hh, sizeof(uint64_t))},
+                          {host_out(out_counts, c.h->sources.n_sources * sizeof(uint64_t))}, "range_sources",
+                          [&](size_t m, void *const *d_in, void *const *d_out, hipStream_t stream) {
+                              return launch_sources_of_ranges(c.h, static_cast<const uint64_t *>(d_in[0]), static_cast<const uint64_t *>(d_in[1]), m,
+                                                              static_cast<uint64_t *>(d_out[0]), stream, kHostFlags);
                           });
 }
 

@@ -246,10 +246,12 @@ class RleBWT(BWT):
             _raise(rc, self._h)
         return (out, sources) if return_sources else out
 
-    def load_merged_many(self, rles):
-        """merge_many, then the result loaded as load_vector would load it."""
+    def load_merged_many(self, rles, keep_sources=False):
+        """merge_many, then the result loaded as load_vector would load it.  With `keep_sources` the merge's source vector stays
+        attached (set_sources): count_kmers_by_source then counts a k-mer in every input."""
         flat, offsets = _pack_rles(rles)
-        rc = _lib.lib().msbwt_rle_load_merged_many(self._h, flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), offsets.size - 1)
+        load = _lib.lib().msbwt_rle_load_merged_many_sources if keep_sources else _lib.lib().msbwt_rle_load_merged_many
+        rc = load(self._h, flat.ctypes.data_as(C.c_void_p) if flat.size else None, offsets.ctypes.data_as(C.c_void_p), offsets.size - 1)
         if rc:
             _raise(rc, self._h)
 
@@ -263,6 +265,70 @@ class RleBWT(BWT):
         out = {name: float(ms[i]) for i, name in enumerate(_lib.MERGE_STAGES)}
         out["iterations"] = int(iterations.value)
         return out
+
+    # ---- counts by source ------------------------------------------------------------
+    def set_sources(self, sources, n_sources=None):
+        """Attaches a source vector -- np.uint8, one entry per row of the loaded index, what merge_many(return_sources=True) returns or
+        np.load of the file merge_numpy_files(sources_out=...) wrote -- so that count_kmers_by_source can answer.  `n_sources`: None =
+        the largest entry + 1.  sources=None detaches."""
+        if sources is None:
+            rc = _lib.lib().msbwt_rle_set_sources(self._h, None, 0, 0)
+        else:
+            a = np.ascontiguousarray(sources, dtype=np.uint8).ravel()
+            if n_sources is None:
+                n_sources = int(a.max(initial=0)) + 1
+            rc = _lib.lib().msbwt_rle_set_sources(self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, int(n_sources))
+        if rc:
+            _raise(rc, self._h)
+
+    def source_count(self):
+        """Sources attached; 0 = none."""
+        return int(_lib.lib().msbwt_rle_source_count(self._h))
+
+    def source_totals(self):
+        """uint64[source_count()]: the rows of every source."""
+        out = np.zeros(max(self.source_count(), 1), dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_source_totals(self._h, out.ctypes.data_as(C.c_void_p))
+        if rc:
+            _raise(rc, self._h)
+        return out[:self.source_count()]
+
+    def count_kmers_by_source(self, kmers):
+        """kmers: (n, k) uint8 symbol codes -> uint64[n, source_count()]: out[i, s] = occurrences of row i in input s."""
+        a = np.ascontiguousarray(kmers, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("kmers must be (n, k)")
+        n, k = a.shape
+        out = np.empty((n, self.source_count()), dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_count_kmers_by_source(self._h, a.ctypes.data_as(C.c_void_p), k, n, out.ctypes.data_as(C.c_void_p) if out.size else None)
+        if rc:
+            _raise(rc, self._h)
+        return out
+
+    def range_sources(self, l, h):
+        """l, h: uint64[n] row ranges [l, h) -> uint64[n, source_count()]: the rows of every source inside each range."""
+        l = np.ascontiguousarray(l, dtype=np.uint64)
+        h = np.ascontiguousarray(h, dtype=np.uint64)
+        if not (l.shape == h.shape and l.ndim == 1):
+            raise ValueError("l, h must be 1-D and equally long")
+        out = np.empty((l.size, self.source_count()), dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_range_sources(self._h, l.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), l.size,
+                                                out.ctypes.data_as(C.c_void_p) if out.size else None)
+        if rc:
+            _raise(rc, self._h)
+        return out
+
+    def count_kmers_by_source_device(self, d_kmers, k, n, d_out, stream=0):
+        """Device pointers (ints): n x k symbol codes -> n x source_count() u64; asynchronous on `stream`."""
+        rc = _lib.lib().msbwt_rle_count_kmers_by_source_device(self._h, d_kmers, k, n, d_out, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def range_sources_device(self, d_l, d_h, n, d_out, stream=0):
+        """Device pointers (ints): l, h (n u64 each) -> n x source_count() u64; asynchronous on `stream`."""
+        rc = _lib.lib().msbwt_rle_range_sources_device(self._h, d_l, d_h, n, d_out, stream)
+        if rc:
+            _raise(rc, self._h)
 
     # ---- batch forms -----------------------------------------------------------------
     def count_kmers(self, kmers, out=None):

@@ -64,6 +64,14 @@ extern "C" {
     fn msbwt_rle_merge_many(bwt: *mut MsbwtRle, rle: *const u8, rle_offsets: *const u64, n_inputs: usize,
                             out_rle: *mut u8, cap: usize, out_len: *mut u64, out_source: *mut u8) -> c_int;
     fn msbwt_rle_load_merged_many(bwt: *mut MsbwtRle, rle: *const u8, rle_offsets: *const u64, n_inputs: usize) -> c_int;
+    // counts by source: the merge's source vector attached to the loaded index, then a k-mer's count in every input
+    fn msbwt_rle_set_sources(bwt: *mut MsbwtRle, sources: *const u8, n_rows: u64, n_sources: usize) -> c_int;
+    fn msbwt_rle_load_merged_many_sources(bwt: *mut MsbwtRle, rle: *const u8, rle_offsets: *const u64, n_inputs: usize) -> c_int;
+    fn msbwt_rle_source_count(bwt: *const MsbwtRle) -> c_int;
+    fn msbwt_rle_source_totals(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_rle_count_kmers_by_source(bwt: *const MsbwtRle, kmers: *const u8, k: usize, n: usize, out_counts: *mut u64) -> c_int;
+    fn msbwt_rle_range_sources(bwt: *const MsbwtRle, l: *const u64, h: *const u64, n: usize, out_counts: *mut u64) -> c_int;
+    fn msbwt_source_index_plan(total_rows: u64, n_sources: usize, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -264,6 +272,67 @@ impl GpuRleBWT {
         let (flat, offsets) = Self::pack_reads(rles);
         let rc = unsafe { msbwt_rle_load_merged_many(self.raw, flat.as_ptr(), offsets.as_ptr(), rles.len()) };
         if rc != MSBWT_OK { panic!("load_merged_many: {}", self.last_error()); }
+    }
+
+    /// `load_merged_many` with the merge's source vector attached: `count_kmers_by_source` then counts a k-mer in every input.
+    pub fn load_merged_many_sources(&mut self, rles: &[&[u8]]) {
+        let (flat, offsets) = Self::pack_reads(rles);
+        let rc = unsafe { msbwt_rle_load_merged_many_sources(self.raw, flat.as_ptr(), offsets.as_ptr(), rles.len()) };
+        if rc != MSBWT_OK { panic!("load_merged_many_sources: {}", self.last_error()); }
+    }
+
+    /// Attaches a source vector (one byte per row of the loaded index: `merge_many`'s second result); any load drops it.
+    pub fn set_sources(&mut self, sources: &[u8], n_sources: usize) {
+        let rc = unsafe { msbwt_rle_set_sources(self.raw, sources.as_ptr(), sources.len() as u64, n_sources) };
+        if rc != MSBWT_OK { panic!("set_sources: {}", self.last_error()); }
+    }
+
+    /// Detaches the source vector.
+    pub fn clear_sources(&mut self) {
+        let rc = unsafe { msbwt_rle_set_sources(self.raw, std::ptr::null(), 0, 0) };
+        if rc != MSBWT_OK { panic!("clear_sources: {}", self.last_error()); }
+    }
+
+    /// Sources attached (0: none).
+    pub fn source_count(&self) -> usize { unsafe { msbwt_rle_source_count(self.raw) as usize } }
+
+    /// Rows of every source.
+    pub fn source_totals(&self) -> Vec<u64> {
+        let mut out = vec![0u64; self.source_count().max(1)];
+        let rc = unsafe { msbwt_rle_source_totals(self.raw, out.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("source_totals: {}", self.last_error()); }
+        out.truncate(self.source_count());
+        out
+    }
+
+    /// `out[i * source_count() + s]` = occurrences of k-mer i (row-major, k symbol codes each) in input s of the merge.
+    pub fn count_kmers_by_source(&self, kmers: &[u8], k: usize) -> Vec<u64> {
+        assert!(k == 0 || kmers.len() % k == 0);
+        let n = if k == 0 { 0 } else { kmers.len() / k };
+        let mut out = vec![0u64; (n * self.source_count()).max(1)];
+        let rc = unsafe { msbwt_rle_count_kmers_by_source(self.raw, kmers.as_ptr(), k, n, out.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("count_kmers_by_source: {}", self.last_error()); }
+        out.truncate(n * self.source_count());
+        out
+    }
+
+    /// The rows of every source inside each range, row-major.
+    pub fn range_sources(&self, ranges: &[BWTRange]) -> Vec<u64> {
+        let l: Vec<u64> = ranges.iter().map(|r| r.l).collect();
+        let h: Vec<u64> = ranges.iter().map(|r| r.h).collect();
+        let mut out = vec![0u64; (l.len() * self.source_count()).max(1)];
+        let rc = unsafe { msbwt_rle_range_sources(self.raw, l.as_ptr(), h.as_ptr(), l.len(), out.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("range_sources: {}", self.last_error()); }
+        out.truncate(l.len() * self.source_count());
+        out
+    }
+
+    /// HBM bytes `set_sources` holds for that many rows and sources (pure function).
+    pub fn source_index_plan(total_rows: u64, n_sources: usize) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_source_index_plan(total_rows, n_sources, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "source_index_plan: {} rows, {} sources", total_rows, n_sources);
+        bytes
     }
 
     /// Batch form of `constrain_range`.
