@@ -299,6 +299,60 @@ int msbwt_source_index_plan(uint64_t total_rows, size_t n_sources, uint64_t *dev
 size_t msbwt_source_block_rows(void);
 size_t msbwt_source_narrow_rows(void);
 
+/* ---- spectrum and enumeration: the k-mers an index HOLDS, and how often (no reference counterpart) ----
+ * Every other query starts from k-mers the caller brings; these start from the index.  The k-mers of an index are the strings q over
+ * A C G T of length k, 1 <= k <= 32, with count_kmer(q) > 0 (a window holding '$' or 'N' is no k-mer); a k-mer's count is
+ * count_kmer(q) and its range that of msbwt_rle_kmer_ranges; it is reported as ONE u64 in the packed form of msbwt_kmers_pack_2bit
+ * (A C G T -> 0 1 2 3, first symbol most significant, last symbol in bits 0-1), which msbwt_rle_count_kmers_packed[_device] takes as it
+ * is.  Ranges of distinct k-mers are disjoint and lie in lexicographic order: "ascending by k-mer word" and "ascending by l" are the
+ * same order.  None of this depends on any knob (block format, pair index, tables, frontier).
+ * How: the frontier expansion that builds the sparse table, run to depth k -- one pair-block line takes a present d-mer to all its
+ * present (d+2)-mers -- from the root or from the flat direct table's non-empty entries; DESIGN.md 3, "Spectrum and enumeration".
+ *
+ * msbwt_rle_kmer_spectrum: out_hist[c], 1 <= c < n_bins - 1, = distinct k-mers whose count is exactly c; out_hist[n_bins - 1] = those
+ * whose count is >= n_bins - 1; out_hist[0] = 0.  n_bins >= 2.  *out_distinct = the sum of the bins, *out_occurrences = the sum of all
+ * counts (the ACGT-only windows of length k in the reads); either may be NULL.
+ *
+ * msbwt_rle_enumerate_kmers: the k-mers with min_count <= count <= max_count (max_count == 0: no upper limit; min_count == 0 is 1;
+ * min_count > max_count != 0: MSBWT_ERR_INVALID_ARG) as records (k-mer, count, l); h = l + count.  *out_n is always set to the number
+ * of such k-mers.  capacity == 0 (and no buffers): the call only counts -- the first half of the two-call pattern.  0 < capacity < n:
+ * NOTHING is written, *out_n = n, MSBWT_ERR_INVALID_ARG and the message names n.  out_counts and out_l may each be NULL.  sorted != 0:
+ * ascending k-mers, the same from run to run; sorted == 0: the order the expansion produces.  A count window prunes the walk: no k-mer
+ * occurs more often than any of its suffixes, so with min_count = m a suffix narrower than m is dropped at every level (on reads with
+ * errors the once-only suffixes then cost nothing).  A call that fills buffers walks twice (count, then write).
+ * The _device form writes to device buffers on the handle's device and synchronises the stream (n has to reach the host); a device
+ * fault is reported by msbwt_rle_device_status as elsewhere.
+ *
+ * Guards, before the first HIP call: NULL handle MSBWT_ERR_INVALID_ARG, nothing loaded MSBWT_ERR_NOT_LOADED ("no BWT loaded"), k
+ * outside 1..32 MSBWT_ERR_INVALID_ARG.  All scratch is allocated per call and freed before it returns (msbwt_rle_device_bytes is
+ * unchanged): msbwt_spectrum_plan bytes -- two frontier buffers and their cursors; sorted dumps: a bit per row and a rank checkpoint
+ * per 1024 rows; host dumps: the records (24 bytes each) -- and the spectrum's 8 n_bins.  Scratch that does not fit: MSBWT_ERR_HIP,
+ * the message names the bytes. */
+int msbwt_rle_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins,
+                            uint64_t *out_distinct, uint64_t *out_occurrences);
+int msbwt_rle_enumerate_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted,
+                              uint64_t *out_kmers2bit, uint64_t *out_counts, uint64_t *out_l, uint64_t capacity, uint64_t *out_n);
+int msbwt_rle_enumerate_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted,
+                                     void *d_out_kmers2bit, void *d_out_counts, void *d_out_l, uint64_t capacity, uint64_t *out_n,
+                                     void *hip_stream);
+/* Most nodes a frontier buffer of the walk holds (24 bytes each, two buffers); 0 = automatic (2^27, or what an eighth of the free HBM
+ * holds, never more than rows + 1024).  The seeds are worked through in chunks that keep the frontiers inside it: a chunk that
+ * overflows is taken again at half the size, a single seed whose subtree does not fit is expanded one level and its children are
+ * walked in its place.  Results never depend on it; it exists so that tests reach the chunking on tiny inputs, as
+ * msbwt_rle_set_build_piece does for the builder.  Below MSBWT_SPECTRUM_MIN_FRONTIER (and not 0): MSBWT_ERR_INVALID_ARG. */
+#define MSBWT_SPECTRUM_MIN_FRONTIER 64
+int msbwt_rle_set_spectrum_frontier(msbwt_rle *bwt, uint64_t nodes);
+/* The last walk of the handle (of a dump that filled buffers: the writing walk): [0] k, [1] seed depth (0: from the root), [2] chunks
+ * run, [3] chunks taken again at half size after an overflow, [4 + d], d = 0..32: nodes at depth d that survived the pruning ([4 + k]:
+ * the k-mers the sink took), [37] milliseconds of the whole call (rounded), [38] the same in microseconds, [39] single seeds that were
+ * expanded a level and re-seeded. */
+#define MSBWT_SPECTRUM_INFO_WORDS 40
+int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_SPECTRUM_INFO_WORDS */);
+/* Pure function, no device: bytes of HBM a call on an index of total_rows rows allocates with free_hbm_bytes free and the automatic
+ * frontier -- `records` records staged for a host dump (0 for the _device form, for counting and for the spectrum, which adds
+ * 8 n_bins).  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on.  device_bytes may be NULL. */
+int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, int sorted, uint64_t *device_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

@@ -241,6 +241,57 @@ class RleBWT final : public BWT {
     static std::size_t source_block_rows() { return msbwt_source_block_rows(); }
     /// The widest range counted from the source bytes alone, without a checkpoint (tests probe its borders).
     static std::size_t source_narrow_rows() { return msbwt_source_narrow_rows(); }
+
+    // ---- spectrum and enumeration: the k-mers the index holds, 1 <= k <= 32 ----
+    /// What kmer_spectrum returns: hist[c] = distinct k-mers that occur exactly c times (the last bin: that often or more).
+    struct Spectrum {
+        std::vector<std::uint64_t> hist;
+        std::uint64_t distinct = 0, occurrences = 0;
+    };
+    /// What enumerate_kmers returns: record i is the k-mer words[i] (the 2-bit word of msbwt_kmers_pack_2bit), which occurs counts[i]
+    /// times in rows [l[i], l[i] + counts[i]).
+    struct Kmers {
+        std::vector<std::uint64_t> words, counts, l;
+    };
+    Spectrum kmer_spectrum(std::size_t k, std::size_t bins = 256) const {
+        Spectrum s;
+        s.hist.assign(bins, 0);
+        check(msbwt_rle_kmer_spectrum(raw_, k, s.hist.data(), bins, &s.distinct, &s.occurrences));
+        return s;
+    }
+    /// The k-mers with min_count <= count <= max_count (0: no upper limit), ascending when `sorted`: both calls of the two-call pattern.
+    Kmers enumerate_kmers(std::size_t k, std::uint64_t min_count = 1, std::uint64_t max_count = 0, bool sorted = true) const {
+        Kmers out;
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmers(raw_, k, min_count, max_count, sorted ? 1 : 0, nullptr, nullptr, nullptr, 0, &n));
+        out.words.resize(static_cast<std::size_t>(n));
+        out.counts.resize(out.words.size());
+        out.l.resize(out.words.size());
+        if (n) check(msbwt_rle_enumerate_kmers(raw_, k, min_count, max_count, sorted ? 1 : 0, out.words.data(), out.counts.data(), out.l.data(), n, &n));
+        return out;
+    }
+    /// Device buffers of `capacity` u64 each (d_counts, d_l may be null) -> the number of k-mers that qualify; capacity 0 only counts.
+    std::uint64_t enumerate_kmers_device(std::size_t k, std::uint64_t min_count, std::uint64_t max_count, bool sorted, void *d_words, void *d_counts, void *d_l,
+                                         std::uint64_t capacity, void *hip_stream) const {
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmers_device(raw_, k, min_count, max_count, sorted ? 1 : 0, d_words, d_counts, d_l, capacity, &n, hip_stream));
+        return n;
+    }
+    /// Most nodes per frontier buffer of the walks (0 = automatic, else at least MSBWT_SPECTRUM_MIN_FRONTIER); results never depend on it.
+    void set_spectrum_frontier(std::uint64_t nodes) { check(msbwt_rle_set_spectrum_frontier(raw_, nodes)); }
+    /// The MSBWT_SPECTRUM_INFO_WORDS words of msbwt_rle_spectrum_info (include/msbwt_hip.h names them).
+    std::vector<std::uint64_t> spectrum_info() const {
+        std::vector<std::uint64_t> out(MSBWT_SPECTRUM_INFO_WORDS);
+        check(msbwt_rle_spectrum_info(raw_, out.data()));
+        return out;
+    }
+    /// HBM bytes a walk allocates (and frees again) with the automatic frontier.
+    static std::uint64_t spectrum_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t records = 0, bool sorted = false) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_spectrum_plan(total_rows, free_hbm_bytes, records, sorted ? 1 : 0, &bytes);
+        if (rc) throw Panic(rc, "msbwt_spectrum_plan");
+        return bytes;
+    }
     /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
     static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
         std::uint64_t total = 0;

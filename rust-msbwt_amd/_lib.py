@@ -15,6 +15,8 @@ SPARSE_INFO_WORDS = 120  # MSBWT_SPARSE_INFO_WORDS
 BUILD_STAGES = ("copy_in", "read_order", "histogram", "collect", "sort", "emit", "encode", "copy_out")  # MSBWT_BUILD_STAGES
 MERGE_MAX_INPUTS = 32  # MSBWT_MERGE_MAX_INPUTS
 SOURCE_INDEX_SLACK = 1024  # MSBWT_SOURCE_INDEX_SLACK
+SPECTRUM_INFO_WORDS = 40  # MSBWT_SPECTRUM_INFO_WORDS
+SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
 SIZE_MAX = C.c_size_t(-1).value
@@ -69,6 +71,12 @@ SIGNATURES = {
     "msbwt_source_index_plan": (_int, [_u64, _sz, _pu64]),
     "msbwt_source_block_rows": (_sz, []),
     "msbwt_source_narrow_rows": (_sz, []),
+    "msbwt_rle_kmer_spectrum": (_int, [_vp, _sz, _vp, _sz, _pu64, _pu64]),
+    "msbwt_rle_enumerate_kmers": (_int, [_vp, _sz, _u64, _u64, _int, _vp, _vp, _vp, _u64, _pu64]),
+    "msbwt_rle_enumerate_kmers_device": (_int, [_vp, _sz, _u64, _u64, _int, _vp, _vp, _vp, _u64, _pu64, _vp]),
+    "msbwt_rle_set_spectrum_frontier": (_int, [_vp, _u64]),
+    "msbwt_rle_spectrum_info": (_int, [_vp, _vp]),
+    "msbwt_spectrum_plan": (_int, [_u64, _u64, _u64, _int, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

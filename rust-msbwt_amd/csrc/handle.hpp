@@ -191,6 +191,8 @@ struct msbwt_rle : Settings {
     uint64_t build_pieces = 0;
     double merge_ms[kMergeStages] = {};       // the stages of the last merge
     uint64_t merge_iterations = 0;
+    uint64_t spectrum_frontier = 0;           // most nodes per frontier buffer of the k-mer walks (0 = automatic): msbwt_rle_set_spectrum_frontier
+    uint64_t spectrum_info[MSBWT_SPECTRUM_INFO_WORDS] = {};  // what the last of them did
     std::mutex mu;
     std::string err;
 };

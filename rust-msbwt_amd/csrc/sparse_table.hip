@@ -16,18 +16,14 @@
 #include <cstdlib>
 #include <vector>
 
+#include "frontier.hpp"
 #include "rank_ops.hpp"
 #include "sparse_build.hpp"
 
 namespace msbwt {
 namespace {
 
-struct Node {
-    uint64_t key, l, h;
-};
-
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kFrontierThreads;  // (frontier.hpp: Node, reserve, block_add, the pair and plane steps)
 // cursor block (u64 words) at the start of the scratch
 constexpr int kCurLevel = 0;    // [0 .. 32): nodes appended to the frontier of depth d (reset per chunk)
 constexpr int kAccLevel = 32;   // [32 .. 64): the same summed over all chunks that completed
@@ -39,50 +35,6 @@ constexpr int kAccSingle = 192;  // [192 .. 224): the same summed over all chunk
 constexpr int kCursorWords = 224;
 static_assert(kSparseMaxDepth < 32, "a cursor per depth the expansion can reach");
 
-// this thread's first of `mine` consecutive slots behind *cursor: one atomic per workgroup.  Every thread of the block calls it.
-__device__ __forceinline__ uint64_t reserve(uint32_t mine, unsigned long long *cursor) {
-    __shared__ uint32_t wave_total[kWaves];
-    __shared__ unsigned long long block_base;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = uint32_t(__shfl_up(int(inc), d));
-        if (int(lane) >= d) inc += y;
-    }
-    if (lane == 63u) wave_total[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kWaves; ++w) {
-            const uint32_t x = wave_total[w];
-            wave_total[w] = t;
-            t += x;
-        }
-        block_base = t ? atomicAdd(cursor, (unsigned long long)t) : 0ull;
-    }
-    __syncthreads();
-    const uint64_t first = block_base + wave_total[wave] + (inc - mine);
-    __syncthreads();  // (the shared words are rewritten by the next call)
-    return first;
-}
-
-// adds the block's sum of `mine` to *acc
-__device__ __forceinline__ void block_add(uint32_t mine, unsigned long long *acc) {
-    __shared__ uint32_t part[kWaves];
-    uint32_t s = mine;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += uint32_t(__shfl_xor(int(s), d));
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kWaves; ++w) t += part[w];
-        if (t) atomicAdd(acc, (unsigned long long)t);
-    }
-    __syncthreads();
-}
-
 // ---- seeds: the non-empty entries [i0, i0 + np) of the flat table (or the root) ------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sparse_seed(const uint4 *__restrict__ flat, uint64_t i0, uint64_t np, uint64_t total, Node *__restrict__ out,
                                                           uint64_t cap, unsigned long long *__restrict__ cur, uint32_t depth) {
@@ -91,12 +43,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_seed(const uint4 *__restric
         Node nd{0, 0, 0};
         bool keep = false;
         if (i < np) {
-            if (flat == nullptr) {
-                nd = Node{0, 0, total};
-            } else {
-                const uint4 e = flat[i0 + i];
-                nd = Node{i0 + i, (uint64_t(e.y) << 32) | e.x, (uint64_t(e.w) << 32) | e.z};
-            }
+            nd = seed_node(flat, i0 + i, total);
             keep = nd.l != nd.h;
         }
         const uint64_t at = reserve(keep ? 1u : 0u, cur + kCurLevel + depth);
@@ -104,39 +51,6 @@ __global__ __launch_bounds__(kThreads) void k_sparse_seed(const uint4 *__restric
             if (at < cap) out[at] = nd;
             else atomicOr(cur + kOverflow, 1ull);
         }
-    }
-}
-
-// ---- what one pair-block line says about a position: the 16 pair counts before it, relative to the superblock ---------------
-struct PairSixteen {
-    uint32_t rel[16];  // header field + matches among the block's first r positions
-};
-
-__device__ __forceinline__ void pair_line_sixteen(const uint4 *__restrict__ blk, uint32_t r, PairSixteen &out) {
-    const uint4 a0 = blk[0], a1 = blk[1], b0 = blk[2], b1 = blk[3], v = blk[kPairValidChunk];
-    const uint4 h5 = blk[kPairLoChunk], h6 = blk[kPairLoChunk + 1], h7 = blk[kPairHiChunk];
-    const uint32_t A0[4] = {a0.x, a0.y, a0.z, a0.w}, A1[4] = {a1.x, a1.y, a1.z, a1.w}, B0[4] = {b0.x, b0.y, b0.z, b0.w},
-                   B1[4] = {b1.x, b1.y, b1.z, b1.w}, V[4] = {v.x, v.y, v.z, v.w};
-    const uint32_t lo16[8] = {h5.x, h5.y, h5.z, h5.w, h6.x, h6.y, h6.z, h6.w}, hi8[4] = {h7.x, h7.y, h7.z, h7.w};
-    uint32_t am[4][4], bm[4][4];  // [code][word]: positions (among the first r) whose S / S2 is that code
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint32_t low = low_bits(min(max(int(r) - 32 * w, 0), 32));
-#pragma unroll
-        for (uint32_t c = 0; c < 4; ++c) {
-            const uint32_t n0 = (c & 1u) - 1u, n1 = ((c >> 1) & 1u) - 1u;
-            am[c][w] = (A0[w] ^ n0) & (A1[w] ^ n1) & V[w] & low;
-            bm[c][w] = (B0[w] ^ n0) & (B1[w] ^ n1);
-        }
-    }
-#pragma unroll
-    for (uint32_t p = 0; p < 16; ++p) {
-        const uint32_t a = p >> 2, b = p & 3u;
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) cnt += uint32_t(__popc(am[a][w] & bm[b][w]));
-        const uint32_t field = ((lo16[p >> 1] >> ((p & 1u) * 16u)) & 0xFFFFu) | (((hi8[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu) << 16);
-        out.rel[p] = field + cnt;
     }
 }
 
@@ -227,29 +141,23 @@ __global__ __launch_bounds__(kThreads) void k_sparse_expand_pair(const Node *__r
     for (uint64_t base = uint64_t(blockIdx.x) * kThreads; base < n; base += uint64_t(gridDim.x) * kThreads) {
         const uint64_t i = base + threadIdx.x;
         uint32_t nonempty = 0, wide = 0, single = 0;
-        PairSixteen L, H;
+        PairStep st;
         Node nd{0, 0, 0};
-        uint64_t sb_l = 0, sb_h = 0;
         if (i < n) {
             nd = in[i];
-            const uint64_t bl = pair_block_of(nd.l, s96), start_l = pair_block_start(bl, s96);
-            const bool same = (nd.h - start_l) < 128u;
-            const uint64_t bh = same ? bl : pair_block_of(nd.h, s96);
-            pair_line_sixteen(pair_blocks + bl * 8u, uint32_t(nd.l - start_l), L);
-            pair_line_sixteen(pair_blocks + bh * 8u, uint32_t(nd.h - pair_block_start(bh, s96)), H);
-            sb_l = bl >> kPairSuperBlocks;
-            sb_h = bh >> kPairSuperBlocks;
-            if (sb_l == sb_h) {
+            pair_step_lines(nd, pair_blocks, s96, st);
+            if (st.same_super()) {
 #pragma unroll
                 for (uint32_t p = 0; p < 16; ++p) {
-                    nonempty |= (H.rel[p] != L.rel[p] ? 1u : 0u) << p;
-                    wide |= (H.rel[p] - L.rel[p] >= kSparseEscapeWidth ? 1u : 0u) << p;
-                    single |= (H.rel[p] - L.rel[p] == 1u ? 1u : 0u) << p;
+                    nonempty |= (st.H.rel[p] != st.L.rel[p] ? 1u : 0u) << p;
+                    wide |= (st.H.rel[p] - st.L.rel[p] >= kSparseEscapeWidth ? 1u : 0u) << p;
+                    single |= (st.H.rel[p] - st.L.rel[p] == 1u ? 1u : 0u) << p;
                 }
             } else {  // rare: the bounds lie in different superblocks
 #pragma unroll
                 for (uint32_t p = 0; p < 16; ++p) {
-                    const uint64_t nl = pair_super[sb_l * 16u + p] + L.rel[p], nh = pair_super[sb_h * 16u + p] + H.rel[p];
+                    uint64_t nl, nh;
+                    pair_child(pair_super, st, p, nl, nh);
                     nonempty |= (nh != nl ? 1u : 0u) << p;
                     wide |= (nh - nl >= kSparseEscapeWidth ? 1u : 0u) << p;
                     single |= (nh - nl == 1u ? 1u : 0u) << p;
@@ -276,8 +184,9 @@ __global__ __launch_bounds__(kThreads) void k_sparse_expand_pair(const Node *__r
 #pragma unroll
         for (uint32_t p = 0; p < 16; ++p) {
             if (((nonempty >> p) & 1u) == 0u) continue;
-            const uint64_t nl = pair_super[sb_l * 16u + p] + L.rel[p], nh = pair_super[sb_h * 16u + p] + H.rel[p];
-            const uint64_t key = nd.key | (uint64_t(p >> 2) << (2u * depth)) | (uint64_t(p & 3u) << (2u * depth + 2u));
+            uint64_t nl, nh;
+            pair_child(pair_super, st, p, nl, nh);
+            const uint64_t key = pair_child_key(nd.key, depth, p);
             if (kFinal) sparse_insert(env, key, nl, nh, cur);
             else out[at++] = Node{key, nl, nh};
         }
@@ -285,29 +194,6 @@ __global__ __launch_bounds__(kThreads) void k_sparse_expand_pair(const Node *__r
 }
 
 // ---- the odd last level: one symbol further from the plane blocks ------------------------------------------------------------
-// start_index[s] + rank(s, pos) for the four ACGT symbols by ONE thread straight from the plane block (plane_index.hpp)
-__device__ __forceinline__ void plane_line_four(const uint4 *__restrict__ blk, uint32_t r, uint64_t (&out)[4]) {
-    uint32_t cnt[4] = {0, 0, 0, 0}, meta[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint4 c = blk[j];
-        meta[j] = c.w;
-        const uint32_t low = low_bits(min(max(int(r) - 32 * j, 0), 32));
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q) {
-            const uint32_t s = q == 3u ? 5u : q + 1u;
-            const uint32_t x0 = (s & 1u) ? 0u : ~0u, x1 = (s & 2u) ? 0u : ~0u, x2 = (s & 4u) ? 0u : ~0u;
-            cnt[q] += uint32_t(__popc((c.x ^ x0) & (c.y ^ x1) & (c.z ^ x2) & low));
-        }
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-        const uint32_t s = q == 3u ? 5u : q + 1u;
-        const uint32_t hi = (((s >> 2) ? meta[7] : meta[6]) >> ((s & 3u) * 8u)) & 0xFFu;
-        out[q] = ((uint64_t(hi) << 32) | meta[s]) + cnt[q];
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void k_sparse_expand_plane(const Node *__restrict__ in, uint64_t in_cap, uint32_t depth,
                                                                   const uint4 *__restrict__ blocks, unsigned long long *__restrict__ cur, FillEnv env) {
     if (cur[kOverflow] != 0ull) return;  // (as in k_sparse_expand_pair)
@@ -319,8 +205,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_expand_plane(const Node *__
         Node nd{0, 0, 0};
         if (i < n) {
             nd = in[i];
-            plane_line_four(blocks + (nd.l >> 8) * 8u, uint32_t(nd.l) & 255u, nl);
-            plane_line_four(blocks + (nd.h >> 8) * 8u, uint32_t(nd.h) & 255u, nh);
+            plane_step(nd, blocks, nl, nh);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 mine += nh[q] != nl[q] ? 1u : 0u;
@@ -337,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_expand_plane(const Node *__
         if (i < n) {
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q)
-                if (nh[q] != nl[q]) sparse_insert(env, nd.key | (uint64_t(q) << (2u * depth)), nl[q], nh[q], cur);
+                if (nh[q] != nl[q]) sparse_insert(env, plane_child_key(nd.key, depth, q), nl[q], nh[q], cur);
         }
     }
 }

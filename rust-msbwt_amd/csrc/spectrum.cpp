@@ -1,0 +1,202 @@
+// The k-mers of a loaded index: abundance spectrum and k-mer dump (msbwt_rle_kmer_spectrum, msbwt_rle_enumerate_kmers[_device]) and their
+// knobs.  Calls spectrum.hip through its header and handle.hpp.  All scratch is allocated per call and freed before the call returns.
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "handle.hpp"
+#include "run_encode.hpp"
+#include "spectrum.hpp"
+
+namespace {
+
+static_assert(MSBWT_SPECTRUM_MIN_FRONTIER == kSpectrumMinFrontier && MSBWT_SPECTRUM_INFO_WORDS == 4 + kSpectrumMaxK + 1 + 3, "the header's constants");
+constexpr uint64_t kRecordBytes = 3 * sizeof(uint64_t);  // k-mer, count, l
+
+// bytes of scratch a call allocates; MSBWT_ERR_TOO_LARGE for what no index can be
+int plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t frontier, uint64_t records, bool sorted, uint64_t *bytes) {
+    if (total_rows >= (1ull << 40) || records >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    *bytes = spectrum_work_bytes(spectrum_frontier_nodes(total_rows, free_bytes, frontier)) + (sorted ? spectrum_rank_bytes(total_rows) : 0) + records * kRecordBytes;
+    return MSBWT_OK;
+}
+
+// where the walk starts: the flat direct table when it is shallower than k, else the root
+SpectrumSeeds seeds_of(const msbwt_rle *h, size_t k) {
+    const DirectTable &t = h->table;
+    if (t.entries && !t.packed && t.depth > 0 && size_t(t.depth) < k) return SpectrumSeeds{t.entries, t.depth};
+    return SpectrumSeeds{};
+}
+
+struct Clock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    uint64_t us() const { return uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count()); }
+};
+
+void record(msbwt_rle *h, const SpectrumInfo &info, const Clock &clock) {
+    uint64_t *w = h->spectrum_info;
+    std::fill(w, w + MSBWT_SPECTRUM_INFO_WORDS, 0ull);
+    w[0] = info.k;
+    w[1] = info.seed_depth;
+    w[2] = info.chunks;
+    w[3] = info.retries;
+    std::copy(info.nodes, info.nodes + kSpectrumMaxK + 1, w + 4);
+    const uint64_t us = clock.us();
+    w[37] = (us + 500) / 1000;
+    w[38] = us;
+    w[39] = info.descents;
+}
+
+// the scratch of one call: freed when it goes out of scope
+struct Scratch {
+    Arena arena;
+    void *work = nullptr, *rank = nullptr;
+    uint64_t frontier = 0;
+};
+
+// work (and, wanted, the rank scratch) in HBM, or MSBWT_ERR_HIP naming the bytes
+int take_scratch(msbwt_rle *h, Scratch &s, bool rank, uint64_t extra_bytes, const char *what) {
+    size_t free_bytes = 0, all_bytes = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+    const uint64_t total = h->totals.total;
+    s.frontier = spectrum_frontier_nodes(total, free_bytes, h->spectrum_frontier);
+    const uint64_t work_bytes = spectrum_work_bytes(s.frontier), rank_bytes = rank ? spectrum_rank_bytes(total) : 0;
+    const std::string need = std::string(what) + ": " + std::to_string(work_bytes + rank_bytes + extra_bytes) + " bytes of HBM needed while it runs";
+    if (free_bytes < work_bytes + rank_bytes + extra_bytes) return fail(h, MSBWT_ERR_HIP, need);
+    if (s.arena.take(&s.work, work_bytes) != hipSuccess || (rank && s.arena.take(&s.rank, rank_bytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, need);
+    }
+    return MSBWT_OK;
+}
+
+// Both forms of the dump.  host: the out_* are host arrays, filled through a device staging of n records; else device arrays.
+int enumerate(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_count, int sorted, bool host, void *out_kmers, void *out_counts, void *out_l,
+              uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
+    Call c(ch);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers needs 1 <= k <= 32");
+    if (max_count != 0 && min_count > max_count) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers: min_count > max_count");
+    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    if (host) stream = h->stream;
+    const Clock clock;
+    *out_n = 0;
+    SpectrumInfo info;
+    info.k = k;
+    if (h->totals.total == 0) {
+        record(h, info, clock);
+        return MSBWT_OK;
+    }
+    const bool rank = sorted != 0 && capacity != 0;
+    Scratch s;
+    if (int rc = take_scratch(h, s, rank, 0, "enumerate_kmers")) return rc;
+    const IndexView v = view_of(h);
+    const SpectrumSeeds seeds = seeds_of(h, k);
+    uint64_t n = 0;
+    HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, &n, &info, stream));
+    *out_n = n;
+    record(h, info, clock);
+    if (capacity == 0 || n == 0) return MSBWT_OK;
+    if (capacity < n)
+        return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
+    uint64_t *d_kmers = static_cast<uint64_t *>(out_kmers), *d_counts = static_cast<uint64_t *>(out_counts), *d_l = static_cast<uint64_t *>(out_l);
+    uint64_t *stage = nullptr;
+    if (host) {  // records staged in HBM, then copied out
+        const uint64_t columns = 1 + (out_counts ? 1 : 0) + (out_l ? 1 : 0);
+        size_t free_bytes = 0, all_bytes = 0;
+        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+        if (free_bytes < n * columns * 8 || s.arena.take(&stage, n * columns * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "enumerate_kmers: " + std::to_string(n * columns * 8) + " more bytes of HBM needed for the records");
+        }
+        d_kmers = stage;
+        d_counts = out_counts ? stage + n : nullptr;
+        d_l = out_l ? stage + n * (out_counts ? 2 : 1) : nullptr;
+        capacity = n;
+    }
+    HIP_TRY(h, spectrum_dump(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, d_kmers, d_counts, d_l, capacity, h->d_flags + which, &info,
+                             stream));
+    record(h, info, clock);
+    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
+    HIP_TRY(h, hipMemcpyAsync(out_kmers, d_kmers, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, d_counts, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, d_l, n * 8, hipMemcpyDeviceToHost, stream));
+    return status_of(h, stream, which);  // synchronises
+}
+
+}  // namespace
+
+extern "C" {
+
+int msbwt_rle_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_distinct, uint64_t *out_occurrences) {
+    Call c(bwt);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum needs 1 <= k <= 32");
+    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum needs a histogram of at least 2 bins");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    const Clock clock;
+    SpectrumInfo info;
+    info.k = k;
+    uint64_t distinct = 0, occurrences = 0;
+    std::fill(out_hist, out_hist + n_bins, 0ull);
+    if (h->totals.total != 0) {
+        Scratch s;
+        if (int rc = take_scratch(h, s, false, uint64_t(n_bins) * 8, "kmer_spectrum")) return rc;
+        uint64_t *d_hist = nullptr;
+        if (s.arena.take(&d_hist, uint64_t(n_bins) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "kmer_spectrum: " + std::to_string(uint64_t(n_bins) * 8) + " bytes of HBM needed for the histogram");
+        }
+        HIP_TRY(h, hipMemsetAsync(d_hist, 0, uint64_t(n_bins) * 8, h->stream));
+        HIP_TRY(h, spectrum_histogram(view_of(h), seeds_of(h, k), uint32_t(k), s.work, s.frontier, d_hist, n_bins, &distinct, &occurrences, &info, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (out_distinct) *out_distinct = distinct;
+    if (out_occurrences) *out_occurrences = occurrences;
+    record(h, info, clock);
+    return MSBWT_OK;
+}
+
+int msbwt_rle_enumerate_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted, uint64_t *out_kmers2bit, uint64_t *out_counts,
+                              uint64_t *out_l, uint64_t capacity, uint64_t *out_n) {
+    return enumerate(bwt, k, min_count, max_count, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr, kHostFlags);
+}
+
+int msbwt_rle_enumerate_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted, void *d_out_kmers2bit, void *d_out_counts,
+                                     void *d_out_l, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
+    return enumerate(bwt, k, min_count, max_count, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n, static_cast<hipStream_t>(hip_stream),
+                     kDeviceFlags);
+}
+
+int msbwt_rle_set_spectrum_frontier(msbwt_rle *bwt, uint64_t nodes) {
+    if (!bwt) return MSBWT_ERR_INVALID_ARG;
+    if (nodes != 0 && nodes < kSpectrumMinFrontier) {
+        std::lock_guard<std::mutex> lock(bwt->mu);
+        return fail(bwt, MSBWT_ERR_INVALID_ARG, "the spectrum frontier holds at least " + std::to_string(kSpectrumMinFrontier) + " nodes (0 = automatic)");
+    }
+    return set_locked(bwt, bwt->spectrum_frontier, nodes);
+}
+
+int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out) {
+    Call c(bwt);
+    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
+    std::copy(c.h->spectrum_info, c.h->spectrum_info + MSBWT_SPECTRUM_INFO_WORDS, out);
+    return MSBWT_OK;
+}
+
+int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, int sorted, uint64_t *device_bytes) {
+    uint64_t bytes = 0;
+    if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, sorted != 0, &bytes)) return rc;
+    if (device_bytes) *device_bytes = bytes;
+    return MSBWT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,54 @@
+// The k-mers an index HOLDS (spectrum.hip): the frontier expansion of the sparse-table builder (frontier.hpp) run to depth k, with a
+// sink at the last level instead of a table -- a histogram of the range widths (the abundance spectrum), or the (k-mer, count, l)
+// records themselves.  All pointers are device pointers; every call synchronises the stream (chunk by chunk: the host steers).
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace msbwt {
+
+constexpr uint32_t kSpectrumMaxK = 32;           // a k-mer is one 2-bit word
+constexpr uint64_t kSpectrumMinFrontier = 64;    // fewest nodes a frontier buffer may be capped to (a node's 16 children must fit four times over)
+constexpr uint64_t kSpectrumRankRows = 1024;     // rows per rank checkpoint of the sorted dump's bitmap
+
+// what the last walk did (msbwt_rle_spectrum_info)
+struct SpectrumInfo {
+    uint64_t k = 0, seed_depth = 0;
+    uint64_t chunks = 0;    // chunks of seeds that went through every level
+    uint64_t retries = 0;   // chunks taken again at half the size after a frontier overflowed
+    uint64_t descents = 0;  // single seeds whose subtree did not fit: expanded one step and re-seeded from their children
+    uint64_t nodes[kSpectrumMaxK + 1] = {};  // nodes at depth d that survived the pruning; [k]: the k-mers the sink took
+};
+
+// where the walk starts: the non-empty entries of a FLAT direct table of flat_depth < k symbols, or (flat == nullptr) the root
+struct SpectrumSeeds {
+    const void *flat = nullptr;
+    int flat_depth = 0;
+};
+
+// ---- sizes (pure) ----
+// nodes per frontier buffer: `wanted` (msbwt_rle_set_spectrum_frontier), or automatic -- 2^27 when HBM is plentiful, what an eighth of
+// the free bytes holds otherwise, 2^16 at least, and never more than the index can fill (a level's nodes are disjoint non-empty ranges)
+uint64_t spectrum_frontier_nodes(uint64_t total, uint64_t free_bytes, uint64_t wanted);
+uint64_t spectrum_work_bytes(uint64_t frontier_nodes);  // cursors, the re-seeding stack, two frontiers
+uint64_t spectrum_rank_bytes(uint64_t total);           // sorted dump: a bit per row, a checkpoint per kSpectrumRankRows rows, the scan's scratch
+
+// ---- the walks ----
+// d_hist[min(count, n_bins - 1)] += 1 for every k-mer (d_hist zeroed by the caller); *distinct, *occurrences: host words
+hipError_t spectrum_histogram(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, void *d_work, uint64_t frontier_nodes, uint64_t *d_hist, uint64_t n_bins,
+                              uint64_t *distinct, uint64_t *occurrences, SpectrumInfo *info, hipStream_t stream);
+// *n = k-mers with min_count <= count (<= max_count unless 0); d_rank != nullptr (spectrum_rank_bytes, for a sorted dump): the bit of
+// every such k-mer's l is set and the checkpoints are made.  Nodes narrower than min_count are dropped at every level.
+hipError_t spectrum_count(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t min_count, uint64_t max_count, void *d_work, uint64_t frontier_nodes,
+                          void *d_rank, uint64_t *n, SpectrumInfo *info, hipStream_t stream);
+// the records of the same k-mers: appended in the order the expansion produces them (d_rank == nullptr), or each at the rank of its l
+// (d_rank as spectrum_count left it: ascending k-mers).  d_counts and d_l may be nullptr.  Nothing is written at or beyond `capacity`
+// (*flags |= kFlagInternal should a record ever want to go there).
+hipError_t spectrum_dump(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t min_count, uint64_t max_count, void *d_work, uint64_t frontier_nodes,
+                         const void *d_rank, uint64_t *d_kmers, uint64_t *d_counts, uint64_t *d_l, uint64_t capacity, uint32_t *flags, SpectrumInfo *info,
+                         hipStream_t stream);
+
+}  // namespace msbwt

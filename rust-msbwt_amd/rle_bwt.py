@@ -330,6 +330,65 @@ class RleBWT(BWT):
         if rc:
             _raise(rc, self._h)
 
+    # ---- the k-mers the index holds: spectrum and enumeration ----------------------------
+    def kmer_spectrum(self, k, bins=256):
+        """msbwt_rle_kmer_spectrum -> (hist, distinct, occurrences): hist[c] = distinct k-mers that occur exactly c times (hist[bins - 1]:
+        bins - 1 times or more, hist[0] = 0) as uint64[bins]; their number; the sum of their counts."""
+        hist = np.zeros(int(bins), dtype=np.uint64)
+        distinct, occurrences = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_kmer_spectrum(self._h, int(k), hist.ctypes.data_as(C.c_void_p) if hist.size else None, hist.size, C.byref(distinct),
+                                                C.byref(occurrences))
+        if rc:
+            _raise(rc, self._h)
+        return hist, distinct.value, occurrences.value
+
+    def enumerate_kmers(self, k, min_count=1, max_count=None, sorted=True, ranges=False):
+        """msbwt_rle_enumerate_kmers, both calls of the two-call pattern -> (words, counts[, l]) as uint64[n]: the k-mers that occur
+        min_count..max_count times (None: no upper limit) as 2-bit words (pack_2bit's layout; unpack_2bit gives the symbols), their
+        counts and, with ranges=True, the start l of each one's range [l, l + count).  sorted: ascending k-mers."""
+        lib, n = _lib.lib(), C.c_uint64(0)
+        args = (self._h, int(k), int(min_count), int(max_count or 0), 1 if sorted else 0)
+        rc = lib.msbwt_rle_enumerate_kmers(*args, None, None, None, 0, C.byref(n))
+        if rc:
+            _raise(rc, self._h)
+        words, counts = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.uint64)
+        l = np.empty(n.value, dtype=np.uint64) if ranges else None
+        if n.value:
+            rc = lib.msbwt_rle_enumerate_kmers(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                               l.ctypes.data_as(C.c_void_p) if ranges else None, n.value, C.byref(n))
+            if rc:
+                _raise(rc, self._h)
+        return (words, counts, l) if ranges else (words, counts)
+
+    def enumerate_kmers_device(self, k, d_words, d_counts, d_l, capacity, min_count=1, max_count=None, sorted=True, stream=0):
+        """msbwt_rle_enumerate_kmers_device: device pointers (ints; d_counts, d_l may be None) of `capacity` u64 each -> n, the k-mers
+        that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
+        n = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_enumerate_kmers_device(self._h, int(k), int(min_count), int(max_count or 0), 1 if sorted else 0, d_words, d_counts, d_l,
+                                                         int(capacity), C.byref(n), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n = n.value  # (set whatever the outcome: a capacity too small still learns n)
+                raise
+        return n.value
+
+    def set_spectrum_frontier(self, nodes):
+        """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_spectrum_frontier(self._h, int(nodes))
+        if rc:
+            _raise(rc, self._h)
+
+    def spectrum_info(self):
+        """What the last k-mer walk did: {"k", "seed_depth", "chunks", "retries", "descents", "nodes": uint64[33] per depth, "ms"}."""
+        w = np.zeros(_lib.SPECTRUM_INFO_WORDS, dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_spectrum_info(self._h, w.ctypes.data_as(C.c_void_p))
+        if rc:
+            _raise(rc, self._h)
+        return {"k": int(w[0]), "seed_depth": int(w[1]), "chunks": int(w[2]), "retries": int(w[3]), "descents": int(w[39]), "nodes": w[4:37].copy(),
+                "ms": int(w[38]) / 1000.0}
+
     # ---- batch forms -----------------------------------------------------------------
     def count_kmers(self, kmers, out=None):
         """kmers: (n, k) uint8 symbol codes -> uint64[n] (`out`: optional preallocated result array)."""
@@ -841,6 +900,16 @@ def pack_2bit(kmers):
     if rc:
         raise MsbwtError(rc, "a symbol outside A C G T cannot be packed into two bits")
     return out
+
+
+def unpack_2bit(words, k):
+    """uint64[n] 2-bit words of k-mers, k <= 32 (pack_2bit's layout: first symbol most significant, last in bits 0-1) -> (n, k) symbol
+    codes (A C G T = 1 2 3 5)."""
+    if not 1 <= k <= 32:
+        raise ValueError("unpack_2bit takes one word per k-mer: 1 <= k <= 32")
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    shifts = (2 * np.arange(k - 1, -1, -1)).astype(np.uint64)
+    return np.array([1, 2, 3, 5], dtype=np.uint8)[((w[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.intp)]
 
 
 def count_read_kmers_multi(replicas, reads, k, ascii=False, forward=True, revcomp=False):

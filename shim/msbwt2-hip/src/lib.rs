@@ -72,6 +72,13 @@ extern "C" {
     fn msbwt_rle_count_kmers_by_source(bwt: *const MsbwtRle, kmers: *const u8, k: usize, n: usize, out_counts: *mut u64) -> c_int;
     fn msbwt_rle_range_sources(bwt: *const MsbwtRle, l: *const u64, h: *const u64, n: usize, out_counts: *mut u64) -> c_int;
     fn msbwt_source_index_plan(total_rows: u64, n_sources: usize, device_bytes: *mut u64) -> c_int;
+    // spectrum and enumeration: the k-mers the index holds, as 2-bit words
+    fn msbwt_rle_kmer_spectrum(bwt: *const MsbwtRle, k: usize, out_hist: *mut u64, n_bins: usize,
+                               out_distinct: *mut u64, out_occurrences: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_kmers(bwt: *const MsbwtRle, k: usize, min_count: u64, max_count: u64, sorted: c_int,
+                                 out_kmers2bit: *mut u64, out_counts: *mut u64, out_l: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
+    fn msbwt_rle_set_spectrum_frontier(bwt: *mut MsbwtRle, nodes: u64) -> c_int;
+    fn msbwt_spectrum_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, sorted: c_int, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -332,6 +339,50 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_source_index_plan(total_rows, n_sources, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "source_index_plan: {} rows, {} sources", total_rows, n_sources);
+        bytes
+    }
+
+    /// Abundance spectrum of the k-mers the index holds, 1 <= k <= 32: (hist, distinct, occurrences); hist[c] = distinct k-mers that
+    /// occur exactly c times, the last bin that often or more.
+    pub fn kmer_spectrum(&self, k: usize, bins: usize) -> (Vec<u64>, u64, u64) {
+        let mut hist = vec![0u64; bins.max(2)];
+        let (mut distinct, mut occurrences) = (0u64, 0u64);
+        let rc = unsafe { msbwt_rle_kmer_spectrum(self.raw, k, hist.as_mut_ptr(), hist.len(), &mut distinct, &mut occurrences) };
+        if rc != MSBWT_OK { panic!("kmer_spectrum: {}", self.last_error()); }
+        (hist, distinct, occurrences)
+    }
+
+    /// The k-mers with min_count <= count <= max_count (0: no upper limit) as (2-bit words, counts, range starts), ascending when
+    /// `sorted`; the range of record i is [l[i], l[i] + counts[i]) -- what `range_sources` takes.
+    pub fn enumerate_kmers(&self, k: usize, min_count: u64, max_count: u64, sorted: bool) -> (Vec<u64>, Vec<u64>, Vec<u64>) {
+        let mut n = 0u64;
+        let rc = unsafe {
+            msbwt_rle_enumerate_kmers(self.raw, k, min_count, max_count, sorted as c_int, std::ptr::null_mut(), std::ptr::null_mut(),
+                                      std::ptr::null_mut(), 0, &mut n)
+        };
+        if rc != MSBWT_OK { panic!("enumerate_kmers: {}", self.last_error()); }
+        let (mut words, mut counts, mut l) = (vec![0u64; n as usize], vec![0u64; n as usize], vec![0u64; n as usize]);
+        if n > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_kmers(self.raw, k, min_count, max_count, sorted as c_int, words.as_mut_ptr(), counts.as_mut_ptr(),
+                                          l.as_mut_ptr(), n, &mut n)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_kmers: {}", self.last_error()); }
+        }
+        (words, counts, l)
+    }
+
+    /// Most nodes per frontier buffer of the k-mer walks (0 = automatic); results never depend on it.
+    pub fn set_spectrum_frontier(&mut self, nodes: u64) {
+        let rc = unsafe { msbwt_rle_set_spectrum_frontier(self.raw, nodes) };
+        if rc != MSBWT_OK { panic!("set_spectrum_frontier: {}", self.last_error()); }
+    }
+
+    /// HBM bytes a k-mer walk allocates and frees again (pure function).
+    pub fn spectrum_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, sorted: bool) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_spectrum_plan(total_rows, free_hbm_bytes, records, sorted as c_int, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "spectrum_plan: {} rows", total_rows);
         bytes
     }
 
