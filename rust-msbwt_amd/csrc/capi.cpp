@@ -52,12 +52,6 @@ double line_rate_of(const void *p, size_t bytes, hipStream_t stream) {
     return double(lines) / (double(ms) * 1e-3);
 }
 
-// the table's packed form exists only beside a pair index: both are rebuilt
-int rebuild_pair_and_table(msbwt_rle *h) {
-    const int rc = rebuild_pair_index(h);
-    return rc ? rc : rebuild_table(h);
-}
-
 // A sparse-table setting changes a loaded plane-block index only when it changes what it would be built as (run blocks: at the next load).
 int set_sparse_wish(msbwt_rle *h, int &wish, int mode) {
     return set_then_rebuild(h, [&] {
@@ -295,13 +289,7 @@ int msbwt_rle_get_table_packed(const msbwt_rle *h) { return (h && h->table.entri
 int msbwt_rle_set_memory_budget(msbwt_rle *h, uint64_t bytes) {
     if (!h) return MSBWT_ERR_INVALID_ARG;
     return set_then_rebuild(h, [&] { h->memory_budget = bytes; return true; }, [&] {
-        // the optional structures are rebuilt under the new budget (the plan counts the memory they hold now as free).  Run blocks: their sparse
-        // table was built at load time and cannot be rebuilt (the plane blocks it came from are gone) -- it stays while the index fits the budget
-        if (h->block_format == kBlocksPlanes || (bytes != 0 && msbwt_rle_device_bytes(h) > bytes)) release_sparse(h);
-        h->table.release();
-        h->pair.release();
-        make_plan(h);
-        if (int rc = rebuild_pair_and_table(h)) return rc;
+        if (int rc = replan(h, bytes)) return rc;  // the optional structures are rebuilt under the new budget
         // a budget that cannot be met is said, not silently exceeded (the call still succeeds: the index works)
         h->err.clear();
         if (bytes != 0 && h->block_format != kBlocksPlanes) h->err = "memory budget: the run-block format has no optional structures to plan; the budget is not applied";

@@ -71,7 +71,7 @@ inline uint64_t sparse_tier_buckets(int depth, uint64_t solid, uint64_t singles)
 // wrap that count.  Nor may the two be equally deep: the kernel searches on after the direct table's range without asking whether any
 // symbol is left, so a k = depth = direct_depth query that ends in the filter would count symbols beyond its own (found by
 // tests/test_gpu_tier_fallback.py).  One rule for both sparse levels -- the loader keeps to it (index_build.cpp: build_sparse, and the deep direct
-// table rebuild_table keeps beside a sparse table), and every query launch refuses what breaks it (handle.hpp, tier_launch_ok).
+// table build_tables keeps beside a sparse table), and every query launch refuses what breaks it (handle.hpp, tier_launch_ok).
 inline bool sparse_tier_fits_direct(int depth, int direct_depth) { return direct_depth < depth; }
 
 // singles[d]: of distinct[d], the suffixes that occur exactly once (nullptr: not counted -- no two-tier form); tiers: -1 = the complete

@@ -581,3 +581,50 @@ def test_second_sparse_level_serves_the_queries_the_first_is_too_deep_for(monkey
     assert b.sparse_table_info()["second_depth"] == 17
     twin = b.replicate(b.device_ordinal())
     assert twin.sparse_table_info()["second_depth"] == 17 and np.array_equal(twin.count_kmers(qs[18]), exp[18])
+
+
+def test_install_setters_and_replan_build_the_same_index_from_explicit_settings(monkeypatch):
+    """The loader's three ways in -- the load (settings made beforehand), the rebuilding setters on a loaded index, and the rebuild under a
+    new memory budget -- build the same index when every setting is explicit (nothing then depends on the free HBM): same direct table,
+    filter, pair stride, sparse table (down to the counts of its sizing pass) and bytes in HBM."""
+    for name in ("MSBWT_SPARSE_TABLE", "MSBWT_SPARSE_TIERS", "MSBWT_SPARSE_SECOND", "MSBWT_TABLE_DEPTH", "MSBWT_TABLE_PACKED", "MSBWT_TABLE_SIDE", "MSBWT_PAIR_INDEX",
+                 "MSBWT_PAIR_STRIDE", "MSBWT_FILTER", "MSBWT_BLOCKS", "MSBWT_MEMORY_BUDGET", "MSBWT_QUERY_K", "MSBWT_BUILD"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("MSBWT_SEARCH", "auto")
+    reads = read_set(11, 3000, 700, 60, repeats=4, err=0.01)
+    rle = bwt_of(reads)
+    ref = orc.OracleRleBWT()
+    ref.load_vector(rle)
+    settings = (("set_pair_index", 1), ("set_pair_stride", 128), ("set_table_depth", 8), ("set_table_packed", 1), ("set_sparse_tiers", 0), ("set_sparse_table", 16))
+
+    def state(b):
+        return (b.get_table_depth(), b.get_table_packed(), b.table_info(), b.get_presence_filter(), b.get_pair_stride(), b.sparse_table_info(), b.device_bytes())
+
+    # (a) configured, then loaded
+    a = RleBWT()
+    for setter, value in settings:
+        getattr(a, setter)(value)
+    a.load_vector(rle)
+    want = state(a)
+    assert want[0] == 10 and want[1] and want[2]["lines"] == (4 ** 10 + 29) // 30 and want[4] == 128, want
+    assert want[5]["depth"] == 16 and not want[5]["two_tier"] and want[5]["second_depth"] == 0 and want[5]["parent_depth"] == 8, want
+    assert want[5]["entries"] == len(np.unique(np.lib.stride_tricks.sliding_window_view(reads, 16, axis=1).reshape(-1, 16), axis=0))
+    # (b) loaded with defaults, then configured through the setters
+    b = RleBWT()
+    b.load_vector(rle)
+    for setter, value in settings:
+        getattr(b, setter)(value)
+    assert state(b) == want
+    # (c) every rebuilding setter again, with the value it already has
+    for setter, value in settings + (("set_table_side", 1), ("set_presence_filter", 1)):
+        getattr(b, setter)(value)
+        assert state(b) == want, setter
+    # (d) a memory budget the index just fits, and none again
+    b.set_memory_budget(b.device_bytes())
+    b.set_memory_budget(0)
+    assert state(b) == want and state(a) == want
+    for k in (12, 17, 31):
+        windows = np.lib.stride_tricks.sliding_window_view(reads, k, axis=1).reshape(-1, k)
+        q = np.ascontiguousarray(np.concatenate([windows[::131], random_kmers(k, 200, k)]))
+        exp = ref.count_kmers(q)
+        assert np.array_equal(a.count_kmers(q), exp) and np.array_equal(b.count_kmers(q), exp), k
