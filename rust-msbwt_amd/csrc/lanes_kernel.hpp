@@ -540,6 +540,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
     auto count = [&](int which, uint64_t ballot) {
         if (lane == 0u) ws.cnt[which] += uint32_t(__popcll(ballot));
     };
+    // ... from DIVERGENT code (a step's own branch: lane 0 may not be among the lanes that took it): the lowest lane that is here adds
+    auto count_here = [&](int which, uint64_t ballot) {
+        if (lane == uint32_t(__builtin_ctzll(__ballot(true)))) ws.cnt[which] += uint32_t(__popcll(ballot));
+    };
     // this lane's part in the line fetches: 16 bytes (one chunk) of the line in list slot 8 i + dma_group
     const uint32_t dma_group = lane >> 3, dma_chunk_bytes = ((lane & 7u) ^ dma_group) * 16u;
 
@@ -1130,11 +1134,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     have = false;
                 }
                 if (counting) {
-                    count(kCntEscapeQueries, __ballot(hit && width == kSparseEscapeWidth));
-                    count(kCntFirstLines, __ballot(hit && width == kSparseEscapeWidth));
-                    count(kCntTableDisplaced, __ballot(!hit && have && !fell));
-                    count(kCntTableDecided, __ballot(!hit && !have));
-                    if (kTier) count(kCntTierFallbacks, __ballot(fell));
+                    count_here(kCntEscapeQueries, __ballot(hit && width == kSparseEscapeWidth));
+                    count_here(kCntFirstLines, __ballot(hit && width == kSparseEscapeWidth));
+                    count_here(kCntTableDisplaced, __ballot(!hit && have && !fell));
+                    count_here(kCntTableDecided, __ballot(!hit && !have));
+                    if (kTier) count_here(kCntTierFallbacks, __ballot(fell));
                 }
             } else if (kTier && dlooking) {  // this step fetched the query's line of the direct table: its range after dd symbols
                 const uint32_t base_d = line_base(slot_l), g_d = slot_l & 7u, dslot = uint32_t(h);
@@ -1167,9 +1171,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     have = false;
                 }
                 if (counting) {
-                    count(kCntEscapeQueries, __ballot(esc));
-                    count(kCntFirstLines, __ballot(esc));
-                    count(kCntTableDecided, __ballot(!have));
+                    count_here(kCntEscapeQueries, __ballot(esc));
+                    count_here(kCntFirstLines, __ballot(esc));
+                    count_here(kCntTableDecided, __ballot(!have));
                 }
             } else if (pair) {
                 PairLine L;

@@ -74,8 +74,9 @@ def table_key(kmers):
     return key
 
 
-def host_lookup(lines, side, info, key):
-    """What the kernel does with one key, on the downloaded table: -> (l, h) or None."""
+def host_lookup(lines, side, info, key, walked=False):
+    """What the kernel does with one key, on the downloaded table: -> (l, h) or None.
+    walked: -> (that, buckets visited beyond the key's own)."""
     b, tag = C.c_uint32(), C.c_uint64()
     assert _lib.lib().msbwt_sparse_hash64(int(key), info["depth"], info["buckets"], C.byref(b), C.byref(tag)) == 0
     bucket = b.value
@@ -97,13 +98,12 @@ def host_lookup(lines, side, info, key):
                 width, hit = t >> 24, (t & 0xFFFFFF) == tag.value
                 lo = int(line[14 + slot]) | (int(raw[112 + slot]) << 32)
             if width != 0 and hit:
-                if width == 255:
-                    return int(side[lo][0]), int(side[lo][1])
-                return lo, lo + width
+                found = (int(side[lo][0]), int(side[lo][1])) if width == 255 else (lo, lo + width)
+                return (found, dist) if walked else found
         header = int(raw[126]) | (int(raw[127]) << 8)
         if header <= nslots:
-            return None
-    return None
+            break
+    return (None, dist) if walked else None
 
 
 def slots_in_use(lines, info):
@@ -319,8 +319,9 @@ def test_when_no_depth_fits_the_direct_table_is_built_instead_and_the_counts_sta
 
 
 # ---- the two-tier form (round 6; csrc/sparse_table.hpp): entries for the suffixes that occur at least twice, filter bits for the rest ----
-def tier_lookup(lines, side, info, key):
-    """What the kernel does with one key on a downloaded TWO-TIER table: -> ("entry", l, h) | ("filter",) | None (count 0)."""
+def tier_lookup(lines, side, info, key, walked=False):
+    """What the kernel does with one key on a downloaded TWO-TIER table: -> ("entry", l, h) | ("filter",) | None (count 0).
+    walked: -> (that, buckets visited beyond the key's own)."""
     b, tag = C.c_uint32(), C.c_uint64()
     assert _lib.lib().msbwt_sparse_hash64(int(key), info["depth"], info["buckets"], C.byref(b), C.byref(tag)) == 0
     wide = info["depth"] >= 25
@@ -341,11 +342,13 @@ def tier_lookup(lines, side, info, key):
                 width, hit, lo = t >> 24, (t & 0xFFFFFF) == tag.value, int(line[10 + slot]) | (int(raw[80 + slot]) << 32)
             if width != 0 and hit:
                 assert width >= 2, "a suffix that occurs once has no entry"
-                return ("entry",) + ((int(side[lo][0]), int(side[lo][1])) if width == 255 else (lo, lo + width))
+                found = ("entry",) + ((int(side[lo][0]), int(side[lo][1])) if width == 255 else (lo, lo + width))
+                return (found, dist) if walked else found
         header = int(raw[90]) | (int(raw[91]) << 8)
         if header <= nslots:
             break
-    return ("filter",) if maybe else None
+    found = ("filter",) if maybe else None
+    return (found, dist) if walked else found
 
 
 def tier_slots_in_use(lines, info):
