@@ -605,7 +605,7 @@ size_t msbwt_rle_download_blocks(const msbwt_rle *ch, void *out_blocks, size_t c
 size_t msbwt_build_plane_blocks(const uint8_t *rle_bytes, size_t len, void *out_blocks, size_t cap_blocks,
                                 uint64_t *out_total) {
     Totals t;
-    if ((!rle_bytes && len) || !compute_totals(rle_bytes, len, &t) || t.total > kMaxTotal) return SIZE_MAX;
+    if ((!rle_bytes && len) || !compute_totals(rle_bytes, len, &t) || t.total >= kMaxSymbols) return SIZE_MAX;
     if (out_total) *out_total = t.total;
     const uint64_t nblocks = plane_block_count(t.total);
     if (out_blocks && cap_blocks >= nblocks) build_plane_blocks(rle_bytes, len, t, static_cast<uint32_t *>(out_blocks), 0);
@@ -615,7 +615,7 @@ size_t msbwt_build_plane_blocks(const uint8_t *rle_bytes, size_t len, void *out_
 size_t msbwt_build_run_blocks(const uint8_t *rle_bytes, size_t len, void *out_blocks, size_t cap_blocks, void *out_overflow,
                               size_t cap_overflow, uint64_t *out_total, uint64_t *out_noverflow) {
     Totals t;
-    if ((!rle_bytes && len) || !compute_totals(rle_bytes, len, &t) || t.total > kMaxTotal) return SIZE_MAX;
+    if ((!rle_bytes && len) || !compute_totals(rle_bytes, len, &t) || t.total >= kMaxSymbols) return SIZE_MAX;
     RunIndex ri;
     build_run_blocks(rle_bytes, len, t, &ri, 0);
     if (out_total) *out_total = t.total;

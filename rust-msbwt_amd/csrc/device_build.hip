@@ -2,7 +2,7 @@
 // the expanded index on the host.  Three kernels and a small scan:
 //
 //   k_tile_sums   every 4 KiB tile of RLE bytes -> {symbols, per-symbol counts} it encodes
-//   k_scan_tiles  exclusive prefix over the tiles (7 x u64 per tile)
+//   k_scan_tile_sums<7>  exclusive prefix over the tiles (7 x u64 per tile; workgroup.hpp, shared with pair_index.hip)
 //   k_paint       every byte is one "sub-run" (digit << 5*index-in-its-run symbols of one
 //                 code): a block-level scan gives its BWT position and the symbol counts
 //                 before it; the thread ORs its bits into the planes (atomicOr: neighbouring
@@ -12,11 +12,14 @@
 //
 // This is what breaks the carry chain of the on-disk format (the weight of a byte depends on
 // how many bytes of the same symbol precede it, reference src/rle_bwt.rs:360-371): the
-// exponent is found by looking back at most 12 bytes, everything else is a prefix sum.
+// exponent is found by looking back at most 16 bytes, everything else is a prefix sum.  The walk over a thread's bytes is
+// rle_subruns.hpp's (shared with the merge decoder), the sums and scans inside a workgroup are workgroup.hpp's.
 #include <hip/hip_runtime.h>
 
 #include "device_build.hpp"
 #include "plane_index.hpp"
+#include "rle_subruns.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 namespace {
@@ -25,101 +28,14 @@ constexpr int kThreads = 256;
 constexpr int kBytesPerThread = 16;
 constexpr int kTileBytes = kThreads * kBytesPerThread;  // 4096
 constexpr uint64_t kLongRun = 2048;                      // symbols; longer sub-runs are deferred
-constexpr int kMaxDigits = 8;                            // 32^8 = 2^40: more digits cannot fit T < 2^40
 
-struct Seven {
-    uint64_t v[7];  // [0..5] per-symbol counts, [6] all symbols
-};
+using Seven = TileSums<7>;  // [0..5] per-symbol counts, [6] all symbols
 
 struct LongRun {
     uint64_t pos, len;
     uint64_t occ[6];  // symbol counts before pos
     uint32_t sym, pad;
 };
-
-__device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t x) {
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
-// Exclusive scan of one u64 per thread across the 256-thread block; *block_total gets the sum.
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t x, uint64_t *lds4, uint64_t *block_total) {
-    const uint64_t inc = wave_inclusive_scan(x);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();  // lds4 may still be read from the previous call
-    if (lane == 63) lds4[wave] = inc;
-    __syncthreads();
-    uint64_t base = 0, total = 0;
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const uint64_t t = lds4[w];
-        if (w < wave) base += t;
-        total += t;
-    }
-    *block_total = total;
-    return base + inc - x;
-}
-
-// The 16 bytes a thread owns (as four dwords) and how their first byte continues a run that
-// started earlier: `carry` = number of bytes right before them with the symbol of byte 0.
-struct ThreadBytes {
-    uint32_t w[4];
-    int valid;  // how many of the 16 bytes exist
-    int carry;
-};
-
-__device__ __forceinline__ uint32_t byte_at(const ThreadBytes &tb, int i) {
-    const uint32_t lo = (i & 4) ? tb.w[1] : tb.w[0], hi = (i & 4) ? tb.w[3] : tb.w[2];
-    return (((i & 8) ? hi : lo) >> ((i & 3) * 8)) & 0xFFu;
-}
-
-__device__ __forceinline__ void load_thread_bytes(const uint8_t *__restrict__ rle, uint64_t n, uint64_t first,
-                                                  ThreadBytes *tb) {
-    // rle is 16-byte aligned and first is a multiple of 16; never read past n
-    tb->valid = first >= n ? 0 : int(min(uint64_t(16), n - first));
-    tb->w[0] = tb->w[1] = tb->w[2] = tb->w[3] = 0;
-    tb->carry = 0;
-    if (tb->valid == 16) {
-        const uint4 c = *reinterpret_cast<const uint4 *>(rle + first);
-        tb->w[0] = c.x; tb->w[1] = c.y; tb->w[2] = c.z; tb->w[3] = c.w;
-    } else {
-        for (int i = 0; i < tb->valid; ++i) {
-            const uint32_t b = uint32_t(rle[first + i]) << ((i & 3) * 8);
-            if (i < 4) tb->w[0] |= b; else if (i < 8) tb->w[1] |= b; else if (i < 12) tb->w[2] |= b; else tb->w[3] |= b;
-        }
-    }
-    if (first >= 16 && tb->valid > 0) {
-        const uint4 p = *reinterpret_cast<const uint4 *>(rle + first - 16);
-        const uint32_t pw[4] = {p.x, p.y, p.z, p.w};
-        const uint32_t sym0 = tb->w[0] & 7u;
-        bool run = true;
-#pragma unroll
-        for (int j = 15; j >= 0; --j) {
-            run = run && (((pw[j >> 2] >> ((j & 3) * 8)) & 7u) == sym0);
-            tb->carry += run ? 1 : 0;
-        }
-    }
-}
-
-// Calls fn(sym, value) for each of the thread's sub-runs in order: value = digit << 5 * (index
-// of the byte inside its run), the index being a recurrence over the bytes.  Returns error bits.
-template <class Fn>
-__device__ __forceinline__ uint32_t for_each_subrun(const ThreadBytes &tb, Fn &&fn) {
-    uint32_t bad = 0, prev_sym = 8;
-    int e = tb.carry;
-    for (int i = 0; i < tb.valid; ++i) {
-        const uint32_t byte = byte_at(tb, i), sym = byte & 7u, digit = byte >> 3;
-        if (i > 0) e = (sym == prev_sym) ? e + 1 : 0;
-        prev_sym = sym;
-        if (sym >= 6u) bad |= kBuildBadSymbol;
-        if (e >= kMaxDigits && digit) bad |= kBuildTooLarge;
-        fn(sym, e < kMaxDigits ? (uint64_t(digit) << (5 * e)) : uint64_t(0));
-    }
-    return bad;
-}
 
 // acc[sym] += v without a runtime-indexed register array
 __device__ __forceinline__ void add_to_symbol(uint64_t acc[7], uint32_t sym, uint64_t v) {
@@ -130,11 +46,9 @@ __device__ __forceinline__ void add_to_symbol(uint64_t acc[7], uint32_t sym, uin
 __global__ __launch_bounds__(kThreads) void k_tile_sums(const uint8_t *__restrict__ rle, uint64_t n,
                                                         Seven *__restrict__ tile_sums, uint32_t *__restrict__ flags,
                                                         unsigned long long *__restrict__ long_count) {
-    __shared__ uint64_t red[7][kThreads / 64];
     for (uint64_t tile = blockIdx.x; tile * kTileBytes < n; tile += gridDim.x) {
         const uint64_t first = tile * kTileBytes + uint64_t(threadIdx.x) * kBytesPerThread;
-        ThreadBytes tb;
-        load_thread_bytes(rle, n, first, &tb);
+        const ThreadBytes tb = load_thread_bytes(rle, n, first);
         uint64_t acc[7] = {0, 0, 0, 0, 0, 0, 0};
         uint32_t longs = 0;
         const uint32_t bad = for_each_subrun(tb, [&](uint32_t sym, uint64_t v) {
@@ -144,48 +58,9 @@ __global__ __launch_bounds__(kThreads) void k_tile_sums(const uint8_t *__restric
         });
         if (bad) atomicOr(flags, bad);
         if (longs) atomicAdd(long_count, (unsigned long long)longs);
-        // block reduction of the 7 sums
-        __syncthreads();
-        for (int k = 0; k < 7; ++k) {
-            uint64_t x = acc[k];
-            for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d);
-            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = x;
-        }
-        __syncthreads();
-        if (threadIdx.x < 7) {
-            uint64_t s = 0;
-            for (int w = 0; w < kThreads / 64; ++w) s += red[threadIdx.x][w];
-            tile_sums[tile].v[threadIdx.x] = s;
-        }
+        const uint64_t sum = block_vector_sum(acc);
+        if (threadIdx.x < 7) tile_sums[tile].v[threadIdx.x] = sum;
     }
-}
-
-// In-place exclusive scan over the tiles; totals[0..6] gets the grand totals.  One workgroup.
-__global__ __launch_bounds__(1024) void k_scan_tiles(Seven *__restrict__ tiles, uint64_t ntiles, uint64_t *__restrict__ totals) {
-    __shared__ uint64_t wave_sum[16];
-    __shared__ uint64_t carry[7];
-    if (threadIdx.x < 7) carry[threadIdx.x] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint64_t base = 0; base < ntiles; base += 1024) {
-        const uint64_t t = base + threadIdx.x;
-        for (int k = 0; k < 7; ++k) {
-            const uint64_t x = t < ntiles ? tiles[t].v[k] : 0;
-            const uint64_t inc = wave_inclusive_scan(x);
-            if (lane == 63) wave_sum[wave] = inc;
-            __syncthreads();
-            uint64_t before = carry[k], all = 0;
-            for (int w = 0; w < 16; ++w) {
-                if (w < wave) before += wave_sum[w];
-                all += wave_sum[w];
-            }
-            if (t < ntiles) tiles[t].v[k] = before + inc - x;
-            __syncthreads();
-            if (threadIdx.x == 0) carry[k] += all;
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x < 7) totals[threadIdx.x] = carry[threadIdx.x];
 }
 
 // Header words of block `b` from the bounds A[s] (layout: plane_index.hpp)
@@ -236,8 +111,7 @@ __global__ __launch_bounds__(kThreads) void k_paint(const uint8_t *__restrict__ 
     __shared__ uint64_t lds4[kThreads / 64];
     for (uint64_t tile = blockIdx.x; tile * kTileBytes < n; tile += gridDim.x) {
         const uint64_t first = tile * kTileBytes + uint64_t(threadIdx.x) * kBytesPerThread;
-        ThreadBytes tb;
-        load_thread_bytes(rle, n, first, &tb);
+        const ThreadBytes tb = load_thread_bytes(rle, n, first);
         uint64_t mine[7] = {0, 0, 0, 0, 0, 0, 0};
         (void)for_each_subrun(tb, [&](uint32_t sym, uint64_t v) {
             add_to_symbol(mine, sym, v);
@@ -245,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_paint(const uint8_t *__restrict__ 
         });
         // position and per-symbol counts at this thread's first byte
         uint64_t at[7], dummy;
-        for (int k = 0; k < 7; ++k) at[k] = tile_base[tile].v[k] + block_exclusive_scan(mine[k], lds4, &dummy);
+        for (int k = 0; k < 7; ++k) at[k] = tile_base[tile].v[k] + block_exclusive_sum(mine[k], lds4, &dummy);
         (void)for_each_subrun(tb, [&](uint32_t sym, uint64_t v) {
             if (v == 0) return;
             const uint64_t pos = at[6];
@@ -307,12 +181,10 @@ __global__ void k_final_header(const uint64_t *__restrict__ start_index, const u
     }
 }
 
-inline uint32_t grid_for_tiles(uint64_t ntiles) { return uint32_t(ntiles < 1 ? 1 : (ntiles > 4096 ? 4096 : ntiles)); }
-
 }  // namespace
 
 size_t device_build_scratch_bytes(size_t n) {
-    const uint64_t ntiles = (n + kTileBytes - 1) / kTileBytes;
+    const uint64_t ntiles = ceil_div(n, kTileBytes);
     return size_t(ntiles + 1) * sizeof(Seven) + 256;
 }
 
@@ -325,13 +197,13 @@ hipError_t device_build_pass1(const uint8_t *d_rle, size_t n, void *d_scratch, D
     st->d_long_count = reinterpret_cast<unsigned long long *>(st->d_start_index + 8);
     st->d_long_cursor = st->d_long_count + 1;
     st->d_tiles = base + 256;
-    st->ntiles = (n + kTileBytes - 1) / kTileBytes;
+    st->ntiles = ceil_div(n, kTileBytes);
     hipError_t e = hipMemsetAsync(base, 0, 256, stream);
     if (e != hipSuccess) return e;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_tile_sums, dim3(grid_for_tiles(st->ntiles)), dim3(kThreads), 0, stream, d_rle, uint64_t(n),
+    hipLaunchKernelGGL(k_tile_sums, dim3(capped_grid(st->ntiles, 1, 4096)), dim3(kThreads), 0, stream, d_rle, uint64_t(n),
                        static_cast<Seven *>(st->d_tiles), st->d_flags, st->d_long_count);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, stream, static_cast<Seven *>(st->d_tiles), st->ntiles, st->d_totals);
+    hipLaunchKernelGGL(k_scan_tile_sums<7>, dim3(1), dim3(1024), 0, stream, static_cast<Seven *>(st->d_tiles), st->ntiles, st->d_totals);
     return hipGetLastError();
 }
 
@@ -339,11 +211,11 @@ hipError_t device_build_pass2(const uint8_t *d_rle, size_t n, const DeviceBuildS
                               uint64_t nlong, void *d_blocks, hipStream_t stream) {
     uint32_t *blocks = static_cast<uint32_t *>(d_blocks);
     if (n) {
-        hipLaunchKernelGGL(k_paint, dim3(grid_for_tiles(st.ntiles)), dim3(kThreads), 0, stream, d_rle, uint64_t(n),
+        hipLaunchKernelGGL(k_paint, dim3(capped_grid(st.ntiles, 1, 4096)), dim3(kThreads), 0, stream, d_rle, uint64_t(n),
                            static_cast<const Seven *>(st.d_tiles), st.d_start_index, blocks,
                            static_cast<LongRun *>(d_long_runs), st.d_long_cursor);
         if (nlong)
-            hipLaunchKernelGGL(k_paint_long, dim3(uint32_t(nlong > 2048 ? 2048 : nlong)), dim3(kThreads), 0, stream,
+            hipLaunchKernelGGL(k_paint_long, dim3(capped_grid(nlong, 1, 2048)), dim3(kThreads), 0, stream,
                                static_cast<const LongRun *>(d_long_runs), nlong, st.d_start_index, blocks);
     }
     hipLaunchKernelGGL(k_final_header, dim3(1), dim3(64), 0, stream, st.d_start_index, st.d_totals, blocks);

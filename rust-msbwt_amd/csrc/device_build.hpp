@@ -7,9 +7,6 @@
 
 namespace msbwt {
 
-constexpr uint32_t kBuildBadSymbol = 1u;  // a byte carries symbol code 6 or 7
-constexpr uint32_t kBuildTooLarge = 2u;   // a run has a non-zero digit beyond 32^7: T >= 2^40
-
 struct DeviceBuildState {
     uint64_t *d_totals = nullptr;       // [0..5] symbol counts, [6] total symbols
     uint64_t *d_start_index = nullptr;  // 6 x u64, written by the host between the passes
@@ -25,7 +22,7 @@ size_t device_build_scratch_bytes(size_t n);
 size_t device_build_long_run_bytes(uint64_t nlong);
 
 // Pass 1: tile sums + scan.  Afterwards st->d_totals / d_flags / d_long_count are valid
-// (read them back after synchronising the stream).
+// (read them back after synchronising the stream); the flags are rle_subruns.hpp's kRleBadSymbol and kRleTooLarge.
 hipError_t device_build_pass1(const uint8_t *d_rle, size_t n, void *d_scratch, DeviceBuildState *st, hipStream_t stream);
 // Pass 2: paint.  d_blocks must be zero-filled, st.d_start_index filled in.
 hipError_t device_build_pass2(const uint8_t *d_rle, size_t n, const DeviceBuildState &st, void *d_long_runs,

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "rank_ops.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 namespace {
@@ -26,12 +27,7 @@ __device__ __forceinline__ uint64_t reserve(uint32_t mine, unsigned long long *c
     __shared__ uint32_t wave_total[kFrontierWaves];
     __shared__ unsigned long long block_base;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = uint32_t(__shfl_up(int(inc), d));
-        if (int(lane) >= d) inc += y;
-    }
+    const uint32_t inc = wave_inclusive_sum(mine);
     if (lane == 63u) wave_total[wave] = inc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -52,9 +48,7 @@ __device__ __forceinline__ uint64_t reserve(uint32_t mine, unsigned long long *c
 // adds the block's sum of `mine` to *acc
 __device__ __forceinline__ void block_add(uint32_t mine, unsigned long long *acc) {
     __shared__ uint32_t part[kFrontierWaves];
-    uint32_t s = mine;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += uint32_t(__shfl_xor(int(s), d));
+    const uint32_t s = wave_sum(mine);
     if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -15,6 +15,7 @@
 #include "handle.hpp"
 #include "pair_index.hpp"
 #include "plane_index.hpp"
+#include "rle_subruns.hpp"
 #include "run_build.hpp"
 #include "run_index.hpp"
 
@@ -62,7 +63,7 @@ uint64_t budget_left(const msbwt_rle *h, uint64_t held) { return h->memory_budge
 // the totals of a stream the host builds from, counted on the host: a bad symbol or 2^40 symbols and more are refused
 int host_totals(msbwt_rle *h, const uint8_t *rle, size_t n, Totals *t) {
     if (!compute_totals(rle, n, t)) return fail(h, MSBWT_ERR_INVALID_SYMBOL, "RLE stream holds a symbol code >= 6");
-    if (t->total > kMaxTotal) return fail(h, MSBWT_ERR_TOO_LARGE, "BWT has 2^40 symbols or more");
+    if (t->total >= kMaxSymbols) return fail(h, MSBWT_ERR_TOO_LARGE, "BWT has 2^40 symbols or more");
     return MSBWT_OK;
 }
 
@@ -407,7 +408,7 @@ int build_on_device(msbwt_rle *h, const uint8_t *rle, size_t n, Totals *t_out, b
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const uint32_t flags = *reinterpret_cast<const uint32_t *>(&head[13]);
     const uint64_t nlong = head[15];
-    if (flags & kBuildBadSymbol) return fail(h, MSBWT_ERR_INVALID_SYMBOL, "RLE stream holds a symbol code >= 6");
+    if (flags & kRleBadSymbol) return fail(h, MSBWT_ERR_INVALID_SYMBOL, "RLE stream holds a symbol code >= 6");
     Totals t{};
     uint64_t acc = 0;
     for (int s = 0; s < kAlphabet; ++s) {
@@ -417,7 +418,7 @@ int build_on_device(msbwt_rle *h, const uint8_t *rle, size_t n, Totals *t_out, b
         t.end_index[s] = acc;
     }
     t.total = acc;
-    if ((flags & kBuildTooLarge) || t.total > kMaxTotal || acc != head[6])
+    if ((flags & kRleTooLarge) || t.total >= kMaxSymbols || acc != head[6])
         return fail(h, MSBWT_ERR_TOO_LARGE, "BWT has 2^40 symbols or more");
     const uint64_t nblocks = plane_block_count(t.total);
     const size_t bytes = size_t(nblocks) * kBlockBytes;

@@ -7,7 +7,8 @@
 // the interleave of the union's BWT; rows of equal rotations stay input 0's first, because the sort is stable and they started so.
 //
 //   1. decode    both RLE streams -> one byte per symbol.  Every RLE byte is a sub-run of digit << 5 * (its index in its run)
-//                symbols; a tile's sub-run sum, a scan, and every thread knows where its sub-runs start.  Sub-runs below 1024
+//                symbols (rle_subruns.hpp: the walk of the index loader, 16 bytes per thread, every input at a 16-byte border);
+//                a tile's sub-run sum, a scan, and every thread knows where its sub-runs start.  Sub-runs below 1024
 //                symbols are written by their thread, longer ones are cut into pieces of at most 2^20 symbols on a list that a
 //                second kernel fills with 16-byte stores, a workgroup per piece.
 //   2. iterate   tiles of kMergeTile rows.  a) set bits per tile, scan: where the tile's rows start in either input (inside a
@@ -30,15 +31,12 @@ namespace {
 
 constexpr uint32_t kTileWords = kMergeTile / 64;       // words of the vector per tile
 constexpr uint32_t kDecodePer = 16, kDecodeTile = kThreads * kDecodePer;  // decode: RLE bytes per thread / workgroup
-constexpr uint32_t kMaxDigits = 8;                     // 32^8 = 2^40: a non-zero digit further up cannot be (the host has checked)
 constexpr uint64_t kShortRun = 1024;                   // sub-runs below this are written by their thread
 constexpr uint64_t kPiece = 1ull << 20;                // symbols per entry of the long sub-runs' list
 constexpr uint32_t kStringWords = kTileWords + 2;      // u64 words of one symbol's bit string: 63 bits of alignment + kMergeTile bits
+static_assert(kDecodePer == 16, "a thread decodes what rle_subruns.hpp loads");
 static_assert(kRowsPer == 16 && kTileWords == 64, "a thread holds a quarter word of the vector; wave 0 scans the tile's words");
 
-inline uint32_t grid_for(uint64_t items, uint64_t per_block, uint32_t cap = 1u << 20) {
-    return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(cap, ceil_div(items, per_block))));
-}
 // entries a sub-run of `value` symbols takes on the list
 __host__ __device__ inline uint64_t pieces_of(uint64_t value) { return value < kShortRun ? 0ull : ceil_div(value, kPiece); }
 
@@ -49,29 +47,17 @@ struct Piece {
     uint32_t len, sym;
 };
 
-// fn(symbol, symbols) for the sub-runs of the thread's kDecodePer bytes from `first` on, in order
-template <class Fn>
-__device__ __forceinline__ void for_each_subrun(const uint8_t *__restrict__ rle, uint64_t n, uint64_t first, Fn &&fn) {
-    if (first >= n) return;
-    uint32_t prev = rle[first] & 7u, e = 0;  // e: bytes of the same symbol right before, as far as it matters
-    for (uint32_t k = 1; k <= kMaxDigits && k <= first; ++k) {
-        if ((rle[first - k] & 7u) != prev) break;
-        ++e;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kDecodePer; ++i) {
-        if (first + i >= n) break;
-        const uint32_t byte = rle[first + i], sym = byte & 7u;
-        if (i) e = sym == prev ? min(e + 1u, kMaxDigits) : 0u;
-        prev = sym;
-        fn(sym, e < kMaxDigits ? uint64_t(byte >> 3) << (5u * e) : 0ull);
-    }
+// the sub-runs of the thread's kDecodePer bytes.  The walk's error bits are not looked at: scan_merge_input has refused a stream
+// that would set one before anything is copied.
+__device__ __forceinline__ ThreadBytes decode_bytes(const uint8_t *__restrict__ rle, uint64_t n) {
+    return load_thread_bytes(rle, n, uint64_t(blockIdx.x) * kDecodeTile + uint64_t(threadIdx.x) * kDecodePer);
 }
 
 __global__ __launch_bounds__(256) void k_decode_sums(const uint8_t *__restrict__ rle, uint64_t n, uint64_t *__restrict__ sums) {
     __shared__ uint64_t wave_sums[kScanWaves];
+    const ThreadBytes tb = decode_bytes(rle, n);
     uint64_t mine = 0;
-    for_each_subrun(rle, n, uint64_t(blockIdx.x) * kDecodeTile + uint64_t(threadIdx.x) * kDecodePer, [&](uint32_t, uint64_t v) { mine += v; });
+    (void)for_each_subrun(tb, [&](uint32_t, uint64_t v) { mine += v; });
     uint64_t total;
     block_exclusive_sum(mine, wave_sums, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
@@ -81,12 +67,12 @@ __global__ __launch_bounds__(256) void k_decode_sums(const uint8_t *__restrict__
 __global__ __launch_bounds__(256) void k_decode_paint(const uint8_t *__restrict__ rle, uint64_t n, const uint64_t *__restrict__ sums, uint8_t *__restrict__ symbols,
                                                       uint64_t total, Piece *__restrict__ pieces, uint64_t capacity, unsigned long long *__restrict__ cursor) {
     __shared__ uint64_t wave_sums[kScanWaves];
-    const uint64_t first = uint64_t(blockIdx.x) * kDecodeTile + uint64_t(threadIdx.x) * kDecodePer;
+    const ThreadBytes tb = decode_bytes(rle, n);
     uint64_t mine = 0;
-    for_each_subrun(rle, n, first, [&](uint32_t, uint64_t v) { mine += v; });
+    (void)for_each_subrun(tb, [&](uint32_t, uint64_t v) { mine += v; });
     uint64_t all;
     uint64_t pos = sums[blockIdx.x] + block_exclusive_sum(mine, wave_sums, &all);
-    for_each_subrun(rle, n, first, [&](uint32_t sym, uint64_t v) {
+    (void)for_each_subrun(tb, [&](uint32_t sym, uint64_t v) {
         if (v < kShortRun) {
             for (uint64_t k = 0; k < v && pos + k < total; ++k) symbols[pos + k] = uint8_t(sym);
         } else {
@@ -133,9 +119,7 @@ __global__ __launch_bounds__(256) void k_first_vector(uint64_t *__restrict__ bit
 // ones[tile] = set bits of the tile, a wave per tile
 __global__ __launch_bounds__(256) void k_tile_ones(const uint64_t *__restrict__ bits, uint64_t nwords, uint64_t ntiles, uint64_t *__restrict__ ones) {
     const uint64_t tile = uint64_t(blockIdx.x) * kScanWaves + (threadIdx.x >> 6), w = tile * kTileWords + (threadIdx.x & 63u);
-    uint32_t c = w < nwords ? uint32_t(__popcll(bits[w])) : 0u;
-#pragma unroll
-    for (uint32_t d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+    const uint32_t c = wave_sum(w < nwords ? uint32_t(__popcll(bits[w])) : 0u);
     if ((threadIdx.x & 63u) == 0u && tile < ntiles) ones[tile] = c;
 }
 
@@ -176,13 +160,7 @@ __device__ __forceinline__ Rows load_rows(TileShared &sh, const uint64_t *__rest
     const uint64_t tile = blockIdx.x, base = tile * kMergeTile, total = in.t0 + in.t1;
     if (t < kTileWords) {  // wave 0
         const uint64_t wi = tile * kTileWords + t, w = wi < nwords ? bits[wi] : 0ull;
-        const uint32_t c = uint32_t(__popcll(w));
-        uint32_t incl = c;
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (t >= d) incl += up;
-        }
+        const uint32_t c = uint32_t(__popcll(w)), incl = wave_inclusive_sum(c);
         sh.words[t] = w;
         sh.before[t] = incl - c;
         if (t == 63u) sh.ones = incl;
@@ -313,7 +291,7 @@ struct BitState {
     const uint32_t word_grid, tile_grid;
     explicit BitState(const MergeJob &j)
         : job(j), nwords(ceil_div(j.total, 64)), inputs{j.d_sym + j.shift[0], j.d_sym + j.first[1] + j.shift[1], j.first[1], j.total - j.first[1]},
-          word_grid(grid_for(nwords, kThreads * 4u)), tile_grid(uint32_t(j.ntiles)) {}
+          word_grid(capped_grid(nwords, kThreads * 4u)), tile_grid(uint32_t(j.ntiles)) {}
 
     hipError_t begin(Arena &, uint64_t *cur) const {
         hipLaunchKernelGGL(k_first_vector, dim3(word_grid), dim3(kThreads), 0, job.stream, cur, nwords, inputs.t0, job.total);
@@ -360,7 +338,7 @@ hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInp
     if ((e = exclusive_scan(d_sums, tiles, d_sums + tiles, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode_paint, dim3(uint32_t(tiles)), dim3(kThreads), 0, stream, d_rle, n, d_sums, d_symbols, in.total, d_pieces, in.long_pieces, d_cursor);
     if (in.long_pieces)
-        hipLaunchKernelGGL(k_decode_fill, dim3(grid_for(in.long_pieces, 1, 1u << 16)), dim3(kThreads), 0, stream, d_pieces, in.long_pieces, d_symbols, in.total);
+        hipLaunchKernelGGL(k_decode_fill, dim3(capped_grid(in.long_pieces, 1, 1u << 16)), dim3(kThreads), 0, stream, d_pieces, in.long_pieces, d_symbols, in.total);
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpyAsync(&taken, d_cursor, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipStreamSynchronize(stream)) != hipSuccess)
         return e;
@@ -376,17 +354,17 @@ hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInp
 
 MergeInputStatus scan_merge_input(const uint8_t *rle, size_t n, MergeInput *out) {
     uint64_t total = 0, pieces = 0;
-    uint32_t prev = 8, e = 0;
+    uint32_t prev = 8;
+    int e = 0;
     for (size_t i = 0; i < n; ++i) {
         const uint32_t sym = rle[i] & 7u, digit = rle[i] >> 3;
         if (sym >= kSymbols) return MergeInputStatus::kInvalidSymbol;
-        e = sym == prev ? std::min(e + 1u, kMaxDigits) : 0u;
+        e = next_exponent(e, sym == prev);
         prev = sym;
-        if (!digit) continue;
-        if (e >= kMaxDigits) return MergeInputStatus::kTooLarge;
-        const uint64_t value = uint64_t(digit) << (5u * e);
+        if (subrun_too_large(digit, e)) return MergeInputStatus::kTooLarge;
+        const uint64_t value = subrun_value(digit, e);
         total += value;  // < 2^41
-        if (total >= kMaxTotal) return MergeInputStatus::kTooLarge;
+        if (total >= kMaxSymbols) return MergeInputStatus::kTooLarge;
         pieces += pieces_of(value);
     }
     out->total = total;

@@ -59,7 +59,7 @@ struct MergeOutput {
 hipError_t merge_rle_pair(const MergeSpan *spans, size_t n, hipStream_t stream, MergeOutput *out);
 
 // The decoder of merge.hip, which merge_many.hip shares: d_rle[0 .. n) in HBM, a stream scan_merge_input accepted (in: what it
-// said) -> d_symbols[0 .. in.total), a byte per symbol; d_symbols is 16-byte aligned.  The stream is drained when it returns.
+// said) -> d_symbols[0 .. in.total), a byte per symbol; d_rle and d_symbols are 16-byte aligned.  The stream is drained when it returns.
 struct Arena;
 hipError_t decode(Arena &arena, const uint8_t *d_rle, uint64_t n, const MergeInput &in, uint8_t *d_symbols, hipStream_t stream, const char **what);
 

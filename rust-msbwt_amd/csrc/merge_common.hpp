@@ -1,6 +1,8 @@
 // What merge.hip (a bit per merged row, two inputs) and merge_many.hip (a byte per merged row, up to kMergeMaxInputs inputs) share,
 // and nobody else includes: the constants and device helpers of the six-way counting sort, and the host side of a merge, which is
-// one sequence whatever the state is -- copy in, decode, iterate until nothing changes, emit, encode.
+// one sequence whatever the state is -- copy in, decode, iterate until nothing changes, emit, encode.  The digit rule of the
+// inputs is rle_subruns.hpp's, the bound on the rows rle_codec.hpp's kMaxSymbols, and ceil_div, capped_grid and the sums over a wave
+// or a workgroup are workgroup.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +12,9 @@
 #include <string>
 
 #include "merge.hpp"
+#include "rle_subruns.hpp"
 #include "run_encode.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 
@@ -19,11 +23,8 @@ namespace {
 constexpr uint32_t kThreads = kScanThreads;
 constexpr uint32_t kRowsPer = kMergeTile / kThreads;  // consecutive rows of a tile one thread holds
 constexpr uint32_t kSymbols = 6, kNoRow = 7;
-constexpr uint64_t kMaxTotal = 1ull << 40;
 constexpr uint64_t kSymbolSlack = 16;  // bytes past the last input's symbols that may be read (not used): see run_merge
 static_assert(kRowsPer == 16, "a thread's rows are 16 bytes of merged symbols, of a byte state, or a quarter word of a bit state");
-
-__host__ __device__ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 // one row per symbol, 16 bits each: symbols 0..3 in *a, 4 and 5 in *b (a tile's sum of a field is <= kMergeTile < 2^16)
 __device__ __forceinline__ void count_symbol(uint32_t s, uint64_t *a, uint64_t *b) {
@@ -81,7 +82,7 @@ hipError_t run_merge(const MergeSpan *spans, size_t n, hipStream_t stream, Merge
     MergeJob job;
     job.stream = stream;
     job.n = uint32_t(n);
-    uint64_t rle_at[kMergeMaxInputs + 1];  // input i's RLE bytes in d_rle
+    uint64_t rle_at[kMergeMaxInputs + 1];  // input i's RLE bytes in d_rle, at a 16-byte border (the decoder's loads); [n]: d_rle's size
     rle_at[0] = 0;
     for (size_t i = 0; i < n; ++i) {
         job.first[i] = job.total;
@@ -89,11 +90,11 @@ hipError_t run_merge(const MergeSpan *spans, size_t n, hipStream_t stream, Merge
         job.shift[i] = job.sym_bytes - job.total;
         job.sym_bytes += spans[i].in.total;
         job.total += spans[i].in.total;
-        rle_at[i + 1] = rle_at[i] + spans[i].len;
+        rle_at[i + 1] = (rle_at[i] + spans[i].len + 15u) & ~15ull;
     }
     job.first[n] = job.total;
     const uint64_t total = job.total;
-    if (total == 0 || total >= kMaxTotal) return hipErrorInvalidValue;
+    if (total == 0 || total >= kMaxSymbols) return hipErrorInvalidValue;
     job.ntiles = ceil_div(total, kMergeTile);
     auto failed = [&](const char *what) {
         out->what = what;

@@ -113,12 +113,7 @@ __device__ __forceinline__ void make_map(TileMap &map, const uint64_t *__restric
         start = starts[at];
         c = uint32_t(min(end - start, uint64_t(kMergeTile)));
     }
-    uint32_t incl = c;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d);
-        if (i >= d) incl += up;
-    }
+    const uint32_t incl = wave_inclusive_sum(c);
     const unsigned long long has = __ballot(c > 0u);
     if (i < kMergeMaxInputs) {
         map.pre[i] = i < in.n ? incl - c : ~0u;

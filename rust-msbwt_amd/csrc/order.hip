@@ -40,6 +40,7 @@
 #include "order.hpp"
 #include "rank_ops.hpp"
 #include "search_common.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 
@@ -243,12 +244,7 @@ __device__ __forceinline__ void scan_1024(uint32_t *part, uint32_t base) {
             mine[i] = total;
             total += part[threadIdx.x * 16u + i];
         }
-        uint32_t incl = total;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (int(threadIdx.x) >= d) incl += up;
-        }
+        const uint32_t incl = wave_inclusive_sum(total);
         const uint32_t before = base + incl - total;
 #pragma unroll
         for (int i = 0; i < 16; ++i) part[threadIdx.x * 16u + i] = before + mine[i];

@@ -7,13 +7,15 @@
 //                     every lane owns one word of each of the five planes of its pair block
 //                     outright (plain stores, no atomics)
 //   k_pair_tile_sums  16 pair counts per tile of 1024 pair blocks
-//   k_pair_scan       exclusive prefix over tiles
+//   k_scan_tile_sums<16>  exclusive prefix over tiles (workgroup.hpp, shared with device_build.hip)
 //   k_pair_headers    24-bit per-block header fields, relative to the 2^24-position superblock
 //   k_pair_super      superblock table K[a][b] + occ2(a, b, superblock start)
+// The sums and scans inside a workgroup are workgroup.hpp's; the scan inside an 8-lane group below is this file's own.
 #include <hip/hip_runtime.h>
 
 #include "pair_index.hpp"
 #include "rank_ops.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 namespace {
@@ -22,9 +24,7 @@ constexpr int kTilePairBlocks = 1024;  // pair blocks per tile; 128 tiles = one 
 constexpr int kThreads = 256;
 constexpr int kBlocksPerThread = kTilePairBlocks / kThreads;  // 4
 
-struct Sixteen {
-    uint64_t v[16];
-};
+using Sixteen = TileSums<16>;
 
 struct StartIndex {
     uint64_t c[6];
@@ -134,57 +134,14 @@ __device__ __forceinline__ void add_block_pair_counts(const uint4 *__restrict__ 
 
 __global__ __launch_bounds__(kThreads) void k_pair_tile_sums(const uint4 *__restrict__ pair_blocks, uint64_t npair,
                                                              Sixteen *__restrict__ tiles, int words) {
-    __shared__ uint32_t red[16][kThreads / 64];
     for (uint64_t tile = blockIdx.x; tile * kTilePairBlocks < npair; tile += gridDim.x) {
         uint32_t acc[16] = {0};
         for (int i = 0; i < kBlocksPerThread; ++i) {
             const uint64_t pb = tile * kTilePairBlocks + uint64_t(threadIdx.x) * kBlocksPerThread + i;
             if (pb < npair) add_block_pair_counts(pair_blocks + pb * 8, acc, words);
         }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-            uint32_t x = acc[p];
-            for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d);
-            if ((threadIdx.x & 63) == 0) red[p][threadIdx.x >> 6] = x;
-        }
-        __syncthreads();
-        if (threadIdx.x < 16) {
-            uint64_t s = 0;
-            for (int w = 0; w < kThreads / 64; ++w) s += red[threadIdx.x][w];
-            tiles[tile].v[threadIdx.x] = s;
-        }
-    }
-}
-
-// in-place exclusive scan of the 16-vectors over tiles; one workgroup of 1024
-__global__ __launch_bounds__(1024) void k_pair_scan(Sixteen *__restrict__ tiles, uint64_t ntiles) {
-    __shared__ uint64_t wave_sum[16];
-    __shared__ uint64_t carry[16];
-    if (threadIdx.x < 16) carry[threadIdx.x] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint64_t base = 0; base < ntiles; base += 1024) {
-        const uint64_t t = base + threadIdx.x;
-        for (int p = 0; p < 16; ++p) {
-            const uint64_t x = t < ntiles ? tiles[t].v[p] : 0;
-            uint64_t inc = x;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint64_t y = __shfl_up(inc, d);
-                if (lane >= d) inc += y;
-            }
-            if (lane == 63) wave_sum[wave] = inc;
-            __syncthreads();
-            uint64_t before = carry[p], all = 0;
-            for (int w = 0; w < 16; ++w) {
-                if (w < wave) before += wave_sum[w];
-                all += wave_sum[w];
-            }
-            if (t < ntiles) tiles[t].v[p] = before + inc - x;
-            __syncthreads();
-            if (threadIdx.x == 0) carry[p] += all;
-            __syncthreads();
-        }
+        const uint64_t sum = block_vector_sum(acc);
+        if (threadIdx.x < 16) tiles[tile].v[threadIdx.x] = sum;
     }
 }
 
@@ -200,12 +157,8 @@ __global__ __launch_bounds__(kThreads) void k_pair_headers(uint4 *__restrict__ p
         uint32_t run[16];
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-        for (int p = 0; p < 16; ++p) {
-            uint32_t inc = mine[p];
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(inc, d);
-                if (lane >= d) inc += y;
-            }
+        for (int p = 0; p < 16; ++p) {  // (not block_exclusive_sum: sixteen of them inlined here cost 27 VGPRs and a wave of occupancy)
+            const uint32_t inc = wave_inclusive_sum(mine[p]);
             __syncthreads();
             if (lane == 63) wave_tot[wave] = inc;
             __syncthreads();
@@ -251,8 +204,8 @@ __global__ void k_pair_super(const Sixteen *__restrict__ tiles, uint64_t ntiles,
 PairIndexSizes pair_index_sizes(uint64_t nblocks, int stride) {
     PairIndexSizes s;
     s.pair_blocks = stride == 96 ? (nblocks * 256) / 96 + 2 : 2 * nblocks;
-    s.tiles = (s.pair_blocks + kTilePairBlocks - 1) / kTilePairBlocks;
-    s.supers = (s.tiles + 127) / 128;
+    s.tiles = ceil_div(s.pair_blocks, kTilePairBlocks);
+    s.supers = ceil_div(s.tiles, 128);
     s.pair_block_bytes = size_t(s.pair_blocks) * 128;
     s.super_bytes = size_t(s.supers) * 16 * sizeof(uint64_t);
     s.scratch_bytes = size_t(s.tiles) * sizeof(Sixteen) + 16 * sizeof(uint64_t);
@@ -274,14 +227,12 @@ hipError_t build_pair_index(const void *d_blocks, uint64_t nblocks, const uint64
     StartIndex st;
     for (int s = 0; s < 6; ++s) st.c[s] = start_index[s];
     hipLaunchKernelGGL(k_pair_consts, dim3(1), dim3(128), 0, stream, blocks, st, K);
-    const uint64_t groups_blocks = (nblocks * 8 + 255) / 256;
-    hipLaunchKernelGGL(k_pair_paint, dim3(uint32_t(groups_blocks > 8192 ? 8192 : (groups_blocks ? groups_blocks : 1))), dim3(256), 0,
-                       stream, blocks, nblocks, pair, stride96);
-    const uint32_t tgrid = uint32_t(sz.tiles > 4096 ? 4096 : (sz.tiles ? sz.tiles : 1));
+    hipLaunchKernelGGL(k_pair_paint, dim3(capped_grid(nblocks * 8, 256, 8192)), dim3(256), 0, stream, blocks, nblocks, pair, stride96);
+    const uint32_t tgrid = capped_grid(sz.tiles, 1, 4096);
     hipLaunchKernelGGL(k_pair_tile_sums, dim3(tgrid), dim3(kThreads), 0, stream, pair, sz.pair_blocks, tiles, words);
-    hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, stream, tiles, sz.tiles);
+    hipLaunchKernelGGL(k_scan_tile_sums<16>, dim3(1), dim3(1024), 0, stream, tiles, sz.tiles, static_cast<uint64_t *>(nullptr));
     hipLaunchKernelGGL(k_pair_headers, dim3(tgrid), dim3(kThreads), 0, stream, pair, sz.pair_blocks, tiles, words);
-    hipLaunchKernelGGL(k_pair_super, dim3(uint32_t((sz.supers * 16 + 255) / 256)), dim3(256), 0, stream, tiles, sz.tiles, K,
+    hipLaunchKernelGGL(k_pair_super, dim3(uint32_t(ceil_div(sz.supers * 16, 256))), dim3(256), 0, stream, tiles, sz.tiles, K,
                        sz.supers, static_cast<uint64_t *>(d_super));
     return hipGetLastError();
 }

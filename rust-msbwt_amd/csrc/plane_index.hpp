@@ -28,7 +28,6 @@ namespace msbwt {
 constexpr int kBlockShift = 8;                  // 256 symbols per block
 constexpr uint64_t kBlockSymbols = 1ull << kBlockShift;
 constexpr size_t kBlockBytes = 128;
-constexpr uint64_t kMaxTotal = (1ull << 40) - 1;  // A[s] must fit 40 bits
 
 inline uint64_t plane_block_count(uint64_t total) { return (total >> kBlockShift) + 1; }
 

@@ -23,7 +23,7 @@ int check_reads(msbwt_rle *h, const uint8_t *reads, const uint64_t *read_offsets
     for (size_t r = 0; r < n_reads; ++r)
         if (read_offsets[r + 1] < read_offsets[r]) return fail(h, MSBWT_ERR_INVALID_ARG, "read_offsets decrease at read " + std::to_string(r));
     const uint64_t lo = read_offsets[0], nbytes = read_offsets[n_reads] - lo;
-    if (nbytes >= (1ull << 40) || nbytes + n_reads >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the read set has 2^40 symbols or more");
+    if (nbytes >= kMaxSymbols || nbytes + n_reads >= kMaxSymbols) return fail(h, MSBWT_ERR_TOO_LARGE, "the read set has 2^40 symbols or more");
     // ASCII: every byte but '$' has a code (string_util.rs:15-32); codes: 1..5.  Large sets are checked by a few threads.
     auto bad_in = [&](uint64_t from, uint64_t to) {
         unsigned bad = 0;
@@ -89,7 +89,7 @@ int check_merge_inputs(msbwt_rle *h, std::vector<MergeSpan> *spans, uint64_t *to
             case MergeInputStatus::kTooLarge: return fail(h, MSBWT_ERR_TOO_LARGE, "input " + std::to_string(i) + " has 2^40 symbols or more");
         }
         *total += span.in.total;  // < 2^45
-        if (*total >= (1ull << 40)) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
+        if (*total >= kMaxSymbols) return fail(h, MSBWT_ERR_TOO_LARGE, "the merged BWT would have 2^40 symbols or more");
     }
     return MSBWT_OK;
 }
@@ -278,16 +278,16 @@ int msbwt_merge_many_plan(const uint64_t *totals, size_t n_inputs, uint64_t *dev
     if (n_inputs > MSBWT_MERGE_MAX_INPUTS || (!totals && n_inputs)) return MSBWT_ERR_INVALID_ARG;
     uint64_t total = 0;
     for (size_t i = 0; i < n_inputs; ++i) {
-        if (totals[i] >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+        if (totals[i] >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
         total += totals[i];  // < 2^45
     }
-    if (total >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (total >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
     if (device_bytes) *device_bytes = plan_merge_many(total);
     return MSBWT_OK;
 }
 
 int msbwt_merge_plan(uint64_t total0, uint64_t total1, uint64_t *device_bytes) {
-    if (total0 >= (1ull << 40) || total1 >= (1ull << 40) || total0 + total1 >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (total0 >= kMaxSymbols || total1 >= kMaxSymbols || total0 + total1 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
     if (device_bytes) *device_bytes = plan_merge(total0, total1);
     return MSBWT_OK;
 }
@@ -308,7 +308,7 @@ int msbwt_rle_set_build_piece(msbwt_rle *h, uint64_t suffixes) {
 }
 
 int msbwt_build_reads_plan(uint64_t total_symbols, uint64_t free_hbm_bytes, uint64_t piece, uint64_t *auto_piece, uint64_t *device_bytes) {
-    if (total_symbols >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (total_symbols >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
     const ReadsBuildPlan p = plan_reads_build(total_symbols, free_hbm_bytes, piece);
     if (auto_piece) *auto_piece = p.auto_piece;
     if (device_bytes) *device_bytes = p.device_bytes;

@@ -27,7 +27,9 @@
 #include <vector>
 
 #include "reads_build.hpp"
+#include "rle_codec.hpp"
 #include "run_encode.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 
@@ -41,11 +43,6 @@ constexpr uint32_t kCollectPer = 8, kCollectTile = kThreads * kCollectPer;  // c
 constexpr uint32_t kBins = 4096;
 constexpr uint32_t kPad = 128;  // zero bytes after the reads and after the text: wide loads past the last symbol stay inside
 static_assert(kRounds * kThreads == kReadsSortTile && kThreads == kDigits, "one thread per digit when a tile's counts are laid out");
-
-__host__ __device__ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-inline uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t cap = 1u << 20) {
-    return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(cap, ceil_div(items, per_block))));
-}
 
 // ---- keys ----
 
@@ -355,7 +352,7 @@ hipError_t sort_elements(const Source &src, SortBuffers<Pos> &b, uint64_t n, uin
     if (n < 2) return hipSuccess;
     const uint64_t ntiles = ceil_div(n, kReadsSortTile);
     for (uint32_t w = nwords; w-- > 0;) {
-        hipLaunchKernelGGL((k_gather_keys<Pos, Source>), dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, src, b.pos_a, n, w, b.keys_a);
+        hipLaunchKernelGGL((k_gather_keys<Pos, Source>), dim3(capped_grid(n, kThreads)), dim3(kThreads), 0, stream, src, b.pos_a, n, w, b.keys_a);
         for (uint32_t pass = 0; pass < kPassesPerWord; ++pass) {
             const uint32_t shift = pass * kDigitBits;
             hipLaunchKernelGGL(k_sort_histogram, dim3(uint32_t(ntiles)), dim3(kThreads), 0, stream, b.keys_a, n, shift, ntiles, b.hist);
@@ -430,7 +427,7 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
     if (e == hipSuccess) e = hipMemcpyAsync(d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = lap(kStageCopyIn);
     if (e != hipSuccess) return failed("copying the reads to HBM");
-    if (ascii && nbytes) hipLaunchKernelGGL(k_ascii_to_codes, dim3(grid_for(nbytes, kThreads)), dim3(kThreads), 0, stream, d_reads, nbytes);
+    if (ascii && nbytes) hipLaunchKernelGGL(k_ascii_to_codes, dim3(capped_grid(nbytes, kThreads)), dim3(kThreads), 0, stream, d_reads, nbytes);
 
     // ---- 1. the reads' order, the text
     const uint64_t text_bytes = ceil_div(total, 64) * 64 + kPad, bitmap_words = ceil_div(total, 64);
@@ -440,12 +437,12 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
         if ((e = sb.take(arena, n)) != hipSuccess || (e = arena.take(&d_starts, (n + 1) * 8 + scan_scratch_words(n + 1) * 8)) != hipSuccess ||
             (e = arena.take(&d_text, text_bytes)) != hipSuccess)
             return failed("the buffers of the read order");
-        hipLaunchKernelGGL((k_iota<Pos>), dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, sb.pos_a, n);
+        hipLaunchKernelGGL((k_iota<Pos>), dim3(capped_grid(n, kThreads)), dim3(kThreads), 0, stream, sb.pos_a, n);
         if ((e = sort_elements(ReadSource{d_reads, d_offsets}, sb, n, nwords, stream)) != hipSuccess) return failed("sorting the reads");
-        hipLaunchKernelGGL((k_read_spans<Pos>), dim3(grid_for(n + 1, kThreads)), dim3(kThreads), 0, stream, sb.pos_a, d_offsets, n, d_starts);
+        hipLaunchKernelGGL((k_read_spans<Pos>), dim3(capped_grid(n + 1, kThreads)), dim3(kThreads), 0, stream, sb.pos_a, d_offsets, n, d_starts);
         if ((e = exclusive_scan(d_starts, n + 1, d_starts + n + 1, stream)) != hipSuccess) return failed("placing the reads");
         if ((e = hipMemsetAsync(d_text + total, 0, text_bytes - total, stream)) != hipSuccess) return failed("clearing the text's padding");
-        hipLaunchKernelGGL((k_layout_text<Pos>), dim3(grid_for(n, kWaves)), dim3(kThreads), 0, stream, sb.pos_a, d_offsets, d_reads, d_starts, n, d_text);
+        hipLaunchKernelGGL((k_layout_text<Pos>), dim3(capped_grid(n, kWaves)), dim3(kThreads), 0, stream, sb.pos_a, d_offsets, d_reads, d_starts, n, d_text);
         if ((e = hipGetLastError()) != hipSuccess || (e = lap(kStageReadOrder)) != hipSuccess) return failed("laying out the text");
         sb.give_back(arena);
         arena.give_back(d_starts);
@@ -458,9 +455,9 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
     unsigned long long *d_bins = nullptr;
     if ((e = arena.take(&d_terminators, bitmap_words * 8)) != hipSuccess || (e = arena.take(&d_bins, kBins * 8)) != hipSuccess) return failed("the terminator bitmap");
     std::vector<uint64_t> bins(kBins);
-    hipLaunchKernelGGL(k_terminator_bits, dim3(grid_for(bitmap_words, kThreads)), dim3(kThreads), 0, stream, d_text, bitmap_words, d_terminators);
+    hipLaunchKernelGGL(k_terminator_bits, dim3(capped_grid(bitmap_words, kThreads)), dim3(kThreads), 0, stream, d_text, bitmap_words, d_terminators);
     if ((e = hipMemsetAsync(d_bins, 0, kBins * 8, stream)) != hipSuccess) return failed("clearing the histogram");
-    hipLaunchKernelGGL(k_bin_histogram, dim3(grid_for(total, kReadsSortTile, 1024)), dim3(kThreads), 0, stream, d_text, total, d_bins);
+    hipLaunchKernelGGL(k_bin_histogram, dim3(capped_grid(total, kReadsSortTile, 1024)), dim3(kThreads), 0, stream, d_text, total, d_bins);
     if ((e = hipMemcpyAsync(bins.data(), d_bins, kBins * 8, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = lap(kStageHistogram)) != hipSuccess)
         return failed("the histogram of the suffixes");
     arena.give_back(d_bins);
@@ -490,7 +487,7 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
         if ((e = hipGetLastError()) != hipSuccess || (e = lap(kStageCollect)) != hipSuccess) return failed("collecting a piece");
         if (p.sort && (e = sort_elements(source, sb, p.count, nwords, stream)) != hipSuccess) return failed("sorting a piece");
         if ((e = lap(kStageSort)) != hipSuccess) return failed("sorting a piece");
-        hipLaunchKernelGGL((k_emit<Pos>), dim3(grid_for(p.count, kThreads)), dim3(kThreads), 0, stream, d_text, sb.pos_a, p.count, d_symbols + p.offset);
+        hipLaunchKernelGGL((k_emit<Pos>), dim3(capped_grid(p.count, kThreads)), dim3(kThreads), 0, stream, d_text, sb.pos_a, p.count, d_symbols + p.offset);
         if ((e = hipGetLastError()) != hipSuccess || (e = lap(kStageEmit)) != hipSuccess) return failed("emitting a piece");
     }
     sb.give_back(arena);
@@ -514,7 +511,7 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
 ReadsBuildPlan plan_reads_build(uint64_t total_symbols, uint64_t free_hbm_bytes, uint64_t piece) {
     // resident: text and symbols (or reads and text) at one byte each, the terminator bitmap, the collect counts; per suffix of a
     // piece: two key and two position arrays (64-bit positions assumed) and its share of the tile histograms
-    constexpr uint64_t kPerSuffix = 2 * (8 + 8) + 1, kMaxPiece = 1ull << 40;
+    constexpr uint64_t kPerSuffix = 2 * (8 + 8) + 1, kMaxPiece = kMaxSymbols;
     const uint64_t resident = 2 * total_symbols + total_symbols / 8 + total_symbols / 128 + (1ull << 20);
     const uint64_t usable = free_hbm_bytes - free_hbm_bytes / 10;
     ReadsBuildPlan p;

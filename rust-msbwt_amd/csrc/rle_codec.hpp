@@ -9,6 +9,9 @@
 namespace msbwt {
 
 constexpr int kAlphabet = 6;  // $ A C G N T
+// The bound on every count of symbols (a BWT's total, a read set's text, a merge's rows): legal when BELOW this.  Block
+// headers hold 40-bit values (plane_index.hpp), and 32^8 = 2^40 is where the digit rule stops (rle_subruns.hpp).
+constexpr uint64_t kMaxSymbols = 1ull << 40;
 
 struct Totals {
     uint64_t symbol_counts[kAlphabet];

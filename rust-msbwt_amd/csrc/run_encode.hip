@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "run_encode.hpp"
+#include "workgroup.hpp"
 
 namespace msbwt {
 
@@ -18,8 +19,6 @@ constexpr uint32_t kThreads = kScanThreads, kWaves = kScanWaves;
 constexpr uint32_t kScanPer = 8, kScanChunk = kThreads * kScanPer;        // scan: elements per thread / workgroup
 constexpr uint32_t kRunPer = 16, kRunTile = kThreads * kRunPer;            // encode: symbols per thread / workgroup
 constexpr uint64_t kNone = ~0ull;
-
-__host__ __device__ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 // minimum of v over the threads AFTER this one, `tail` beyond the last; *all = the minimum over every thread and tail.
 // buf: 2 x kThreads words of LDS.
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(256) void k_run_bytes(const uint8_t *__restrict__ s
     uint64_t len[kRunPer];
     const uint32_t mine = run_lengths(s, next_heads[blockIdx.x], buf, len);
     uint64_t total;
-    block_exclusive_sum(mine, wave_sums, &total);
+    block_exclusive_sum(uint64_t(mine), wave_sums, &total);
     if (threadIdx.x == 0) {
         bytes[blockIdx.x] = total;
         if (blockIdx.x + 1u == gridDim.x) bytes[gridDim.x] = 0ull;
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(256) void k_run_write(const uint8_t *__restrict__ s
     uint64_t len[kRunPer];
     const uint32_t mine = run_lengths(s, next_heads[blockIdx.x], buf, len);
     uint64_t total;
-    uint64_t at = bytes[blockIdx.x] + block_exclusive_sum(mine, wave_sums, &total);  // + the run's digits <= bytes[ntiles], the buffer's size
+    uint64_t at = bytes[blockIdx.x] + block_exclusive_sum(uint64_t(mine), wave_sums, &total);  // + the run's digits <= bytes[ntiles], the buffer's size
 #pragma unroll
     for (uint32_t j = 0; j < kRunPer; ++j)
         for (uint64_t left = len[j]; left > 0; left >>= 5) rle[at++] = uint8_t(s.sym[j] | ((left & 31u) << 3));

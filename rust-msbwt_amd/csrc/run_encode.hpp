@@ -1,5 +1,6 @@
-// What the device builders share (run_encode.hip): the workgroup prefix sum, the exclusive scan of u64 in HBM, the arena of a
-// build's allocations, and the encoder symbols -> RLE bytes.  reads_build.hip and merge.hip both call this one copy.
+// What the device builders share (run_encode.hip): the exclusive scan of u64 in HBM, the arena of a build's allocations, and the
+// encoder symbols -> RLE bytes.  reads_build.hip and merge.hip both call this one copy.  The primitives inside a workgroup
+// (prefix sum, wave sums, ceil_div, capped_grid) are workgroup.hpp's; this header is for host translation units as well.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,31 +11,6 @@
 namespace msbwt {
 
 constexpr uint32_t kScanThreads = 256, kScanWaves = kScanThreads / 64;  // every kernel of the builders runs 256 threads
-
-#if defined(__HIPCC__)
-// exclusive prefix sum of v over the workgroup's threads; *total = the sum.  wave_sums: kScanWaves words of LDS.
-__device__ __forceinline__ uint64_t block_exclusive_sum(uint64_t v, uint64_t *wave_sums, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint64_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    __syncthreads();  // the words are free again
-    if (lane == 63u) wave_sums[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kScanWaves; ++w) {
-        const uint64_t s = wave_sums[w];
-        before += w < wave ? s : 0ull;
-        all += s;
-    }
-    *total = all;
-    return before + incl - v;
-}
-#endif
 
 // words of scratch a scan of n elements needs (the sums of every level)
 uint64_t scan_scratch_words(uint64_t n);

@@ -11,7 +11,7 @@ namespace {
 // bytes the attachment holds in HBM; MSBWT_ERR_* for arguments no attachment can have
 int plan_bytes(uint64_t total_rows, size_t n_sources, uint64_t *bytes) {
     if (n_sources < 1 || n_sources > MSBWT_MERGE_MAX_INPUTS) return MSBWT_ERR_INVALID_ARG;
-    if (total_rows >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (total_rows >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
     const SourceSizes z = source_sizes(total_rows, uint32_t(n_sources));
     *bytes = z.row_bytes + z.checkpoint_bytes;
     return MSBWT_OK;

@@ -16,7 +16,7 @@ constexpr uint64_t kRecordBytes = 3 * sizeof(uint64_t);  // k-mer, count, l
 
 // bytes of scratch a call allocates; MSBWT_ERR_TOO_LARGE for what no index can be
 int plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t frontier, uint64_t records, bool sorted, uint64_t *bytes) {
-    if (total_rows >= (1ull << 40) || records >= (1ull << 40)) return MSBWT_ERR_TOO_LARGE;
+    if (total_rows >= kMaxSymbols || records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
     *bytes = spectrum_work_bytes(spectrum_frontier_nodes(total_rows, free_bytes, frontier)) + (sorted ? spectrum_rank_bytes(total_rows) : 0) + records * kRecordBytes;
     return MSBWT_OK;
 }

@@ -69,9 +69,7 @@ struct Sink {
 };
 
 __device__ __forceinline__ void block_add64(uint64_t mine, unsigned long long *acc) {  // one atomic per wave
-    unsigned long long s = mine;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    const unsigned long long s = wave_sum<unsigned long long>(mine);
     if ((threadIdx.x & 63u) == 0u && s) atomicAdd(acc, s);
 }
 

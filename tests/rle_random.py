@@ -64,6 +64,46 @@ def raw_byte_stream(seed, nbytes):
     return (sym | (digit << 3)).astype(np.uint8)
 
 
+def run_across_byte(first_byte, length, tail=(3, 40)):
+    """A stream in which the digits of ONE run of `length` symbols start at byte `first_byte`: that many alternating one-byte
+    runs of A and C in front of it, the run itself of T, and a short run of `tail` = (symbol, length) behind it.  The device
+    walks a stream 16 bytes to a thread and 4096 to a workgroup, and a byte's weight depends on the bytes of its run before it:
+    a run whose digits lie on both sides of such a border has its weight carried across."""
+    syms = [1 + i % 2 for i in range(first_byte)] + [5, tail[0]]
+    stream = runs_to_bytes(syms, [1] * first_byte + [length, tail[1]])
+    ndigits = (int(length).bit_length() + 4) // 5
+    assert (stream[first_byte:first_byte + ndigits] & 7 == 5).all() and (stream[first_byte - 1] & 7, stream[first_byte + ndigits] & 7) == (1 + (first_byte - 1) % 2, tail[0])
+    return stream
+
+
+# four digits, the third of them zero: at bytes 4095 | 4096..4098 (a tile's last byte and the next tile's first three) and at bytes
+# 15 | 16..18 (the same for two threads)
+FOUR_DIGITS = 5 + 7 * 32 + 0 * 32 ** 2 + 3 * 32 ** 3
+BORDER_STREAMS = {"tile border": lambda: run_across_byte(4095, FOUR_DIGITS), "thread border": lambda: run_across_byte(15, FOUR_DIGITS)}
+# eight digits, the eighth the only one that is not zero, at bytes 13..15 | 16..20: the largest weight a byte can have, 32^7 -- so
+# this stream has 2^35 symbols, and nothing that expands it is small
+EIGHT_DIGITS = lambda: run_across_byte(13, 32 ** 7)
+
+
+def canonical_runs(stream):
+    """The canonical RLE bytes of what `stream` decodes to, from its runs alone (no symbol array): a run is a maximal group of
+    bytes of one symbol, neighbouring runs of one symbol join, a run of no symbols vanishes."""
+    stream = np.asarray(stream, dtype=np.uint8)
+    if stream.size == 0:
+        return stream
+    sym = stream & 7
+    head = np.flatnonzero(np.concatenate([[True], sym[1:] != sym[:-1]]))
+    index = np.arange(stream.size) - np.repeat(head, np.diff(np.concatenate([head, [stream.size]])))
+    assert index.max() < 12
+    value = (stream >> 3).astype(np.uint64) << (np.uint64(5) * index.astype(np.uint64))
+    lens, syms = np.add.reduceat(value, head), sym[head]
+    syms, lens = syms[lens > 0], lens[lens > 0]
+    if syms.size == 0:
+        return np.empty(0, dtype=np.uint8)
+    head = np.flatnonzero(np.concatenate([[True], syms[1:] != syms[:-1]]))
+    return runs_to_bytes(syms[head], np.add.reduceat(lens, head))
+
+
 def random_kmers(seed, n, k, alphabet=(1, 2, 3, 5)):
     rng = np.random.default_rng(seed)
     alphabet = np.asarray(alphabet, dtype=np.uint8)

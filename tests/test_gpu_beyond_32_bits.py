@@ -40,6 +40,8 @@ ROWS = {"windows": 25_000, "mutants": 12_000, "random": 9_000, "odd": 4_000}   #
 HBM_GB = {"defaults": 88.60, "declared_k31": 88.60, "sparse27": 88.60, "sparse25": 87.60, "two_tier": 89.78, "no_sparse": 84.30,
           "no_pair": 7.30, "runs_sparse0": 2.82, "runs_sparseauto": 5.64, "host_planes": 88.60, "host_runs": 2.82, "replica": 2 * 88.60,
           "device_forms_planes": 88.60, "device_forms_runs": 5.64,
+          "eight_digits_load": 34.36,   # (2^35 symbols: plane blocks 17.2 GB and the direct table; no pair index, no sparse table)
+          "eight_digits_merge": 115.0,  # (no index: the one-pass merge of 2^35 rows by merge.hpp's plan_merge_many)
           "read_set": 6.49}     # (not an index: the peak of torch's allocations while the fixture builds the read set's BWT)
 
 
@@ -397,3 +399,49 @@ def test_device_forms_fused_reads_and_packed_queries(blocks, index, cases, monke
     assert got64.dtype == np.uint64 and got32.dtype == np.uint32
     same(got64, c.cnt[plain], blocks + ", packed, 64-bit counts")
     same(got32, c.cnt[plain], blocks + ", packed, 32-bit counts")
+
+
+# ---- the largest weight an RLE byte can have --------------------------------------------------------------------------------------------
+def test_a_run_of_eight_digits_across_a_thread_border_loads(monkeypatch, handles):
+    """The eighth digit of a run weighs 32^7 = 2^35 symbols, so no small stream has one.  Here the run's eight bytes lie at bytes
+    13..20 of the stream, on both sides of byte 16, where the device walk (csrc/rle_subruns.hpp: 16 bytes to a thread) hands the
+    count of a run's bytes from one thread to the next; the first seven digits are zero.  The loader's plane blocks equal the
+    host builder's word for word (17.2 GB each)."""
+    from rle_random import EIGHT_DIGITS
+    from test_gpu_parity import _download_blocks, _host_blocks
+    _gate("eight_digits_load")
+    stream, total = EIGHT_DIGITS(), 13 + 2 ** 35 + 40
+    monkeypatch.setenv("MSBWT_SPARSE_TABLE", "0")
+    b = RleBWT(device=0)
+    handles.append(b)
+    b.set_pair_index(0)
+    t0 = time.time()
+    b.load_vector(stream)
+    assert b.get_total_size() == total and b.get_block_format() == "planes"
+    t1 = time.time()
+    print("eight digits: device_bytes() = %.2f GB" % (b.device_bytes() / 1e9))
+    dev = _download_blocks(b)
+    release(b)
+    host = _host_blocks(stream)
+    t2 = time.time()
+    assert dev.shape == host.shape == (total // 256 + 1, 8, 4)
+    assert np.array_equal(dev, host)
+    print("eight digits: load %.1f s, download and host build %.1f s, compare %.1f s" % (t1 - t0, t2 - t1, time.time() - t2))
+
+
+def test_a_run_of_eight_digits_across_a_thread_border_merges(handles):
+    """The same stream through the decoder of both merges: merged with nothing it comes back in canonical form -- expected from
+    the runs alone (rle_random.canonical_runs, which tests/test_gpu_merge.py's small streams tie to the oracle's decoder): what
+    the oracle would decode to does not fit a test."""
+    from rle_random import EIGHT_DIGITS, canonical_runs
+    _gate("eight_digits_merge")
+    stream, empty, total = EIGHT_DIGITS(), np.empty(0, dtype=np.uint8), 13 + 2 ** 35 + 40
+    want = canonical_runs(stream)
+    assert want.size == stream.size and msbwt.rle_bwt.rle_total(want) == total
+    t0 = time.time()
+    m = RleBWT(device=0)
+    handles.append(m)
+    assert np.array_equal(m.merge(stream, empty), want)
+    assert np.array_equal(m.merge(empty, stream), want)
+    assert np.array_equal(m.merge_many([stream]), want)
+    print("eight digits: three merges %.1f s" % (time.time() - t0))

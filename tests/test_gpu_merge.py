@@ -12,6 +12,7 @@ import time
 import numpy as np
 import pytest
 
+from rle_random import BORDER_STREAMS, canonical_runs, random_stream, raw_byte_stream
 from test_gpu_reads_build import READ_SETS, digits, naive_rle, ragged_set, read_set
 
 pytestmark = pytest.mark.gpu
@@ -238,6 +239,26 @@ def test_two_runs_join_into_one_and_split_runs_decode_the_same(bwt, orc):
     empty = np.empty(0, dtype=np.uint8)
     assert np.array_equal(bwt.merge(loose, empty), want)
     assert np.array_equal(bwt.merge(empty, loose), want)
+
+
+# ---- the decoder on streams that are no BWT of anything ----
+
+DECODER_STREAMS = dict(BORDER_STREAMS, mixed=lambda: random_stream(31, 20000, "mixed"),
+                       **{"raw %d" % s: (lambda s=s: raw_byte_stream(s, 5000)) for s in range(4)})
+
+
+@pytest.mark.parametrize("name", sorted(DECODER_STREAMS))
+def test_any_stream_merged_with_nothing_comes_back_canonical(bwt, orc, name):
+    """A merge with an empty input needs no read set behind the other one: it decodes the stream and encodes the symbols again.
+    Zero digits, runs of no symbols, a run's digits across a thread's (16 bytes) and a tile's (4096) border of the decoder, and
+    sub-runs on both sides of 1024 symbols, where a second kernel takes over."""
+    import synth
+    stream, empty = DECODER_STREAMS[name](), np.empty(0, dtype=np.uint8)
+    want = synth.rle_encode(orc.decompress(stream))
+    assert np.array_equal(canonical_runs(stream), want)  # (the restatement that stands in where a stream is too long to decode)
+    assert np.array_equal(bwt.merge(stream, empty), want)
+    assert np.array_equal(bwt.merge(empty, stream), want)
+    assert np.array_equal(bwt.merge_many([stream]), want)
 
 
 # ---- read sets ----

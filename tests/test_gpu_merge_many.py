@@ -198,6 +198,33 @@ def test_one_input_that_is_not_canonical_comes_back_canonical(bwt, orc):
     assert rc == 0 and need == want.size and np.array_equal(out[:need], want) and (out[need:] == 0xAB).all()
 
 
+# ---- the inputs' places in the one array of RLE bytes ----
+
+def trimmed_to(orc, reads, residue):
+    """`reads` with letters taken off their ends, one at a time, until their BWT takes `residue` RLE bytes modulo 16."""
+    reads = list(reads)
+    for step in range(200):
+        if naive_rle(orc, reads).size % 16 == residue:
+            return reads
+        longest = max(range(len(reads)), key=lambda i: len(reads[i]))
+        reads[longest] = reads[longest][:-1]
+    raise AssertionError("no trim of the read set takes %d bytes modulo 16" % residue)
+
+
+def test_inputs_whose_rle_bytes_end_off_a_16_byte_border(bwt, orc):
+    """The inputs' RLE bytes lie one after the other in HBM, each at a 16-byte border (the decoder loads 16 bytes at a time):
+    three inputs of 1, 0 and 15 bytes modulo 16, and one of no bytes between two of them."""
+    sets = [trimmed_to(orc, ragged_set(seed), residue) for seed, residue in ((300, 1), (302, 0), (303, 15))]
+    rles = [naive_rle(orc, reads) for reads in sets]
+    assert [r.size % 16 for r in rles] == [1, 0, 15] and all(r.size > 16 for r in rles)
+    rles.insert(1, EMPTY)
+    merged, sources = bwt.merge_many(rles, return_sources=True)
+    assert np.array_equal(merged, bwt.build_from_reads(sets[0] + sets[1] + sets[2], ascii=True))
+    assert np.array_equal(merged, naive_rle(orc, sets[0] + sets[1] + sets[2]))
+    assert np.array_equal(sources, expected_sources(rles))
+    check_sources(sources, merged, rles)
+
+
 # ---- convergence ----
 
 def test_convergence_takes_longer_than_the_read_length(bwt, orc):

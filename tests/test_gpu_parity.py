@@ -9,7 +9,7 @@ import pytest
 import rust_msbwt_amd as msbwt
 from rust_msbwt_amd import BWTRange, RleBWT
 from oracle import oracle as orc
-from rle_random import random_kmers, random_stream, raw_byte_stream, runs_to_bytes
+from rle_random import BORDER_STREAMS, random_kmers, random_stream, raw_byte_stream, runs_to_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -363,7 +363,7 @@ def _host_blocks(rle):
     return out
 
 
-@pytest.mark.parametrize("case", ["ones", "short", "long", "mixed", "raw", "edges", "big_short"])
+@pytest.mark.parametrize("case", ["ones", "short", "long", "mixed", "raw", "edges", "big_short", "second_scan_round"])
 def test_device_built_index_equals_host_built(case, search_kernel):
     """The device-side builder (scan + atomic paint) against the host builder, word for word."""
     needs_plane_blocks(search_kernel)
@@ -375,8 +375,12 @@ def test_device_built_index_equals_host_built(case, search_kernel):
                                                    ([2], [2047]), ([2], [2048]), ([1, 2, 1], [2049, 1, 4096])]]
         streams.append(np.zeros(0, dtype=np.uint8))
         streams.append(orc.convert_to_vec("GTN$$ACCC$G"))
+        streams += [make() for make in BORDER_STREAMS.values()]  # one run's digits on both sides of a tile's and of a thread's border
     elif case == "big_short":
         streams = [random_stream(12, 300000, "short")]          # many 4 KiB tiles: exercises the tile scan
+    elif case == "second_scan_round":
+        streams = [random_stream(13, 4_500_000, "ones")]        # the tile scan takes 1024 tiles a round and carries their sum on
+        assert streams[0].size > 1024 * 4096
     else:
         streams = [random_stream(31, 20000, case)]
     for rle in streams:
