@@ -353,6 +353,51 @@ int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_SPECTRU
  * 8 n_bins).  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on.  device_bytes may be NULL. */
 int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, int sorted, uint64_t *device_bytes);
 
+/* ---- canonical k-mers: the spectrum and the dump with a k-mer and its reverse complement as ONE k-mer (no reference counterpart) ----
+ * Reads come from both strands, so a census of k-mers counts q and rc(q) together (a k-mer counter's "canonical" mode).
+ * rc(q) is the reverse complement of a k-mer over A C G T (COMPLEMENT_INT, msbwt_reverse_complement_i); on the packed 2-bit form
+ * (A C G T -> 0 1 2 3, first symbol most significant) it reverses the order of the k 2-bit fields and XORs each with 3.  The CANONICAL
+ * k-mer of the class {q, rc(q)} is the one with the smaller packed word (lexicographic order and word order agree).  A class OCCURS
+ * when count_kmer(q) + count_kmer(rc(q)) > 0 and is reported as ONE record (w, own, other): w the canonical word, own = count_kmer(w),
+ * other = count_kmer(rc(w)) -- for a palindrome (w == rc(w), even k only) other = 0.  The class's COUNT is own + other, so a palindrome
+ * is counted once, not twice, and the counts of all classes sum to the `occurrences` of the plain spectrum.
+ *
+ * msbwt_kmers_reverse_complement_2bit: pure host function, no device: out[i] = packed reverse complement of words[i] (bits above 2 k
+ * are ignored); 1 <= k <= 32, else MSBWT_ERR_INVALID_ARG.  words == out is allowed.
+ *
+ * msbwt_rle_canonical_kmer_spectrum: as msbwt_rle_kmer_spectrum over the classes: out_hist[min(count, n_bins - 1)] += 1 per class, bin 0
+ * empty, *out_distinct = the classes, *out_occurrences = the sum of their counts.
+ * msbwt_rle_enumerate_canonical_kmers[_device]: the classes whose count own + other lies in the window (min_count == 0 is 1, max_count
+ * == 0: no upper limit, min_count > max_count != 0: MSBWT_ERR_INVALID_ARG), with the two-call capacity pattern of
+ * msbwt_rle_enumerate_kmers: capacity == 0 only counts; 0 < capacity < n writes NOTHING, sets *out_n = n, returns
+ * MSBWT_ERR_INVALID_ARG and names n in the message.  out_own and out_other may each be NULL.  A call that fills buffers walks twice.
+ * ORDER: the records come in the order the walk produces them, and there is no `sorted` argument -- a class whose canonical member is
+ * absent from the index has no row of its own, so the placement by rank that sorts the plain dump does not carry over, and the
+ * library has no general device sort.  Sort by word on the host where order matters (the Python mirror does, on request).
+ *
+ * How: the walk of the plain calls stages each chunk's k-mers (word, count) instead of sinking them; their reverse complements are
+ * written as packed words and counted by the search behind msbwt_rle_count_kmers_packed_device; one more pass emits every class from
+ * exactly one member -- the strand with the larger count, on a tie the canonical one.  With a window minimum m the walk prunes at
+ * ceil(m / 2), not m: of two strands whose counts sum to m or more the larger has ceil(m / 2) or more, and so has each of its suffixes,
+ * so the emitting member survives even where the other strand is pruned or absent ("Canonical spectrum").
+ * Guards before the first HIP call, scratch per call and freed on return (msbwt_rle_device_bytes unchanged; what the search keeps
+ * for its launches it keeps as for any count call), MSBWT_ERR_HIP naming the bytes when it does not fit, independence of every knob:
+ * as for the plain calls.  msbwt_rle_spectrum_info reports the walk as it does for them: [4 + k] is the number of k-mers the last
+ * level handed on (both strands, after pruning), not the number of classes. */
+int msbwt_kmers_reverse_complement_2bit(const uint64_t *words, size_t k, size_t n, uint64_t *out);
+int msbwt_rle_canonical_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins,
+                                      uint64_t *out_distinct, uint64_t *out_occurrences);
+int msbwt_rle_enumerate_canonical_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count,
+                                        uint64_t *out_kmers2bit, uint64_t *out_own, uint64_t *out_other, uint64_t capacity, uint64_t *out_n);
+int msbwt_rle_enumerate_canonical_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count,
+                                               void *d_out_kmers2bit, void *d_out_own, void *d_out_other, uint64_t capacity, uint64_t *out_n,
+                                               void *hip_stream);
+/* Pure function, no device: bytes of HBM a canonical call allocates and frees again with the automatic frontier: what
+ * msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, 0) gives for the walk -- whose last frontier IS the staging of (word, count) --
+ * plus 16 bytes per frontier node for the other strand (word, count), plus 24 bytes per record staged for a host dump (0 for the
+ * _device form, for counting and for the spectrum, which adds 8 n_bins).  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on. */
+int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

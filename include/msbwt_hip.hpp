@@ -292,6 +292,44 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_spectrum_plan");
         return bytes;
     }
+    // ---- canonical k-mers: a k-mer and its reverse complement as one class (include/msbwt_hip.h has the definitions) ----
+    /// What enumerate_canonical_kmers returns: class i has the canonical word words[i], which occurs own[i] times, and its reverse
+    /// complement other[i] times (0 for a palindrome); the class count is own[i] + other[i].  In the order the walk produces them.
+    struct CanonicalKmers {
+        std::vector<std::uint64_t> words, own, other;
+    };
+    /// The spectrum over the classes: hist[min(own + other, bins - 1)], the number of classes, the sum of their counts.
+    Spectrum canonical_kmer_spectrum(std::size_t k, std::size_t bins = 256) const {
+        Spectrum s;
+        s.hist.assign(bins, 0);
+        check(msbwt_rle_canonical_kmer_spectrum(raw_, k, s.hist.data(), bins, &s.distinct, &s.occurrences));
+        return s;
+    }
+    /// The classes with min_count <= own + other <= max_count (0: no upper limit): both calls of the two-call pattern.
+    CanonicalKmers enumerate_canonical_kmers(std::size_t k, std::uint64_t min_count = 1, std::uint64_t max_count = 0) const {
+        CanonicalKmers out;
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_canonical_kmers(raw_, k, min_count, max_count, nullptr, nullptr, nullptr, 0, &n));
+        out.words.resize(static_cast<std::size_t>(n));
+        out.own.resize(out.words.size());
+        out.other.resize(out.words.size());
+        if (n) check(msbwt_rle_enumerate_canonical_kmers(raw_, k, min_count, max_count, out.words.data(), out.own.data(), out.other.data(), n, &n));
+        return out;
+    }
+    /// Packed reverse complements of packed k-mers, 1 <= k <= 32 (pure host function).
+    static std::vector<std::uint64_t> reverse_complement_2bit(const std::vector<std::uint64_t> &words, std::size_t k) {
+        std::vector<std::uint64_t> out(words.size());
+        const int rc = msbwt_kmers_reverse_complement_2bit(words.data(), k, words.size(), out.data());
+        if (rc) throw Panic(rc, "msbwt_kmers_reverse_complement_2bit");
+        return out;
+    }
+    /// HBM bytes a canonical call allocates (and frees again) with the automatic frontier.
+    static std::uint64_t canonical_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t records = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_canonical_plan(total_rows, free_hbm_bytes, records, &bytes);
+        if (rc) throw Panic(rc, "msbwt_canonical_plan");
+        return bytes;
+    }
     /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
     static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
         std::uint64_t total = 0;

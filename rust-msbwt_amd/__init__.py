@@ -17,7 +17,7 @@ from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -127,6 +127,17 @@ def spectrum_plan(total_rows, free_hbm_bytes, records=0, sorted=False):
     rc = _lib.lib().msbwt_spectrum_plan(int(total_rows), int(free_hbm_bytes), int(records), 1 if sorted else 0, ctypes.byref(size))
     if rc:
         raise MsbwtError(rc, "msbwt_spectrum_plan")
+    return size.value
+
+
+def canonical_plan(total_rows, free_hbm_bytes, records=0):
+    """HBM bytes a RleBWT.canonical_kmer_spectrum / enumerate_canonical_kmers call allocates (and frees again): the frontiers of
+    spectrum_plan, 16 bytes per frontier node for the other strand, and `records` records staged for a host dump.  Pure host logic."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_canonical_plan(int(total_rows), int(free_hbm_bytes), int(records), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_canonical_plan")
     return size.value
 
 

@@ -77,6 +77,11 @@ SIGNATURES = {
     "msbwt_rle_set_spectrum_frontier": (_int, [_vp, _u64]),
     "msbwt_rle_spectrum_info": (_int, [_vp, _vp]),
     "msbwt_spectrum_plan": (_int, [_u64, _u64, _u64, _int, _pu64]),
+    "msbwt_kmers_reverse_complement_2bit": (_int, [_vp, _sz, _sz, _vp]),
+    "msbwt_rle_canonical_kmer_spectrum": (_int, [_vp, _sz, _vp, _sz, _pu64, _pu64]),
+    "msbwt_rle_enumerate_canonical_kmers": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _u64, _pu64]),
+    "msbwt_rle_enumerate_canonical_kmers_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _u64, _pu64, _vp]),
+    "msbwt_canonical_plan": (_int, [_u64, _u64, _u64, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

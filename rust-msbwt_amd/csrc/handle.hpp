@@ -1,6 +1,6 @@
 // What the units of the C API share (capi.cpp, index_build.cpp, query.cpp, sources.cpp, produce.cpp, multi_device.cpp; included by those only): the handle,
 // the parts of its index, its status block's layout and the plumbing of a call.  Shared names live in msbwt_capi, hidden from the library's
-// symbol table; a unit's own names stay in its anonymous namespace.  The helpers declared here are defined in capi.cpp, launch_count in query.cpp, attach_sources in sources.cpp.
+// symbol table; a unit's own names stay in its anonymous namespace.  The helpers declared here are defined in capi.cpp, launch_count and launch_count_2bit in query.cpp, attach_sources in sources.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -248,6 +248,7 @@ int flags_to_code(msbwt_rle *h, uint32_t flags);
 int status_of(msbwt_rle *h, hipStream_t stream, int which);
 int drain_timing_events(msbwt_rle *h, bool wait = true);
 int launch_count(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which);
+int launch_count_2bit(msbwt_rle *h, const uint64_t *d_packed, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which);  // query.cpp: 2-bit words, 1 <= k <= 64
 // sources.cpp: the source vector of n_rows rows (from the host through the pinned pipeline, or already in HBM) attached to the loaded index;
 // the caller holds h->mu and has made the handle's device current.  Whatever was attached before is gone either way.
 int attach_sources(msbwt_rle *h, const uint8_t *host_rows, const uint8_t *device_rows, uint64_t n_rows, size_t n_sources);

@@ -1,10 +1,13 @@
-// The k-mers of a loaded index: abundance spectrum and k-mer dump (msbwt_rle_kmer_spectrum, msbwt_rle_enumerate_kmers[_device]) and their
-// knobs.  Calls spectrum.hip through its header and handle.hpp.  All scratch is allocated per call and freed before the call returns.
+// The k-mers of a loaded index: abundance spectrum and k-mer dump (msbwt_rle_kmer_spectrum, msbwt_rle_enumerate_kmers[_device]), their
+// knobs, and the same two with a k-mer and its reverse complement merged into one class (msbwt_rle_canonical_kmer_spectrum,
+// msbwt_rle_enumerate_canonical_kmers[_device]: canonical.hpp; the other strand is counted by query.cpp's packed search).  Calls
+// spectrum.hip and canonical.hip through their headers and handle.hpp.  All scratch is allocated per call and freed before the call returns.
 #include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
 
+#include "canonical.hpp"
 #include "handle.hpp"
 #include "run_encode.hpp"
 #include "spectrum.hpp"
@@ -52,18 +55,26 @@ struct Scratch {
     Arena arena;
     void *work = nullptr, *rank = nullptr;
     uint64_t frontier = 0;
+    uint64_t *rc_words = nullptr, *rc_counts = nullptr;  // canonical calls: the other strand of a chunk's k-mers, `frontier` words each
+    unsigned long long *totals = nullptr;                // and the words of CanonicalSink::totals
 };
 
-// work (and, wanted, the rank scratch) in HBM, or MSBWT_ERR_HIP naming the bytes
-int take_scratch(msbwt_rle *h, Scratch &s, bool rank, uint64_t extra_bytes, const char *what) {
+// work (and, wanted, the rank scratch or the canonical calls' staging) in HBM, or MSBWT_ERR_HIP naming the bytes
+int take_scratch(msbwt_rle *h, Scratch &s, bool rank, uint64_t extra_bytes, const char *what, bool canonical = false) {
     size_t free_bytes = 0, all_bytes = 0;
     HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
     const uint64_t total = h->totals.total;
     s.frontier = spectrum_frontier_nodes(total, free_bytes, h->spectrum_frontier);
     const uint64_t work_bytes = spectrum_work_bytes(s.frontier), rank_bytes = rank ? spectrum_rank_bytes(total) : 0;
+    if (canonical) extra_bytes += s.frontier * kCanonicalStageBytes;
     const std::string need = std::string(what) + ": " + std::to_string(work_bytes + rank_bytes + extra_bytes) + " bytes of HBM needed while it runs";
     if (free_bytes < work_bytes + rank_bytes + extra_bytes) return fail(h, MSBWT_ERR_HIP, need);
     if (s.arena.take(&s.work, work_bytes) != hipSuccess || (rank && s.arena.take(&s.rank, rank_bytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, need);
+    }
+    if (canonical && (s.arena.take(&s.rc_words, s.frontier * 8) != hipSuccess || s.arena.take(&s.rc_counts, s.frontier * 8) != hipSuccess ||
+                      s.arena.take(&s.totals, kCanonicalTotalWords * 8) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(h, MSBWT_ERR_HIP, need);
     }
@@ -125,6 +136,96 @@ int enumerate(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_co
     HIP_TRY(h, hipMemcpyAsync(out_kmers, d_kmers, n * 8, hipMemcpyDeviceToHost, stream));
     if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, d_counts, n * 8, hipMemcpyDeviceToHost, stream));
     if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, d_l, n * 8, hipMemcpyDeviceToHost, stream));
+    return status_of(h, stream, which);  // synchronises
+}
+
+// ---- canonical k-mers ----
+
+// One walk of a canonical call: chunk by chunk the k-mers at least `prune` wide are staged, their reverse complements written as packed
+// words and counted by the packed search, and the classes they emit go to `sink` (its totals: s.totals, copied to totals[] at the end).
+// Synchronises the stream.
+int canonical_walk(msbwt_rle *h, const Scratch &s, size_t k, uint64_t prune, CanonicalSink sink, SpectrumInfo *info, hipStream_t stream, int which, uint64_t *totals) {
+    sink.totals = s.totals;
+    HIP_TRY(h, hipMemsetAsync(s.totals, 0, kCanonicalTotalWords * 8, stream));
+    int search_rc = MSBWT_OK;
+    const SpectrumChunkHook per_chunk = [&](const void *d_kmers, uint64_t m) {
+        const hipError_t e = launch_canonical_rc(d_kmers, m, uint32_t(k), s.rc_words, stream);
+        if (e != hipSuccess) return e;
+        if ((search_rc = launch_count_2bit(h, s.rc_words, k, size_t(m), s.rc_counts, stream, which)) != MSBWT_OK) return hipErrorUnknown;
+        return launch_canonical_combine(d_kmers, s.rc_words, s.rc_counts, m, sink, stream);
+    };
+    const hipError_t walked = spectrum_stage(view_of(h), seeds_of(h, k), uint32_t(k), prune, s.work, s.frontier, per_chunk, info, stream);
+    if (search_rc) return search_rc;
+    HIP_TRY(h, walked);
+    HIP_TRY(h, hipMemcpyAsync(totals, s.totals, kCanonicalTotalWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    return MSBWT_OK;
+}
+
+// Both forms of the canonical dump, as enumerate() above: records (canonical word, own, other), in the order the walk produces them.
+int enumerate_canonical(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_count, bool host, void *out_kmers, void *out_own, void *out_other,
+                        uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
+    Call c(ch);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_canonical_kmers needs 1 <= k <= 32");
+    if (max_count != 0 && min_count > max_count) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_canonical_kmers: min_count > max_count");
+    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    if (host) stream = h->stream;
+    const Clock clock;
+    *out_n = 0;
+    SpectrumInfo info;
+    info.k = k;
+    if (h->totals.total == 0) {
+        record(h, info, clock);
+        return MSBWT_OK;
+    }
+    Scratch s;
+    if (int rc = take_scratch(h, s, false, 0, "enumerate_canonical_kmers", true)) return rc;
+    CanonicalSink sink{};
+    sink.mode = kCanonicalCount;
+    sink.min = std::max<uint64_t>(min_count, 1);
+    sink.max = max_count ? max_count : ~0ull;
+    // of two strands whose counts sum to sink.min or more, the one that emits the class -- the larger -- has at least half of it
+    const uint64_t prune = sink.min / 2 + sink.min % 2;
+    uint64_t totals[kCanonicalTotalWords] = {};
+    if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
+    const uint64_t n = totals[kCanonicalClasses];
+    *out_n = n;
+    record(h, info, clock);
+    if (capacity == 0 || n == 0) return host ? status_of(h, stream, which) : int(MSBWT_OK);
+    if (capacity < n)
+        return fail(h, MSBWT_ERR_INVALID_ARG,
+                    "enumerate_canonical_kmers: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " classes that qualify");
+    sink.mode = kCanonicalAppend;
+    sink.kmers = static_cast<uint64_t *>(out_kmers);
+    sink.own = static_cast<uint64_t *>(out_own);
+    sink.other = static_cast<uint64_t *>(out_other);
+    sink.capacity = capacity;
+    sink.flags = h->d_flags + which;
+    if (host) {  // records staged in HBM, then copied out
+        const uint64_t columns = 1 + (out_own ? 1 : 0) + (out_other ? 1 : 0);
+        uint64_t *stage = nullptr;
+        size_t free_bytes = 0, all_bytes = 0;
+        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+        if (free_bytes < n * columns * 8 || s.arena.take(&stage, n * columns * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "enumerate_canonical_kmers: " + std::to_string(n * columns * 8) + " more bytes of HBM needed for the records");
+        }
+        sink.kmers = stage;
+        sink.own = out_own ? stage + n : nullptr;
+        sink.other = out_other ? stage + n * (out_own ? 2 : 1) : nullptr;
+        sink.capacity = n;
+    }
+    if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
+    record(h, info, clock);
+    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
+    HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_own) HIP_TRY(h, hipMemcpyAsync(out_own, sink.own, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_other) HIP_TRY(h, hipMemcpyAsync(out_other, sink.other, n * 8, hipMemcpyDeviceToHost, stream));
     return status_of(h, stream, which);  // synchronises
 }
 
@@ -196,6 +297,71 @@ int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t r
     uint64_t bytes = 0;
     if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, sorted != 0, &bytes)) return rc;
     if (device_bytes) *device_bytes = bytes;
+    return MSBWT_OK;
+}
+
+// ---- canonical k-mers: a k-mer and its reverse complement as one class ----
+
+int msbwt_kmers_reverse_complement_2bit(const uint64_t *words, size_t k, size_t n, uint64_t *out) {
+    if (k < 1 || k > kSpectrumMaxK || (n && (!words || !out))) return MSBWT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; ++i) out[i] = reverse_complement_2bit(words[i], uint32_t(k));
+    return MSBWT_OK;
+}
+
+int msbwt_rle_canonical_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_distinct, uint64_t *out_occurrences) {
+    Call c(bwt);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "canonical_kmer_spectrum needs 1 <= k <= 32");
+    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "canonical_kmer_spectrum needs a histogram of at least 2 bins");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    const Clock clock;
+    SpectrumInfo info;
+    info.k = k;
+    uint64_t totals[kCanonicalTotalWords] = {};
+    std::fill(out_hist, out_hist + n_bins, 0ull);
+    if (h->totals.total != 0) {
+        Scratch s;
+        if (int rc = take_scratch(h, s, false, uint64_t(n_bins) * 8, "canonical_kmer_spectrum", true)) return rc;
+        uint64_t *d_hist = nullptr;
+        if (s.arena.take(&d_hist, uint64_t(n_bins) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "canonical_kmer_spectrum: " + std::to_string(uint64_t(n_bins) * 8) + " bytes of HBM needed for the histogram");
+        }
+        HIP_TRY(h, hipMemsetAsync(d_hist, 0, uint64_t(n_bins) * 8, h->stream));
+        CanonicalSink sink{};
+        sink.mode = kCanonicalHist;
+        sink.min = 1;
+        sink.max = ~0ull;
+        sink.hist = reinterpret_cast<unsigned long long *>(d_hist);
+        sink.n_bins = n_bins;
+        if (int rc = canonical_walk(h, s, k, 1, sink, &info, h->stream, kHostFlags, totals)) return rc;
+        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = status_of(h, h->stream, kHostFlags)) return rc;  // synchronises; the search's flags
+    }
+    if (out_distinct) *out_distinct = totals[kCanonicalClasses];
+    if (out_occurrences) *out_occurrences = totals[kCanonicalOccurrences];
+    record(h, info, clock);
+    return MSBWT_OK;
+}
+
+int msbwt_rle_enumerate_canonical_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, uint64_t *out_kmers2bit, uint64_t *out_own,
+                                        uint64_t *out_other, uint64_t capacity, uint64_t *out_n) {
+    return enumerate_canonical(bwt, k, min_count, max_count, true, out_kmers2bit, out_own, out_other, capacity, out_n, nullptr, kHostFlags);
+}
+
+int msbwt_rle_enumerate_canonical_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, void *d_out_kmers2bit, void *d_out_own,
+                                               void *d_out_other, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
+    return enumerate_canonical(bwt, k, min_count, max_count, false, d_out_kmers2bit, d_out_own, d_out_other, capacity, out_n, static_cast<hipStream_t>(hip_stream),
+                               kDeviceFlags);
+}
+
+int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
+    uint64_t bytes = 0;
+    if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, false, &bytes)) return rc;
+    if (device_bytes) *device_bytes = bytes + spectrum_frontier_nodes(total_rows, free_hbm_bytes, 0) * kCanonicalStageBytes;
     return MSBWT_OK;
 }
 

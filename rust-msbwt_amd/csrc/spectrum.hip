@@ -11,6 +11,9 @@
 //     append      the records, wherever the workgroup's reservation puts them
 //     scatter     the records, each at rank(l) of the bitmap: ranges of distinct k-mers are disjoint and in lexicographic order, so
 //                 the number of marked rows below l IS the record's place in ascending k-mer order -- no sort
+//     stage       (the canonical calls, canonical.hip) the last level IS materialised, by the step that fills every other frontier, and
+//                 the chunk's k-mers {word, l, h} are handed to the caller's hook before the next chunk overwrites them; a last
+//                 frontier that overflows is a frontier that overflows
 // A count window [m, ..] prunes: a k-mer never occurs more often than any of its suffixes, so a node narrower than m is dropped at
 // every level (the spectrum itself does not prune).
 // The seeds are worked through in chunks that keep the frontiers inside a fixed scratch allocation, as in the builder: a chunk that
@@ -46,7 +49,7 @@ static_assert(kSpectrumMinFrontier >= kStackNodes, "a single node's children alw
 
 constexpr uint32_t kLdsBins = 2048;  // counts below this are tallied in LDS (8 KB): almost all of a read set's mass
 constexpr int kStepPair = 0, kStepPlane = 1, kStepRuns = 2;
-constexpr int kSinkHist = 0, kSinkCount = 1, kSinkAppend = 2, kSinkScatter = 3;
+constexpr int kSinkHist = 0, kSinkCount = 1, kSinkAppend = 2, kSinkScatter = 3, kSinkStage = 4;  // (kSinkStage: the host's alone, no kernel sees it)
 constexpr uint32_t kRankWords = uint32_t(kSpectrumRankRows / 32);
 
 struct Env {  // the index, and what the levels before the last keep
@@ -273,8 +276,8 @@ RankView rank_view(const void *d_rank, uint64_t total) {
 class Walker {
   public:
     Walker(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t prune, const Sink &sink, void *d_work, uint64_t frontier_nodes, SpectrumInfo *info,
-           hipStream_t stream)
-        : ix_(ix), seeds_(seeds), k_(k), sink_(sink), w_(carve(d_work, frontier_nodes)), info_(info), stream_(stream), cur_(kCursorWords, 0ull) {
+           hipStream_t stream, const SpectrumChunkHook *hook = nullptr)
+        : ix_(ix), seeds_(seeds), k_(k), sink_(sink), w_(carve(d_work, frontier_nodes)), info_(info), stream_(stream), hook_(hook), cur_(kCursorWords, 0ull) {
         env_ = Env{static_cast<const uint4 *>(ix.blocks), static_cast<const uint4 *>(ix.overflow), static_cast<const uint4 *>(ix.pair_blocks), ix.pair_super,
                    ix.pair_stride96 ? 1u : 0u, std::max<uint64_t>(prune, 1)};
         if (seeds_.flat == nullptr || seeds_.flat_depth <= 0 || uint32_t(seeds_.flat_depth) >= k) seeds_ = SpectrumSeeds{};
@@ -332,11 +335,12 @@ class Walker {
         Node *in = w_.a, *out = w_.b;
         while (depth < k_) {
             const int step = step_at(depth);
-            if (depth + advance(step) >= k_) expand<true>(step, in, w_.cap, depth, out, w_.cap);
+            if (depth + advance(step) >= k_ && !staging()) expand<true>(step, in, w_.cap, depth, out, w_.cap);
             else expand<false>(step, in, w_.cap, depth, out, w_.cap);
             depth += advance(step);
             std::swap(in, out);
         }
+        staged_ = in;  // (the frontier written last)
         return read_cursors();
     }
 
@@ -355,8 +359,8 @@ class Walker {
                     np = std::max<uint64_t>(1, c / 2);
                     continue;
                 }
-                // one seed's subtree does not fit: one step into the stack (never the last step: that one materialises nothing and
-                // cannot overflow), and its children are the seeds of a walk one level down
+                // one seed's subtree does not fit: one step into the stack (never the last step: that one materialises nothing, or when
+                // staging at most 16 nodes, and cannot overflow), and its children are the seeds of a walk one level down
                 const int step = step_at(depth);
                 if (depth + advance(step) >= k_ || level + 1 > kSpectrumMaxK) return hipErrorOutOfMemory;
                 Node *kids = w_.stack + uint64_t(level + 1) * kStackNodes;
@@ -377,8 +381,9 @@ class Walker {
             unsigned long long widest = 1;
             for (uint32_t d = depth; d <= k_; ++d) {
                 info_->nodes[d] += cur_[kCur + d];
-                if (d < k_) widest = std::max(widest, cur_[kCur + d]);  // (the last level is not materialised)
+                if (d < k_ || staging()) widest = std::max(widest, cur_[kCur + d]);  // (the last level is not materialised unless staged)
             }
+            if (staging() && cur_[kCur + k_] != 0 && (e = (*hook_)(staged_, cur_[kCur + k_])) != hipSuccess) return e;
             if ((e = reset_chunk()) != hipSuccess) return e;
             i0 += c;
             const double per_seed = double(widest) / double(c);
@@ -386,6 +391,8 @@ class Walker {
         }
         return hipSuccess;
     }
+
+    bool staging() const { return sink_.mode == kSinkStage; }
 
     const IndexView &ix_;
     SpectrumSeeds seeds_;
@@ -395,6 +402,8 @@ class Walker {
     Work w_;
     SpectrumInfo *info_;
     hipStream_t stream_;
+    const SpectrumChunkHook *hook_;  // kSinkStage: what takes a chunk's k-mers
+    const Node *staged_ = nullptr;
     std::vector<unsigned long long> cur_;
 };
 
@@ -476,6 +485,15 @@ hipError_t spectrum_dump(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, u
     sink.capacity = capacity;
     sink.flags = flags;
     Walker walker(ix, seeds, k, sink.min, sink, d_work, frontier_nodes, info, stream);
+    return walker.run();
+}
+
+hipError_t spectrum_stage(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t prune, void *d_work, uint64_t frontier_nodes, const SpectrumChunkHook &per_chunk,
+                          SpectrumInfo *info, hipStream_t stream) {
+    if (!d_work || !per_chunk) return hipErrorInvalidValue;
+    Sink sink{};
+    sink.mode = kSinkStage;
+    Walker walker(ix, seeds, k, prune, sink, d_work, frontier_nodes, info, stream, &per_chunk);
     return walker.run();
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <functional>
 
 #include "kernels.hpp"
 
@@ -50,5 +51,13 @@ hipError_t spectrum_count(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, 
 hipError_t spectrum_dump(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t min_count, uint64_t max_count, void *d_work, uint64_t frontier_nodes,
                          const void *d_rank, uint64_t *d_kmers, uint64_t *d_counts, uint64_t *d_l, uint64_t capacity, uint32_t *flags, SpectrumInfo *info,
                          hipStream_t stream);
+
+// The walk with the last level STAGED instead of sunk (the canonical calls, canonical.hpp): chunk by chunk, after the synchronisation
+// that reads the chunk's cursors, per_chunk(d_kmers, m) gets the m >= 1 k-mers of the chunk that are at least `prune` wide as 24-byte
+// records {word, l, h} in a frontier buffer, which the next chunk overwrites: what the hook enqueues on `stream` reads them in time,
+// what it returns other than hipSuccess ends the walk.  At most frontier_nodes records a chunk; more is a frontier overflow.
+using SpectrumChunkHook = std::function<hipError_t(const void *d_kmers, uint64_t m)>;
+hipError_t spectrum_stage(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, uint64_t prune, void *d_work, uint64_t frontier_nodes, const SpectrumChunkHook &per_chunk,
+                          SpectrumInfo *info, hipStream_t stream);
 
 }  // namespace msbwt

@@ -374,6 +374,53 @@ class RleBWT(BWT):
                 raise
         return n.value
 
+    # ---- the same with a k-mer and its reverse complement as one class ----
+    def canonical_kmer_spectrum(self, k, bins=256):
+        """msbwt_rle_canonical_kmer_spectrum -> (hist, distinct, occurrences) over the classes {q, rc(q)}: hist[c] = classes whose two
+        strands occur c times together (a palindrome counted once), their number, the sum of their counts."""
+        hist = np.zeros(int(bins), dtype=np.uint64)
+        distinct, occurrences = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_canonical_kmer_spectrum(self._h, int(k), hist.ctypes.data_as(C.c_void_p) if hist.size else None, hist.size,
+                                                          C.byref(distinct), C.byref(occurrences))
+        if rc:
+            _raise(rc, self._h)
+        return hist, distinct.value, occurrences.value
+
+    def enumerate_canonical_kmers(self, k, min_count=1, max_count=None, sorted=False, strands=False):
+        """msbwt_rle_enumerate_canonical_kmers, both calls of the two-call pattern -> (words, counts), or with strands=True (words, own,
+        other), as uint64[n]: the classes whose count own + other lies in min_count..max_count (None: no upper limit); words = the
+        canonical (smaller) 2-bit word of each, own = its count, other = its reverse complement's (0 for a palindrome).  The library
+        returns them in the order its walk produces; sorted=True orders them by word here, on the host."""
+        lib, n = _lib.lib(), C.c_uint64(0)
+        args = (self._h, int(k), int(min_count), int(max_count or 0))
+        rc = lib.msbwt_rle_enumerate_canonical_kmers(*args, None, None, None, 0, C.byref(n))
+        if rc:
+            _raise(rc, self._h)
+        words, own, other = (np.empty(n.value, dtype=np.uint64) for _ in range(3))
+        if n.value:
+            rc = lib.msbwt_rle_enumerate_canonical_kmers(*args, words.ctypes.data_as(C.c_void_p), own.ctypes.data_as(C.c_void_p),
+                                                         other.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+            if rc:
+                _raise(rc, self._h)
+        if sorted:
+            order = np.argsort(words, kind="stable")
+            words, own, other = words[order], own[order], other[order]
+        return (words, own, other) if strands else (words, own + other)
+
+    def enumerate_canonical_kmers_device(self, k, d_words, d_own, d_other, capacity, min_count=1, max_count=None, stream=0):
+        """msbwt_rle_enumerate_canonical_kmers_device: device pointers (ints; d_own, d_other may be None) of `capacity` u64 each -> n, the
+        classes that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
+        n = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_enumerate_canonical_kmers_device(self._h, int(k), int(min_count), int(max_count or 0), d_words, d_own, d_other, int(capacity),
+                                                                   C.byref(n), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n = n.value
+                raise
+        return n.value
+
     def set_spectrum_frontier(self, nodes):
         """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""
         rc = _lib.lib().msbwt_rle_set_spectrum_frontier(self._h, int(nodes))
@@ -910,6 +957,16 @@ def unpack_2bit(words, k):
     w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
     shifts = (2 * np.arange(k - 1, -1, -1)).astype(np.uint64)
     return np.array([1, 2, 3, 5], dtype=np.uint8)[((w[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.intp)]
+
+
+def reverse_complement_2bit(words, k):
+    """uint64 2-bit words of k-mers, 1 <= k <= 32 -> the words of their reverse complements, same shape (msbwt_kmers_reverse_complement_2bit)."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    out = np.empty_like(w)
+    rc = _lib.lib().msbwt_kmers_reverse_complement_2bit(w.ctypes.data_as(C.c_void_p), int(k), w.size, out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("reverse_complement_2bit takes one word per k-mer: 1 <= k <= 32")
+    return out
 
 
 def count_read_kmers_multi(replicas, reads, k, ascii=False, forward=True, revcomp=False):

@@ -79,6 +79,13 @@ extern "C" {
                                  out_kmers2bit: *mut u64, out_counts: *mut u64, out_l: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
     fn msbwt_rle_set_spectrum_frontier(bwt: *mut MsbwtRle, nodes: u64) -> c_int;
     fn msbwt_spectrum_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, sorted: c_int, device_bytes: *mut u64) -> c_int;
+    // canonical k-mers: a k-mer and its reverse complement as one class (word, own, other)
+    fn msbwt_kmers_reverse_complement_2bit(words: *const u64, k: usize, n: usize, out: *mut u64) -> c_int;
+    fn msbwt_rle_canonical_kmer_spectrum(bwt: *const MsbwtRle, k: usize, out_hist: *mut u64, n_bins: usize,
+                                         out_distinct: *mut u64, out_occurrences: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_canonical_kmers(bwt: *const MsbwtRle, k: usize, min_count: u64, max_count: u64,
+                                           out_kmers2bit: *mut u64, out_own: *mut u64, out_other: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
+    fn msbwt_canonical_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -370,6 +377,53 @@ impl GpuRleBWT {
             if rc != MSBWT_OK { panic!("enumerate_kmers: {}", self.last_error()); }
         }
         (words, counts, l)
+    }
+
+    /// The spectrum with a k-mer and its reverse complement as one class: (hist, classes, occurrences); hist[c] = classes whose two
+    /// strands occur c times together (a palindrome counted once), the last bin that often or more.
+    pub fn canonical_kmer_spectrum(&self, k: usize, bins: usize) -> (Vec<u64>, u64, u64) {
+        let mut hist = vec![0u64; bins.max(2)];
+        let (mut distinct, mut occurrences) = (0u64, 0u64);
+        let rc = unsafe { msbwt_rle_canonical_kmer_spectrum(self.raw, k, hist.as_mut_ptr(), hist.len(), &mut distinct, &mut occurrences) };
+        if rc != MSBWT_OK { panic!("canonical_kmer_spectrum: {}", self.last_error()); }
+        (hist, distinct, occurrences)
+    }
+
+    /// The classes with min_count <= own + other <= max_count (0: no upper limit) as (canonical 2-bit words, own, other): own the
+    /// count of the word, other that of its reverse complement (0 for a palindrome).  In the order the walk produces; sort by word
+    /// where order matters.
+    pub fn enumerate_canonical_kmers(&self, k: usize, min_count: u64, max_count: u64) -> (Vec<u64>, Vec<u64>, Vec<u64>) {
+        let mut n = 0u64;
+        let rc = unsafe {
+            msbwt_rle_enumerate_canonical_kmers(self.raw, k, min_count, max_count, std::ptr::null_mut(), std::ptr::null_mut(),
+                                                std::ptr::null_mut(), 0, &mut n)
+        };
+        if rc != MSBWT_OK { panic!("enumerate_canonical_kmers: {}", self.last_error()); }
+        let (mut words, mut own, mut other) = (vec![0u64; n as usize], vec![0u64; n as usize], vec![0u64; n as usize]);
+        if n > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_canonical_kmers(self.raw, k, min_count, max_count, words.as_mut_ptr(), own.as_mut_ptr(),
+                                                    other.as_mut_ptr(), n, &mut n)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_canonical_kmers: {}", self.last_error()); }
+        }
+        (words, own, other)
+    }
+
+    /// Packed reverse complements of packed k-mers, 1 <= k <= 32 (pure function).
+    pub fn reverse_complement_2bit(words: &[u64], k: usize) -> Vec<u64> {
+        let mut out = vec![0u64; words.len()];
+        let rc = unsafe { msbwt_kmers_reverse_complement_2bit(words.as_ptr(), k, words.len(), out.as_mut_ptr()) };
+        assert_eq!(rc, MSBWT_OK, "reverse_complement_2bit: k = {}", k);
+        out
+    }
+
+    /// HBM bytes a canonical call allocates and frees again (pure function).
+    pub fn canonical_plan(total_rows: u64, free_hbm_bytes: u64, records: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_canonical_plan(total_rows, free_hbm_bytes, records, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "canonical_plan: {} rows", total_rows);
+        bytes
     }
 
     /// Most nodes per frontier buffer of the k-mer walks (0 = automatic); results never depend on it.
