@@ -549,6 +549,9 @@ int msbwt_rle_get_table_packed(const msbwt_rle *bwt);
  * the deep direct table of an index without a sparse table (packed depth 17) does not fit beside it but a table of the 17-symbol suffixes
  * does, that one is built as well and serves 17 <= k < 23 (MSBWT_SPARSE_SECOND=0: never), so that no k loses to the index without a
  * sparse table.
+ * [113] / [114] / [115] chunks, retries and descents of the sizing pass's frontier walk, [116] / [117] / [118] of the last fill pass's
+ * (as msbwt_rle_spectrum_info reports them for a spectrum walk; MSBWT_SPARSE_FRONTIER=<nodes> in the environment caps the builder's
+ * frontier buffers, 64 nodes at least: tests).
  * The counts are kept even when no table was built.
  * TWO-TIER form (msbwt_rle_set_sparse_tiers; rust-msbwt_amd/csrc/sparse_table.hpp): the complete table's size follows the distinct
  * suffixes, and on reads WITH errors most of those occur once (a 30x human read set with 0.5 % substitutions: 1.3e10 distinct 23-mers,

@@ -20,7 +20,7 @@ namespace msbwt {
 namespace {
 
 constexpr int kThreads = kFrontierThreads;
-constexpr uint32_t kLdsBins = 2048;  // class counts below this are tallied in LDS (8 KB), as in k_spectrum_expand
+constexpr uint32_t kLdsBins = 2048;  // class counts below this are tallied in LDS (8 KB), as in the spectrum's histogram sink
 
 uint32_t grid_for(uint64_t m) { return capped_grid(m, kThreads, 256u * 8u); }
 

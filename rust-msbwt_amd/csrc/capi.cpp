@@ -25,8 +25,8 @@ static_assert(MSBWT_SEARCH_COUNTERS == kSearchCounters, "the header's counter bl
 static_assert(MSBWT_BUILD_STAGES == kReadsBuildStages, "the header's stage count is the builder's");
 static_assert(MSBWT_MERGE_STAGES == kMergeStages, "the header's stage count is the merge's");
 static_assert(MSBWT_MERGE_MAX_INPUTS == kMergeMaxInputs, "the header's input count is the merge's");
-static_assert(10 + kSparseMaxDepth + 1 <= 42 && 45 + kSparseMaxDepth + 1 <= 80 && 80 + kSparseMaxDepth + 1 <= MSBWT_SPARSE_INFO_WORDS,
-              "msbwt_rle_sparse_table_info: [10 + d] distinct, [42] filtered, [45 + d] wide, [80 + d] once");
+static_assert(10 + kSparseMaxDepth + 1 <= 42 && 45 + kSparseMaxDepth + 1 <= 80 && 80 + kSparseMaxDepth + 1 <= 112 && 119 <= MSBWT_SPARSE_INFO_WORDS,
+              "msbwt_rle_sparse_table_info: [10 + d] distinct, [42] filtered, [45 + d] wide, [80 + d] once, [112] second tier, [113 .. 119) the walks");
 
 const char *kVersion = "rust-msbwt_amd 0.1.0 (gfx950 plane-block index)";
 
@@ -395,6 +395,10 @@ int msbwt_rle_sparse_table_info(const msbwt_rle *ch, uint64_t *out) {
         out[10 + d] = r.distinct[d];
         out[45 + d] = r.escapes[d];
         out[80 + d] = r.singles[d];
+    }
+    for (int j = 0; j < 3; ++j) {
+        out[113 + j] = r.sizing_walk[j];
+        out[116 + j] = r.fill_walk[j];
     }
     return MSBWT_OK;
 }

@@ -1,6 +1,7 @@
-// Frontier expansion over the suffixes that OCCUR, shared by the builder of the sparse suffix table (sparse_table.hip) and the
-// k-mer spectrum / enumeration (spectrum.hip): the node, the workgroup's slot reservation and sums, the seeds, and what one pair-block
-// line (16 children, two symbols deeper) or one plane-block line (4 children, one symbol deeper) says about a node's bounds.
+// Frontier expansion over the suffixes that OCCUR -- the leaves: the node, the workgroup's slot reservation and sums, the seeds, and
+// what one pair-block line (16 children, two symbols deeper) or one plane-block line (4 children, one symbol deeper) says about a
+// node's bounds.  frontier_walk.hpp is the walk made of them (its kernels, chunks, retries and descents), which the builder of the
+// sparse suffix table (sparse_table.hip) and the k-mer spectrum / enumeration (spectrum.hip) run with their own sinks.
 // Include from HIP translation units only (the names are per translation unit, as in rank_ops.hpp).
 #pragma once
 #include <hip/hip_runtime.h>

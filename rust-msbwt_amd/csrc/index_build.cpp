@@ -182,7 +182,7 @@ hipError_t fill_sparse_level(msbwt_rle *h, const SparseWork &w, const SparseChoi
 // With k undeclared the first table is 23 deep and k = 17..22 fall to the direct table, which stays at packed depth 15 beside a sparse
 // table: measured at human scale (round 6, present k-mers), k = 17 / 19 / 21 run 2.5 / 1.8 / 1.5 x slower than on the index WITHOUT a
 // sparse table (packed depth 17).  Where the deep direct table itself fits (build_tables keeps it then) nothing is needed; otherwise the
-// same sizing counts and chunk plan fill a table of the suffixes of 17 symbols -- when it fits what is left, an eighth of the device still
+// same sizing counts fill a table of the suffixes of 17 symbols -- when it fits what is left, an eighth of the device still
 // free.  A declared k gets none (the caller has said what it will ask), an explicit depth neither.
 // (run blocks are the memory-lean format: no second level there)
 // Optional: an entry without a slot, no memory -- the index simply has no second level.  Sized and filled while the first level's work
@@ -234,9 +234,9 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
                                                   std::to_string(direct_depth) + " deep)");
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return MSBWT_OK;
-    // (never more scratch than the index can fill: the nodes of a level are disjoint non-empty ranges, at most `total` of them -- a toy
-    // index must not pay for a 6 GB allocation per build)
-    const size_t work_bytes = std::min<size_t>(sparse_work_bytes(free_b), 4096 + 2 * 24 * size_t(std::max<uint64_t>(h->totals.total + 1024, 4096)));
+    // MSBWT_SPARSE_FRONTIER=<nodes>: (tests) caps the builder's frontier buffers, so that a toy index meets the walker's chunks, retries and descents
+    const char *frontier = std::getenv("MSBWT_SPARSE_FRONTIER");
+    const size_t work_bytes = sparse_work_bytes(h->totals.total, free_b, frontier ? std::strtoull(frontier, nullptr, 10) : 0);
     auto optional = [&](hipError_t e, const char *what) -> int {  // an optional structure gives way; an explicit wish does not
         (void)hipGetLastError();
         if (explicit_depth) return hip_fail(h, e, what);
@@ -268,9 +268,12 @@ int build_sparse(msbwt_rle *h, uint64_t keep_free, uint64_t allowance, int direc
     if (e != hipSuccess) return optional(e, what);
     h->sparse_report = rep;
     if (verbose())
-        std::fprintf(stderr, "[msbwt] sparse table: depth %d%s, %llu entries in %u buckets (%.2f per bucket, %llu displaced, %llu in the side array, %llu in the filters), %.2f GB\n",
+        std::fprintf(stderr, "[msbwt] sparse table: depth %d%s, %llu entries in %u buckets (%.2f per bucket, %llu displaced, %llu in the side array, %llu in the filters), %.2f GB; "
+                             "chunks / retries / descents: sizing %llu / %llu / %llu, fill %llu / %llu / %llu\n",
                      choice.depth, choice.tier ? " two-tier" : "", (unsigned long long)rep.entries, h->sparse.nbuckets, double(rep.entries) / double(h->sparse.nbuckets),
-                     (unsigned long long)rep.displaced, (unsigned long long)rep.nescapes, (unsigned long long)rep.filtered, double(h->sparse.bytes + h->sparse.side_bytes) / 1e9);
+                     (unsigned long long)rep.displaced, (unsigned long long)rep.nescapes, (unsigned long long)rep.filtered, double(h->sparse.bytes + h->sparse.side_bytes) / 1e9,
+                     (unsigned long long)rep.sizing_walk[0], (unsigned long long)rep.sizing_walk[1], (unsigned long long)rep.sizing_walk[2],
+                     (unsigned long long)rep.fill_walk[0], (unsigned long long)rep.fill_walk[1], (unsigned long long)rep.fill_walk[2]);
     build_second_sparse_level(h, w, rep, tiers, direct_depth, deep_direct_depth, keep_free, allowance);
     return MSBWT_OK;
 }

@@ -1,5 +1,5 @@
-// Builder of the sparse suffix table (sparse_table.hpp; sparse_table.hip): frontier expansion on the device with the
-// index's own rank code -- each present d-mer -> its <= 16 present (d+2)-mers by one pair step -- so the table is
+// Builder of the sparse suffix table (sparse_table.hpp; sparse_table.hip): the frontier walk (frontier_walk.hpp) on the device with
+// the index's own rank code -- each present d-mer -> its <= 16 present (d+2)-mers by one pair step -- so the table is
 // bit-exact by construction.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -21,13 +21,17 @@ struct SparseBuildReport {
     uint64_t filtered = 0;                        // two-tier form: suffixes that went into the filters instead of taking an entry
     bool tier = false;
     int depth = 0, parent_depth = 0;
+    uint64_t sizing_walk[3] = {}, fill_walk[3] = {};  // chunks, retries, descents of the sizing pass and of the last fill pass
 };
 
-// Scratch both passes work in (two frontier buffers + cursors), sized once.
-size_t sparse_work_bytes(uint64_t free_bytes);
+// Scratch both passes work in (cursors, the re-seeding stack, two frontier buffers), sized once: frontiers of `wanted_nodes` nodes
+// (at least the walker's 64), or, 0, automatic -- 2^27 nodes when HBM is plentiful, what an eighth of the free bytes holds otherwise,
+// 2^16 at least, and never more than an index of `total` symbols can fill.
+size_t sparse_work_bytes(uint64_t total, uint64_t free_bytes, uint64_t wanted_nodes);
 
 // Sizing pass: expands the non-empty entries of the flat table of `flat_depth` levels (flat_entries == nullptr: from
 // [0, total), depth 0) level by level up to max_depth and reports the distinct counts on the way.  Synchronises the stream.
+// Both passes chunk, retry and descend on their own as the scratch demands (report->sizing_walk, report->fill_walk).
 hipError_t sparse_count_levels(const IndexView &ix, const void *flat_entries, int flat_depth, int max_depth, void *d_work, size_t work_bytes,
                                SparseBuildReport *report, hipStream_t stream);
 // Fill pass at `depth` (any depth the sizing pass reached or passed): `lines` (nbuckets x 128 bytes, zeroed here) and `side`

@@ -114,10 +114,8 @@ def slots_in_use(lines, info):
     return int(((lines[:, :14] >> 24) != 0).sum())
 
 
-@pytest.mark.parametrize("depth", [16, 17, 20, 25, 27, 28, 30, 31])
-def test_every_entry_of_the_table_is_the_oracles_range(depth, monkeypatch):
-    reads = read_set(11, 3000, 700, 60, repeats=4, err=0.01)
-    b, ref = load_pair(bwt_of(reads), monkeypatch, depth)
+def check_every_entry_is_the_oracles_range(b, ref, reads, depth):
+    """A complete table of `depth`: every present suffix looks up to the oracle's range, absent ones miss, nothing else is in it."""
     assert b.get_sparse_table() == depth and b.get_pair_index()
     info = b.sparse_table_info()
     lines, side = b.download_sparse_table()
@@ -139,6 +137,13 @@ def test_every_entry_of_the_table_is_the_oracles_range(depth, monkeypatch):
     for d, n in info["distinct"].items():
         if 4 <= d <= depth:
             assert n == len(np.unique(np.lib.stride_tricks.sliding_window_view(reads, d, axis=1).reshape(-1, d), axis=0)), d
+
+
+@pytest.mark.parametrize("depth", [16, 17, 20, 25, 27, 28, 30, 31])
+def test_every_entry_of_the_table_is_the_oracles_range(depth, monkeypatch):
+    reads = read_set(11, 3000, 700, 60, repeats=4, err=0.01)
+    b, ref = load_pair(bwt_of(reads), monkeypatch, depth)
+    check_every_entry_is_the_oracles_range(b, ref, reads, depth)
 
 
 def test_the_automatic_depth_follows_the_declared_query_length(monkeypatch):
@@ -356,13 +361,10 @@ def tier_slots_in_use(lines, info):
     return int((raw[:, 81:90] != 0).sum()) if info["depth"] >= 25 else int(((lines[:, :10] >> 24) != 0).sum())
 
 
-@pytest.mark.parametrize("depth", [16, 17, 20, 24, 25, 27, 28, 29])
-def test_two_tier_table_holds_the_solid_suffixes_and_filters_the_ones_that_occur_once(depth, monkeypatch):
-    """MSBWT_SPARSE_TIERS=1: every suffix that occurs at least twice has an entry with the oracle's range; every suffix that occurs once has
-    NO entry and its four filter bits set in its own bucket; an absent suffix is a miss or (rarely) a filter false positive; the slots
-    in use are exactly the solid suffixes."""
-    reads = read_set(31, 3000, 700, 60, repeats=4, err=0.02)
-    b, ref = load_pair(bwt_of(reads), monkeypatch, depth, MSBWT_SPARSE_TIERS=1)
+def check_two_tier_table(b, ref, reads, depth):
+    """A two-tier table of `depth`: every suffix that occurs at least twice has an entry with the oracle's range; every suffix that occurs
+    once has NO entry and its four filter bits set in its own bucket; an absent suffix is a miss or (rarely) a filter false positive; the
+    slots in use are exactly the solid suffixes."""
     assert b.get_sparse_table() == depth and b.get_sparse_tiers() and b.get_pair_index()
     info = b.sparse_table_info()
     assert info["two_tier"]
@@ -393,6 +395,56 @@ def test_two_tier_table_holds_the_solid_suffixes_and_filters_the_ones_that_occur
             w = np.lib.stride_tricks.sliding_window_view(reads, d, axis=1).reshape(-1, d)
             _, cnt = np.unique(w, axis=0, return_counts=True)
             assert n == int((cnt == 1).sum()), d
+
+
+@pytest.mark.parametrize("depth", [16, 17, 20, 24, 25, 27, 28, 29])
+def test_two_tier_table_holds_the_solid_suffixes_and_filters_the_ones_that_occur_once(depth, monkeypatch):
+    """MSBWT_SPARSE_TIERS=1: check_two_tier_table at every layout and both parities of the last step."""
+    reads = read_set(31, 3000, 700, 60, repeats=4, err=0.02)
+    b, ref = load_pair(bwt_of(reads), monkeypatch, depth, MSBWT_SPARSE_TIERS=1)
+    check_two_tier_table(b, ref, reads, depth)
+
+
+# ---- the builder's frontier walk where a toy index can reach it: MSBWT_SPARSE_FRONTIER caps its frontier buffers (csrc/frontier_walk.hpp) ----
+def check_build_under_a_64_node_frontier(depth, tiers, monkeypatch, **env):
+    """The same index built with the automatic frontier (one chunk: a level never has more nodes than the index has symbols) and with
+    frontiers of 64 nodes, where both passes of the builder chunk, halve and -- from the root -- descend: the same counts, and a table
+    that holds every suffix's range.  -> the capped build's report."""
+    reads = read_set(11, 3000, 700, 60, repeats=4, err=0.01)
+    rle = bwt_of(reads)
+    monkeypatch.delenv("MSBWT_SPARSE_FRONTIER", raising=False)
+    b, ref = load_pair(rle, monkeypatch, depth, MSBWT_SPARSE_TIERS=tiers, **env)
+    auto = b.sparse_table_info()
+    assert auto["depth"] == depth and auto["two_tier"] == bool(tiers)
+    for walk in ("sizing", "fill"):
+        assert auto[walk + "_chunks"] >= 1 and auto[walk + "_retries"] == 0 and auto[walk + "_descents"] == 0
+    del b
+    b, ref = load_pair(rle, monkeypatch, depth, MSBWT_SPARSE_TIERS=tiers, MSBWT_SPARSE_FRONTIER=64, **env)
+    if tiers:
+        check_two_tier_table(b, ref, reads, depth)
+    else:
+        check_every_entry_is_the_oracles_range(b, ref, reads, depth)
+    info = b.sparse_table_info()
+    for word in ("parent_depth", "distinct", "wide", "once", "entries", "side_entries", "filtered"):
+        assert info[word] == auto[word], word
+    for walk in ("sizing", "fill"):
+        assert info[walk + "_chunks"] > 1 and info[walk + "_retries"] >= 1
+    return info
+
+
+@pytest.mark.parametrize("depth,tiers", [(17, 0), (20, 0), (25, 0), (30, 0), (20, 1)])
+def test_builder_under_a_64_node_frontier_seeded_from_the_flat_table(depth, tiers, monkeypatch):
+    """An odd last step, the 24-, 32- and 40-bit layouts, and a two-tier build."""
+    info = check_build_under_a_64_node_frontier(depth, tiers, monkeypatch)
+    assert info["parent_depth"] > 0
+
+
+@pytest.mark.parametrize("depth,tiers", [(25, 0), (20, 1)])
+def test_builder_under_a_64_node_frontier_from_the_root(depth, tiers, monkeypatch):
+    """Without a direct table the one seed is the root, whose subtree never fits 64 nodes: both passes descend (before the builder walked
+    with the spectrum's walker, this build failed for want of memory)."""
+    info = check_build_under_a_64_node_frontier(depth, tiers, monkeypatch, MSBWT_TABLE_DEPTH=0)
+    assert info["parent_depth"] == 0 and info["sizing_descents"] >= 1 and info["fill_descents"] >= 1
 
 
 @pytest.mark.parametrize("direct", ["packed", "flat", "none", "deep"])
