@@ -407,7 +407,7 @@ int msbwt_sparse_hash(uint64_t key, int depth, uint64_t nbuckets, uint32_t *buck
     if (depth < kSparseMinDepth || depth > kSparseMaxDepth || nbuckets == 0 || nbuckets > 0xFFFFFFFFull || !bucket || !tag) return MSBWT_ERR_INVALID_ARG;
     const uint64_t x = sparse_mix(key, uint32_t(2 * depth));
     *bucket = sparse_bucket(x, uint32_t(2 * depth), uint32_t(nbuckets));
-    *tag = sparse_tag(x, uint32_t(depth));
+    *tag = sparse_tag(x, sparse_layout(uint32_t(depth)));
     return MSBWT_OK;
 }
 
@@ -415,7 +415,7 @@ int msbwt_sparse_hash64(uint64_t key, int depth, uint64_t nbuckets, uint32_t *bu
     if (depth < kSparseMinDepth || depth > kSparseMaxDepth || nbuckets == 0 || nbuckets > 0xFFFFFFFFull || !bucket || !tag) return MSBWT_ERR_INVALID_ARG;
     const uint64_t x = sparse_mix(key, uint32_t(2 * depth));
     *bucket = sparse_bucket(x, uint32_t(2 * depth), uint32_t(nbuckets));
-    *tag = (uint64_t(sparse_tag_hi(x, uint32_t(depth))) << 32) | sparse_tag(x, uint32_t(depth));
+    *tag = (uint64_t(sparse_tag_hi(x, sparse_layout(uint32_t(depth)))) << 32) | sparse_tag(x, sparse_layout(uint32_t(depth)));
     return MSBWT_OK;
 }
 

@@ -1,6 +1,6 @@
 // The one-query-per-lane search kernel's launch (kernel and helpers: lanes_kernel.hpp): this translation unit holds the direct-table
-// instantiations (kSparse = 0) and those of the 24-bit-tag sparse table (1); the other layouts live in lanes_wide.hip, lanes_xwide.hip
-// and lanes_tier.hip.
+// instantiations (kDirectTable) and those of the 24-bit-tag sparse table (kSparseComplete); the other layouts live in lanes_wide.hip,
+// lanes_xwide.hip and lanes_tier.hip.
 #include "lanes_kernel.hpp"
 
 namespace msbwt {
@@ -12,14 +12,15 @@ hipError_t launch_shape(bool pair, bool longk, hipStream_t stream, const IndexVi
     // -- one kernel per table LAYOUT, so that each carries a single scan (round 6: with the three complete layouts behind launch-uniform
     // branches in one kernel the lookup-heavy lines lost 8-13 % against round 5's single-layout kernel on the same box)
     if (const SparseView *sp = sparse_for(ix, src.k)) {
-        if (sp->tier) return launch_lanes_sparse_tier(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
-        if (sparse_xwide(sp->depth)) return launch_lanes_sparse_xwide(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
-        if (sparse_wide(sp->depth)) return launch_lanes_sparse_wide(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
-        return launch_sparse_shape<kReads, kPacked, 1, kRange>(pair, longk, stream, ix, src, flags);
+        const SparseLayout layout = sparse_layout(sp->depth, sp->tier != 0u);
+        if (layout.filter_word != 0u) return launch_lanes_sparse_tier(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
+        if (layout.tag_bits == 40u) return launch_lanes_sparse_xwide(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
+        if (layout.tag_bits == 32u) return launch_lanes_sparse_wide(kReads, kPacked, kRange, pair, longk, stream, ix, src, flags);
+        return launch_sparse_shape<kReads, kPacked, kSparseComplete, kRange>(pair, longk, stream, ix, src, flags);
     }
-    if (!pair) return longk ? launch_variant<kReads, false, 6, false, kPacked, 0, kRange>(stream, ix, src, flags) : launch_variant<kReads, false, 3, false, kPacked, 0, kRange>(stream, ix, src, flags);
-    if (ix.pair_stride96) return longk ? launch_variant<kReads, true, 6, true, kPacked, 0, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, true, kPacked, 0, kRange>(stream, ix, src, flags);
-    return longk ? launch_variant<kReads, true, 6, false, kPacked, 0, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, false, kPacked, 0, kRange>(stream, ix, src, flags);
+    if (!pair) return longk ? launch_variant<kReads, false, 6, false, kPacked, kDirectTable, kRange>(stream, ix, src, flags) : launch_variant<kReads, false, 3, false, kPacked, kDirectTable, kRange>(stream, ix, src, flags);
+    if (ix.pair_stride96) return longk ? launch_variant<kReads, true, 6, true, kPacked, kDirectTable, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, true, kPacked, kDirectTable, kRange>(stream, ix, src, flags);
+    return longk ? launch_variant<kReads, true, 6, false, kPacked, kDirectTable, kRange>(stream, ix, src, flags) : launch_variant<kReads, true, 3, false, kPacked, kDirectTable, kRange>(stream, ix, src, flags);
 }
 
 }  // namespace

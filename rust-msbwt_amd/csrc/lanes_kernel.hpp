@@ -295,124 +295,99 @@ __device__ __forceinline__ uint64_t pair_line_bound(const PairLine &L, uint64_t 
     return super_base + L.field + pair_line_count(L, r);
 }
 
-// ---- sparse suffix table (sparse_table.hpp): this lane's key among the 14 entries of a staged bucket line -------------------------
-// The line: 14 tags in words 0..13 (chunks 0-3), l in words 14..27 and bytes 112..125, the bucket's header in bytes 126..127.  A
-// key sits in at most one slot of at most one bucket, so a tag match IS the entry.  -> true: l and width (255 = the range lives
-// in the side array, l = its index there); false: not in this bucket -- header > 14 says that entries of it were displaced.
-__device__ __forceinline__ bool sparse_scan(const uint4 *lines, uint32_t slot, uint32_t want, uint64_t &l, uint32_t &width, uint32_t &header) {
-    const uint32_t base = line_base(slot), g = slot & 7u;
-    const uint4 c0 = lines[base + (0u ^ g)], c1 = lines[base + (1u ^ g)], c2 = lines[base + (2u ^ g)], c3 = lines[base + (3u ^ g)];
-    const uint32_t tags[kSparseSlots] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y};
-    // Three instructions per slot (and, compare, select), from the highest slot down so that the LOWEST matching slot wins: a
-    // bucket fills from slot 0 up, so an entry always beats an empty slot (tag 0, width 0), which a key whose tag is 0 matches too.
-    uint32_t hit = kSparseSlots;
-#pragma unroll
-    for (int i = int(kSparseSlots) - 1; i >= 0; --i) hit = (tags[i] & ((1u << kSparseTagBits) - 1u)) == want ? uint32_t(i) : hit;
-    header = lines[base + (7u ^ g)].w >> 16;
-    width = 0;
-    if (hit >= kSparseSlots) return false;
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(lines);
-    width = words[(base + ((hit >> 2) ^ g)) * 4u + (hit & 3u)] >> kSparseTagBits;
-    if (width == 0u) return false;  // an empty slot: the key is not in this bucket (and none was displaced from a bucket with room)
-    const uint32_t word = kSparseL0Word + hit;
-    const uint32_t lo = words[(base + ((word >> 2) ^ g)) * 4u + (word & 3u)];
-    const uint32_t hi = reinterpret_cast<const uint8_t *>(lines)[(base + (7u ^ g)) * 16u + hit];
-    l = (uint64_t(hi) << 32) | lo;
-    return true;
-}
+// ---- sparse suffix table (sparse_table.hpp): this lane's key among the entries of a staged bucket line ---------------------------
+// Which table an instantiation of the kernel looks its queries up in: its kSparse (the numbers are the ones benchmark records carry).
+enum SparseKernel : int { kDirectTable = 0, kSparseComplete = 1, kSparseTier = 2, kSparseWide = 3, kSparseXwide = 4 };
 
-// The WIDE layout of depths 25..28 (sparse_table.hpp): 12 entries, the tag is the whole word, the width a byte of its own.
-__device__ __forceinline__ bool sparse_scan_wide(const uint4 *lines, uint32_t slot, uint32_t want, uint64_t &l, uint32_t &width, uint32_t &header) {
-    const uint32_t base = line_base(slot), g = slot & 7u;
-    const uint4 c0 = lines[base + (0u ^ g)], c1 = lines[base + (1u ^ g)], c2 = lines[base + (2u ^ g)];
-    const uint32_t tags[kSparseWideSlots] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w};
-    uint32_t hit = kSparseWideSlots;
-#pragma unroll
-    for (int i = int(kSparseWideSlots) - 1; i >= 0; --i) hit = tags[i] == want ? uint32_t(i) : hit;  // the lowest matching slot: an entry beats an empty slot
-    header = lines[base + (7u ^ g)].w >> 16;
-    width = 0;
-    if (hit >= kSparseWideSlots) return false;
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lines);
-    const uint32_t wb = kSparseWideWidthByte + hit, hb = kSparseWideHiByte + hit;
-    width = bytes[(base + ((wb >> 4) ^ g)) * 16u + (wb & 15u)];
-    if (width == 0u) return false;  // an empty slot (a key whose tag is 0 matches it)
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(lines);
-    const uint32_t word = kSparseWideL0Word + hit;
-    const uint32_t lo = words[(base + ((word >> 2) ^ g)) * 4u + (word & 3u)];
-    const uint32_t hi = bytes[(base + ((hb >> 4) ^ g)) * 16u + (hb & 15u)];
-    l = (uint64_t(hi) << 32) | lo;
-    return true;
+// The layout an instantiation scans: a constant -- one scan per kernel --, only the two-tier form still tells its two tag widths apart at
+// run time (launch-uniform: by the table's depth).
+template <int kSparse>
+__device__ __forceinline__ constexpr SparseLayout kernel_layout(uint32_t depth) {
+    if constexpr (kSparse == kSparseTier) return sparse_layout(depth, true);
+    else return kSparse == kSparseXwide ? kLayoutXwide : kSparse == kSparseWide ? kLayoutWide : kLayoutComplete;
 }
+static_assert(kLayoutTierWide.slots <= kLayoutTier.slots, "kernel_layout<kSparseTier>(kSparseMinDepth) has the most slots of its two");
 
-// The XWIDE layout of depths 30..31: 11 entries, 40-bit tags (a low word and a byte).  The low words alone nearly always decide; the
-// candidate's high byte is checked, and should it differ the scan goes on behind it (two keys of one probe window may share their low
-// 32 bits -- never all 40).
-__device__ __forceinline__ bool sparse_scan_xwide(const uint4 *lines, uint32_t slot, uint64_t want, uint64_t &l, uint32_t &width, uint32_t &header) {
+// A key sits in at most one slot of at most one bucket, so a tag match IS the entry.  -> true: l and width (255 = the range lives in the
+// side array, l = its index there); false: not in this bucket -- header > L.slots says that entries of it were displaced.  Two-tier
+// layouts also -> `maybe`: the four filter bits of this key are all set in THIS bucket's filter (meaningful in the key's own bucket: a
+// suffix that occurs once has no entry anywhere, only those bits).  kMaxSlots: the most slots a layout passed here can have.
+template <uint32_t kMaxSlots>
+__device__ __forceinline__ bool sparse_scan(const uint4 *lines, uint32_t slot, const SparseLayout &L, uint64_t want, uint64_t &l, uint32_t &width, uint32_t &header,
+                                            bool &maybe) {
     const uint32_t base = line_base(slot), g = slot & 7u;
-    const uint4 c0 = lines[base + (0u ^ g)], c1 = lines[base + (1u ^ g)], c2 = lines[base + (2u ^ g)];
-    const uint32_t tags[kSparseXSlots] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z};
-    const uint32_t want_lo = uint32_t(want), want_hi = uint32_t(want >> 32) & 0xFFu;
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lines);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(lines);
-    auto byte_at = [&](uint32_t b) -> uint32_t { return bytes[(base + ((b >> 4) ^ g)) * 16u + (b & 15u)]; };
-    header = lines[base + (7u ^ g)].w >> 16;
-    width = 0;
-    uint32_t cand = 0;  // bit i: slot i's low word matches (the words need not stay in registers beyond this)
-#pragma unroll
-    for (uint32_t i = 0; i < kSparseXSlots; ++i) cand |= (tags[i] == want_lo ? 1u : 0u) << i;
-    while (cand != 0u) {  // lowest candidate first: one round, but for low words shared by chance
-        const uint32_t hit = uint32_t(__builtin_ctz(cand));
-        const uint32_t w = byte_at(kSparseXWidthByte + hit);
-        if (w == 0u) return false;  // an empty slot whose zero low word matched: a bucket fills from slot 0 up, nothing lies behind it
-        if (byte_at(kSparseXTagHiByte + hit) == want_hi) {
-            width = w;
-            const uint32_t word = kSparseXL0Word + hit;
-            const uint32_t lo = words[(base + ((word >> 2) ^ g)) * 4u + (word & 3u)];
-            l = (uint64_t(byte_at(kSparseXHiByte + hit)) << 32) | lo;
-            return true;
-        }
-        cand &= cand - 1u;  // an entry that shares the low word only
-    }
-    return false;
-}
-
-// The TWO-TIER forms (sparse_table.hpp): 10 entries with 24-bit tags or 9 with 32-bit tags, the bucket's header in bytes 90..91 and eight
-// filter words behind it.  -> also `maybe`: the four filter bits of this key are all set in THIS bucket's filter (meaningful in the key's
-// own bucket: a suffix that occurs once has no entry anywhere, only those bits).
-__device__ __forceinline__ bool sparse_scan_tier(const uint4 *lines, uint32_t slot, uint32_t want, bool wide_layout, uint64_t &l, uint32_t &width, uint32_t &header, bool &maybe) {
-    const uint32_t base = line_base(slot), g = slot & 7u;
-    const uint4 c0 = lines[base + (0u ^ g)], c1 = lines[base + (1u ^ g)], c2 = lines[base + (2u ^ g)];
-    const uint32_t tags[kTierSlots] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y};
     const uint32_t *words = reinterpret_cast<const uint32_t *>(lines);
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lines);
     auto word_at = [&](uint32_t w) -> uint32_t { return words[(base + ((w >> 2) ^ g)) * 4u + (w & 3u)]; };
     auto byte_at = [&](uint32_t b) -> uint32_t { return bytes[(base + ((b >> 4) ^ g)) * 16u + (b & 15u)]; };
-    const uint32_t nslots = wide_layout ? kTierWideSlots : kTierSlots, tag_mask = wide_layout ? ~0u : ((1u << kSparseTagBits) - 1u);
-    uint32_t hit = kTierSlots;
+    auto width_at = [&](uint32_t i) -> uint32_t { return L.width_byte ? byte_at(L.width_byte + i) : word_at(i) >> kSparseWidthShift; };
+    auto take = [&](uint32_t i) {
+        const uint32_t lo = word_at(L.l_lo_word + i), hi = byte_at(L.l_hi_byte + i);
+        l = (uint64_t(hi) << 32) | lo;
+    };
+    constexpr uint32_t kChunks = (kMaxSlots + 3u) / 4u;
+    uint32_t tags[kChunks * 4u];
 #pragma unroll
-    for (int i = int(kTierSlots) - 1; i >= 0; --i) hit = ((tags[i] & tag_mask) == want && uint32_t(i) < nslots) ? uint32_t(i) : hit;  // the lowest matching slot
-    header = word_at(kTierHeaderByte / 4u) >> 16;
-    const uint32_t f = sparse_filter_hash(want), m = sparse_filter_mask(f);
-    maybe = (word_at(kTierFilterWord + sparse_filter_word(f)) & m) == m;
+    for (uint32_t c = 0; c < kChunks; ++c) {
+        const uint4 v = lines[base + (c ^ g)];
+        tags[4u * c] = v.x, tags[4u * c + 1u] = v.y, tags[4u * c + 2u] = v.z, tags[4u * c + 3u] = v.w;
+    }
+    const uint32_t want_lo = uint32_t(want), tag_mask = L.width_byte ? ~0u : (1u << kSparseWidthShift) - 1u;
+    header = word_at(L.header_byte / 4u) >> 16;
+    maybe = false;
     width = 0;
-    if (hit >= nslots) return false;
-    width = wide_layout ? byte_at(kTierWideWidthByte + hit) : (word_at(hit) >> kSparseTagBits);
-    if (width == 0u) return false;  // an empty slot (a key whose tag is 0 matches it)
-    const uint32_t lo = word_at((wide_layout ? kTierWideL0Word : kTierL0Word) + hit), hi = byte_at((wide_layout ? kTierWideHiByte : kTierHiByte) + hit);
-    l = (uint64_t(hi) << 32) | lo;
+    if (L.tag_hi_byte != 0u) {  // (no such layout has a filter: sparse_layout_sound)
+        // 40-bit tags: the low words alone nearly always decide; the candidate's high byte is checked, and should it differ the scan goes
+        // on behind it (two keys of one probe window may share their low 32 bits -- never all 40).
+        const uint32_t want_hi = uint32_t(want >> 32) & 0xFFu;
+        uint32_t cand = 0;  // bit i: slot i's low word matches (the words need not stay in registers beyond this)
+#pragma unroll
+        for (uint32_t i = 0; i < kMaxSlots; ++i) cand |= (tags[i] == want_lo ? 1u : 0u) << i;
+        while (cand != 0u) {  // lowest candidate first: one round, but for low words shared by chance
+            const uint32_t hit = uint32_t(__builtin_ctz(cand));
+            const uint32_t w = width_at(hit);
+            if (w == 0u) return false;  // an empty slot whose zero low word matched: a bucket fills from slot 0 up, nothing lies behind it
+            if (byte_at(L.tag_hi_byte + hit) == want_hi) {
+                width = w;
+                take(hit);
+                return true;
+            }
+            cand &= cand - 1u;  // an entry that shares the low word only
+        }
+        return false;
+    }
+    // Three instructions per slot (and, compare, select), from the highest slot down so that the LOWEST matching slot wins: a
+    // bucket fills from slot 0 up, so an entry always beats an empty slot (tag 0, width 0), which a key whose tag is 0 matches too.
+    // (Words behind the layout's last slot are compared too where kMaxSlots exceeds L.slots: a match there is no slot, see below.)
+    uint32_t hit = kMaxSlots;
+#pragma unroll
+    for (int i = int(kMaxSlots) - 1; i >= 0; --i) hit = (tags[i] & tag_mask) == want_lo ? uint32_t(i) : hit;
+    if (L.filter_word != 0u) {
+        const uint32_t f = sparse_filter_hash(want_lo), m = sparse_filter_mask(f);
+        maybe = (word_at(L.filter_word + sparse_filter_word(f)) & m) == m;
+    }
+    if (hit >= L.slots) return false;  // no word matches, or the lowest match lies behind the last slot: no slot matches
+    width = width_at(hit);
+    if (width == 0u) return false;  // an empty slot: the key is not in this bucket (and none was displaced from a bucket with room)
+    take(hit);
     return true;
 }
 
-// (the k > 32 instantiations sit at their register limit: they take the two-tier scan as a call too)
-struct TierScanOut {
+// (the k > 32 instantiations of the 40-bit and of the two-tier layouts sit at their register limit: they take the scan as a call, not inlined)
+struct SparseScanOut {
     uint64_t l;
-    uint32_t width, header, hit, maybe;
+    uint32_t width, header, found;  // found: bit 0 = the entry, bit 1 = `maybe`
 };
-[[maybe_unused]] __device__ __attribute__((noinline)) TierScanOut sparse_scan_tier_call(const uint4 *lines, uint32_t slot, uint32_t want, bool wide_layout) {  // (results by value: no stack)
-    TierScanOut o{0, 0, 0, 0, 0};
+template <int kSparse>
+[[maybe_unused]] __device__ __attribute__((noinline)) SparseScanOut sparse_scan_call(const uint4 *lines, uint32_t slot, uint32_t depth, uint64_t want) {  // (results by value: no stack)
+    SparseScanOut o{0, 0, 0, 0};
     bool maybe = false;
-    o.hit = sparse_scan_tier(lines, slot, want, wide_layout, o.l, o.width, o.header, maybe) ? 1u : 0u;
-    o.maybe = maybe ? 1u : 0u;
+    // The callers keep what lives across this call in the registers behind the ones it uses, 64- and 128-bit values in aligned tuples: the
+    // two-tier scan needs v0..v24, and with that ODD count two of its callers (matrix queries, pair steps, k > 32), which have 168
+    // registers and not one to spare, spill 2 and 5 of them.  So it claims v25 as well -- 26, the count this call has always had.
+    if constexpr (kSparse == kSparseTier) asm volatile("" ::: "v25");
+    o.found = sparse_scan<kernel_layout<kSparse>(kSparseMinDepth).slots>(lines, slot, kernel_layout<kSparse>(depth), want, o.l, o.width, o.header, maybe) ? 1u : 0u;
+    o.found |= maybe ? 2u : 0u;
     return o;
 }
 
@@ -432,28 +407,17 @@ __device__ __forceinline__ void consume_symbols_uniform(uint32_t (&w)[kWords], u
     for (int i = 0; i < kWords; ++i) w[i] = __builtin_amdgcn_alignbit(t[i + 1], t[i], rest);
 }
 
-// (the k > 32 instantiations sit at their register limit: they take the xwide scan as a call, not inlined)
-struct SparseScanOut {
-    uint64_t l;
-    uint32_t width, header, hit;
-};
-[[maybe_unused]] __device__ __attribute__((noinline)) SparseScanOut sparse_scan_xwide_call(const uint4 *lines, uint32_t slot, uint64_t want) {  // (results by value: no stack)
-    SparseScanOut o{0, 0, 0, 0};
-    o.hit = sparse_scan_xwide(lines, slot, want, o.l, o.width, o.header) ? 1u : 0u;
-    return o;
-}
-
 // kPacked (matrix mode only): the queries come as 2-bit words (QuerySource::packed), possibly with a place for each count.
 // A compile-time switch, not a launch-uniform branch: with both ways of fetching a tile in one kernel the compiler merged
 // their results through register copies, i.e. WAITED for the tile's bytes right after asking for them -- setup no longer
 // ran ahead of memory (same box, C2 random 21-mers: 0.253 ms per 10^7 against 0.225 ms before packed queries existed).
 // kSparse (kPair only): the launch looks its queries up in the SPARSE suffix table (sparse_table.hpp) instead of the direct one --
 // `table` = its bucket lines, `depth` = its depth, `table_side` = its side array.  A lookup is a search step of its own kind: the
-// lane's line is its key's bucket, fetched with the other lanes' lines, and the lane finds its entry among the line's 14 tags.
+// lane's line is its key's bucket, fetched with the other lanes' lines, and the lane finds its entry among the line's tags.
 // A compile-time switch for the same reason as kPacked -- and so that the direct-table kernels carry none of it.
-// kSparse = 2: the table is of the TWO-TIER form (entries for the suffixes at least 2 wide, filter bits for the ones that occur once):
+// kSparse = kSparseTier: the table is of the TWO-TIER form (entries for the suffixes at least 2 wide, filter bits for the ones that occur once):
 // a lookup that ends in the filter goes on through the DIRECT table (`dtable`: its line is the query's next step, decoded by the lane)
-// and searches from there -- the complete-table kernels (kSparse = 1) carry none of that.
+// and searches from there -- the complete-table kernels carry none of that.
 // kPair = false with kSparse (round 6): run blocks behind a sparse table -- the post-lookup steps are single-symbol steps.
 // kRange (matrix byte queries only): every query ends with its FM range stored instead of its count (QuerySource::range_stride) --
 // (0, 0) for an empty one, all-ones for a query holding a symbol >= 6; the search itself is the same.
@@ -471,9 +435,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                                                           const uint4 *__restrict__ dside) {
     static_assert(!(kReads && kPacked), "packed queries are a matrix-mode input");
     static_assert(!(kRange && (kReads || kPacked)), "ranges are served for matrix byte queries");
-    static_assert(kSparse >= 0 && kSparse <= 4, "0 = direct table; sparse table: 1 = 24-bit tags (depths up to 24), 2 = two-tier form, 3 = 32-bit tags (25..29), 4 = 40-bit tags (30..31)");
-    constexpr bool kTier = kSparse == 2, kWideTags = kSparse == 3, kXwide = kSparse == 4;
-    constexpr int kReach = kSparse >= 2 ? 32 : 24;  // how deep this kernel's table index may reach (search_common.hpp, pack_row_swar)
+    static_assert(kSparse >= kDirectTable && kSparse <= kSparseXwide, "a SparseKernel");
+    constexpr bool kTier = kSparse == kSparseTier, kXwide = kSparse == kSparseXwide;
+    constexpr int kReach = (kSparse == kDirectTable || kSparse == kSparseComplete) ? 24 : 32;  // how deep this kernel's table index may reach (search_common.hpp, pack_row_swar)
     using Scratch = LaneScratchT<kWords, kPacked, kTier>;
     // run blocks (run_index.hpp; launch-uniform): `blocks` are 128-byte lines of 512 positions with 96 one-byte runs, decoded
     // by the lane that owns the query; single-symbol steps only (the kPair instantiations never see them)
@@ -496,42 +460,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
     // stream).  Round 5, human scale, alternating on one box: 38.4 ms (36.7-39.8) by default, 36.1 ms (35.6-36.6) streaming; C3 fused,
     // whose pair blocks half live in the Infinity Cache, 14.9 -> 19.8 ms -- hence a launch-uniform switch, not a constant.
     const bool stream_lines = (table_packed & 2u) != 0u;
-    // the sparse table's layout follows its depth (launch-uniform): 14 entries with 24-bit tags up to depth 24, 12 with 32-bit tags beyond
-    // (the table's layout is the kernel's: one scan per instantiation; only the two-tier form still tells its two tag widths apart at run time)
-    const bool sparse_wide_layout = kTier && sparse_wide(depth);
-    const uint32_t sparse_nslots = kTier ? sparse_slots(depth, true) : (kXwide ? kSparseXSlots : kWideTags ? kSparseWideSlots : kSparseSlots);
+    // the sparse table's layout (sparse_table.hpp) is the kernel's: a constant, but for the two-tier form's launch-uniform choice of two
+    const SparseLayout layout = kernel_layout<kSparse>(depth);
     // two-tier: the direct table a lookup falls back to -- dd symbols deep (0: none, such a query searches from [0, total)), packed or flat
     const uint32_t dd = kTier ? (dinfo & 0xFFu) : 0u;
     const bool dpacked = kTier && ((dinfo >> 8) & 1u) != 0u;
     const uint64_t dkey_mask = (1ull << (2u * dd)) - 1ull;  // (dd <= 18: the direct table's index takes up to 36 bits -- a query carries its LINE there (32 bits) and its slot in the line (5 bits))
     auto scan_bucket = [&](uint32_t slot, uint64_t want, uint64_t &tl, uint32_t &tw, uint32_t &header, bool &maybe) -> bool {  // want: the tag, up to 40 bits
-        maybe = false;
-        if constexpr (kTier && kWords == 6) {
-            const TierScanOut o = sparse_scan_tier_call(ws.lines, slot, uint32_t(want), sparse_wide_layout);
-            tl = o.hit ? o.l : tl;
+        if constexpr (kSparse == kDirectTable) {
+            return false;
+        } else if constexpr ((kTier || kXwide) && kWords == 6) {
+            const SparseScanOut o = sparse_scan_call<kSparse>(ws.lines, slot, depth, want);
+            tl = (o.found & 1u) ? o.l : tl;
             tw = o.width;
             header = o.header;
-            maybe = o.maybe != 0u;
-            return o.hit != 0u;
-        } else if constexpr (kTier) {
-            return sparse_scan_tier(ws.lines, slot, uint32_t(want), sparse_wide_layout, tl, tw, header, maybe);
-        }
-        if constexpr (kXwide) {
-            if constexpr (kWords == 6) {
-                const SparseScanOut o = sparse_scan_xwide_call(ws.lines, slot, want);
-                tl = o.hit ? o.l : tl;
-                tw = o.width;
-                header = o.header;
-                return o.hit != 0u;
-            } else {
-                return sparse_scan_xwide(ws.lines, slot, want, tl, tw, header);
-            }
-        } else if constexpr (kWideTags) {
-            return sparse_scan_wide(ws.lines, slot, uint32_t(want), tl, tw, header);
-        } else if constexpr (kSparse == 1) {
-            return sparse_scan(ws.lines, slot, uint32_t(want), tl, tw, header);
+            maybe = (o.found & 2u) != 0u;
+            return (o.found & 1u) != 0u;
         } else {
-            return false;
+            return sparse_scan<kernel_layout<kSparse>(kSparseMinDepth).slots>(ws.lines, slot, layout, want, tl, tw, header, maybe);
         }
     };
     // optional search counters (kernels.hpp, SearchCounter): wave sums kept in LDS, added to the caller's block at the end
@@ -897,8 +843,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                         if constexpr (kSparse) {  // nothing to fetch here: the bucket line is the query's first search step
                             const uint64_t x = sparse_mix(pq.tidx, 2u * depth);
                             prep_entry.x = sparse_bucket(x, 2u * depth, sparse_nbuckets);
-                            prep_entry.y = (kWideTags || kXwide || sparse_wide_layout) ? uint32_t(x) : uint32_t(x) & ((1u << kSparseTagBits) - 1u);  // sparse_tag
-                            prep_entry.z = kXwide ? (uint32_t(x >> 32) & 0xFFu) << 8 : 0u;  // sparse_tag_hi  // low byte: buckets gone beyond its own; next byte: bits 32..39 of the tag (xwide layout; else 0)
+                            prep_entry.y = sparse_tag(x, layout);
+                            prep_entry.z = sparse_tag_hi(x, layout) << 8;  // low byte: buckets gone beyond its own; next byte: bits 32..39 of the tag (xwide layout; else 0)
                             if constexpr (kTier) {  // where the direct table keeps this query's suffix: line (w) and slot in it (z, bits 10..14)
                                 const uint64_t dk = pq.tidx & dkey_mask, dline = dpacked ? dk / kPackedPerLine : dk >> 3;
                                 prep_entry.w = uint32_t(dline);
@@ -1060,7 +1006,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                     prep_entry.x = uint32_t(tl);
                     prep_entry.y = uint32_t(tl >> 32) | (tw << 8);
                     prep_kind = 4;
-                } else if (header > sparse_nslots && (prep_entry.z & 0xFFu) < sparse_probe) {  // entries of this bucket were displaced: the next one, next time
+                } else if (header > layout.slots && (prep_entry.z & 0xFFu) < sparse_probe) {  // entries of this bucket were displaced: the next one, next time
                     ++prep_entry.x;
                     ++prep_entry.z;
                 } else if (kTier && ((prep_entry.z >> 9) & 1u) != 0u) {  // no entry, but the filter knows it (occurs once, or a false positive): the direct table's path
@@ -1114,7 +1060,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 4))) void
                         else store_count<kReads>(src, qid, h - l);
                         have = false;
                     }
-                } else if (header > sparse_nslots && (kTier ? (tdist & 0xFFu) : tdist) < sparse_probe) {  // entries of this bucket were displaced: the next one
+                } else if (header > layout.slots && (kTier ? (tdist & 0xFFu) : tdist) < sparse_probe) {  // entries of this bucket were displaced: the next one
                     ++l;
                     ++tdist;
                 } else if (kTier && tmaybe) {  // no entry, but the filter knows it (occurs once, or a false positive): the direct table's path
@@ -1301,9 +1247,9 @@ hipError_t launch_variant(hipStream_t stream, const IndexView &ix, const QuerySo
                        tickets ? static_cast<unsigned long long *>(ix.tile_counter) : nullptr, grain, waves == 1 ? ix.done : nullptr, ix.done_seq, ix.counters,
                        uint32_t(ix.block_format), static_cast<const uint4 *>(ix.overflow), sp.nbuckets, sp.probe,
                        // two-tier: the direct table its filter sends queries to (depth | packed << 8), and that table's side array
-                       static_cast<const uint4 *>(kSparse == 2 ? ix.table.entries : nullptr),
-                       kSparse == 2 && ix.table.entries ? (uint32_t(ix.table.depth) & 0xFFu) | (ix.table.packed ? 0x100u : 0u) : 0u,
-                       static_cast<const uint4 *>(kSparse == 2 && ix.table.entries ? ix.table.side : nullptr));
+                       static_cast<const uint4 *>(kSparse == kSparseTier ? ix.table.entries : nullptr),
+                       kSparse == kSparseTier && ix.table.entries ? (uint32_t(ix.table.depth) & 0xFFu) | (ix.table.packed ? 0x100u : 0u) : 0u,
+                       static_cast<const uint4 *>(kSparse == kSparseTier && ix.table.entries ? ix.table.side : nullptr));
     return hipGetLastError();
 }
 
@@ -1319,7 +1265,7 @@ hipError_t launch_sparse_shape(bool pair, bool longk, hipStream_t stream, const 
 
 }  // namespace
 
-// the sparse-table launches of the other translation units (kSparse: 2 = two-tier, 3 = 32-bit tags, 4 = 40-bit tags); range: the
+// the sparse-table launches of the other translation units (kSparseTier, kSparseWide, kSparseXwide); range: the
 // kRange instantiations (matrix byte queries)
 hipError_t launch_lanes_sparse_tier(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);
 hipError_t launch_lanes_sparse_wide(bool reads, bool packed, bool range, bool pair, bool longk, hipStream_t stream, const IndexView &ix, const QuerySource &src, uint32_t *flags);

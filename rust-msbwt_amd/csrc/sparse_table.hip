@@ -48,17 +48,26 @@ struct FillEnv : PlainSink {  // the fill pass
     __device__ __forceinline__ void take(Thread &, uint32_t *, unsigned long long *cur, uint64_t key, uint64_t nl, uint64_t nh, uint64_t &) const;
 };
 
+// stores one entry into slot `slot` of a bucket line: tag word, l, then the width and the tag's high byte wherever the layout keeps them
+__device__ __forceinline__ void sparse_store(uint32_t *line, const SparseLayout &L, uint32_t slot, uint32_t tag, uint32_t tag_hi, uint64_t lval, uint32_t width) {
+    uint8_t *bytes = reinterpret_cast<uint8_t *>(line);
+    line[slot] = L.width_byte ? tag : tag | (width << kSparseWidthShift);
+    line[L.l_lo_word + slot] = uint32_t(lval);
+    bytes[L.l_hi_byte + slot] = uint8_t(lval >> 32);
+    if (L.width_byte) bytes[L.width_byte + slot] = uint8_t(width);
+    if (L.tag_hi_byte) bytes[L.tag_hi_byte + slot] = uint8_t(tag_hi);
+}
+
 // puts the entry of (key, [nl, nh)) into its bucket; `cur`: the cursor block (side cursor, displaced, failed)
 __device__ __forceinline__ void sparse_insert(const FillEnv &env, uint64_t key, uint64_t nl, uint64_t nh, unsigned long long *cur) {
     const uint64_t x = sparse_mix(key, env.n);
     uint32_t b = sparse_bucket(x, env.n, env.nbuckets);
-    const uint32_t depth = env.n >> 1;
-    const bool wide = sparse_wide(depth), xwide = sparse_xwide(depth);  // launch-uniform: the layout follows the depth (sparse_table.hpp)
     const bool tier = env.tier != 0u;
-    const uint32_t tag = sparse_tag(x, depth), tag_hi = sparse_tag_hi(x, depth), slots = sparse_slots(depth, tier);
+    const SparseLayout L = sparse_layout(env.n >> 1, tier);  // launch-uniform: the layout follows the depth and the form (sparse_table.hpp)
+    const uint32_t tag = sparse_tag(x, L), tag_hi = sparse_tag_hi(x, L);
     if (tier && nh - nl == 1u) {  // occurs once: four bits of one filter word of its OWN bucket (never displaced), no entry
         const uint32_t f = sparse_filter_hash(tag);
-        atomicOr(reinterpret_cast<uint32_t *>(env.lines + uint64_t(b) * 8u) + kTierFilterWord + sparse_filter_word(f), sparse_filter_mask(f));
+        atomicOr(reinterpret_cast<uint32_t *>(env.lines + uint64_t(b) * 8u) + L.filter_word + sparse_filter_word(f), sparse_filter_mask(f));
         atomicAdd(cur + kFiltered, 1ull);
         return;
     }
@@ -76,33 +85,8 @@ __device__ __forceinline__ void sparse_insert(const FillEnv &env, uint64_t key, 
     }
     for (uint32_t dist = 0; dist <= env.probe; ++dist, ++b) {
         const uint32_t slot = atomicAdd(env.counts + b, 1u);
-        if (slot < slots) {
-            uint32_t *line = reinterpret_cast<uint32_t *>(env.lines + uint64_t(b) * 8u);
-            if (tier && wide) {
-                line[slot] = tag;
-                line[kTierWideL0Word + slot] = uint32_t(lval);
-                reinterpret_cast<uint8_t *>(line)[kTierWideHiByte + slot] = uint8_t(lval >> 32);
-                reinterpret_cast<uint8_t *>(line)[kTierWideWidthByte + slot] = uint8_t(wf);
-            } else if (tier) {
-                line[slot] = tag | (wf << kSparseTagBits);
-                line[kTierL0Word + slot] = uint32_t(lval);
-                reinterpret_cast<uint8_t *>(line)[kTierHiByte + slot] = uint8_t(lval >> 32);
-            } else if (xwide) {
-                line[slot] = tag;
-                line[kSparseXL0Word + slot] = uint32_t(lval);
-                reinterpret_cast<uint8_t *>(line)[kSparseXTagHiByte + slot] = uint8_t(tag_hi);
-                reinterpret_cast<uint8_t *>(line)[kSparseXHiByte + slot] = uint8_t(lval >> 32);
-                reinterpret_cast<uint8_t *>(line)[kSparseXWidthByte + slot] = uint8_t(wf);
-            } else if (wide) {
-                line[slot] = tag;
-                line[kSparseWideL0Word + slot] = uint32_t(lval);
-                reinterpret_cast<uint8_t *>(line)[kSparseWideHiByte + slot] = uint8_t(lval >> 32);
-                reinterpret_cast<uint8_t *>(line)[kSparseWideWidthByte + slot] = uint8_t(wf);
-            } else {
-                line[slot] = tag | (wf << kSparseTagBits);
-                line[kSparseL0Word + slot] = uint32_t(lval);
-                reinterpret_cast<uint8_t *>(line)[kSparseHiByte + slot] = uint8_t(lval >> 32);
-            }
+        if (slot < L.slots) {
+            sparse_store(reinterpret_cast<uint32_t *>(env.lines + uint64_t(b) * 8u), L, slot, tag, tag_hi, lval, wf);
             if (dist != 0u) atomicAdd(cur + kDisplaced, 1ull);
             return;
         }
@@ -114,7 +98,7 @@ __device__ __forceinline__ void FillEnv::take(Thread &, uint32_t *, unsigned lon
     sparse_insert(*this, key, nl, nh, cur);
 }
 
-// bytes 126..127 of every bucket: how many entries wanted it
+// the header of every bucket: how many entries wanted it
 __global__ __launch_bounds__(256) void k_sparse_headers(uint4 *__restrict__ lines, const uint32_t *__restrict__ counts, uint64_t nlines, uint32_t header_byte) {
     for (uint64_t b = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; b < nlines; b += uint64_t(gridDim.x) * blockDim.x)
         reinterpret_cast<uint16_t *>(lines + b * 8u)[header_byte / 2] = uint16_t(min(counts[b], 0xFFFFu));
@@ -167,7 +151,7 @@ hipError_t sparse_fill(const IndexView &ix, const void *flat_entries, int flat_d
     Walker<FillEnv, false> walker(ix, flat_entries, flat_depth, uint32_t(depth), 1, env, d_work, walk_nodes_in(work_bytes), stream);
     if ((e = walker.run()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sparse_headers, dim3(uint32_t(std::min<uint64_t>((nlines + 255) / 256, 2048))), dim3(256), 0, stream, static_cast<uint4 *>(lines),
-                       static_cast<const uint32_t *>(d_counts), nlines, tier ? kTierHeaderByte : kSparseHeaderByte);
+                       static_cast<const uint32_t *>(d_counts), nlines, sparse_layout(uint32_t(depth), tier).header_byte);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
