@@ -398,6 +398,64 @@ int msbwt_rle_enumerate_canonical_kmers_device(const msbwt_rle *bwt, size_t k, u
  * _device form, for counting and for the spectrum, which adds 8 n_bins).  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on. */
 int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes);
 
+/* ---- k-mers by source: one spectrum per input of a merged index, and the dump filtered by per-source counts (no reference counterpart) ----
+ * "The k-mers that occur at least 5 times in the tumour and never in the normal", "the k-mers all lanes share", an abundance spectrum
+ * per sample out of ONE merged index: the k-mers come from the index (as in the spectrum section), their per-source counts from the
+ * source vector (as msbwt_rle_range_sources), and the two meet on the device, chunk by chunk -- neither the dump of all k-mers nor an
+ * n x S count matrix is ever made.  All calls need a loaded index WITH sources attached (msbwt_rle_set_sources,
+ * msbwt_rle_load_merged_many_sources); S = msbwt_rle_source_count, c_s(q) = the rows of source s in q's range, which is
+ * count_kmer(q) on input s's own BWT; the c_s of a k-mer sum to its count.
+ *
+ * msbwt_rle_kmer_spectrum_by_source: out_hist is S x n_bins, row-major; over the k-mers of the merged index out_hist[s * n_bins + c],
+ * 1 <= c < n_bins - 1, = the k-mers with c_s == c, the last bin those with c_s >= n_bins - 1, and bin 0 the k-mers of the index that
+ * source s does NOT hold (non-zero here, unlike in the plain spectrum).  n_bins >= 2.  out_sharing (S + 1 words, may be NULL): [j] = the
+ * k-mers held by exactly j sources, [0] = 0.  out_distinct (S, may be NULL): the sum of row s's bins >= 1.  out_occurrences (S, may be
+ * NULL): the sum of c_s.  Row s equals msbwt_rle_kmer_spectrum of input s loaded alone, bin 0 apart.
+ *
+ * msbwt_rle_enumerate_kmers_by_source[_device]: the k-mers with min_counts[s] <= c_s <= max_counts[s] for EVERY s and min_total <= sum
+ * of the c_s <= max_total, as records (k-mer, c_0 .. c_{S-1}, l); out_counts is n x S, row-major.  min_counts and max_counts are HOST
+ * arrays of S words in both forms; min_counts == NULL: all zeros, max_counts == NULL: no limits.
+ * NOTE the convention of max_counts: UINT64_MAX means no limit and 0 means ABSENT FROM THIS SOURCE -- that is the point of the call
+ * ("private to input 0": max_counts = {UINT64_MAX, 0, 0, ...}).  It deliberately differs from max_count == 0 = "no upper limit" of
+ * msbwt_rle_enumerate_kmers, which min_total and max_total keep: min_total == 0 is 1, max_total == 0 is no limit.
+ * min_counts[s] > max_counts[s], or min_total > max_total != 0: MSBWT_ERR_INVALID_ARG.
+ * Capacity, order and the two forms are exactly msbwt_rle_enumerate_kmers': *out_n is always set; capacity == 0 only counts; 0 <
+ * capacity < n writes NOTHING, sets *out_n = n, returns MSBWT_ERR_INVALID_ARG and names n in the message; out_counts and out_l may each
+ * be NULL; a call that fills buffers walks twice; sorted != 0: ascending k-mers, the same from run to run (every emitted k-mer has rows
+ * of its own, so the placement by the rank of l carries over); sorted == 0: the order the walk produces.  The _device form writes to
+ * device buffers on the handle's device, synchronises the stream and reports a device fault through msbwt_rle_device_status.
+ * The walk prunes with max(min_total, the sum of min_counts, 1): a suffix occurs at least as often as the k-mer.  (It does not prune
+ * per source at inner levels.)
+ *
+ * Guards, before the first HIP call: NULL handle MSBWT_ERR_INVALID_ARG; nothing loaded MSBWT_ERR_NOT_LOADED ("no BWT loaded"); no
+ * attachment MSBWT_ERR_NOT_LOADED ("no sources attached"); k outside 1..32 MSBWT_ERR_INVALID_ARG.  Scratch per call, freed on return
+ * (msbwt_rle_device_bytes unchanged): msbwt_kmers_by_source_plan bytes, and the spectrum's 8 S n_bins.  A k-mer's S counts live in the
+ * registers of the eight lanes that count it: apart from the records staged for a host dump NO scratch grows with frontier x S.
+ * msbwt_rle_spectrum_info reports these walks as it does the others: [4 + k] is the number of k-mers the last level handed to the
+ * sink, before the predicate ("K-mers by source"). */
+int msbwt_rle_kmer_spectrum_by_source(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_sharing,
+                                      uint64_t *out_distinct, uint64_t *out_occurrences);
+int msbwt_rle_enumerate_kmers_by_source(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts,
+                                        uint64_t min_total, uint64_t max_total, int sorted, uint64_t *out_kmers2bit,
+                                        uint64_t *out_counts, uint64_t *out_l, uint64_t capacity, uint64_t *out_n);
+int msbwt_rle_enumerate_kmers_by_source_device(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts,
+                                               uint64_t min_total, uint64_t max_total, int sorted, void *d_out_kmers2bit,
+                                               void *d_out_counts, void *d_out_l, uint64_t capacity, uint64_t *out_n, void *hip_stream);
+/* Pure function, no device: bytes of HBM a by-source call allocates and frees again with the automatic frontier: what
+ * msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, sorted) gives for the walk, the sink's fixed words (its limits and totals: the
+ * same at every size and every S), plus 8 (2 + n_sources) bytes per record staged for a host dump (0 for the _device form and for
+ * counting).  n_sources outside 1..MSBWT_MERGE_MAX_INPUTS: MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on. */
+int msbwt_kmers_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, size_t n_sources, uint64_t records, int sorted,
+                               uint64_t *device_bytes);
+
+/* The bytes of scratch the handle's last k-mer walk call (any call of the three sections above that walks) allocated in HBM and freed
+ * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves
+ * it as it was).  Every allocation counts with its size, 256 bytes at the least.  For the by-source calls this is what
+ * msbwt_kmers_by_source_plan(rows, free, S, records, sorted) says, with records = n for a host dump that asked for counts AND l (8 S or
+ * 8 bytes per record less without them) and 0 otherwise, sorted = 1 for a sorted call that fills buffers (a call that only counts marks
+ * nothing), plus 8 S n_bins for the spectrum -- the tests hold the two against each other.  NULL handle or pointer: MSBWT_ERR_INVALID_ARG. */
+int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

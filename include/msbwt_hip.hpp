@@ -330,6 +330,72 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_canonical_plan");
         return bytes;
     }
+    // ---- k-mers by source: one spectrum per input of a merged index, the dump filtered by per-source counts (sources attached) ----
+    /// What kmer_spectrum_by_source returns: hist[s * bins + c] = k-mers of the index that input s holds exactly c times (the last bin:
+    /// that often or more; bin 0: not at all), sharing[j] = k-mers held by exactly j inputs, per input the k-mers it holds and their occurrences.
+    struct SourceSpectrum {
+        std::size_t sources = 0, bins = 0;
+        std::vector<std::uint64_t> hist, sharing, distinct, occurrences;
+    };
+    /// What enumerate_kmers_by_source returns: k-mer words[i] occurs counts[i * sources + s] times in input s, in rows from l[i] on.
+    struct SourceKmers {
+        std::size_t sources = 0;
+        std::vector<std::uint64_t> words, counts, l;
+    };
+    /// "No upper limit" in max_counts; 0 there means ABSENT from that input.
+    static constexpr std::uint64_t kNoLimit = ~std::uint64_t(0);
+    SourceSpectrum kmer_spectrum_by_source(std::size_t k, std::size_t bins = 256) const {
+        SourceSpectrum s;
+        s.sources = static_cast<std::size_t>(msbwt_rle_source_count(raw_));
+        s.bins = bins;
+        s.hist.assign(std::max<std::size_t>(s.sources, 1) * bins, 0);
+        s.sharing.assign(s.sources + 1, 0);
+        s.distinct.assign(std::max<std::size_t>(s.sources, 1), 0);
+        s.occurrences.assign(std::max<std::size_t>(s.sources, 1), 0);
+        check(msbwt_rle_kmer_spectrum_by_source(raw_, k, s.hist.data(), bins, s.sharing.data(), s.distinct.data(), s.occurrences.data()));
+        return s;
+    }
+    /// The k-mers with min_counts[s] <= c_s <= max_counts[s] for every input s (empty vectors: zeros / no limits) and min_total <= sum <=
+    /// max_total (0: no upper limit), ascending when `sorted`: both calls of the two-call pattern.
+    SourceKmers enumerate_kmers_by_source(std::size_t k, const std::vector<std::uint64_t> &min_counts, const std::vector<std::uint64_t> &max_counts,
+                                          std::uint64_t min_total = 1, std::uint64_t max_total = 0, bool sorted = true) const {
+        SourceKmers out;
+        out.sources = static_cast<std::size_t>(msbwt_rle_source_count(raw_));
+        if ((!min_counts.empty() && min_counts.size() != out.sources) || (!max_counts.empty() && max_counts.size() != out.sources))
+            throw Panic(MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source: one limit per source");
+        const std::uint64_t *lo = min_counts.empty() ? nullptr : min_counts.data(), *hi = max_counts.empty() ? nullptr : max_counts.data();
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmers_by_source(raw_, k, lo, hi, min_total, max_total, sorted ? 1 : 0, nullptr, nullptr, nullptr, 0, &n));
+        out.words.resize(static_cast<std::size_t>(n));
+        out.counts.resize(out.words.size() * out.sources);
+        out.l.resize(out.words.size());
+        if (n) check(msbwt_rle_enumerate_kmers_by_source(raw_, k, lo, hi, min_total, max_total, sorted ? 1 : 0, out.words.data(), out.counts.data(), out.l.data(), n, &n));
+        return out;
+    }
+    /// Device buffers (d_counts: capacity x sources u64; d_counts, d_l may be null) -> the number of k-mers that qualify; capacity 0 only
+    /// counts.  The limits are host arrays (null: zeros / no limits).
+    std::uint64_t enumerate_kmers_by_source_device(std::size_t k, const std::uint64_t *min_counts, const std::uint64_t *max_counts, std::uint64_t min_total,
+                                                   std::uint64_t max_total, bool sorted, void *d_words, void *d_counts, void *d_l, std::uint64_t capacity,
+                                                   void *hip_stream) const {
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmers_by_source_device(raw_, k, min_counts, max_counts, min_total, max_total, sorted ? 1 : 0, d_words, d_counts, d_l, capacity, &n,
+                                                         hip_stream));
+        return n;
+    }
+    /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
+    std::uint64_t spectrum_scratch_bytes() const {
+        std::uint64_t bytes = 0;
+        check(msbwt_rle_spectrum_scratch_bytes(raw_, &bytes));
+        return bytes;
+    }
+    /// HBM bytes a by-source call allocates (and frees again) with the automatic frontier.
+    static std::uint64_t kmers_by_source_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::size_t n_sources, std::uint64_t records = 0,
+                                              bool sorted = false) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_kmers_by_source_plan(total_rows, free_hbm_bytes, n_sources, records, sorted ? 1 : 0, &bytes);
+        if (rc) throw Panic(rc, "msbwt_kmers_by_source_plan");
+        return bytes;
+    }
     /// Symbols an RLE stream encodes, counted up to 2^40 (the library refuses more).
     static std::uint64_t symbols_of(const std::vector<std::uint8_t> &rle) {
         std::uint64_t total = 0;

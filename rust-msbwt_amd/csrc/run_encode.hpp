@@ -20,6 +20,7 @@ hipError_t exclusive_scan(uint64_t *d, uint64_t n, uint64_t *scratch, hipStream_
 // device allocations of one build: whatever is still held when the build ends, however it ends, is freed
 struct Arena {
     std::vector<void *> held;
+    uint64_t taken = 0;  // bytes of every allocation made through take(), given back or not: what a call's scratch came to
     ~Arena() {
         for (void *p : held) (void)hipFree(p);
     }
@@ -27,7 +28,10 @@ struct Arena {
     hipError_t take(T **p, uint64_t bytes) {
         void *raw = nullptr;
         const hipError_t e = hipMalloc(&raw, size_t(std::max<uint64_t>(bytes, 256)));
-        if (e == hipSuccess) held.push_back(raw);
+        if (e == hipSuccess) {
+            held.push_back(raw);
+            taken += std::max<uint64_t>(bytes, 256);
+        }
         *p = static_cast<T *>(raw);
         return e;
     }

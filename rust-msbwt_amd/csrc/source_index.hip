@@ -20,6 +20,7 @@
 // rank(h) - rank(l): each bound its checkpoint plus the bytes from its block's start, at most 64 chunks, counted the same way.
 // Per-source counters never sit in an array indexed at run time (that would live in scratch memory): the loop over sources keeps
 // one count at a time and lane s & 7 of the group holds source s until eight of them leave as one 64-byte store.
+// The counting itself (source_count.hpp) is shared with the by-source k-mer sink (source_spectrum.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -28,6 +29,7 @@
 #include "rank_ops.hpp"
 #include "run_encode.hpp"
 #include "search_common.hpp"
+#include "source_count.hpp"
 #include "source_index.hpp"
 
 namespace msbwt {
@@ -35,7 +37,6 @@ namespace {
 
 constexpr uint32_t kThreads = 256;
 static_assert(kSourceBlockRows == kThreads * 4, "k_source_block_counts: one dword of rows per thread");
-static_assert(kSourceNarrow + 15 <= 2 * kGroup * 16 && kSourceNarrow <= 255, "a narrow range lies in two chunks per lane and its counts in a byte");
 
 // counts[s * columns + b] = rows of source s in block b (columns = nblocks + 1, the last column stays zero)
 __global__ __launch_bounds__(256) void k_source_block_counts(const uint32_t *__restrict__ rows4, uint64_t total, uint32_t n_sources, uint64_t nblocks,
@@ -76,35 +77,6 @@ __global__ __launch_bounds__(256) void k_source_checkpoints(const uint64_t *__re
     }
 }
 
-__device__ __forceinline__ uint32_t low_bytes(int n) {  // the n lowest bytes of a dword, n clamped to 0..4
-    n = min(max(n, 0), 4);
-    return n >= 4 ? ~0u : ((1u << (8 * n)) - 1u);
-}
-
-// the 16-byte chunk at byte p of the vector with every byte outside [l, h) made 0xFF, which equals no source
-__device__ __forceinline__ uint4 only_rows(uint4 c, uint64_t p, uint64_t l, uint64_t h) {
-    const int lo = l > p ? int(min(l - p, uint64_t(16))) : 0, hi = h > p ? int(min(h - p, uint64_t(16))) : 0;  // bytes lo .. hi - 1 of the chunk stay
-    return make_uint4(c.x | ~(low_bytes(hi) & ~low_bytes(lo)), c.y | ~(low_bytes(hi - 4) & ~low_bytes(lo - 4)),
-                      c.z | ~(low_bytes(hi - 8) & ~low_bytes(lo - 8)), c.w | ~(low_bytes(hi - 12) & ~low_bytes(lo - 12)));
-}
-
-// bytes of w equal to the byte s4 repeats (exact for any bytes: no borrow or carry crosses a byte)
-__device__ __forceinline__ uint32_t equal_bytes(uint32_t w, uint32_t s4) {
-    const uint32_t x = w ^ s4;
-    return uint32_t(__popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu)));
-}
-__device__ __forceinline__ uint32_t equal_bytes(uint4 c, uint32_t s4) {
-    return equal_bytes(c.x, s4) + equal_bytes(c.y, s4) + equal_bytes(c.z, s4) + equal_bytes(c.w, s4);
-}
-
-// this lane's share of the rows of source s4 in [from, to), `from` a multiple of 16 and to - from <= kSourceBlockRows
-__device__ __forceinline__ uint32_t span_count(const uint4 *__restrict__ rows16, uint64_t from, uint64_t to, uint32_t s4, uint32_t sub) {
-    uint32_t cnt = 0;
-#pragma unroll 1
-    for (uint64_t p = from + sub * 16u; p < to; p += kGroup * 16u) cnt += equal_bytes(only_rows(rows16[p >> 4], p, from, to), s4);
-    return cnt;
-}
-
 __global__ __launch_bounds__(256) void k_range_sources(const uint4 *__restrict__ rows16, const uint64_t *__restrict__ checkpoints, uint64_t total,
                                                        uint32_t n_sources, uint32_t stride, const uint64_t *__restrict__ ls, const uint64_t *__restrict__ hs,
                                                        uint32_t range_stride, uint64_t n, uint64_t *__restrict__ out, uint32_t *__restrict__ flags) {
@@ -118,30 +90,17 @@ __global__ __launch_bounds__(256) void k_range_sources(const uint4 *__restrict__
             if (fill && !(l == ~0ull && h == ~0ull) && sub == 0u) atomicOr(flags, kFlagInternal);
             for (uint32_t s = sub; s < n_sources; s += kGroup) row[s] = fill;
         } else if (h - l <= kSourceNarrow) {
-            const uint64_t p0 = (l & ~15ull) + sub * 16u, p1 = p0 + kGroup * 16u;
-            uint4 c0 = make_uint4(~0u, ~0u, ~0u, ~0u), c1 = c0;
-            if (p0 < h) c0 = only_rows(rows16[p0 >> 4], p0, l, h);
-            if (p1 < h) c1 = only_rows(rows16[p1 >> 4], p1, l, h);
+            const NarrowRows r = narrow_rows(rows16, l, h, sub);
 #pragma unroll 1
             for (uint32_t s0 = 0; s0 < n_sources; s0 += 4u) {  // sources s0 .. s0 + 3 in the four bytes of one dword: at most 32 each here, kSourceNarrow summed
-                uint32_t packed = 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 4u; ++j) {
-                    const uint32_t s4 = (s0 + j) * 0x01010101u;
-                    packed |= (equal_bytes(c0, s4) + equal_bytes(c1, s4)) << (8u * j);
-                }
-                packed = group_sum(packed);
+                const uint32_t packed = narrow_four(r, s0);
                 if (sub < 4u && s0 + sub < n_sources) row[s0 + sub] = (packed >> (8u * sub)) & 0xFFu;
             }
         } else {
-            const uint64_t bl = l >> kSourceBlockShift, bh = h >> kSourceBlockShift;
-            const uint64_t *cl = checkpoints + bl * stride, *ch = checkpoints + bh * stride;
             uint64_t mine = 0;  // source s in lane s & 7
 #pragma unroll 1
             for (uint32_t s = 0; s < n_sources; ++s) {
-                const uint32_t s4 = s * 0x01010101u;
-                const uint32_t part = span_count(rows16, bh << kSourceBlockShift, h, s4, sub) - span_count(rows16, bl << kSourceBlockShift, l, s4, sub);
-                const uint64_t count = ch[s] - cl[s] + uint64_t(int64_t(int32_t(group_sum(part))));
+                const uint64_t count = wide_count(rows16, checkpoints, stride, l, h, s, sub);
                 if (sub == (s & 7u)) mine = count;
                 if ((s & 7u) == 7u || s + 1u == n_sources) {
                     if ((s & ~7u) + sub <= s) row[(s & ~7u) + sub] = mine;

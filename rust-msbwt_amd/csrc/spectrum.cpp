@@ -1,7 +1,9 @@
 // The k-mers of a loaded index: abundance spectrum and k-mer dump (msbwt_rle_kmer_spectrum, msbwt_rle_enumerate_kmers[_device]), their
 // knobs, and the same two with a k-mer and its reverse complement merged into one class (msbwt_rle_canonical_kmer_spectrum,
 // msbwt_rle_enumerate_canonical_kmers[_device]: canonical.hpp; the other strand is counted by query.cpp's packed search).  Calls
-// spectrum.hip and canonical.hip through their headers and handle.hpp.  All scratch is allocated per call and freed before the call returns.
+// spectrum.hip and canonical.hip through their headers and handle.hpp.  The k-mers by source (msbwt_rle_kmer_spectrum_by_source,
+// msbwt_rle_enumerate_kmers_by_source[_device]: source_spectrum.hpp) are the same staged walk with the source sink behind it.  All
+// scratch is allocated per call and freed before the call returns.
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -10,6 +12,7 @@
 #include "canonical.hpp"
 #include "handle.hpp"
 #include "run_encode.hpp"
+#include "source_spectrum.hpp"
 #include "spectrum.hpp"
 
 namespace {
@@ -36,7 +39,8 @@ struct Clock {
     uint64_t us() const { return uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count()); }
 };
 
-void record(msbwt_rle *h, const SpectrumInfo &info, const Clock &clock) {
+void record(msbwt_rle *h, const SpectrumInfo &info, const Clock &clock, uint64_t scratch_bytes = 0) {
+    h->spectrum_scratch = scratch_bytes;
     uint64_t *w = h->spectrum_info;
     std::fill(w, w + MSBWT_SPECTRUM_INFO_WORDS, 0ull);
     w[0] = info.k;
@@ -110,7 +114,7 @@ int enumerate(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_co
     uint64_t n = 0;
     HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, &n, &info, stream));
     *out_n = n;
-    record(h, info, clock);
+    record(h, info, clock, s.arena.taken);
     if (capacity == 0 || n == 0) return MSBWT_OK;
     if (capacity < n)
         return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
@@ -131,7 +135,7 @@ int enumerate(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_co
     }
     HIP_TRY(h, spectrum_dump(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, d_kmers, d_counts, d_l, capacity, h->d_flags + which, &info,
                              stream));
-    record(h, info, clock);
+    record(h, info, clock, s.arena.taken);
     if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
     HIP_TRY(h, hipMemcpyAsync(out_kmers, d_kmers, n * 8, hipMemcpyDeviceToHost, stream));
     if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, d_counts, n * 8, hipMemcpyDeviceToHost, stream));
@@ -195,7 +199,7 @@ int enumerate_canonical(const msbwt_rle *ch, size_t k, uint64_t min_count, uint6
     if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
     const uint64_t n = totals[kCanonicalClasses];
     *out_n = n;
-    record(h, info, clock);
+    record(h, info, clock, s.arena.taken);
     if (capacity == 0 || n == 0) return host ? status_of(h, stream, which) : int(MSBWT_OK);
     if (capacity < n)
         return fail(h, MSBWT_ERR_INVALID_ARG,
@@ -221,11 +225,148 @@ int enumerate_canonical(const msbwt_rle *ch, size_t k, uint64_t min_count, uint6
         sink.capacity = n;
     }
     if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
-    record(h, info, clock);
+    record(h, info, clock, s.arena.taken);
     if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
     HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
     if (out_own) HIP_TRY(h, hipMemcpyAsync(out_own, sink.own, n * 8, hipMemcpyDeviceToHost, stream));
     if (out_other) HIP_TRY(h, hipMemcpyAsync(out_other, sink.other, n * 8, hipMemcpyDeviceToHost, stream));
+    return status_of(h, stream, which);  // synchronises
+}
+
+// ---- k-mers by source ----
+
+int need_sources(msbwt_rle *h) { return h->sources.n_sources ? int(MSBWT_OK) : fail(h, MSBWT_ERR_NOT_LOADED, "no sources attached"); }
+
+// bytes of scratch a by-source call allocates: the walk's (plan_bytes), the sink's fixed words, and per record staged for a host dump
+// the word, l and the S counts.  Nothing here grows with frontier x sources.
+int by_source_plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t frontier, size_t n_sources, uint64_t records, bool sorted, uint64_t *bytes) {
+    if (n_sources < 1 || n_sources > kSourceMax) return MSBWT_ERR_INVALID_ARG;
+    if (records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
+    if (int rc = plan_bytes(total_rows, free_bytes, frontier, 0, sorted, bytes)) return rc;
+    *bytes += kSourceSinkFixedBytes + records * (2 + n_sources) * sizeof(uint64_t);
+    return MSBWT_OK;
+}
+
+// the sink's fixed words: the limits, then the totals
+struct SourceFixed {
+    uint64_t *limits = nullptr;
+    unsigned long long *totals = nullptr;
+};
+
+int take_source_fixed(msbwt_rle *h, Scratch &s, SourceFixed &f, const char *what) {
+    if (s.arena.take(&f.limits, kSourceSinkFixedBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, std::string(what) + ": " + std::to_string(kSourceSinkFixedBytes) + " more bytes of HBM needed for the sink");
+    }
+    f.totals = reinterpret_cast<unsigned long long *>(f.limits + 2 * kSourceMax);
+    return MSBWT_OK;
+}
+
+// One walk of a by-source call: chunk by chunk the k-mers at least `prune` wide are staged and handed to the source sink (its totals:
+// f.totals, copied to totals[] at the end).  Synchronises the stream.
+int by_source_walk(msbwt_rle *h, const Scratch &s, const SourceFixed &f, size_t k, uint64_t prune, SourceSink sink, SpectrumInfo *info, hipStream_t stream, uint64_t *totals) {
+    sink.totals = f.totals;
+    sink.limits = f.limits;
+    HIP_TRY(h, hipMemsetAsync(f.totals, 0, kSourceTotalWords * 8, stream));
+    const SourceView view = h->sources.view(h->totals.total);
+    const SpectrumChunkHook per_chunk = [&](const void *d_kmers, uint64_t m) { return launch_source_sink(d_kmers, m, view, sink, stream); };
+    HIP_TRY(h, spectrum_stage(view_of(h), seeds_of(h, k), uint32_t(k), prune, s.work, s.frontier, per_chunk, info, stream));
+    HIP_TRY(h, hipMemcpyAsync(totals, f.totals, kSourceTotalWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    return MSBWT_OK;
+}
+
+uint64_t add_saturating(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+
+// Both forms of the by-source dump, as enumerate() above: records (word, c_0 .. c_{S-1}, l).
+int enumerate_by_source(const msbwt_rle *ch, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total, uint64_t max_total, int sorted, bool host,
+                        void *out_kmers, void *out_counts, void *out_l, uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
+    Call c(ch);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (int rc = need_sources(h)) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source needs 1 <= k <= 32");
+    const uint64_t S = h->sources.n_sources;
+    uint64_t limits[2 * kSourceMax];
+    uint64_t prune = std::max<uint64_t>(min_total, 1), min_sum = 0;
+    for (uint32_t s = 0; s < kSourceMax; ++s) {
+        limits[s] = s < S && min_counts ? min_counts[s] : 0ull;
+        limits[kSourceMax + s] = s < S && max_counts ? max_counts[s] : ~0ull;
+        if (limits[s] > limits[kSourceMax + s]) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source: min_counts[" + std::to_string(s) + "] > max_counts[" + std::to_string(s) + "]");
+        min_sum = add_saturating(min_sum, limits[s]);
+    }
+    if (max_total != 0 && min_total > max_total) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source: min_total > max_total");
+    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    if (host) stream = h->stream;
+    const Clock clock;
+    *out_n = 0;
+    SpectrumInfo info;
+    info.k = k;
+    if (h->totals.total == 0) {
+        record(h, info, clock);
+        return MSBWT_OK;
+    }
+    // a suffix's total is at least the k-mer's, and the k-mer's is at least the sum of its minima
+    prune = std::max(prune, min_sum);
+    const bool rank = sorted != 0 && capacity != 0;
+    Scratch s;
+    if (int rc = take_scratch(h, s, rank, kSourceSinkFixedBytes, "enumerate_kmers_by_source")) return rc;
+    SourceFixed f;
+    if (int rc = take_source_fixed(h, s, f, "enumerate_kmers_by_source")) return rc;
+    HIP_TRY(h, hipMemcpyAsync(f.limits, limits, sizeof limits, hipMemcpyHostToDevice, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));  // (the limits are this frame's)
+    SourceSink sink{};
+    sink.mode = kSourceSinkCount;
+    sink.min_total = std::max<uint64_t>(min_total, 1);
+    sink.max_total = max_total ? max_total : ~0ull;
+    sink.flags = h->d_flags + which;
+    SpectrumRank r{};
+    if (rank) {
+        r = spectrum_rank_view(s.rank, h->totals.total);
+        HIP_TRY(h, spectrum_rank_clear(r, stream));
+        sink.bitmap = r.bitmap;
+    }
+    uint64_t totals[kSourceTotalWords] = {};
+    if (int rc = by_source_walk(h, s, f, k, prune, sink, &info, stream, totals)) return rc;
+    const uint64_t n = totals[kSourcePassed];
+    *out_n = n;
+    record(h, info, clock, s.arena.taken);
+    if (capacity == 0 || n == 0) return host ? status_of(h, stream, which) : int(MSBWT_OK);
+    if (capacity < n)
+        return fail(h, MSBWT_ERR_INVALID_ARG,
+                    "enumerate_kmers_by_source: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
+    sink.mode = rank ? kSourceSinkScatter : kSourceSinkAppend;
+    sink.kmers = static_cast<uint64_t *>(out_kmers);
+    sink.counts = static_cast<uint64_t *>(out_counts);
+    sink.l = static_cast<uint64_t *>(out_l);
+    sink.capacity = capacity;
+    if (rank) {
+        HIP_TRY(h, spectrum_rank_close(r, stream));
+        sink.prefix = r.prefix;
+    }
+    if (host) {  // records staged in HBM, then copied out
+        const uint64_t words = n * (1 + (out_counts ? S : 0) + (out_l ? 1 : 0));
+        uint64_t *stage = nullptr;
+        size_t free_bytes = 0, all_bytes = 0;
+        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+        if (free_bytes < words * 8 || s.arena.take(&stage, words * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "enumerate_kmers_by_source: " + std::to_string(words * 8) + " more bytes of HBM needed for the records");
+        }
+        sink.kmers = stage;
+        sink.l = out_l ? stage + n : nullptr;
+        sink.counts = out_counts ? stage + n * (out_l ? 2 : 1) : nullptr;
+        sink.capacity = n;
+    }
+    if (int rc = by_source_walk(h, s, f, k, prune, sink, &info, stream, totals)) return rc;
+    record(h, info, clock, s.arena.taken);
+    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
+    HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, sink.counts, n * S * 8, hipMemcpyDeviceToHost, stream));
+    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, sink.l, n * 8, hipMemcpyDeviceToHost, stream));
     return status_of(h, stream, which);  // synchronises
 }
 
@@ -243,6 +384,7 @@ int msbwt_rle_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, 
     if (int rc = c.bind()) return rc;
     if (int rc = ensure_runtime(h)) return rc;
     const Clock clock;
+    uint64_t scratch_bytes = 0;
     SpectrumInfo info;
     info.k = k;
     uint64_t distinct = 0, occurrences = 0;
@@ -259,10 +401,11 @@ int msbwt_rle_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, 
         HIP_TRY(h, spectrum_histogram(view_of(h), seeds_of(h, k), uint32_t(k), s.work, s.frontier, d_hist, n_bins, &distinct, &occurrences, &info, h->stream));
         HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
+        scratch_bytes = s.arena.taken;
     }
     if (out_distinct) *out_distinct = distinct;
     if (out_occurrences) *out_occurrences = occurrences;
-    record(h, info, clock);
+    record(h, info, clock, scratch_bytes);
     return MSBWT_OK;
 }
 
@@ -318,6 +461,7 @@ int msbwt_rle_canonical_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *
     if (int rc = c.bind()) return rc;
     if (int rc = ensure_runtime(h)) return rc;
     const Clock clock;
+    uint64_t scratch_bytes = 0;
     SpectrumInfo info;
     info.k = k;
     uint64_t totals[kCanonicalTotalWords] = {};
@@ -340,10 +484,11 @@ int msbwt_rle_canonical_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *
         if (int rc = canonical_walk(h, s, k, 1, sink, &info, h->stream, kHostFlags, totals)) return rc;
         HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
         if (int rc = status_of(h, h->stream, kHostFlags)) return rc;  // synchronises; the search's flags
+        scratch_bytes = s.arena.taken;
     }
     if (out_distinct) *out_distinct = totals[kCanonicalClasses];
     if (out_occurrences) *out_occurrences = totals[kCanonicalOccurrences];
-    record(h, info, clock);
+    record(h, info, clock, scratch_bytes);
     return MSBWT_OK;
 }
 
@@ -362,6 +507,87 @@ int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t 
     uint64_t bytes = 0;
     if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, false, &bytes)) return rc;
     if (device_bytes) *device_bytes = bytes + spectrum_frontier_nodes(total_rows, free_hbm_bytes, 0) * kCanonicalStageBytes;
+    return MSBWT_OK;
+}
+
+// ---- k-mers by source: one spectrum per input of a merged index, and the dump filtered by per-source counts ----
+
+int msbwt_rle_kmer_spectrum_by_source(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_sharing, uint64_t *out_distinct,
+                                      uint64_t *out_occurrences) {
+    Call c(bwt);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (int rc = need_sources(h)) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum_by_source needs 1 <= k <= 32");
+    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum_by_source needs histograms of at least 2 bins");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    const Clock clock;
+    uint64_t scratch_bytes = 0;
+    SpectrumInfo info;
+    info.k = k;
+    const uint64_t S = h->sources.n_sources, hist_bytes = S * uint64_t(n_bins) * 8;
+    uint64_t totals[kSourceTotalWords] = {};
+    std::fill(out_hist, out_hist + S * n_bins, 0ull);
+    if (h->totals.total != 0) {
+        Scratch s;
+        if (int rc = take_scratch(h, s, false, hist_bytes + kSourceSinkFixedBytes, "kmer_spectrum_by_source")) return rc;
+        SourceFixed f;
+        if (int rc = take_source_fixed(h, s, f, "kmer_spectrum_by_source")) return rc;
+        uint64_t *d_hist = nullptr;
+        if (s.arena.take(&d_hist, hist_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, "kmer_spectrum_by_source: " + std::to_string(hist_bytes) + " bytes of HBM needed for the histograms");
+        }
+        HIP_TRY(h, hipMemsetAsync(d_hist, 0, hist_bytes, h->stream));
+        SourceSink sink{};
+        sink.mode = kSourceSinkHist;
+        sink.min_total = 1;
+        sink.max_total = ~0ull;
+        sink.hist = reinterpret_cast<unsigned long long *>(d_hist);
+        sink.n_bins = n_bins;
+        sink.flags = h->d_flags + kHostFlags;
+        if (int rc = by_source_walk(h, s, f, k, 1, sink, &info, h->stream, totals)) return rc;
+        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = status_of(h, h->stream, kHostFlags)) return rc;  // synchronises
+        scratch_bytes = s.arena.taken;
+    }
+    for (uint64_t s = 0; s < S; ++s) {  // bin 0: the k-mers of the index that source s does not hold
+        uint64_t *row = out_hist + s * n_bins, distinct = 0;
+        for (size_t b = 1; b < n_bins; ++b) distinct += row[b];
+        row[0] = info.nodes[k] - distinct;
+        if (out_distinct) out_distinct[s] = distinct;
+        if (out_occurrences) out_occurrences[s] = totals[kSourceOccurrences + s];
+    }
+    if (out_sharing) std::copy(totals + kSourceSharing, totals + kSourceSharing + S + 1, out_sharing);
+    record(h, info, clock, scratch_bytes);
+    return MSBWT_OK;
+}
+
+int msbwt_rle_enumerate_kmers_by_source(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total, uint64_t max_total,
+                                        int sorted, uint64_t *out_kmers2bit, uint64_t *out_counts, uint64_t *out_l, uint64_t capacity, uint64_t *out_n) {
+    return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr, kHostFlags);
+}
+
+int msbwt_rle_enumerate_kmers_by_source_device(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total,
+                                               uint64_t max_total, int sorted, void *d_out_kmers2bit, void *d_out_counts, void *d_out_l, uint64_t capacity,
+                                               uint64_t *out_n, void *hip_stream) {
+    return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n,
+                               static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+}
+
+int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes) {
+    Call c(bwt);
+    if (!c.h || !out_bytes) return MSBWT_ERR_INVALID_ARG;
+    *out_bytes = c.h->spectrum_scratch;
+    return MSBWT_OK;
+}
+
+int msbwt_kmers_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, size_t n_sources, uint64_t records, int sorted, uint64_t *device_bytes) {
+    uint64_t bytes = 0;
+    if (int rc = by_source_plan_bytes(total_rows, free_hbm_bytes, 0, n_sources, records, sorted != 0, &bytes)) return rc;
+    if (device_bytes) *device_bytes = bytes;
     return MSBWT_OK;
 }
 

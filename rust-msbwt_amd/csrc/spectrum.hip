@@ -69,12 +69,7 @@ struct Sink : PlainSink {
             if (bitmap) atomicOr(bitmap + (a >> 5), 1u << (uint32_t(a) & 31u));
         } else {
             uint64_t place = at++;
-            if (mode == kSinkScatter) {  // marked rows below a: the checkpoint, whole words of the block, the word's low bits
-                const uint64_t word = a >> 5, first = (a / kSpectrumRankRows) * kRankWords;
-                place = prefix[a / kSpectrumRankRows];
-                for (uint64_t j = first; j < word; ++j) place += uint32_t(__popc(bitmap[j]));
-                place += uint32_t(__popc(bitmap[word] & low_bits(int(uint32_t(a) & 31u))));
-            }
+            if (mode == kSinkScatter) place = spectrum_rank_below(bitmap, prefix, a);
             if (place < capacity) {
                 kmers[place] = key;
                 if (counts) counts[place] = width;
@@ -129,14 +124,14 @@ __global__ __launch_bounds__(256) void k_spectrum_block_marks(const uint32_t *__
 
 uint64_t rank_blocks(uint64_t total) { return total / kSpectrumRankRows + 1; }
 
-struct RankView {  // the sorted dump's scratch: bitmap | checkpoints | scan scratch
-    uint32_t *bitmap;
-    uint64_t *prefix, *scan;
-    uint64_t nblocks;
-};
+}  // namespace
 
-RankView rank_view(const void *d_rank, uint64_t total) {
-    RankView r;
+uint64_t spectrum_frontier_nodes(uint64_t total, uint64_t free_bytes, uint64_t wanted) { return walk_frontier_nodes(total, free_bytes, wanted); }
+
+uint64_t spectrum_work_bytes(uint64_t frontier_nodes) { return walk_work_bytes(frontier_nodes); }
+
+SpectrumRank spectrum_rank_view(const void *d_rank, uint64_t total) {
+    SpectrumRank r;
     r.nblocks = rank_blocks(total);
     char *base = static_cast<char *>(const_cast<void *>(d_rank));
     r.bitmap = reinterpret_cast<uint32_t *>(base);
@@ -145,11 +140,13 @@ RankView rank_view(const void *d_rank, uint64_t total) {
     return r;
 }
 
-}  // namespace
+hipError_t spectrum_rank_clear(const SpectrumRank &r, hipStream_t stream) { return hipMemsetAsync(r.bitmap, 0, r.nblocks * (kSpectrumRankRows / 8), stream); }
 
-uint64_t spectrum_frontier_nodes(uint64_t total, uint64_t free_bytes, uint64_t wanted) { return walk_frontier_nodes(total, free_bytes, wanted); }
-
-uint64_t spectrum_work_bytes(uint64_t frontier_nodes) { return walk_work_bytes(frontier_nodes); }
+hipError_t spectrum_rank_close(const SpectrumRank &r, hipStream_t stream) {
+    hipLaunchKernelGGL(k_spectrum_block_marks, dim3(uint32_t(std::min<uint64_t>((r.nblocks + 255) / 256, 2048))), dim3(256), 0, stream, r.bitmap, r.nblocks, r.prefix);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : exclusive_scan(r.prefix, r.nblocks, r.scan, stream);
+}
 
 uint64_t spectrum_rank_bytes(uint64_t total) {
     const uint64_t nblocks = rank_blocks(total);
@@ -177,10 +174,10 @@ hipError_t spectrum_count(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, 
     sink.mode = kSinkCount;
     sink.min = std::max<uint64_t>(min_count, 1);
     sink.max = max_count ? max_count : ~0ull;
-    RankView r{};
+    SpectrumRank r{};
     if (d_rank) {
-        r = rank_view(d_rank, ix.total);
-        const hipError_t e = hipMemsetAsync(r.bitmap, 0, r.nblocks * (kSpectrumRankRows / 8), stream);
+        r = spectrum_rank_view(d_rank, ix.total);
+        const hipError_t e = spectrum_rank_clear(r, stream);
         if (e != hipSuccess) return e;
         sink.bitmap = r.bitmap;
     }
@@ -188,9 +185,7 @@ hipError_t spectrum_count(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, 
     if (e != hipSuccess) return e;
     *n = info->nodes[k];
     if (d_rank) {
-        hipLaunchKernelGGL(k_spectrum_block_marks, dim3(uint32_t(std::min<uint64_t>((r.nblocks + 255) / 256, 2048))), dim3(256), 0, stream, r.bitmap, r.nblocks, r.prefix);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = exclusive_scan(r.prefix, r.nblocks, r.scan, stream)) != hipSuccess) return e;
+        if ((e = spectrum_rank_close(r, stream)) != hipSuccess) return e;
         e = hipStreamSynchronize(stream);
     }
     return e;
@@ -205,7 +200,7 @@ hipError_t spectrum_dump(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, u
     sink.min = std::max<uint64_t>(min_count, 1);
     sink.max = max_count ? max_count : ~0ull;
     if (d_rank) {
-        const RankView r = rank_view(d_rank, ix.total);
+        const SpectrumRank r = spectrum_rank_view(d_rank, ix.total);
         sink.bitmap = r.bitmap;
         sink.prefix = r.prefix;
     }

@@ -52,6 +52,28 @@ hipError_t spectrum_dump(const IndexView &ix, SpectrumSeeds seeds, uint32_t k, u
                          const void *d_rank, uint64_t *d_kmers, uint64_t *d_counts, uint64_t *d_l, uint64_t capacity, uint32_t *flags, SpectrumInfo *info,
                          hipStream_t stream);
 
+// ---- the rank view of a sorted dump: the scratch of spectrum_rank_bytes as bitmap | checkpoints | scan scratch ----
+// The counting walk sets the bit of every emitted k-mer's l; spectrum_rank_close makes the checkpoints; the writing walk places each
+// record at spectrum_rank_below(l).  Shared with the by-source dump (source_spectrum.hip), whose emitted k-mers have rows of their own too.
+struct SpectrumRank {
+    uint32_t *bitmap;
+    uint64_t *prefix, *scan;
+    uint64_t nblocks;
+};
+SpectrumRank spectrum_rank_view(const void *d_rank, uint64_t total);
+hipError_t spectrum_rank_clear(const SpectrumRank &r, hipStream_t stream);  // no row marked
+hipError_t spectrum_rank_close(const SpectrumRank &r, hipStream_t stream);  // prefix[b] = marked rows before block b (enqueued; nothing synchronises)
+#ifdef __HIP__
+// marked rows below row a: the checkpoint, whole words of the block, the word's low bits
+__device__ __forceinline__ uint64_t spectrum_rank_below(const uint32_t *__restrict__ bitmap, const uint64_t *__restrict__ prefix, uint64_t a) {
+    constexpr uint64_t kWords = kSpectrumRankRows / 32;
+    const uint64_t word = a >> 5, first = (a / kSpectrumRankRows) * kWords;
+    uint64_t below = prefix[a / kSpectrumRankRows];
+    for (uint64_t j = first; j < word; ++j) below += uint32_t(__popc(bitmap[j]));
+    return below + uint32_t(__popc(bitmap[word] & ((1u << (uint32_t(a) & 31u)) - 1u)));
+}
+#endif
+
 // The walk with the last level STAGED instead of sunk (the canonical calls, canonical.hpp): chunk by chunk, after the synchronisation
 // that reads the chunk's cursors, per_chunk(d_kmers, m) gets the m >= 1 k-mers of the chunk that are at least `prune` wide as 24-byte
 // records {word, l, h} in a frontier buffer, which the next chunk overwrites: what the hook enqueues on `stream` reads them in time,

@@ -89,6 +89,9 @@ def _pack_rles(rles):
     return (np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)), offsets
 
 
+_U64_MAX = (1 << 64) - 1
+
+
 def _call_growing(call, cap):
     """call(out, cap, &length) with an output buffer of `cap` bytes, once more with a larger one if the library says it needs more:
     (return code, the bytes written)."""
@@ -420,6 +423,81 @@ class RleBWT(BWT):
                 err.n = n.value
                 raise
         return n.value
+
+    # ---- the k-mers of a merged index by source: one spectrum per input, and the dump filtered by per-source counts ----
+    def _source_limits(self, min_counts, max_counts):
+        """(min, max) as uint64[S] or None; in max_counts None or a negative entry is "no limit", 0 is "absent from this source"."""
+        S = self.source_count()
+        lo = hi = None
+        if min_counts is not None:
+            lo = np.ascontiguousarray(min_counts, dtype=np.uint64)
+        if max_counts is not None:
+            hi = np.array([_U64_MAX if m is None or int(m) < 0 else int(m) for m in max_counts], dtype=np.uint64)
+        for a in (lo, hi):
+            if a is not None and a.shape != (S,):
+                raise ValueError("min_counts and max_counts hold one entry per source (%d)" % S)
+        return lo, hi
+
+    def kmer_spectrum_by_source(self, k, bins=256):
+        """msbwt_rle_kmer_spectrum_by_source -> (hist[S, bins], sharing[S + 1], distinct[S], occurrences[S]), uint64: hist[s, c] = k-mers
+        of the merged index that input s holds exactly c times (hist[s, bins - 1]: bins - 1 times or more, hist[s, 0]: not at all);
+        sharing[j] = k-mers held by exactly j inputs; per input the k-mers it holds and the sum of their counts."""
+        S = self.source_count()
+        hist = np.zeros((max(S, 1), int(bins)), dtype=np.uint64)
+        sharing, distinct, occurrences = np.zeros(S + 1, dtype=np.uint64), np.zeros(max(S, 1), dtype=np.uint64), np.zeros(max(S, 1), dtype=np.uint64)
+        rc = _lib.lib().msbwt_rle_kmer_spectrum_by_source(self._h, int(k), hist.ctypes.data_as(C.c_void_p) if hist.size else None, int(bins),
+                                                          sharing.ctypes.data_as(C.c_void_p), distinct.ctypes.data_as(C.c_void_p),
+                                                          occurrences.ctypes.data_as(C.c_void_p))
+        if rc:
+            _raise(rc, self._h)
+        return hist[:S], sharing, distinct[:S], occurrences[:S]
+
+    def enumerate_kmers_by_source(self, k, min_counts=None, max_counts=None, min_total=1, max_total=None, sorted=True, ranges=False):
+        """msbwt_rle_enumerate_kmers_by_source, both calls of the two-call pattern -> (words, counts[n, S][, l]): the k-mers with
+        min_counts[s] <= counts[:, s] <= max_counts[s] for every input s and min_total <= counts.sum(1) <= max_total.  In max_counts
+        None (the whole argument or an entry) is no limit and 0 means ABSENT from that input: "private to input 0" is
+        max_counts=[None, 0, 0, ...].  sorted: ascending k-mers; ranges=True adds the start l of each one's range."""
+        lib, n, S = _lib.lib(), C.c_uint64(0), self.source_count()
+        lo, hi = self._source_limits(min_counts, max_counts) if S else (None, None)
+        args = (self._h, int(k), lo.ctypes.data_as(C.c_void_p) if lo is not None else None, hi.ctypes.data_as(C.c_void_p) if hi is not None else None,
+                int(min_total), int(max_total or 0), 1 if sorted else 0)
+        rc = lib.msbwt_rle_enumerate_kmers_by_source(*args, None, None, None, 0, C.byref(n))
+        if rc:
+            _raise(rc, self._h)
+        words, counts = np.empty(n.value, dtype=np.uint64), np.empty((n.value, S), dtype=np.uint64)
+        l = np.empty(n.value, dtype=np.uint64) if ranges else None
+        if n.value:
+            rc = lib.msbwt_rle_enumerate_kmers_by_source(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                         l.ctypes.data_as(C.c_void_p) if ranges else None, n.value, C.byref(n))
+            if rc:
+                _raise(rc, self._h)
+        return (words, counts, l) if ranges else (words, counts)
+
+    def enumerate_kmers_by_source_device(self, k, d_words, d_counts, d_l, capacity, min_counts=None, max_counts=None, min_total=1, max_total=None, sorted=True,
+                                         stream=0):
+        """msbwt_rle_enumerate_kmers_by_source_device: device pointers (ints; d_counts -- capacity x S u64 -- and d_l may be None) -> n,
+        the k-mers that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  The limits are host arrays, as in
+        enumerate_kmers_by_source.  Synchronises `stream`."""
+        n = C.c_uint64(0)
+        lo, hi = self._source_limits(min_counts, max_counts) if self.source_count() else (None, None)
+        rc = _lib.lib().msbwt_rle_enumerate_kmers_by_source_device(self._h, int(k), lo.ctypes.data_as(C.c_void_p) if lo is not None else None,
+                                                                   hi.ctypes.data_as(C.c_void_p) if hi is not None else None, int(min_total), int(max_total or 0),
+                                                                   1 if sorted else 0, d_words, d_counts, d_l, int(capacity), C.byref(n), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n = n.value
+                raise
+        return n.value
+
+    def spectrum_scratch_bytes(self):
+        """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""
+        out = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_spectrum_scratch_bytes(self._h, C.byref(out))
+        if rc:
+            _raise(rc, self._h)
+        return out.value
 
     def set_spectrum_frontier(self, nodes):
         """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""

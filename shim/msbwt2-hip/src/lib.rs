@@ -86,6 +86,15 @@ extern "C" {
     fn msbwt_rle_enumerate_canonical_kmers(bwt: *const MsbwtRle, k: usize, min_count: u64, max_count: u64,
                                            out_kmers2bit: *mut u64, out_own: *mut u64, out_other: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
     fn msbwt_canonical_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, device_bytes: *mut u64) -> c_int;
+    // k-mers by source: one spectrum per input of a merged index, and the dump filtered by per-source counts (word, c_0 .. c_{S-1}, l)
+    fn msbwt_rle_kmer_spectrum_by_source(bwt: *const MsbwtRle, k: usize, out_hist: *mut u64, n_bins: usize, out_sharing: *mut u64,
+                                         out_distinct: *mut u64, out_occurrences: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_kmers_by_source(bwt: *const MsbwtRle, k: usize, min_counts: *const u64, max_counts: *const u64,
+                                           min_total: u64, max_total: u64, sorted: c_int, out_kmers2bit: *mut u64,
+                                           out_counts: *mut u64, out_l: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
+    fn msbwt_kmers_by_source_plan(total_rows: u64, free_hbm_bytes: u64, n_sources: usize, records: u64, sorted: c_int,
+                                  device_bytes: *mut u64) -> c_int;
+    fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -423,6 +432,64 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_canonical_plan(total_rows, free_hbm_bytes, records, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "canonical_plan: {} rows", total_rows);
+        bytes
+    }
+
+    /// One abundance spectrum per input of a merged index (sources attached): (hist[S x bins] row-major, sharing[S + 1], distinct[S],
+    /// occurrences[S]); hist[s * bins + c] = k-mers of the index that input s holds exactly c times (the last bin: that often or
+    /// more; bin 0: not at all), sharing[j] = k-mers held by exactly j inputs.
+    pub fn kmer_spectrum_by_source(&self, k: usize, bins: usize) -> (Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>) {
+        let s = self.source_count();
+        let mut hist = vec![0u64; (s * bins).max(1)];  // (fewer than 2 bins: the library refuses them)
+        let (mut sharing, mut distinct, mut occurrences) = (vec![0u64; s + 1], vec![0u64; s.max(1)], vec![0u64; s.max(1)]);
+        let rc = unsafe {
+            msbwt_rle_kmer_spectrum_by_source(self.raw, k, hist.as_mut_ptr(), bins, sharing.as_mut_ptr(), distinct.as_mut_ptr(),
+                                              occurrences.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("kmer_spectrum_by_source: {}", self.last_error()); }
+        hist.truncate(s * bins);
+        distinct.truncate(s);
+        occurrences.truncate(s);
+        (hist, sharing, distinct, occurrences)
+    }
+
+    /// The k-mers with min_counts[s] <= c_s <= max_counts[s] for every input s and min_total <= sum <= max_total (0: no upper limit)
+    /// as (2-bit words, counts[n x S] row-major, range starts), ascending when `sorted`.  In max_counts u64::MAX is "no limit" and 0
+    /// means ABSENT from that input: private to input 0 is max_counts = [u64::MAX, 0, 0, ..].
+    pub fn enumerate_kmers_by_source(&self, k: usize, min_counts: &[u64], max_counts: &[u64], min_total: u64, max_total: u64,
+                                     sorted: bool) -> (Vec<u64>, Vec<u64>, Vec<u64>) {
+        let s = self.source_count();
+        assert!(min_counts.len() == s && max_counts.len() == s, "enumerate_kmers_by_source: one limit per source ({})", s);
+        let mut n = 0u64;
+        let rc = unsafe {
+            msbwt_rle_enumerate_kmers_by_source(self.raw, k, min_counts.as_ptr(), max_counts.as_ptr(), min_total, max_total, sorted as c_int,
+                                                std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n)
+        };
+        if rc != MSBWT_OK { panic!("enumerate_kmers_by_source: {}", self.last_error()); }
+        let (mut words, mut counts, mut l) = (vec![0u64; n as usize], vec![0u64; n as usize * s], vec![0u64; n as usize]);
+        if n > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_kmers_by_source(self.raw, k, min_counts.as_ptr(), max_counts.as_ptr(), min_total, max_total, sorted as c_int,
+                                                    words.as_mut_ptr(), counts.as_mut_ptr(), l.as_mut_ptr(), n, &mut n)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_kmers_by_source: {}", self.last_error()); }
+        }
+        (words, counts, l)
+    }
+
+    /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
+    pub fn spectrum_scratch_bytes(&self) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_rle_spectrum_scratch_bytes(self.raw, &mut bytes) };
+        if rc != MSBWT_OK { panic!("spectrum_scratch_bytes: {}", self.last_error()); }
+        bytes
+    }
+
+    /// HBM bytes a by-source call allocates and frees again (pure function).
+    pub fn kmers_by_source_plan(total_rows: u64, free_hbm_bytes: u64, n_sources: usize, records: u64, sorted: bool) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_kmers_by_source_plan(total_rows, free_hbm_bytes, n_sources, records, sorted as c_int, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "kmers_by_source_plan: {} rows, {} sources", total_rows, n_sources);
         bytes
     }
 
