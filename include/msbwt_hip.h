@@ -448,7 +448,54 @@ int msbwt_rle_enumerate_kmers_by_source_device(const msbwt_rle *bwt, size_t k, c
 int msbwt_kmers_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, size_t n_sources, uint64_t records, int sorted,
                                uint64_t *device_bytes);
 
-/* The bytes of scratch the handle's last k-mer walk call (any call of the three sections above that walks) allocated in HBM and freed
+/* ---- the k-mer graph: how the k-mers of an index connect (no reference counterpart) ----
+ * The de Bruijn graph of the reads as ONE object: the sorted k-mer dump with an edge byte per k-mer, and the table of (in, out) degrees.
+ * Everything is defined through count_kmer alone.  NODES: for 1 <= k <= 32 and the node threshold m = max(min_count, 1), the k-mers q
+ * over A C G T with count_kmer(q) >= m.  EDGES: with the edge threshold me (min_edge == 0: me = m; 0 < min_edge < m:
+ * MSBWT_ERR_INVALID_ARG), the (k+1)-mers e over A C G T with count_kmer(e) >= me; e goes from e[0..k) to e[1..k].  Both ends of every
+ * edge are nodes -- a k-mer occurs at least as often as any (k+1)-mer that holds it, and me >= m -- which is why the call has no
+ * max_count: a caller drops high-copy nodes by the counts it gets back.
+ * EDGE BYTE of a node q: bit j (j = 0..3 for A C G T) is set when the edge j.q exists (its predecessors), bit 4 + j when the edge q.j
+ * exists (its successors).  A window that holds '$' or 'N' is no k-mer and no edge, so a read that starts or ends at q adds no bit; a
+ * self-loop (A^k with A^(k+1)) sets a predecessor bit and a successor bit of the same node.
+ *
+ * msbwt_rle_enumerate_kmer_graph[_device]: records in ascending k-mer order, always (placement by rank is what the edge pass rests on):
+ * words, counts and l exactly as msbwt_rle_enumerate_kmers(k, m, 0, sorted = 1, ..) gives them, and out_edges, one byte per record.
+ * Capacity as for the other dumps: *out_n is always set; capacity == 0 only counts; 0 < capacity < n writes NOTHING, returns
+ * MSBWT_ERR_INVALID_ARG and names n in the message.  Any of the four output buffers may be NULL.  The _device form writes to device
+ * buffers on the handle's device (d_out_edges needs no alignment, and nothing past its first n bytes is touched), synchronises the
+ * stream and reports a device fault through msbwt_rle_device_status.  A call that fills buffers walks twice (count and mark, then write).
+ * msbwt_rle_kmer_graph_degrees: out_table[5 i + o] = the nodes with i predecessors and o successors; *out_nodes = the sum of the
+ * table; *out_edges = the number of edges, which is the sum of the in-degrees and the sum of the out-degrees alike.  Either pointer
+ * (and out_table) may be NULL.  No record leaves the device.
+ *
+ * How: the counting walk of the sorted dump marks every node's l; the writing walk stages each chunk's nodes, and one kernel per chunk
+ * takes every node q one step to its (k+1)-mers e = c.q: each e at least me wide sets predecessor bit c of q and the successor bit
+ * (last symbol of q) of e's prefix e[0..k) -- whose range holds e's, so its record is the last marked row at or below e.l (DESIGN.md
+ * 3, "K-mer graph").  Results depend on no knob (block format, pair index, stride, tables, frontier).
+ * Guards, before the first HIP call: NULL handle MSBWT_ERR_INVALID_ARG; nothing loaded MSBWT_ERR_NOT_LOADED ("no BWT loaded"); k
+ * outside 1..32 MSBWT_ERR_INVALID_ARG; min_edge below the node threshold and not 0 MSBWT_ERR_INVALID_ARG.  Scratch per call, freed on
+ * return (msbwt_rle_device_bytes unchanged); scratch that does not fit: MSBWT_ERR_HIP naming the bytes.  msbwt_rle_spectrum_info
+ * reports the writing walk as it does for the others. */
+int msbwt_rle_enumerate_kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_kmers2bit,
+                                   uint64_t *out_counts, uint64_t *out_l, uint8_t *out_edges, uint64_t capacity, uint64_t *out_n);
+int msbwt_rle_enumerate_kmer_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_kmers2bit,
+                                          void *d_out_counts, void *d_out_l, void *d_out_edges, uint64_t capacity, uint64_t *out_n,
+                                          void *hip_stream);
+int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_table /* 25 */,
+                                 uint64_t *out_nodes, uint64_t *out_edges);
+/* Pure function, no device: bytes of HBM a host dump of `records` nodes with all of words, counts and l allocates and frees again with
+ * the automatic frontier, EXACTLY
+ *     msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, 1)   the walk, the bit per row and the rank checkpoints
+ *     + 256                                                   the 25 degree counters, padded
+ *     + 4 ceil(records / 4)                                   the edge bytes: one per node, as whole 32-bit words
+ *     + 24 records                                            words, counts and l staged for the host (8 records less per NULL buffer)
+ * The _device form and msbwt_rle_kmer_graph_degrees stage nothing: 24 records less.  A call that only counts (capacity == 0) allocates
+ * what msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, 0) says.  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on; device_bytes
+ * may be NULL. */
+int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes);
+
+/* The bytes of scratch the handle's last k-mer walk call (any call of the four sections above that walks) allocated in HBM and freed
  * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves
  * it as it was).  Every allocation counts with its size, 256 bytes at the least.  For the by-source calls this is what
  * msbwt_kmers_by_source_plan(rows, free, S, records, sorted) says, with records = n for a host dump that asked for counts AND l (8 S or

@@ -382,6 +382,48 @@ class RleBWT final : public BWT {
                                                          hip_stream));
         return n;
     }
+    /// What enumerate_kmer_graph returns: the k-mers that occur often enough, ascending, with one edge byte each -- bit j (A C G T ->
+    /// 0..3): the (k+1)-mer j.q is an edge (a predecessor), bit 4 + j: q.j is one (a successor).
+    struct KmerGraph {
+        std::vector<std::uint64_t> words, counts, l;
+        std::vector<std::uint8_t> edges;
+    };
+    /// What kmer_graph_degrees returns: table[5 * i + o] = the k-mers with i predecessors and o successors.
+    struct GraphDegrees {
+        std::uint64_t table[25] = {};
+        std::uint64_t nodes = 0, edges = 0;
+    };
+    /// Nodes: the k-mers with count >= max(min_count, 1); edges: the (k+1)-mers with count >= min_edge (0: the node threshold).
+    KmerGraph enumerate_kmer_graph(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0) const {
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmer_graph(raw_, k, min_count, min_edge, nullptr, nullptr, nullptr, nullptr, 0, &n));
+        KmerGraph g;
+        g.words.resize(n);
+        g.counts.resize(n);
+        g.l.resize(n);
+        g.edges.resize(n);
+        if (n) check(msbwt_rle_enumerate_kmer_graph(raw_, k, min_count, min_edge, g.words.data(), g.counts.data(), g.l.data(), g.edges.data(), n, &n));
+        return g;
+    }
+    /// Device buffers (each may be null; d_edges: bytes, any alignment) -> the number of k-mers that qualify; capacity 0 only counts.
+    std::uint64_t enumerate_kmer_graph_device(std::size_t k, std::uint64_t min_count, std::uint64_t min_edge, void *d_words, void *d_counts, void *d_l, void *d_edges,
+                                              std::uint64_t capacity, void *hip_stream) const {
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_kmer_graph_device(raw_, k, min_count, min_edge, d_words, d_counts, d_l, d_edges, capacity, &n, hip_stream));
+        return n;
+    }
+    GraphDegrees kmer_graph_degrees(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0) const {
+        GraphDegrees d;
+        check(msbwt_rle_kmer_graph_degrees(raw_, k, min_count, min_edge, d.table, &d.nodes, &d.edges));
+        return d;
+    }
+    /// HBM bytes a host graph dump of `records` nodes allocates (and frees again) with the automatic frontier.
+    static std::uint64_t kmer_graph_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t records = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_kmer_graph_plan(total_rows, free_hbm_bytes, records, &bytes);
+        if (rc) throw Panic(rc, "msbwt_kmer_graph_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

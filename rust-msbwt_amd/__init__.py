@@ -17,7 +17,7 @@ from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -150,6 +150,18 @@ def kmers_by_source_plan(total_rows, free_hbm_bytes, n_sources, records=0, sorte
     rc = _lib.lib().msbwt_kmers_by_source_plan(int(total_rows), int(free_hbm_bytes), int(n_sources), int(records), 1 if sorted else 0, ctypes.byref(size))
     if rc:
         raise MsbwtError(rc, "msbwt_kmers_by_source_plan")
+    return size.value
+
+
+def kmer_graph_plan(total_rows, free_hbm_bytes, records=0):
+    """HBM bytes a RleBWT.enumerate_kmer_graph call (the host dump of `records` nodes with words, counts and l) allocates and frees
+    again: what spectrum_plan(total_rows, free_hbm_bytes, 0, sorted=True) gives, 256 bytes of degree counters, the edge bytes as whole
+    32-bit words and 24 bytes per record staged; the device form and kmer_graph_degrees take 24 * records less.  Pure host logic."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    rc = _lib.lib().msbwt_kmer_graph_plan(int(total_rows), int(free_hbm_bytes), int(records), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, "msbwt_kmer_graph_plan")
     return size.value
 
 

@@ -86,6 +86,10 @@ SIGNATURES = {
     "msbwt_rle_enumerate_kmers_by_source": (_int, [_vp, _sz, _vp, _vp, _u64, _u64, _int, _vp, _vp, _vp, _u64, _pu64]),
     "msbwt_rle_enumerate_kmers_by_source_device": (_int, [_vp, _sz, _vp, _vp, _u64, _u64, _int, _vp, _vp, _vp, _u64, _pu64, _vp]),
     "msbwt_kmers_by_source_plan": (_int, [_u64, _u64, _sz, _u64, _int, _pu64]),
+    "msbwt_rle_enumerate_kmer_graph": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _pu64]),
+    "msbwt_rle_enumerate_kmer_graph_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _pu64, _vp]),
+    "msbwt_rle_kmer_graph_degrees": (_int, [_vp, _sz, _u64, _u64, _vp, _pu64, _pu64]),
+    "msbwt_kmer_graph_plan": (_int, [_u64, _u64, _u64, _pu64]),
     "msbwt_rle_spectrum_scratch_bytes": (_int, [_vp, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),

@@ -2,8 +2,9 @@
 // knobs, and the same two with a k-mer and its reverse complement merged into one class (msbwt_rle_canonical_kmer_spectrum,
 // msbwt_rle_enumerate_canonical_kmers[_device]: canonical.hpp; the other strand is counted by query.cpp's packed search).  Calls
 // spectrum.hip and canonical.hip through their headers and handle.hpp.  The k-mers by source (msbwt_rle_kmer_spectrum_by_source,
-// msbwt_rle_enumerate_kmers_by_source[_device]: source_spectrum.hpp) are the same staged walk with the source sink behind it.  All
-// scratch is allocated per call and freed before the call returns.
+// msbwt_rle_enumerate_kmers_by_source[_device]: source_spectrum.hpp) are the same staged walk with the source sink behind it, and the
+// k-mer graph (msbwt_rle_enumerate_kmer_graph[_device], msbwt_rle_kmer_graph_degrees: kmer_graph.hpp) is the sorted dump's counting
+// walk followed by the staged walk with the edge pass behind it.  All scratch is allocated per call and freed before the call returns.
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "canonical.hpp"
 #include "handle.hpp"
+#include "kmer_graph.hpp"
 #include "run_encode.hpp"
 #include "source_spectrum.hpp"
 #include "spectrum.hpp"
@@ -370,6 +372,116 @@ int enumerate_by_source(const msbwt_rle *ch, size_t k, const uint64_t *min_count
     return status_of(h, stream, which);  // synchronises
 }
 
+// ---- the k-mer graph ----
+
+// bytes of scratch a graph call that fills buffers (or the degree table) allocates: the sorted walk's (plan_bytes), the degree counters,
+// the edge bytes of `records` nodes as whole 32-bit words, and `columns` 8-byte words per record staged for a host dump
+int graph_plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t records, uint64_t columns, uint64_t *bytes) {
+    if (records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
+    if (int rc = plan_bytes(total_rows, free_bytes, 0, 0, true, bytes)) return rc;
+    *bytes += kGraphFixedBytes + graph_edge_words(records) * 4 + records * columns * 8;
+    return MSBWT_OK;
+}
+
+// The dump (both forms) and the degree table (table != nullptr: no record outputs, *out_n = the nodes, *out_edge_count = the edges).
+// host: the out_* are host arrays, filled through a device staging of n records; else device arrays.
+int kmer_graph(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_kmers, void *out_counts, void *out_l, void *out_edges,
+               uint64_t capacity, uint64_t *out_n, uint64_t *table, uint64_t *out_edge_count, hipStream_t stream, int which) {
+    const bool degrees = table != nullptr;
+    const char *what = degrees ? "kmer_graph_degrees" : "enumerate_kmer_graph";
+    Call c(ch);
+    msbwt_rle *h = c.h;
+    if (!h) return MSBWT_ERR_INVALID_ARG;
+    if (int rc = c.loaded()) return rc;
+    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + " needs 1 <= k <= 32");
+    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
+    if (me < m) return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + ": min_edge is below the node threshold (0 = the node threshold)");
+    if (!degrees && !out_n) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
+    if (int rc = c.bind()) return rc;
+    if (int rc = ensure_runtime(h)) return rc;
+    if (host) stream = h->stream;
+    const Clock clock;
+    uint64_t n = 0;
+    if (out_n) *out_n = 0;
+    if (out_edge_count) *out_edge_count = 0;
+    if (degrees) std::fill(table, table + kGraphTableWords, 0ull);
+    SpectrumInfo info;
+    info.k = k;
+    if (h->totals.total == 0) {
+        record(h, info, clock);
+        return MSBWT_OK;
+    }
+    const bool fill = degrees || capacity != 0;
+    Scratch s;
+    if (int rc = take_scratch(h, s, fill, fill ? kGraphFixedBytes : 0, what)) return rc;
+    const IndexView v = view_of(h);
+    const SpectrumSeeds seeds = seeds_of(h, k);
+    HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), m, 0, s.work, s.frontier, s.rank, &n, &info, stream));
+    if (out_n) *out_n = n;
+    record(h, info, clock, s.arena.taken);
+    if (!fill || n == 0) return MSBWT_OK;
+    if (!degrees && capacity < n)
+        return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + ": capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
+    // one allocation: the records staged for a host dump | the degree counters | the edge words
+    const uint64_t columns = host && !degrees ? (out_kmers ? 1 : 0) + (out_counts ? 1 : 0) + (out_l ? 1 : 0) : 0;
+    const uint64_t stage_bytes = n * columns * 8, edge_bytes = graph_edge_words(n) * 4, more = stage_bytes + kGraphFixedBytes + edge_bytes;
+    char *block = nullptr;
+    size_t free_bytes = 0, all_bytes = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+    if (free_bytes < more || s.arena.take(&block, more) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, MSBWT_ERR_HIP, std::string(what) + ": " + std::to_string(more) + " more bytes of HBM needed for the edge bytes and the records");
+    }
+    uint64_t *stage = reinterpret_cast<uint64_t *>(block), *d_table = reinterpret_cast<uint64_t *>(block + stage_bytes);
+    uint32_t *edge_words = reinterpret_cast<uint32_t *>(block + stage_bytes + kGraphFixedBytes);
+    HIP_TRY(h, hipMemsetAsync(d_table, 0, kGraphFixedBytes + edge_bytes, stream));
+    const SpectrumRank r = spectrum_rank_view(s.rank, h->totals.total);
+    GraphSink sink{};
+    sink.bitmap = r.bitmap;
+    sink.prefix = r.prefix;
+    sink.edge_words = edge_words;
+    sink.n = n;
+    sink.min_edge = me;
+    sink.flags = h->d_flags + which;
+    if (host && !degrees) {
+        uint64_t *next = stage;
+        auto column = [&](const void *wanted) {
+            uint64_t *at = wanted ? next : nullptr;
+            if (wanted) next += n;
+            return at;
+        };
+        sink.kmers = column(out_kmers);
+        sink.counts = column(out_counts);
+        sink.l = column(out_l);
+    } else if (!degrees) {
+        sink.kmers = static_cast<uint64_t *>(out_kmers);
+        sink.counts = static_cast<uint64_t *>(out_counts);
+        sink.l = static_cast<uint64_t *>(out_l);
+    }
+    const SpectrumChunkHook per_chunk = [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, stream); };
+    HIP_TRY(h, spectrum_stage(v, seeds, uint32_t(k), m, s.work, s.frontier, per_chunk, &info, stream));
+    record(h, info, clock, s.arena.taken);
+    if (degrees) {
+        HIP_TRY(h, launch_graph_degrees(edge_words, n, d_table, stream));
+        HIP_TRY(h, hipMemcpyAsync(table, d_table, kGraphTableWords * 8, hipMemcpyDeviceToHost, stream));
+        if (int rc = status_of(h, stream, which)) return rc;  // synchronises
+        uint64_t edges = 0;
+        for (uint32_t i = 0; i < kGraphTableWords; ++i) edges += uint64_t(i / kGraphDegrees) * table[i];  // (the in-degrees; the out-degrees sum to the same)
+        if (out_edge_count) *out_edge_count = edges;
+        return MSBWT_OK;
+    }
+    if (!host) {  // (a fault is in the device status word: msbwt_rle_device_status)
+        if (out_edges) HIP_TRY(h, hipMemcpyAsync(out_edges, edge_words, n, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));  // (the last chunk's edge pass, and the scratch is freed on return)
+        return MSBWT_OK;
+    }
+    if (out_kmers) HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, sink.counts, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, sink.l, n * 8, hipMemcpyDeviceToHost, stream));
+    if (out_edges) HIP_TRY(h, hipMemcpyAsync(out_edges, edge_words, n, hipMemcpyDeviceToHost, stream));
+    return status_of(h, stream, which);  // synchronises
+}
+
 }  // namespace
 
 extern "C" {
@@ -575,6 +687,31 @@ int msbwt_rle_enumerate_kmers_by_source_device(const msbwt_rle *bwt, size_t k, c
                                                uint64_t *out_n, void *hip_stream) {
     return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n,
                                static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+}
+
+// ---- the k-mer graph: an edge byte per k-mer of the sorted dump, and the table of (in, out) degrees ----
+
+int msbwt_rle_enumerate_kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_kmers2bit, uint64_t *out_counts, uint64_t *out_l,
+                                   uint8_t *out_edges, uint64_t capacity, uint64_t *out_n) {
+    return kmer_graph(bwt, k, min_count, min_edge, true, out_kmers2bit, out_counts, out_l, out_edges, capacity, out_n, nullptr, nullptr, nullptr, kHostFlags);
+}
+
+int msbwt_rle_enumerate_kmer_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_kmers2bit, void *d_out_counts, void *d_out_l,
+                                          void *d_out_edges, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
+    return kmer_graph(bwt, k, min_count, min_edge, false, d_out_kmers2bit, d_out_counts, d_out_l, d_out_edges, capacity, out_n, nullptr, nullptr,
+                      static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+}
+
+int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_table, uint64_t *out_nodes, uint64_t *out_edges) {
+    uint64_t unwanted[kGraphTableWords];
+    return kmer_graph(bwt, k, min_count, min_edge, true, nullptr, nullptr, nullptr, nullptr, 0, out_nodes, out_table ? out_table : unwanted, out_edges, nullptr, kHostFlags);
+}
+
+int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
+    uint64_t bytes = 0;
+    if (int rc = graph_plan_bytes(total_rows, free_hbm_bytes, records, 3, &bytes)) return rc;
+    if (device_bytes) *device_bytes = bytes;
+    return MSBWT_OK;
 }
 
 int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes) {

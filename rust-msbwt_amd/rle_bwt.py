@@ -491,6 +491,52 @@ class RleBWT(BWT):
                 raise
         return n.value
 
+    # ---- the k-mer graph: an edge byte per k-mer of the sorted dump, and the table of (in, out) degrees ----
+    def enumerate_kmer_graph(self, k, min_count=1, min_edge=None, ranges=False):
+        """msbwt_rle_enumerate_kmer_graph, both calls of the two-call pattern -> (words, counts, edges[, l]): the k-mers that occur at
+        least min_count times, ascending, as enumerate_kmers gives them, and per k-mer q one uint8: bit j (A C G T -> 0..3) = the
+        (k+1)-mer j.q occurs at least min_edge times (None: min_count) -- a predecessor --, bit 4 + j = q.j does -- a successor.
+        graph_successors / graph_predecessors turn the bits into neighbour words."""
+        lib, n = _lib.lib(), C.c_uint64(0)
+        args = (self._h, int(k), int(min_count), int(min_edge or 0))
+        rc = lib.msbwt_rle_enumerate_kmer_graph(*args, None, None, None, None, 0, C.byref(n))
+        if rc:
+            _raise(rc, self._h)
+        words, counts = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.uint64)
+        edges = np.zeros(n.value, dtype=np.uint8)
+        l = np.empty(n.value, dtype=np.uint64) if ranges else None
+        if n.value:
+            rc = lib.msbwt_rle_enumerate_kmer_graph(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                    l.ctypes.data_as(C.c_void_p) if ranges else None, edges.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+            if rc:
+                _raise(rc, self._h)
+        return (words, counts, edges, l) if ranges else (words, counts, edges)
+
+    def enumerate_kmer_graph_device(self, k, d_words, d_counts, d_l, d_edges, capacity, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_enumerate_kmer_graph_device: device pointers (ints, each may be None) of `capacity` u64 -- d_edges: bytes, any
+        alignment -- -> n, the k-mers that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
+        n = C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_enumerate_kmer_graph_device(self._h, int(k), int(min_count), int(min_edge or 0), d_words, d_counts, d_l, d_edges, int(capacity),
+                                                              C.byref(n), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n = n.value
+                raise
+        return n.value
+
+    def kmer_graph_degrees(self, k, min_count=1, min_edge=None):
+        """msbwt_rle_kmer_graph_degrees -> (table, nodes, edges): table[i, o] (uint64, 5 x 5) = the k-mers with i predecessors and o
+        successors, their number, and the number of (k+1)-mers that are edges.  No record leaves the device."""
+        table = np.zeros((5, 5), dtype=np.uint64)
+        nodes, edges = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_kmer_graph_degrees(self._h, int(k), int(min_count), int(min_edge or 0), table.ctypes.data_as(C.c_void_p), C.byref(nodes),
+                                                     C.byref(edges))
+        if rc:
+            _raise(rc, self._h)
+        return table, nodes.value, edges.value
+
     def spectrum_scratch_bytes(self):
         """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""
         out = C.c_uint64(0)
@@ -1047,6 +1093,37 @@ def reverse_complement_2bit(words, k):
     if rc:
         raise ValueError("reverse_complement_2bit takes one word per k-mer: 1 <= k <= 32")
     return out
+
+
+def _graph_neighbours(words, edges, k, successors):
+    words, edges, k = np.ascontiguousarray(words, dtype=np.uint64), np.ascontiguousarray(edges, dtype=np.uint8), int(k)
+    if not 1 <= k <= 32 or words.shape != edges.shape or words.ndim != 1:
+        raise ValueError("graph neighbours need 1 <= k <= 32 and one edge byte per word")
+    j = np.arange(4, dtype=np.uint64)
+    bits = (edges[:, None] >> (np.arange(4, dtype=np.uint8) + np.uint8(4 if successors else 0))[None, :]) & np.uint8(1)
+    mask = np.uint64((1 << (2 * k)) - 1)
+    if successors:  # q.j: q loses its first symbol and gains j as the last
+        if k == 32:
+            shifted = (words << np.uint64(2))[:, None]
+        else:
+            shifted = ((words << np.uint64(2)) & mask)[:, None]
+        grid = shifted | j[None, :]
+    else:  # j.q: q loses its last symbol and gains j as the first
+        grid = (words >> np.uint64(2))[:, None] | (j << np.uint64(2 * (k - 1)))[None, :]
+    rec, sym = np.nonzero(bits)
+    return rec.astype(np.int64), grid[rec, sym]
+
+
+def graph_successors(words, edges, k):
+    """(index, neighbours): for every successor bit 4 + j of edges[i], in the order of i then j, the record i and the 2-bit word of the
+    node the edge words[i].j leads to (words[i] without its first symbol, with j appended).  Pure host logic."""
+    return _graph_neighbours(words, edges, k, True)
+
+
+def graph_predecessors(words, edges, k):
+    """(index, neighbours): for every predecessor bit j of edges[i], in the order of i then j, the record i and the 2-bit word of the
+    node the edge j.words[i] comes from (j, then words[i] without its last symbol).  Pure host logic."""
+    return _graph_neighbours(words, edges, k, False)
 
 
 def count_read_kmers_multi(replicas, reads, k, ascii=False, forward=True, revcomp=False):

@@ -94,6 +94,12 @@ extern "C" {
                                            out_counts: *mut u64, out_l: *mut u64, capacity: u64, out_n: *mut u64) -> c_int;
     fn msbwt_kmers_by_source_plan(total_rows: u64, free_hbm_bytes: u64, n_sources: usize, records: u64, sorted: c_int,
                                   device_bytes: *mut u64) -> c_int;
+    // the k-mer graph: the sorted dump with an edge byte per k-mer (bit j: predecessor j, bit 4 + j: successor j), and the degree table
+    fn msbwt_rle_enumerate_kmer_graph(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_kmers2bit: *mut u64,
+                                      out_counts: *mut u64, out_l: *mut u64, out_edges: *mut u8, capacity: u64, out_n: *mut u64) -> c_int;
+    fn msbwt_rle_kmer_graph_degrees(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_table: *mut u64,
+                                    out_nodes: *mut u64, out_edges: *mut u64) -> c_int;
+    fn msbwt_kmer_graph_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
@@ -475,6 +481,43 @@ impl GpuRleBWT {
             if rc != MSBWT_OK { panic!("enumerate_kmers_by_source: {}", self.last_error()); }
         }
         (words, counts, l)
+    }
+
+    /// The k-mer graph: the k-mers that occur at least `min_count` times, ascending, as (2-bit words, counts, range starts, edge bytes).
+    /// Bit j of an edge byte (A C G T -> 0..3): the (k+1)-mer j.q occurs at least `min_edge` times (0: `min_count`) -- a predecessor;
+    /// bit 4 + j: q.j does -- a successor.
+    pub fn enumerate_kmer_graph(&self, k: usize, min_count: u64, min_edge: u64) -> (Vec<u64>, Vec<u64>, Vec<u64>, Vec<u8>) {
+        let mut n = 0u64;
+        let rc = unsafe {
+            msbwt_rle_enumerate_kmer_graph(self.raw, k, min_count, min_edge, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                           std::ptr::null_mut(), 0, &mut n)
+        };
+        if rc != MSBWT_OK { panic!("enumerate_kmer_graph: {}", self.last_error()); }
+        let (mut words, mut counts, mut l, mut edges) = (vec![0u64; n as usize], vec![0u64; n as usize], vec![0u64; n as usize], vec![0u8; n as usize]);
+        if n > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_kmer_graph(self.raw, k, min_count, min_edge, words.as_mut_ptr(), counts.as_mut_ptr(), l.as_mut_ptr(),
+                                               edges.as_mut_ptr(), n, &mut n)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_kmer_graph: {}", self.last_error()); }
+        }
+        (words, counts, l, edges)
+    }
+
+    /// (table, nodes, edges): table[5 * i + o] = the k-mers with i predecessors and o successors; no record leaves the device.
+    pub fn kmer_graph_degrees(&self, k: usize, min_count: u64, min_edge: u64) -> ([u64; 25], u64, u64) {
+        let (mut table, mut nodes, mut edges) = ([0u64; 25], 0u64, 0u64);
+        let rc = unsafe { msbwt_rle_kmer_graph_degrees(self.raw, k, min_count, min_edge, table.as_mut_ptr(), &mut nodes, &mut edges) };
+        if rc != MSBWT_OK { panic!("kmer_graph_degrees: {}", self.last_error()); }
+        (table, nodes, edges)
+    }
+
+    /// HBM bytes a host graph dump of `records` nodes allocates and frees again (pure function).
+    pub fn kmer_graph_plan(total_rows: u64, free_hbm_bytes: u64, records: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_kmer_graph_plan(total_rows, free_hbm_bytes, records, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "kmer_graph_plan: {} rows, {} records", total_rows, records);
+        bytes
     }
 
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
