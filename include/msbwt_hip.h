@@ -395,7 +395,9 @@ int msbwt_rle_enumerate_canonical_kmers_device(const msbwt_rle *bwt, size_t k, u
 /* Pure function, no device: bytes of HBM a canonical call allocates and frees again with the automatic frontier: what
  * msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, 0) gives for the walk -- whose last frontier IS the staging of (word, count) --
  * plus 16 bytes per frontier node for the other strand (word, count), plus 24 bytes per record staged for a host dump (0 for the
- * _device form, for counting and for the spectrum, which adds 8 n_bins).  MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on. */
+ * _device form, for counting and for the spectrum, which adds 8 n_bins).  A call's real scratch (msbwt_rle_spectrum_scratch_bytes)
+ * is 256 bytes above this: the words of its totals, an allocation of their own that the plan leaves out.
+ * MSBWT_ERR_TOO_LARGE from 2^40 rows (or records) on. */
 int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes);
 
 /* ---- k-mers by source: one spectrum per input of a merged index, and the dump filtered by per-source counts (no reference counterpart) ----

@@ -1,14 +1,20 @@
-// The k-mers of a loaded index: abundance spectrum and k-mer dump (msbwt_rle_kmer_spectrum, msbwt_rle_enumerate_kmers[_device]), their
-// knobs, and the same two with a k-mer and its reverse complement merged into one class (msbwt_rle_canonical_kmer_spectrum,
-// msbwt_rle_enumerate_canonical_kmers[_device]: canonical.hpp; the other strand is counted by query.cpp's packed search).  Calls
-// spectrum.hip and canonical.hip through their headers and handle.hpp.  The k-mers by source (msbwt_rle_kmer_spectrum_by_source,
-// msbwt_rle_enumerate_kmers_by_source[_device]: source_spectrum.hpp) are the same staged walk with the source sink behind it, and the
-// k-mer graph (msbwt_rle_enumerate_kmer_graph[_device], msbwt_rle_kmer_graph_degrees: kmer_graph.hpp) is the sorted dump's counting
-// walk followed by the staged walk with the edge pass behind it.  All scratch is allocated per call and freed before the call returns.
+// The k-mer walk calls of a loaded index, four families of three: the abundance spectrum, the k-mer dump in its host and its device
+// form (the graph: and the degree table) of the plain k-mers (spectrum.hpp), of a k-mer and its reverse complement as one class
+// (canonical.hpp; the other strand is counted by query.cpp's packed search), of the k-mers by source of a merged index
+// (source_spectrum.hpp) and of the k-mer graph (kmer_graph.hpp).  The kernels are behind those headers; this file is the host side, and
+// what the calls share is written once:
+//   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
+//                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
+//                 the one name the call passes, every text it can say
+//   Shape         what a family allocates: its msbwt_*_plan and the sufficiency check of take_scratch are the same sum over it
+//   two_pass      a dump: the counting pass, *out_n, the capacity pattern, the filling pass, the record after either
+//   stage_records / copy_out   the columns of a dump: the caller's device arrays, or one staged block carved up and copied out
+//   staged_walk   a walk whose chunks go to a sink behind it (canonical, by source, the graph's edge pass)
+//   spectrum      a spectrum: the histograms zeroed, taken, walked into and copied out
+// A body below is what is left: its argument checks, its sink, and the order of its passes.
 #include <algorithm>
 #include <chrono>
 #include <string>
-#include <vector>
 
 #include "canonical.hpp"
 #include "handle.hpp"
@@ -22,175 +28,326 @@ namespace {
 static_assert(MSBWT_SPECTRUM_MIN_FRONTIER == kSpectrumMinFrontier && MSBWT_SPECTRUM_INFO_WORDS == 4 + kSpectrumMaxK + 1 + 3, "the header's constants");
 constexpr uint64_t kRecordBytes = 3 * sizeof(uint64_t);  // k-mer, count, l
 
-// bytes of scratch a call allocates; MSBWT_ERR_TOO_LARGE for what no index can be
-int plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t frontier, uint64_t records, bool sorted, uint64_t *bytes) {
+// ---- what a family allocates ----
+
+// The scratch of a call beyond the walk's own frontiers.  A plan counts `record_bytes` per record staged for a host dump; the call
+// itself stages only the columns its caller wants.
+struct Shape {
+    bool rank;              // the bitmap over the rows and its checkpoints: a sorted call that fills buffers
+    bool canonical;         // kCanonicalStageBytes per frontier node: the other strand of a chunk's k-mers
+    uint64_t fixed;         // the sink's words, the histograms
+    uint64_t record_bytes;
+};
+
+Shape plain_shape(bool rank) { return Shape{rank, false, 0, kRecordBytes}; }
+constexpr Shape kCanonicalShape{false, true, 0, kRecordBytes};  // (its totals, 256 bytes more, are in no plan)
+Shape by_source_shape(bool rank, uint64_t n_sources) { return Shape{rank, false, kSourceSinkFixedBytes, (2 + n_sources) * sizeof(uint64_t)}; }
+Shape graph_shape(bool fill) { return Shape{fill, false, fill ? kGraphFixedBytes : 0, kRecordBytes}; }  // (and the edge words of its records)
+
+uint64_t shape_bytes(const Shape &p, uint64_t total_rows, uint64_t frontier, uint64_t records) {
+    return spectrum_work_bytes(frontier) + (p.rank ? spectrum_rank_bytes(total_rows) : 0) + (p.canonical ? frontier * kCanonicalStageBytes : 0) + p.fixed +
+           records * p.record_bytes;
+}
+
+// a msbwt_*_plan: the shape at the automatic frontier, and `more`; MSBWT_ERR_TOO_LARGE for what no index can be
+int plan(const Shape &p, uint64_t total_rows, uint64_t free_bytes, uint64_t records, uint64_t more, uint64_t *device_bytes) {
     if (total_rows >= kMaxSymbols || records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
-    *bytes = spectrum_work_bytes(spectrum_frontier_nodes(total_rows, free_bytes, frontier)) + (sorted ? spectrum_rank_bytes(total_rows) : 0) + records * kRecordBytes;
+    if (device_bytes) *device_bytes = shape_bytes(p, total_rows, spectrum_frontier_nodes(total_rows, free_bytes, 0), records) + more;
     return MSBWT_OK;
 }
 
-// where the walk starts: the flat direct table when it is shallower than k, else the root
-SpectrumSeeds seeds_of(const msbwt_rle *h, size_t k) {
-    const DirectTable &t = h->table;
-    if (t.entries && !t.packed && t.depth > 0 && size_t(t.depth) < k) return SpectrumSeeds{t.entries, t.depth};
-    return SpectrumSeeds{};
-}
+// ---- a call ----
 
 struct Clock {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     uint64_t us() const { return uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count()); }
 };
 
-void record(msbwt_rle *h, const SpectrumInfo &info, const Clock &clock, uint64_t scratch_bytes = 0) {
-    h->spectrum_scratch = scratch_bytes;
-    uint64_t *w = h->spectrum_info;
-    std::fill(w, w + MSBWT_SPECTRUM_INFO_WORDS, 0ull);
-    w[0] = info.k;
-    w[1] = info.seed_depth;
-    w[2] = info.chunks;
-    w[3] = info.retries;
-    std::copy(info.nodes, info.nodes + kSpectrumMaxK + 1, w + 4);
-    const uint64_t us = clock.us();
-    w[37] = (us + 500) / 1000;
-    w[38] = us;
-    w[39] = info.descents;
-}
-
-// the scratch of one call: freed when it goes out of scope
-struct Scratch {
+struct Frame {
+    Call c;
+    msbwt_rle *const h;
+    const std::string name;  // as the texts say it: "enumerate_kmers"
+    const size_t k;
+    const bool host;         // the outputs are host arrays, and the call runs on the handle's stream and reads its flags before it returns
+    hipStream_t stream;
+    const int which;         // the word of the status block its kernels flag: the host forms', or the device forms'
+    Clock clock;
+    SpectrumInfo info;
+    // the scratch, freed with the frame
     Arena arena;
     void *work = nullptr, *rank = nullptr;
     uint64_t frontier = 0;
     uint64_t *rc_words = nullptr, *rc_counts = nullptr;  // canonical calls: the other strand of a chunk's k-mers, `frontier` words each
     unsigned long long *totals = nullptr;                // and the words of CanonicalSink::totals
+    int hook_rc = MSBWT_OK;                              // what a chunk hook's own call returned (staged_walk)
+
+    // a host form (nullptr: the handle's stream, once open), or the device form on the caller's stream
+    Frame(const msbwt_rle *bwt, const char *name, size_t k, bool host = true, hipStream_t stream = nullptr)
+        : c(bwt), h(c.h), name(name), k(k), host(host), stream(stream), which(host ? kHostFlags : kDeviceFlags) {}
+
+    int refuse(const std::string &why) const { return fail(h, MSBWT_ERR_INVALID_ARG, name + why); }
+    // a dump's pointers: out_n always, the k-mers once there is a capacity
+    int need_outputs(const uint64_t *out_n, uint64_t capacity, const void *out_kmers) const {
+        return !out_n || (capacity && !out_kmers) ? fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer") : int(MSBWT_OK);
+    }
+
+    // The guard ladder: no handle, no index, (sources wanted) none attached, k, the call's own arguments -- args() refuses or returns
+    // MSBWT_OK --, the device.  From here on the clock runs.
+    template <class Args>
+    int open(bool sources, Args &&args) {
+        if (!h) return MSBWT_ERR_INVALID_ARG;
+        if (int rc = c.loaded()) return rc;
+        if (sources && !h->sources.n_sources) return fail(h, MSBWT_ERR_NOT_LOADED, "no sources attached");
+        if (k < 1 || k > kSpectrumMaxK) return refuse(" needs 1 <= k <= 32");
+        if (int rc = args()) return rc;
+        if (int rc = c.bind()) return rc;
+        if (int rc = ensure_runtime(h)) return rc;
+        if (host) stream = h->stream;
+        clock = Clock{};
+        info.k = k;
+        return MSBWT_OK;
+    }
+    bool empty() const { return h->totals.total == 0; }  // nothing to walk: the call returns zeros, having allocated nothing
+
+    // what the walks so far did, the time since open() and the scratch taken: msbwt_rle_spectrum_info, msbwt_rle_spectrum_scratch_bytes
+    void record() {
+        h->spectrum_scratch = arena.taken;
+        uint64_t *w = h->spectrum_info;
+        std::fill(w, w + MSBWT_SPECTRUM_INFO_WORDS, 0ull);
+        w[0] = info.k;
+        w[1] = info.seed_depth;
+        w[2] = info.chunks;
+        w[3] = info.retries;
+        std::copy(info.nodes, info.nodes + kSpectrumMaxK + 1, w + 4);
+        const uint64_t us = clock.us();
+        w[37] = (us + 500) / 1000;
+        w[38] = us;
+        w[39] = info.descents;
+    }
+    void release() {  // the scratch given back before the frame goes (a spectrum: before it records)
+        for (void *p : arena.held) (void)hipFree(p);
+        arena.held.clear();
+    }
+
+    // the text of an allocation that failed or would: the call, the bytes, "more" for one on top of the scratch, and what for
+    std::string needs(uint64_t bytes, bool more, const char *for_what) const {
+        return name + ": " + std::to_string(bytes) + (more ? " more" : "") + " bytes of HBM needed " + for_what;
+    }
+    // One more allocation, or MSBWT_ERR_HIP saying `or_say`; ask_free: refused already where the device says it has less free.
+    template <class T>
+    int take(T **p, uint64_t bytes, const std::string &or_say, bool ask_free = false) {
+        size_t free_bytes = ~size_t(0), all_bytes = 0;
+        if (ask_free) HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
+        if (free_bytes < bytes || arena.take(p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MSBWT_ERR_HIP, or_say);
+        }
+        return MSBWT_OK;
+    }
 };
 
-// work (and, wanted, the rank scratch or the canonical calls' staging) in HBM, or MSBWT_ERR_HIP naming the bytes
-int take_scratch(msbwt_rle *h, Scratch &s, bool rank, uint64_t extra_bytes, const char *what, bool canonical = false) {
+// where the walk starts: the flat direct table when it is shallower than k, else the root
+SpectrumSeeds seeds_of(const Frame &f) {
+    const DirectTable &t = f.h->table;
+    if (t.entries && !t.packed && t.depth > 0 && size_t(t.depth) < f.k) return SpectrumSeeds{t.entries, t.depth};
+    return SpectrumSeeds{};
+}
+
+// The frontiers and what else of `p` does not wait for the records (the rank scratch, the canonical staging and totals) in HBM, or
+// MSBWT_ERR_HIP naming the bytes of the shape.  p.fixed is checked for here and taken by the call.
+int take_scratch(Frame &f, const Shape &p) {
+    msbwt_rle *h = f.h;
     size_t free_bytes = 0, all_bytes = 0;
     HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
     const uint64_t total = h->totals.total;
-    s.frontier = spectrum_frontier_nodes(total, free_bytes, h->spectrum_frontier);
-    const uint64_t work_bytes = spectrum_work_bytes(s.frontier), rank_bytes = rank ? spectrum_rank_bytes(total) : 0;
-    if (canonical) extra_bytes += s.frontier * kCanonicalStageBytes;
-    const std::string need = std::string(what) + ": " + std::to_string(work_bytes + rank_bytes + extra_bytes) + " bytes of HBM needed while it runs";
-    if (free_bytes < work_bytes + rank_bytes + extra_bytes) return fail(h, MSBWT_ERR_HIP, need);
-    if (s.arena.take(&s.work, work_bytes) != hipSuccess || (rank && s.arena.take(&s.rank, rank_bytes) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, need);
-    }
-    if (canonical && (s.arena.take(&s.rc_words, s.frontier * 8) != hipSuccess || s.arena.take(&s.rc_counts, s.frontier * 8) != hipSuccess ||
-                      s.arena.take(&s.totals, kCanonicalTotalWords * 8) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, need);
+    f.frontier = spectrum_frontier_nodes(total, free_bytes, h->spectrum_frontier);
+    const uint64_t bytes = shape_bytes(p, total, f.frontier, 0);
+    const std::string need = f.needs(bytes, false, "while it runs");
+    if (free_bytes < bytes) return fail(h, MSBWT_ERR_HIP, need);
+    if (int rc = f.take(&f.work, spectrum_work_bytes(f.frontier), need)) return rc;
+    if (p.rank)
+        if (int rc = f.take(&f.rank, spectrum_rank_bytes(total), need)) return rc;
+    if (p.canonical) {
+        if (int rc = f.take(&f.rc_words, f.frontier * 8, need)) return rc;
+        if (int rc = f.take(&f.rc_counts, f.frontier * 8, need)) return rc;
+        if (int rc = f.take(&f.totals, kCanonicalTotalWords * 8, need)) return rc;
     }
     return MSBWT_OK;
 }
 
-// Both forms of the dump.  host: the out_* are host arrays, filled through a device staging of n records; else device arrays.
-int enumerate(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_count, int sorted, bool host, void *out_kmers, void *out_counts, void *out_l,
-              uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
-    Call c(ch);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers needs 1 <= k <= 32");
-    if (max_count != 0 && min_count > max_count) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers: min_count > max_count");
-    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    if (host) stream = h->stream;
-    const Clock clock;
-    *out_n = 0;
-    SpectrumInfo info;
-    info.k = k;
-    if (h->totals.total == 0) {
-        record(h, info, clock);
+// a spectrum's histograms in HBM, zeroed
+int take_histogram(Frame &f, uint64_t bytes, const char *for_what, uint64_t **d_hist) {
+    if (int rc = f.take(d_hist, bytes, f.needs(bytes, false, for_what))) return rc;
+    HIP_TRY(f.h, hipMemsetAsync(*d_hist, 0, bytes, f.stream));
+    return MSBWT_OK;
+}
+
+// ---- the records of a dump ----
+
+// A column of a dump's records: the caller's array (`out`: of the host or of the device, as the frame says; nullptr = not wanted) of
+// `words` 64-bit words per record, and where the sink writes it (`at`).
+struct Column {
+    void *out;
+    uint64_t words = 1;
+    uint64_t *at = nullptr;
+};
+
+// Where the sink writes: a device form's columns are the caller's own; a host form's are carved from one allocation of the n records'
+// wanted words -- *capacity becomes n --, `tail_bytes` more behind them in either form (*tail).  Nothing to stage and no tail: no allocation.
+template <size_t N>
+int stage_records(Frame &f, Column (&cols)[N], uint64_t n, uint64_t *capacity, const char *for_what, uint64_t tail_bytes = 0, char **tail = nullptr) {
+    uint64_t words = 0;
+    for (Column &c : cols) {
+        c.at = static_cast<uint64_t *>(c.out);
+        if (f.host && c.out) words += c.words;
+    }
+    const uint64_t bytes = n * words * 8 + tail_bytes;
+    if (bytes == 0) return MSBWT_OK;
+    char *block = nullptr;
+    if (int rc = f.take(&block, bytes, f.needs(bytes, true, for_what), true)) return rc;
+    if (tail) *tail = block + n * words * 8;
+    if (!f.host) return MSBWT_OK;
+    uint64_t *next = reinterpret_cast<uint64_t *>(block);
+    for (Column &c : cols)
+        if (c.out) {
+            c.at = next;
+            next += n * c.words;
+        }
+    *capacity = n;
+    return MSBWT_OK;
+}
+
+// A host form's wanted columns copied out, and the flags its kernels left (synchronises).  A device form has its records where they
+// belong, and a fault is in the device status word: msbwt_rle_device_status.
+template <size_t N>
+int copy_out(Frame &f, const Column (&cols)[N], uint64_t n) {
+    if (!f.host) return MSBWT_OK;
+    for (const Column &c : cols)
+        if (c.out) HIP_TRY(f.h, hipMemcpyAsync(c.out, c.at, n * c.words * 8, hipMemcpyDeviceToHost, f.stream));
+    return status_of(f.h, f.stream, f.which);
+}
+
+// ---- the passes ----
+
+// A dump, or any call of the two-call pattern.  count(&n) walks once and says how many records qualify: *out_n (which only the degree
+// table leaves out).  capacity 0, or nothing qualifies: that was the call (a host form whose counting pass can flag -- flags_after_count
+// -- reads the flags first); a capacity below n is refused; else fill(n) walks again, into the buffers, and deliver(n) hands them over
+// once the walk is recorded.  `things`: what qualifies, for the refusal.
+template <class Count, class Fill, class Deliver>
+int two_pass(Frame &f, uint64_t capacity, uint64_t *out_n, const char *things, bool flags_after_count, Count &&count, Fill &&fill, Deliver &&deliver) {
+    if (out_n) *out_n = 0;
+    if (f.empty()) {
+        f.record();
         return MSBWT_OK;
     }
-    const bool rank = sorted != 0 && capacity != 0;
-    Scratch s;
-    if (int rc = take_scratch(h, s, rank, 0, "enumerate_kmers")) return rc;
-    const IndexView v = view_of(h);
-    const SpectrumSeeds seeds = seeds_of(h, k);
     uint64_t n = 0;
-    HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, &n, &info, stream));
-    *out_n = n;
-    record(h, info, clock, s.arena.taken);
-    if (capacity == 0 || n == 0) return MSBWT_OK;
-    if (capacity < n)
-        return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
-    uint64_t *d_kmers = static_cast<uint64_t *>(out_kmers), *d_counts = static_cast<uint64_t *>(out_counts), *d_l = static_cast<uint64_t *>(out_l);
-    uint64_t *stage = nullptr;
-    if (host) {  // records staged in HBM, then copied out
-        const uint64_t columns = 1 + (out_counts ? 1 : 0) + (out_l ? 1 : 0);
-        size_t free_bytes = 0, all_bytes = 0;
-        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
-        if (free_bytes < n * columns * 8 || s.arena.take(&stage, n * columns * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "enumerate_kmers: " + std::to_string(n * columns * 8) + " more bytes of HBM needed for the records");
+    if (int rc = count(&n)) return rc;
+    if (out_n) *out_n = n;
+    f.record();
+    if (capacity == 0 || n == 0) return flags_after_count && f.host ? status_of(f.h, f.stream, f.which) : int(MSBWT_OK);
+    if (capacity < n) return f.refuse(": capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " " + things + " that qualify");
+    if (int rc = fill(n)) return rc;
+    f.record();
+    return deliver(n);
+}
+
+// One staged walk: chunk by chunk the k-mers at least `prune` wide are staged and handed to per_chunk, which launches the sink.  The
+// sink's totals (`words` of them at d_totals; nullptr: it has none) are zeroed before and copied to totals[] after, and then the stream
+// is synchronised.  A hook that fails in a call of its own leaves that call's code in f.hook_rc, which wins over the walk's error.
+int staged_walk(Frame &f, uint64_t prune, unsigned long long *d_totals, uint32_t words, uint64_t *totals, const SpectrumChunkHook &per_chunk) {
+    msbwt_rle *h = f.h;
+    f.hook_rc = MSBWT_OK;
+    if (d_totals) HIP_TRY(h, hipMemsetAsync(d_totals, 0, words * 8, f.stream));
+    const hipError_t walked = spectrum_stage(view_of(h), seeds_of(f), uint32_t(f.k), prune, f.work, f.frontier, per_chunk, &f.info, f.stream);
+    if (f.hook_rc) return f.hook_rc;
+    HIP_TRY(h, walked);
+    if (!d_totals) return MSBWT_OK;
+    HIP_TRY(h, hipMemcpyAsync(totals, d_totals, words * 8, hipMemcpyDeviceToHost, f.stream));
+    HIP_TRY(h, hipStreamSynchronize(f.stream));
+    return MSBWT_OK;
+}
+
+// A spectrum: out_hist (one histogram of n_bins bins, or one per source) zeroed, and on an index that holds something the scratch of
+// `p` and the histograms taken, walk(bytes, &d_hist) -- which allocates the histograms (take_histogram) behind whatever else its sink
+// needs, and walks -- and the histograms copied out; flags: the walk's kernels can flag, so the host flags are read.  Records the call.
+template <class Walk>
+int spectrum(Frame &f, bool sources, Shape p, bool flags, uint64_t *out_hist, size_t n_bins, Walk &&walk) {
+    const char *too_few = sources ? " needs histograms of at least 2 bins" : " needs a histogram of at least 2 bins";
+    if (int rc = f.open(sources, [&] { return n_bins < 2 || !out_hist ? f.refuse(too_few) : int(MSBWT_OK); })) return rc;
+    msbwt_rle *h = f.h;
+    const uint64_t words = (sources ? h->sources.n_sources : 1) * uint64_t(n_bins);
+    std::fill(out_hist, out_hist + words, 0ull);
+    if (!f.empty()) {
+        p.fixed += words * 8;
+        if (int rc = take_scratch(f, p)) return rc;
+        uint64_t *d_hist = nullptr;
+        if (int rc = walk(words * 8, &d_hist)) return rc;
+        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, words * 8, hipMemcpyDeviceToHost, f.stream));
+        if (flags) {
+            if (int rc = status_of(h, f.stream, f.which)) return rc;  // synchronises
+        } else {
+            HIP_TRY(h, hipStreamSynchronize(f.stream));
         }
-        d_kmers = stage;
-        d_counts = out_counts ? stage + n : nullptr;
-        d_l = out_l ? stage + n * (out_counts ? 2 : 1) : nullptr;
-        capacity = n;
+        f.release();
     }
-    HIP_TRY(h, spectrum_dump(v, seeds, uint32_t(k), min_count, max_count, s.work, s.frontier, s.rank, d_kmers, d_counts, d_l, capacity, h->d_flags + which, &info,
-                             stream));
-    record(h, info, clock, s.arena.taken);
-    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
-    HIP_TRY(h, hipMemcpyAsync(out_kmers, d_kmers, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, d_counts, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, d_l, n * 8, hipMemcpyDeviceToHost, stream));
-    return status_of(h, stream, which);  // synchronises
+    f.record();
+    return MSBWT_OK;
+}
+
+// ---- plain k-mers ----
+
+// Both forms of the dump: records (k-mer, count, l).
+int enumerate(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted, bool host, void *out_kmers, void *out_counts, void *out_l,
+              uint64_t capacity, uint64_t *out_n, hipStream_t stream) {
+    Frame f(bwt, "enumerate_kmers", k, host, stream);
+    if (int rc = f.open(false, [&] {
+            if (max_count != 0 && min_count > max_count) return f.refuse(": min_count > max_count");
+            return f.need_outputs(out_n, capacity, out_kmers);
+        }))
+        return rc;
+    msbwt_rle *h = f.h;
+    const IndexView v = view_of(h);
+    const SpectrumSeeds seeds = seeds_of(f);
+    Column cols[] = {{out_kmers}, {out_counts}, {out_l}};
+    return two_pass(
+        f, capacity, out_n, "k-mers", false,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, plain_shape(sorted != 0 && capacity != 0))) return rc;
+            HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), min_count, max_count, f.work, f.frontier, f.rank, n, &f.info, f.stream));
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) -> int {
+            if (int rc = stage_records(f, cols, n, &capacity, "for the records")) return rc;
+            HIP_TRY(h, spectrum_dump(v, seeds, uint32_t(k), min_count, max_count, f.work, f.frontier, f.rank, cols[0].at, cols[1].at, cols[2].at, capacity,
+                                     h->d_flags + f.which, &f.info, f.stream));
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) { return copy_out(f, cols, n); });
 }
 
 // ---- canonical k-mers ----
 
-// One walk of a canonical call: chunk by chunk the k-mers at least `prune` wide are staged, their reverse complements written as packed
-// words and counted by the packed search, and the classes they emit go to `sink` (its totals: s.totals, copied to totals[] at the end).
-// Synchronises the stream.
-int canonical_walk(msbwt_rle *h, const Scratch &s, size_t k, uint64_t prune, CanonicalSink sink, SpectrumInfo *info, hipStream_t stream, int which, uint64_t *totals) {
-    sink.totals = s.totals;
-    HIP_TRY(h, hipMemsetAsync(s.totals, 0, kCanonicalTotalWords * 8, stream));
-    int search_rc = MSBWT_OK;
-    const SpectrumChunkHook per_chunk = [&](const void *d_kmers, uint64_t m) {
-        const hipError_t e = launch_canonical_rc(d_kmers, m, uint32_t(k), s.rc_words, stream);
+// One walk of a canonical call: the reverse complements of a chunk's k-mers are written as packed words and counted by the packed
+// search, and the classes they emit go to `sink` (its totals: f.totals, copied to totals[] at the end).  Synchronises the stream.
+int canonical_walk(Frame &f, uint64_t prune, CanonicalSink sink, uint64_t *totals) {
+    sink.totals = f.totals;
+    return staged_walk(f, prune, f.totals, kCanonicalTotalWords, totals, [&](const void *d_kmers, uint64_t m) {
+        const hipError_t e = launch_canonical_rc(d_kmers, m, uint32_t(f.k), f.rc_words, f.stream);
         if (e != hipSuccess) return e;
-        if ((search_rc = launch_count_2bit(h, s.rc_words, k, size_t(m), s.rc_counts, stream, which)) != MSBWT_OK) return hipErrorUnknown;
-        return launch_canonical_combine(d_kmers, s.rc_words, s.rc_counts, m, sink, stream);
-    };
-    const hipError_t walked = spectrum_stage(view_of(h), seeds_of(h, k), uint32_t(k), prune, s.work, s.frontier, per_chunk, info, stream);
-    if (search_rc) return search_rc;
-    HIP_TRY(h, walked);
-    HIP_TRY(h, hipMemcpyAsync(totals, s.totals, kCanonicalTotalWords * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(h, hipStreamSynchronize(stream));
-    return MSBWT_OK;
+        if ((f.hook_rc = launch_count_2bit(f.h, f.rc_words, f.k, size_t(m), f.rc_counts, f.stream, f.which)) != MSBWT_OK) return hipErrorUnknown;
+        return launch_canonical_combine(d_kmers, f.rc_words, f.rc_counts, m, sink, f.stream);
+    });
 }
 
-// Both forms of the canonical dump, as enumerate() above: records (canonical word, own, other), in the order the walk produces them.
-int enumerate_canonical(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t max_count, bool host, void *out_kmers, void *out_own, void *out_other,
-                        uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
-    Call c(ch);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_canonical_kmers needs 1 <= k <= 32");
-    if (max_count != 0 && min_count > max_count) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_canonical_kmers: min_count > max_count");
-    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    if (host) stream = h->stream;
-    const Clock clock;
-    *out_n = 0;
-    SpectrumInfo info;
-    info.k = k;
-    if (h->totals.total == 0) {
-        record(h, info, clock);
-        return MSBWT_OK;
-    }
-    Scratch s;
-    if (int rc = take_scratch(h, s, false, 0, "enumerate_canonical_kmers", true)) return rc;
+// Both forms of the canonical dump: records (canonical word, own, other), in the order the walk produces them.
+int enumerate_canonical(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, bool host, void *out_kmers, void *out_own, void *out_other,
+                        uint64_t capacity, uint64_t *out_n, hipStream_t stream) {
+    Frame f(bwt, "enumerate_canonical_kmers", k, host, stream);
+    if (int rc = f.open(false, [&] {
+            if (max_count != 0 && min_count > max_count) return f.refuse(": min_count > max_count");
+            return f.need_outputs(out_n, capacity, out_kmers);
+        }))
+        return rc;
     CanonicalSink sink{};
     sink.mode = kCanonicalCount;
     sink.min = std::max<uint64_t>(min_count, 1);
@@ -198,56 +355,29 @@ int enumerate_canonical(const msbwt_rle *ch, size_t k, uint64_t min_count, uint6
     // of two strands whose counts sum to sink.min or more, the one that emits the class -- the larger -- has at least half of it
     const uint64_t prune = sink.min / 2 + sink.min % 2;
     uint64_t totals[kCanonicalTotalWords] = {};
-    if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
-    const uint64_t n = totals[kCanonicalClasses];
-    *out_n = n;
-    record(h, info, clock, s.arena.taken);
-    if (capacity == 0 || n == 0) return host ? status_of(h, stream, which) : int(MSBWT_OK);
-    if (capacity < n)
-        return fail(h, MSBWT_ERR_INVALID_ARG,
-                    "enumerate_canonical_kmers: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " classes that qualify");
-    sink.mode = kCanonicalAppend;
-    sink.kmers = static_cast<uint64_t *>(out_kmers);
-    sink.own = static_cast<uint64_t *>(out_own);
-    sink.other = static_cast<uint64_t *>(out_other);
-    sink.capacity = capacity;
-    sink.flags = h->d_flags + which;
-    if (host) {  // records staged in HBM, then copied out
-        const uint64_t columns = 1 + (out_own ? 1 : 0) + (out_other ? 1 : 0);
-        uint64_t *stage = nullptr;
-        size_t free_bytes = 0, all_bytes = 0;
-        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
-        if (free_bytes < n * columns * 8 || s.arena.take(&stage, n * columns * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "enumerate_canonical_kmers: " + std::to_string(n * columns * 8) + " more bytes of HBM needed for the records");
-        }
-        sink.kmers = stage;
-        sink.own = out_own ? stage + n : nullptr;
-        sink.other = out_other ? stage + n * (out_own ? 2 : 1) : nullptr;
-        sink.capacity = n;
-    }
-    if (int rc = canonical_walk(h, s, k, prune, sink, &info, stream, which, totals)) return rc;
-    record(h, info, clock, s.arena.taken);
-    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
-    HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_own) HIP_TRY(h, hipMemcpyAsync(out_own, sink.own, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_other) HIP_TRY(h, hipMemcpyAsync(out_other, sink.other, n * 8, hipMemcpyDeviceToHost, stream));
-    return status_of(h, stream, which);  // synchronises
+    Column cols[] = {{out_kmers}, {out_own}, {out_other}};
+    return two_pass(
+        f, capacity, out_n, "classes", true,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, kCanonicalShape)) return rc;
+            if (int rc = canonical_walk(f, prune, sink, totals)) return rc;
+            *n = totals[kCanonicalClasses];
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) -> int {
+            if (int rc = stage_records(f, cols, n, &capacity, "for the records")) return rc;
+            sink.mode = kCanonicalAppend;
+            sink.kmers = cols[0].at;
+            sink.own = cols[1].at;
+            sink.other = cols[2].at;
+            sink.capacity = capacity;
+            sink.flags = f.h->d_flags + f.which;
+            return canonical_walk(f, prune, sink, totals);
+        },
+        [&](uint64_t n) { return copy_out(f, cols, n); });
 }
 
 // ---- k-mers by source ----
-
-int need_sources(msbwt_rle *h) { return h->sources.n_sources ? int(MSBWT_OK) : fail(h, MSBWT_ERR_NOT_LOADED, "no sources attached"); }
-
-// bytes of scratch a by-source call allocates: the walk's (plan_bytes), the sink's fixed words, and per record staged for a host dump
-// the word, l and the S counts.  Nothing here grows with frontier x sources.
-int by_source_plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t frontier, size_t n_sources, uint64_t records, bool sorted, uint64_t *bytes) {
-    if (n_sources < 1 || n_sources > kSourceMax) return MSBWT_ERR_INVALID_ARG;
-    if (records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
-    if (int rc = plan_bytes(total_rows, free_bytes, frontier, 0, sorted, bytes)) return rc;
-    *bytes += kSourceSinkFixedBytes + records * (2 + n_sources) * sizeof(uint64_t);
-    return MSBWT_OK;
-}
 
 // the sink's fixed words: the limits, then the totals
 struct SourceFixed {
@@ -255,231 +385,150 @@ struct SourceFixed {
     unsigned long long *totals = nullptr;
 };
 
-int take_source_fixed(msbwt_rle *h, Scratch &s, SourceFixed &f, const char *what) {
-    if (s.arena.take(&f.limits, kSourceSinkFixedBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, std::string(what) + ": " + std::to_string(kSourceSinkFixedBytes) + " more bytes of HBM needed for the sink");
-    }
-    f.totals = reinterpret_cast<unsigned long long *>(f.limits + 2 * kSourceMax);
+int take_source_fixed(Frame &f, SourceFixed &x) {
+    if (int rc = f.take(&x.limits, kSourceSinkFixedBytes, f.needs(kSourceSinkFixedBytes, true, "for the sink"))) return rc;
+    x.totals = reinterpret_cast<unsigned long long *>(x.limits + 2 * kSourceMax);
     return MSBWT_OK;
 }
 
-// One walk of a by-source call: chunk by chunk the k-mers at least `prune` wide are staged and handed to the source sink (its totals:
-// f.totals, copied to totals[] at the end).  Synchronises the stream.
-int by_source_walk(msbwt_rle *h, const Scratch &s, const SourceFixed &f, size_t k, uint64_t prune, SourceSink sink, SpectrumInfo *info, hipStream_t stream, uint64_t *totals) {
-    sink.totals = f.totals;
-    sink.limits = f.limits;
-    HIP_TRY(h, hipMemsetAsync(f.totals, 0, kSourceTotalWords * 8, stream));
-    const SourceView view = h->sources.view(h->totals.total);
-    const SpectrumChunkHook per_chunk = [&](const void *d_kmers, uint64_t m) { return launch_source_sink(d_kmers, m, view, sink, stream); };
-    HIP_TRY(h, spectrum_stage(view_of(h), seeds_of(h, k), uint32_t(k), prune, s.work, s.frontier, per_chunk, info, stream));
-    HIP_TRY(h, hipMemcpyAsync(totals, f.totals, kSourceTotalWords * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(h, hipStreamSynchronize(stream));
-    return MSBWT_OK;
+// One walk of a by-source call: a chunk's k-mers go to the source sink (its totals: x.totals, copied to totals[] at the end).
+// Synchronises the stream.
+int by_source_walk(Frame &f, const SourceFixed &x, uint64_t prune, SourceSink sink, uint64_t *totals) {
+    sink.totals = x.totals;
+    sink.limits = x.limits;
+    const SourceView view = f.h->sources.view(f.h->totals.total);
+    return staged_walk(f, prune, x.totals, kSourceTotalWords, totals, [&](const void *d_kmers, uint64_t m) { return launch_source_sink(d_kmers, m, view, sink, f.stream); });
 }
 
 uint64_t add_saturating(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
 
-// Both forms of the by-source dump, as enumerate() above: records (word, c_0 .. c_{S-1}, l).
-int enumerate_by_source(const msbwt_rle *ch, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total, uint64_t max_total, int sorted, bool host,
-                        void *out_kmers, void *out_counts, void *out_l, uint64_t capacity, uint64_t *out_n, hipStream_t stream, int which) {
-    Call c(ch);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (int rc = need_sources(h)) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source needs 1 <= k <= 32");
-    const uint64_t S = h->sources.n_sources;
+// Both forms of the by-source dump: records (word, c_0 .. c_{S-1}, l).
+int enumerate_by_source(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total, uint64_t max_total, int sorted, bool host,
+                        void *out_kmers, void *out_counts, void *out_l, uint64_t capacity, uint64_t *out_n, hipStream_t stream) {
+    Frame f(bwt, "enumerate_kmers_by_source", k, host, stream);
     uint64_t limits[2 * kSourceMax];
-    uint64_t prune = std::max<uint64_t>(min_total, 1), min_sum = 0;
-    for (uint32_t s = 0; s < kSourceMax; ++s) {
-        limits[s] = s < S && min_counts ? min_counts[s] : 0ull;
-        limits[kSourceMax + s] = s < S && max_counts ? max_counts[s] : ~0ull;
-        if (limits[s] > limits[kSourceMax + s]) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source: min_counts[" + std::to_string(s) + "] > max_counts[" + std::to_string(s) + "]");
-        min_sum = add_saturating(min_sum, limits[s]);
-    }
-    if (max_total != 0 && min_total > max_total) return fail(h, MSBWT_ERR_INVALID_ARG, "enumerate_kmers_by_source: min_total > max_total");
-    if (!out_n || (capacity && !out_kmers)) return fail(h, MSBWT_ERR_INVALID_ARG, host ? "null pointer" : "null device pointer");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    if (host) stream = h->stream;
-    const Clock clock;
-    *out_n = 0;
-    SpectrumInfo info;
-    info.k = k;
-    if (h->totals.total == 0) {
-        record(h, info, clock);
-        return MSBWT_OK;
-    }
+    uint64_t min_sum = 0;
+    if (int rc = f.open(true, [&] {
+            const uint64_t S = f.h->sources.n_sources;
+            for (uint32_t s = 0; s < kSourceMax; ++s) {
+                limits[s] = s < S && min_counts ? min_counts[s] : 0ull;
+                limits[kSourceMax + s] = s < S && max_counts ? max_counts[s] : ~0ull;
+                if (limits[s] > limits[kSourceMax + s]) return f.refuse(": min_counts[" + std::to_string(s) + "] > max_counts[" + std::to_string(s) + "]");
+                min_sum = add_saturating(min_sum, limits[s]);
+            }
+            if (max_total != 0 && min_total > max_total) return f.refuse(": min_total > max_total");
+            return f.need_outputs(out_n, capacity, out_kmers);
+        }))
+        return rc;
+    msbwt_rle *h = f.h;
     // a suffix's total is at least the k-mer's, and the k-mer's is at least the sum of its minima
-    prune = std::max(prune, min_sum);
+    const uint64_t prune = std::max(std::max<uint64_t>(min_total, 1), min_sum);
     const bool rank = sorted != 0 && capacity != 0;
-    Scratch s;
-    if (int rc = take_scratch(h, s, rank, kSourceSinkFixedBytes, "enumerate_kmers_by_source")) return rc;
-    SourceFixed f;
-    if (int rc = take_source_fixed(h, s, f, "enumerate_kmers_by_source")) return rc;
-    HIP_TRY(h, hipMemcpyAsync(f.limits, limits, sizeof limits, hipMemcpyHostToDevice, stream));
-    HIP_TRY(h, hipStreamSynchronize(stream));  // (the limits are this frame's)
+    SourceFixed x;
     SourceSink sink{};
     sink.mode = kSourceSinkCount;
     sink.min_total = std::max<uint64_t>(min_total, 1);
     sink.max_total = max_total ? max_total : ~0ull;
-    sink.flags = h->d_flags + which;
     SpectrumRank r{};
-    if (rank) {
-        r = spectrum_rank_view(s.rank, h->totals.total);
-        HIP_TRY(h, spectrum_rank_clear(r, stream));
-        sink.bitmap = r.bitmap;
-    }
     uint64_t totals[kSourceTotalWords] = {};
-    if (int rc = by_source_walk(h, s, f, k, prune, sink, &info, stream, totals)) return rc;
-    const uint64_t n = totals[kSourcePassed];
-    *out_n = n;
-    record(h, info, clock, s.arena.taken);
-    if (capacity == 0 || n == 0) return host ? status_of(h, stream, which) : int(MSBWT_OK);
-    if (capacity < n)
-        return fail(h, MSBWT_ERR_INVALID_ARG,
-                    "enumerate_kmers_by_source: capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
-    sink.mode = rank ? kSourceSinkScatter : kSourceSinkAppend;
-    sink.kmers = static_cast<uint64_t *>(out_kmers);
-    sink.counts = static_cast<uint64_t *>(out_counts);
-    sink.l = static_cast<uint64_t *>(out_l);
-    sink.capacity = capacity;
-    if (rank) {
-        HIP_TRY(h, spectrum_rank_close(r, stream));
-        sink.prefix = r.prefix;
-    }
-    if (host) {  // records staged in HBM, then copied out
-        const uint64_t words = n * (1 + (out_counts ? S : 0) + (out_l ? 1 : 0));
-        uint64_t *stage = nullptr;
-        size_t free_bytes = 0, all_bytes = 0;
-        HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
-        if (free_bytes < words * 8 || s.arena.take(&stage, words * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "enumerate_kmers_by_source: " + std::to_string(words * 8) + " more bytes of HBM needed for the records");
-        }
-        sink.kmers = stage;
-        sink.l = out_l ? stage + n : nullptr;
-        sink.counts = out_counts ? stage + n * (out_l ? 2 : 1) : nullptr;
-        sink.capacity = n;
-    }
-    if (int rc = by_source_walk(h, s, f, k, prune, sink, &info, stream, totals)) return rc;
-    record(h, info, clock, s.arena.taken);
-    if (!host) return MSBWT_OK;  // (a fault is in the device status word: msbwt_rle_device_status)
-    HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, sink.counts, n * S * 8, hipMemcpyDeviceToHost, stream));
-    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, sink.l, n * 8, hipMemcpyDeviceToHost, stream));
-    return status_of(h, stream, which);  // synchronises
+    Column cols[] = {{out_kmers}, {out_counts, h->sources.n_sources}, {out_l}};
+    return two_pass(
+        f, capacity, out_n, "k-mers", true,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, by_source_shape(rank, h->sources.n_sources))) return rc;
+            if (int rc = take_source_fixed(f, x)) return rc;
+            HIP_TRY(h, hipMemcpyAsync(x.limits, limits, sizeof limits, hipMemcpyHostToDevice, f.stream));
+            HIP_TRY(h, hipStreamSynchronize(f.stream));  // (the limits are this frame's)
+            sink.flags = h->d_flags + f.which;
+            if (rank) {
+                r = spectrum_rank_view(f.rank, h->totals.total);
+                HIP_TRY(h, spectrum_rank_clear(r, f.stream));
+                sink.bitmap = r.bitmap;
+            }
+            if (int rc = by_source_walk(f, x, prune, sink, totals)) return rc;
+            *n = totals[kSourcePassed];
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) -> int {
+            sink.mode = rank ? kSourceSinkScatter : kSourceSinkAppend;
+            if (rank) {
+                HIP_TRY(h, spectrum_rank_close(r, f.stream));
+                sink.prefix = r.prefix;
+            }
+            if (int rc = stage_records(f, cols, n, &capacity, "for the records")) return rc;
+            sink.kmers = cols[0].at;
+            sink.counts = cols[1].at;
+            sink.l = cols[2].at;
+            sink.capacity = capacity;
+            return by_source_walk(f, x, prune, sink, totals);
+        },
+        [&](uint64_t n) { return copy_out(f, cols, n); });
 }
 
 // ---- the k-mer graph ----
 
-// bytes of scratch a graph call that fills buffers (or the degree table) allocates: the sorted walk's (plan_bytes), the degree counters,
-// the edge bytes of `records` nodes as whole 32-bit words, and `columns` 8-byte words per record staged for a host dump
-int graph_plan_bytes(uint64_t total_rows, uint64_t free_bytes, uint64_t records, uint64_t columns, uint64_t *bytes) {
-    if (records >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
-    if (int rc = plan_bytes(total_rows, free_bytes, 0, 0, true, bytes)) return rc;
-    *bytes += kGraphFixedBytes + graph_edge_words(records) * 4 + records * columns * 8;
-    return MSBWT_OK;
-}
-
-// The dump (both forms) and the degree table (table != nullptr: no record outputs, *out_n = the nodes, *out_edge_count = the edges).
-// host: the out_* are host arrays, filled through a device staging of n records; else device arrays.
-int kmer_graph(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_kmers, void *out_counts, void *out_l, void *out_edges,
-               uint64_t capacity, uint64_t *out_n, uint64_t *table, uint64_t *out_edge_count, hipStream_t stream, int which) {
+// The dump (both forms) and the degree table (table != nullptr: no record outputs, *out_n = the nodes, *out_edge_count = the edges):
+// the sorted dump's counting walk, then the staged walk with the edge pass behind it.
+int kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_kmers, void *out_counts, void *out_l, void *out_edges,
+               uint64_t capacity, uint64_t *out_n, uint64_t *table, uint64_t *out_edge_count, hipStream_t stream) {
     const bool degrees = table != nullptr;
-    const char *what = degrees ? "kmer_graph_degrees" : "enumerate_kmer_graph";
-    Call c(ch);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + " needs 1 <= k <= 32");
+    Frame f(bwt, degrees ? "kmer_graph_degrees" : "enumerate_kmer_graph", k, host, stream);
     const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
-    if (me < m) return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + ": min_edge is below the node threshold (0 = the node threshold)");
-    if (!degrees && !out_n) return fail(h, MSBWT_ERR_INVALID_ARG, "null pointer");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    if (host) stream = h->stream;
-    const Clock clock;
-    uint64_t n = 0;
-    if (out_n) *out_n = 0;
+    if (int rc = f.open(false, [&] {
+            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
+            return !degrees && !out_n ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
+        }))
+        return rc;
+    msbwt_rle *h = f.h;
     if (out_edge_count) *out_edge_count = 0;
     if (degrees) std::fill(table, table + kGraphTableWords, 0ull);
-    SpectrumInfo info;
-    info.k = k;
-    if (h->totals.total == 0) {
-        record(h, info, clock);
-        return MSBWT_OK;
-    }
-    const bool fill = degrees || capacity != 0;
-    Scratch s;
-    if (int rc = take_scratch(h, s, fill, fill ? kGraphFixedBytes : 0, what)) return rc;
+    const bool fill = degrees || capacity != 0;  // (the degree table has no capacity to fall short)
     const IndexView v = view_of(h);
-    const SpectrumSeeds seeds = seeds_of(h, k);
-    HIP_TRY(h, spectrum_count(v, seeds, uint32_t(k), m, 0, s.work, s.frontier, s.rank, &n, &info, stream));
-    if (out_n) *out_n = n;
-    record(h, info, clock, s.arena.taken);
-    if (!fill || n == 0) return MSBWT_OK;
-    if (!degrees && capacity < n)
-        return fail(h, MSBWT_ERR_INVALID_ARG, std::string(what) + ": capacity " + std::to_string(capacity) + " is less than the n = " + std::to_string(n) + " k-mers that qualify");
-    // one allocation: the records staged for a host dump | the degree counters | the edge words
-    const uint64_t columns = host && !degrees ? (out_kmers ? 1 : 0) + (out_counts ? 1 : 0) + (out_l ? 1 : 0) : 0;
-    const uint64_t stage_bytes = n * columns * 8, edge_bytes = graph_edge_words(n) * 4, more = stage_bytes + kGraphFixedBytes + edge_bytes;
-    char *block = nullptr;
-    size_t free_bytes = 0, all_bytes = 0;
-    HIP_TRY(h, hipMemGetInfo(&free_bytes, &all_bytes));
-    if (free_bytes < more || s.arena.take(&block, more) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, MSBWT_ERR_HIP, std::string(what) + ": " + std::to_string(more) + " more bytes of HBM needed for the edge bytes and the records");
-    }
-    uint64_t *stage = reinterpret_cast<uint64_t *>(block), *d_table = reinterpret_cast<uint64_t *>(block + stage_bytes);
-    uint32_t *edge_words = reinterpret_cast<uint32_t *>(block + stage_bytes + kGraphFixedBytes);
-    HIP_TRY(h, hipMemsetAsync(d_table, 0, kGraphFixedBytes + edge_bytes, stream));
-    const SpectrumRank r = spectrum_rank_view(s.rank, h->totals.total);
-    GraphSink sink{};
-    sink.bitmap = r.bitmap;
-    sink.prefix = r.prefix;
-    sink.edge_words = edge_words;
-    sink.n = n;
-    sink.min_edge = me;
-    sink.flags = h->d_flags + which;
-    if (host && !degrees) {
-        uint64_t *next = stage;
-        auto column = [&](const void *wanted) {
-            uint64_t *at = wanted ? next : nullptr;
-            if (wanted) next += n;
-            return at;
-        };
-        sink.kmers = column(out_kmers);
-        sink.counts = column(out_counts);
-        sink.l = column(out_l);
-    } else if (!degrees) {
-        sink.kmers = static_cast<uint64_t *>(out_kmers);
-        sink.counts = static_cast<uint64_t *>(out_counts);
-        sink.l = static_cast<uint64_t *>(out_l);
-    }
-    const SpectrumChunkHook per_chunk = [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, stream); };
-    HIP_TRY(h, spectrum_stage(v, seeds, uint32_t(k), m, s.work, s.frontier, per_chunk, &info, stream));
-    record(h, info, clock, s.arena.taken);
-    if (degrees) {
-        HIP_TRY(h, launch_graph_degrees(edge_words, n, d_table, stream));
-        HIP_TRY(h, hipMemcpyAsync(table, d_table, kGraphTableWords * 8, hipMemcpyDeviceToHost, stream));
-        if (int rc = status_of(h, stream, which)) return rc;  // synchronises
-        uint64_t edges = 0;
-        for (uint32_t i = 0; i < kGraphTableWords; ++i) edges += uint64_t(i / kGraphDegrees) * table[i];  // (the in-degrees; the out-degrees sum to the same)
-        if (out_edge_count) *out_edge_count = edges;
-        return MSBWT_OK;
-    }
-    if (!host) {  // (a fault is in the device status word: msbwt_rle_device_status)
-        if (out_edges) HIP_TRY(h, hipMemcpyAsync(out_edges, edge_words, n, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(h, hipStreamSynchronize(stream));  // (the last chunk's edge pass, and the scratch is freed on return)
-        return MSBWT_OK;
-    }
-    if (out_kmers) HIP_TRY(h, hipMemcpyAsync(out_kmers, sink.kmers, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_counts) HIP_TRY(h, hipMemcpyAsync(out_counts, sink.counts, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_l) HIP_TRY(h, hipMemcpyAsync(out_l, sink.l, n * 8, hipMemcpyDeviceToHost, stream));
-    if (out_edges) HIP_TRY(h, hipMemcpyAsync(out_edges, edge_words, n, hipMemcpyDeviceToHost, stream));
-    return status_of(h, stream, which);  // synchronises
+    Column cols[] = {{out_kmers}, {out_counts}, {out_l}};
+    uint64_t *d_table = nullptr;
+    uint32_t *edge_words = nullptr;
+    return two_pass(
+        f, degrees ? ~0ull : capacity, out_n, "k-mers", false,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, graph_shape(fill))) return rc;
+            HIP_TRY(h, spectrum_count(v, seeds_of(f), uint32_t(k), m, 0, f.work, f.frontier, f.rank, n, &f.info, f.stream));
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) -> int {
+            // one allocation: the records staged for a host dump | the degree counters | the edge words
+            const uint64_t edge_bytes = graph_edge_words(n) * 4;
+            char *tail = nullptr;
+            if (int rc = stage_records(f, cols, n, &capacity, "for the edge bytes and the records", kGraphFixedBytes + edge_bytes, &tail)) return rc;
+            d_table = reinterpret_cast<uint64_t *>(tail);
+            edge_words = reinterpret_cast<uint32_t *>(tail + kGraphFixedBytes);
+            HIP_TRY(h, hipMemsetAsync(d_table, 0, kGraphFixedBytes + edge_bytes, f.stream));
+            const SpectrumRank r = spectrum_rank_view(f.rank, h->totals.total);
+            GraphSink sink{};
+            sink.bitmap = r.bitmap;
+            sink.prefix = r.prefix;
+            sink.edge_words = edge_words;
+            sink.n = n;
+            sink.min_edge = me;
+            sink.flags = h->d_flags + f.which;
+            sink.kmers = cols[0].at;
+            sink.counts = cols[1].at;
+            sink.l = cols[2].at;
+            return staged_walk(f, m, nullptr, 0, nullptr, [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, f.stream); });
+        },
+        [&](uint64_t n) -> int {
+            if (degrees) {
+                HIP_TRY(h, launch_graph_degrees(edge_words, n, d_table, f.stream));
+                HIP_TRY(h, hipMemcpyAsync(table, d_table, kGraphTableWords * 8, hipMemcpyDeviceToHost, f.stream));
+                if (int rc = status_of(h, f.stream, f.which)) return rc;  // synchronises
+                uint64_t edges = 0;
+                for (uint32_t i = 0; i < kGraphTableWords; ++i) edges += uint64_t(i / kGraphDegrees) * table[i];  // (the in-degrees; the out-degrees sum to the same)
+                if (out_edge_count) *out_edge_count = edges;
+                return MSBWT_OK;
+            }
+            if (out_edges) HIP_TRY(h, hipMemcpyAsync(out_edges, edge_words, n, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, f.stream));
+            if (!host) HIP_TRY(h, hipStreamSynchronize(f.stream));  // (the last chunk's edge pass, and the scratch is freed on return)
+            return copy_out(f, cols, n);
+        });
 }
 
 }  // namespace
@@ -487,49 +536,27 @@ int kmer_graph(const msbwt_rle *ch, size_t k, uint64_t min_count, uint64_t min_e
 extern "C" {
 
 int msbwt_rle_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_distinct, uint64_t *out_occurrences) {
-    Call c(bwt);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum needs 1 <= k <= 32");
-    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum needs a histogram of at least 2 bins");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    const Clock clock;
-    uint64_t scratch_bytes = 0;
-    SpectrumInfo info;
-    info.k = k;
+    Frame f(bwt, "kmer_spectrum", k);
     uint64_t distinct = 0, occurrences = 0;
-    std::fill(out_hist, out_hist + n_bins, 0ull);
-    if (h->totals.total != 0) {
-        Scratch s;
-        if (int rc = take_scratch(h, s, false, uint64_t(n_bins) * 8, "kmer_spectrum")) return rc;
-        uint64_t *d_hist = nullptr;
-        if (s.arena.take(&d_hist, uint64_t(n_bins) * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "kmer_spectrum: " + std::to_string(uint64_t(n_bins) * 8) + " bytes of HBM needed for the histogram");
-        }
-        HIP_TRY(h, hipMemsetAsync(d_hist, 0, uint64_t(n_bins) * 8, h->stream));
-        HIP_TRY(h, spectrum_histogram(view_of(h), seeds_of(h, k), uint32_t(k), s.work, s.frontier, d_hist, n_bins, &distinct, &occurrences, &info, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        scratch_bytes = s.arena.taken;
-    }
+    if (int rc = spectrum(f, false, plain_shape(false), false, out_hist, n_bins, [&](uint64_t bytes, uint64_t **d_hist) -> int {
+            if (int rc = take_histogram(f, bytes, "for the histogram", d_hist)) return rc;
+            HIP_TRY(f.h, spectrum_histogram(view_of(f.h), seeds_of(f), uint32_t(k), f.work, f.frontier, *d_hist, n_bins, &distinct, &occurrences, &f.info, f.stream));
+            return MSBWT_OK;
+        }))
+        return rc;
     if (out_distinct) *out_distinct = distinct;
     if (out_occurrences) *out_occurrences = occurrences;
-    record(h, info, clock, scratch_bytes);
     return MSBWT_OK;
 }
 
 int msbwt_rle_enumerate_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted, uint64_t *out_kmers2bit, uint64_t *out_counts,
                               uint64_t *out_l, uint64_t capacity, uint64_t *out_n) {
-    return enumerate(bwt, k, min_count, max_count, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr, kHostFlags);
+    return enumerate(bwt, k, min_count, max_count, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr);
 }
 
 int msbwt_rle_enumerate_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, int sorted, void *d_out_kmers2bit, void *d_out_counts,
                                      void *d_out_l, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
-    return enumerate(bwt, k, min_count, max_count, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n, static_cast<hipStream_t>(hip_stream),
-                     kDeviceFlags);
+    return enumerate(bwt, k, min_count, max_count, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n, static_cast<hipStream_t>(hip_stream));
 }
 
 int msbwt_rle_set_spectrum_frontier(msbwt_rle *bwt, uint64_t nodes) {
@@ -548,11 +575,15 @@ int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out) {
     return MSBWT_OK;
 }
 
-int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, int sorted, uint64_t *device_bytes) {
-    uint64_t bytes = 0;
-    if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, sorted != 0, &bytes)) return rc;
-    if (device_bytes) *device_bytes = bytes;
+int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes) {
+    Call c(bwt);
+    if (!c.h || !out_bytes) return MSBWT_ERR_INVALID_ARG;
+    *out_bytes = c.h->spectrum_scratch;
     return MSBWT_OK;
+}
+
+int msbwt_spectrum_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, int sorted, uint64_t *device_bytes) {
+    return plan(plain_shape(sorted != 0), total_rows, free_hbm_bytes, records, 0, device_bytes);
 }
 
 // ---- canonical k-mers: a k-mer and its reverse complement as one class ----
@@ -564,168 +595,108 @@ int msbwt_kmers_reverse_complement_2bit(const uint64_t *words, size_t k, size_t 
 }
 
 int msbwt_rle_canonical_kmer_spectrum(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_distinct, uint64_t *out_occurrences) {
-    Call c(bwt);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "canonical_kmer_spectrum needs 1 <= k <= 32");
-    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "canonical_kmer_spectrum needs a histogram of at least 2 bins");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    const Clock clock;
-    uint64_t scratch_bytes = 0;
-    SpectrumInfo info;
-    info.k = k;
+    Frame f(bwt, "canonical_kmer_spectrum", k);
     uint64_t totals[kCanonicalTotalWords] = {};
-    std::fill(out_hist, out_hist + n_bins, 0ull);
-    if (h->totals.total != 0) {
-        Scratch s;
-        if (int rc = take_scratch(h, s, false, uint64_t(n_bins) * 8, "canonical_kmer_spectrum", true)) return rc;
-        uint64_t *d_hist = nullptr;
-        if (s.arena.take(&d_hist, uint64_t(n_bins) * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "canonical_kmer_spectrum: " + std::to_string(uint64_t(n_bins) * 8) + " bytes of HBM needed for the histogram");
-        }
-        HIP_TRY(h, hipMemsetAsync(d_hist, 0, uint64_t(n_bins) * 8, h->stream));
-        CanonicalSink sink{};
-        sink.mode = kCanonicalHist;
-        sink.min = 1;
-        sink.max = ~0ull;
-        sink.hist = reinterpret_cast<unsigned long long *>(d_hist);
-        sink.n_bins = n_bins;
-        if (int rc = canonical_walk(h, s, k, 1, sink, &info, h->stream, kHostFlags, totals)) return rc;
-        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, uint64_t(n_bins) * 8, hipMemcpyDeviceToHost, h->stream));
-        if (int rc = status_of(h, h->stream, kHostFlags)) return rc;  // synchronises; the search's flags
-        scratch_bytes = s.arena.taken;
-    }
+    if (int rc = spectrum(f, false, kCanonicalShape, true, out_hist, n_bins, [&](uint64_t bytes, uint64_t **d_hist) -> int {  // (flags: the search's)
+            if (int rc = take_histogram(f, bytes, "for the histogram", d_hist)) return rc;
+            CanonicalSink sink{};
+            sink.mode = kCanonicalHist;
+            sink.min = 1;
+            sink.max = ~0ull;
+            sink.hist = reinterpret_cast<unsigned long long *>(*d_hist);
+            sink.n_bins = n_bins;
+            return canonical_walk(f, 1, sink, totals);
+        }))
+        return rc;
     if (out_distinct) *out_distinct = totals[kCanonicalClasses];
     if (out_occurrences) *out_occurrences = totals[kCanonicalOccurrences];
-    record(h, info, clock, scratch_bytes);
     return MSBWT_OK;
 }
 
 int msbwt_rle_enumerate_canonical_kmers(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, uint64_t *out_kmers2bit, uint64_t *out_own,
                                         uint64_t *out_other, uint64_t capacity, uint64_t *out_n) {
-    return enumerate_canonical(bwt, k, min_count, max_count, true, out_kmers2bit, out_own, out_other, capacity, out_n, nullptr, kHostFlags);
+    return enumerate_canonical(bwt, k, min_count, max_count, true, out_kmers2bit, out_own, out_other, capacity, out_n, nullptr);
 }
 
 int msbwt_rle_enumerate_canonical_kmers_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t max_count, void *d_out_kmers2bit, void *d_out_own,
                                                void *d_out_other, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
-    return enumerate_canonical(bwt, k, min_count, max_count, false, d_out_kmers2bit, d_out_own, d_out_other, capacity, out_n, static_cast<hipStream_t>(hip_stream),
-                               kDeviceFlags);
+    return enumerate_canonical(bwt, k, min_count, max_count, false, d_out_kmers2bit, d_out_own, d_out_other, capacity, out_n, static_cast<hipStream_t>(hip_stream));
 }
 
 int msbwt_canonical_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
-    uint64_t bytes = 0;
-    if (int rc = plan_bytes(total_rows, free_hbm_bytes, 0, records, false, &bytes)) return rc;
-    if (device_bytes) *device_bytes = bytes + spectrum_frontier_nodes(total_rows, free_hbm_bytes, 0) * kCanonicalStageBytes;
-    return MSBWT_OK;
+    return plan(kCanonicalShape, total_rows, free_hbm_bytes, records, 0, device_bytes);
 }
 
 // ---- k-mers by source: one spectrum per input of a merged index, and the dump filtered by per-source counts ----
 
 int msbwt_rle_kmer_spectrum_by_source(const msbwt_rle *bwt, size_t k, uint64_t *out_hist, size_t n_bins, uint64_t *out_sharing, uint64_t *out_distinct,
                                       uint64_t *out_occurrences) {
-    Call c(bwt);
-    msbwt_rle *h = c.h;
-    if (!h) return MSBWT_ERR_INVALID_ARG;
-    if (int rc = c.loaded()) return rc;
-    if (int rc = need_sources(h)) return rc;
-    if (k < 1 || k > kSpectrumMaxK) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum_by_source needs 1 <= k <= 32");
-    if (n_bins < 2 || !out_hist) return fail(h, MSBWT_ERR_INVALID_ARG, "kmer_spectrum_by_source needs histograms of at least 2 bins");
-    if (int rc = c.bind()) return rc;
-    if (int rc = ensure_runtime(h)) return rc;
-    const Clock clock;
-    uint64_t scratch_bytes = 0;
-    SpectrumInfo info;
-    info.k = k;
-    const uint64_t S = h->sources.n_sources, hist_bytes = S * uint64_t(n_bins) * 8;
+    Frame f(bwt, "kmer_spectrum_by_source", k);
     uint64_t totals[kSourceTotalWords] = {};
-    std::fill(out_hist, out_hist + S * n_bins, 0ull);
-    if (h->totals.total != 0) {
-        Scratch s;
-        if (int rc = take_scratch(h, s, false, hist_bytes + kSourceSinkFixedBytes, "kmer_spectrum_by_source")) return rc;
-        SourceFixed f;
-        if (int rc = take_source_fixed(h, s, f, "kmer_spectrum_by_source")) return rc;
-        uint64_t *d_hist = nullptr;
-        if (s.arena.take(&d_hist, hist_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, MSBWT_ERR_HIP, "kmer_spectrum_by_source: " + std::to_string(hist_bytes) + " bytes of HBM needed for the histograms");
-        }
-        HIP_TRY(h, hipMemsetAsync(d_hist, 0, hist_bytes, h->stream));
-        SourceSink sink{};
-        sink.mode = kSourceSinkHist;
-        sink.min_total = 1;
-        sink.max_total = ~0ull;
-        sink.hist = reinterpret_cast<unsigned long long *>(d_hist);
-        sink.n_bins = n_bins;
-        sink.flags = h->d_flags + kHostFlags;
-        if (int rc = by_source_walk(h, s, f, k, 1, sink, &info, h->stream, totals)) return rc;
-        HIP_TRY(h, hipMemcpyAsync(out_hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, h->stream));
-        if (int rc = status_of(h, h->stream, kHostFlags)) return rc;  // synchronises
-        scratch_bytes = s.arena.taken;
-    }
+    if (int rc = spectrum(f, true, by_source_shape(false, f.h ? f.h->sources.n_sources : 0), true, out_hist, n_bins, [&](uint64_t bytes, uint64_t **d_hist) -> int {
+            SourceFixed x;
+            if (int rc = take_source_fixed(f, x)) return rc;
+            if (int rc = take_histogram(f, bytes, "for the histograms", d_hist)) return rc;
+            SourceSink sink{};
+            sink.mode = kSourceSinkHist;
+            sink.min_total = 1;
+            sink.max_total = ~0ull;
+            sink.hist = reinterpret_cast<unsigned long long *>(*d_hist);
+            sink.n_bins = n_bins;
+            sink.flags = f.h->d_flags + f.which;
+            return by_source_walk(f, x, 1, sink, totals);
+        }))
+        return rc;
+    const uint64_t S = f.h->sources.n_sources;
     for (uint64_t s = 0; s < S; ++s) {  // bin 0: the k-mers of the index that source s does not hold
         uint64_t *row = out_hist + s * n_bins, distinct = 0;
         for (size_t b = 1; b < n_bins; ++b) distinct += row[b];
-        row[0] = info.nodes[k] - distinct;
+        row[0] = f.info.nodes[k] - distinct;
         if (out_distinct) out_distinct[s] = distinct;
         if (out_occurrences) out_occurrences[s] = totals[kSourceOccurrences + s];
     }
     if (out_sharing) std::copy(totals + kSourceSharing, totals + kSourceSharing + S + 1, out_sharing);
-    record(h, info, clock, scratch_bytes);
     return MSBWT_OK;
 }
 
 int msbwt_rle_enumerate_kmers_by_source(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total, uint64_t max_total,
                                         int sorted, uint64_t *out_kmers2bit, uint64_t *out_counts, uint64_t *out_l, uint64_t capacity, uint64_t *out_n) {
-    return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr, kHostFlags);
+    return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, true, out_kmers2bit, out_counts, out_l, capacity, out_n, nullptr);
 }
 
 int msbwt_rle_enumerate_kmers_by_source_device(const msbwt_rle *bwt, size_t k, const uint64_t *min_counts, const uint64_t *max_counts, uint64_t min_total,
                                                uint64_t max_total, int sorted, void *d_out_kmers2bit, void *d_out_counts, void *d_out_l, uint64_t capacity,
                                                uint64_t *out_n, void *hip_stream) {
     return enumerate_by_source(bwt, k, min_counts, max_counts, min_total, max_total, sorted, false, d_out_kmers2bit, d_out_counts, d_out_l, capacity, out_n,
-                               static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+                               static_cast<hipStream_t>(hip_stream));
+}
+
+int msbwt_kmers_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, size_t n_sources, uint64_t records, int sorted, uint64_t *device_bytes) {
+    if (n_sources < 1 || n_sources > kSourceMax) return MSBWT_ERR_INVALID_ARG;
+    return plan(by_source_shape(sorted != 0, n_sources), total_rows, free_hbm_bytes, records, 0, device_bytes);
 }
 
 // ---- the k-mer graph: an edge byte per k-mer of the sorted dump, and the table of (in, out) degrees ----
 
 int msbwt_rle_enumerate_kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_kmers2bit, uint64_t *out_counts, uint64_t *out_l,
                                    uint8_t *out_edges, uint64_t capacity, uint64_t *out_n) {
-    return kmer_graph(bwt, k, min_count, min_edge, true, out_kmers2bit, out_counts, out_l, out_edges, capacity, out_n, nullptr, nullptr, nullptr, kHostFlags);
+    return kmer_graph(bwt, k, min_count, min_edge, true, out_kmers2bit, out_counts, out_l, out_edges, capacity, out_n, nullptr, nullptr, nullptr);
 }
 
 int msbwt_rle_enumerate_kmer_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_kmers2bit, void *d_out_counts, void *d_out_l,
                                           void *d_out_edges, uint64_t capacity, uint64_t *out_n, void *hip_stream) {
     return kmer_graph(bwt, k, min_count, min_edge, false, d_out_kmers2bit, d_out_counts, d_out_l, d_out_edges, capacity, out_n, nullptr, nullptr,
-                      static_cast<hipStream_t>(hip_stream), kDeviceFlags);
+                      static_cast<hipStream_t>(hip_stream));
 }
 
 int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint64_t *out_table, uint64_t *out_nodes, uint64_t *out_edges) {
     uint64_t unwanted[kGraphTableWords];
-    return kmer_graph(bwt, k, min_count, min_edge, true, nullptr, nullptr, nullptr, nullptr, 0, out_nodes, out_table ? out_table : unwanted, out_edges, nullptr, kHostFlags);
+    return kmer_graph(bwt, k, min_count, min_edge, true, nullptr, nullptr, nullptr, nullptr, 0, out_nodes, out_table ? out_table : unwanted, out_edges, nullptr);
 }
 
+// the host dump of `records` nodes with words, counts and l
 int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
-    uint64_t bytes = 0;
-    if (int rc = graph_plan_bytes(total_rows, free_hbm_bytes, records, 3, &bytes)) return rc;
-    if (device_bytes) *device_bytes = bytes;
-    return MSBWT_OK;
-}
-
-int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes) {
-    Call c(bwt);
-    if (!c.h || !out_bytes) return MSBWT_ERR_INVALID_ARG;
-    *out_bytes = c.h->spectrum_scratch;
-    return MSBWT_OK;
-}
-
-int msbwt_kmers_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, size_t n_sources, uint64_t records, int sorted, uint64_t *device_bytes) {
-    uint64_t bytes = 0;
-    if (int rc = by_source_plan_bytes(total_rows, free_hbm_bytes, 0, n_sources, records, sorted != 0, &bytes)) return rc;
-    if (device_bytes) *device_bytes = bytes;
-    return MSBWT_OK;
+    return plan(graph_shape(true), total_rows, free_hbm_bytes, records, graph_edge_words(records) * 4, device_bytes);
 }
 
 }  // extern "C"

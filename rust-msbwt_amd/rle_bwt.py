@@ -334,6 +334,32 @@ class RleBWT(BWT):
             _raise(rc, self._h)
 
     # ---- the k-mers the index holds: spectrum and enumeration ----------------------------
+    def _two_calls(self, fn, args, n_columns, columns):
+        """The two-call pattern of a host dump fn(handle, *args, <a pointer per column>, capacity, &n): without buffers it counts;
+        columns(n) then makes the n_columns numpy arrays (None: a column not wanted) that a second call fills when n > 0."""
+        n = C.c_uint64(0)
+        rc = fn(self._h, *args, *[None] * n_columns, 0, C.byref(n))
+        if rc:
+            _raise(rc, self._h)
+        out = columns(n.value)
+        if n.value:
+            rc = fn(self._h, *args, *[None if a is None else a.ctypes.data_as(C.c_void_p) for a in out], n.value, C.byref(n))
+            if rc:
+                _raise(rc, self._h)
+        return out
+
+    def _device_dump(self, fn, *args, stream):
+        """A device dump fn(handle, *args, &n, stream) -> n; an MsbwtError it raises carries n too (a capacity too small still learns it)."""
+        n = C.c_uint64(0)
+        rc = fn(self._h, *args, C.byref(n), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n = n.value  # (set whatever the outcome)
+                raise
+        return n.value
+
     def kmer_spectrum(self, k, bins=256):
         """msbwt_rle_kmer_spectrum -> (hist, distinct, occurrences): hist[c] = distinct k-mers that occur exactly c times (hist[bins - 1]:
         bins - 1 times or more, hist[0] = 0) as uint64[bins]; their number; the sum of their counts."""
@@ -349,33 +375,15 @@ class RleBWT(BWT):
         """msbwt_rle_enumerate_kmers, both calls of the two-call pattern -> (words, counts[, l]) as uint64[n]: the k-mers that occur
         min_count..max_count times (None: no upper limit) as 2-bit words (pack_2bit's layout; unpack_2bit gives the symbols), their
         counts and, with ranges=True, the start l of each one's range [l, l + count).  sorted: ascending k-mers."""
-        lib, n = _lib.lib(), C.c_uint64(0)
-        args = (self._h, int(k), int(min_count), int(max_count or 0), 1 if sorted else 0)
-        rc = lib.msbwt_rle_enumerate_kmers(*args, None, None, None, 0, C.byref(n))
-        if rc:
-            _raise(rc, self._h)
-        words, counts = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.uint64)
-        l = np.empty(n.value, dtype=np.uint64) if ranges else None
-        if n.value:
-            rc = lib.msbwt_rle_enumerate_kmers(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
-                                               l.ctypes.data_as(C.c_void_p) if ranges else None, n.value, C.byref(n))
-            if rc:
-                _raise(rc, self._h)
+        words, counts, l = self._two_calls(_lib.lib().msbwt_rle_enumerate_kmers, (int(k), int(min_count), int(max_count or 0), 1 if sorted else 0), 3,
+                                           lambda n: [np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64) if ranges else None])
         return (words, counts, l) if ranges else (words, counts)
 
     def enumerate_kmers_device(self, k, d_words, d_counts, d_l, capacity, min_count=1, max_count=None, sorted=True, stream=0):
         """msbwt_rle_enumerate_kmers_device: device pointers (ints; d_counts, d_l may be None) of `capacity` u64 each -> n, the k-mers
         that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
-        n = C.c_uint64(0)
-        rc = _lib.lib().msbwt_rle_enumerate_kmers_device(self._h, int(k), int(min_count), int(max_count or 0), 1 if sorted else 0, d_words, d_counts, d_l,
-                                                         int(capacity), C.byref(n), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n = n.value  # (set whatever the outcome: a capacity too small still learns n)
-                raise
-        return n.value
+        return self._device_dump(_lib.lib().msbwt_rle_enumerate_kmers_device, int(k), int(min_count), int(max_count or 0), 1 if sorted else 0, d_words, d_counts, d_l,
+                                 int(capacity), stream=stream)
 
     # ---- the same with a k-mer and its reverse complement as one class ----
     def canonical_kmer_spectrum(self, k, bins=256):
@@ -394,17 +402,8 @@ class RleBWT(BWT):
         other), as uint64[n]: the classes whose count own + other lies in min_count..max_count (None: no upper limit); words = the
         canonical (smaller) 2-bit word of each, own = its count, other = its reverse complement's (0 for a palindrome).  The library
         returns them in the order its walk produces; sorted=True orders them by word here, on the host."""
-        lib, n = _lib.lib(), C.c_uint64(0)
-        args = (self._h, int(k), int(min_count), int(max_count or 0))
-        rc = lib.msbwt_rle_enumerate_canonical_kmers(*args, None, None, None, 0, C.byref(n))
-        if rc:
-            _raise(rc, self._h)
-        words, own, other = (np.empty(n.value, dtype=np.uint64) for _ in range(3))
-        if n.value:
-            rc = lib.msbwt_rle_enumerate_canonical_kmers(*args, words.ctypes.data_as(C.c_void_p), own.ctypes.data_as(C.c_void_p),
-                                                         other.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
-            if rc:
-                _raise(rc, self._h)
+        words, own, other = self._two_calls(_lib.lib().msbwt_rle_enumerate_canonical_kmers, (int(k), int(min_count), int(max_count or 0)), 3,
+                                            lambda n: [np.empty(n, dtype=np.uint64) for _ in range(3)])
         if sorted:
             order = np.argsort(words, kind="stable")
             words, own, other = words[order], own[order], other[order]
@@ -413,16 +412,8 @@ class RleBWT(BWT):
     def enumerate_canonical_kmers_device(self, k, d_words, d_own, d_other, capacity, min_count=1, max_count=None, stream=0):
         """msbwt_rle_enumerate_canonical_kmers_device: device pointers (ints; d_own, d_other may be None) of `capacity` u64 each -> n, the
         classes that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
-        n = C.c_uint64(0)
-        rc = _lib.lib().msbwt_rle_enumerate_canonical_kmers_device(self._h, int(k), int(min_count), int(max_count or 0), d_words, d_own, d_other, int(capacity),
-                                                                   C.byref(n), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n = n.value
-                raise
-        return n.value
+        return self._device_dump(_lib.lib().msbwt_rle_enumerate_canonical_kmers_device, int(k), int(min_count), int(max_count or 0), d_words, d_own, d_other,
+                                 int(capacity), stream=stream)
 
     # ---- the k-mers of a merged index by source: one spectrum per input, and the dump filtered by per-source counts ----
     def _source_limits(self, min_counts, max_counts):
@@ -437,6 +428,12 @@ class RleBWT(BWT):
             if a is not None and a.shape != (S,):
                 raise ValueError("min_counts and max_counts hold one entry per source (%d)" % S)
         return lo, hi
+
+    def _by_source_args(self, k, min_counts, max_counts, min_total, max_total, sorted):
+        """(the arguments of both by-source dumps up to `sorted`, the limit arrays they point into -- to be kept alive)"""
+        lo, hi = self._source_limits(min_counts, max_counts) if self.source_count() else (None, None)
+        return (int(k), lo.ctypes.data_as(C.c_void_p) if lo is not None else None, hi.ctypes.data_as(C.c_void_p) if hi is not None else None, int(min_total),
+                int(max_total or 0), 1 if sorted else 0), (lo, hi)
 
     def kmer_spectrum_by_source(self, k, bins=256):
         """msbwt_rle_kmer_spectrum_by_source -> (hist[S, bins], sharing[S + 1], distinct[S], occurrences[S]), uint64: hist[s, c] = k-mers
@@ -457,20 +454,10 @@ class RleBWT(BWT):
         min_counts[s] <= counts[:, s] <= max_counts[s] for every input s and min_total <= counts.sum(1) <= max_total.  In max_counts
         None (the whole argument or an entry) is no limit and 0 means ABSENT from that input: "private to input 0" is
         max_counts=[None, 0, 0, ...].  sorted: ascending k-mers; ranges=True adds the start l of each one's range."""
-        lib, n, S = _lib.lib(), C.c_uint64(0), self.source_count()
-        lo, hi = self._source_limits(min_counts, max_counts) if S else (None, None)
-        args = (self._h, int(k), lo.ctypes.data_as(C.c_void_p) if lo is not None else None, hi.ctypes.data_as(C.c_void_p) if hi is not None else None,
-                int(min_total), int(max_total or 0), 1 if sorted else 0)
-        rc = lib.msbwt_rle_enumerate_kmers_by_source(*args, None, None, None, 0, C.byref(n))
-        if rc:
-            _raise(rc, self._h)
-        words, counts = np.empty(n.value, dtype=np.uint64), np.empty((n.value, S), dtype=np.uint64)
-        l = np.empty(n.value, dtype=np.uint64) if ranges else None
-        if n.value:
-            rc = lib.msbwt_rle_enumerate_kmers_by_source(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
-                                                         l.ctypes.data_as(C.c_void_p) if ranges else None, n.value, C.byref(n))
-            if rc:
-                _raise(rc, self._h)
+        S = self.source_count()
+        args, _limits = self._by_source_args(k, min_counts, max_counts, min_total, max_total, sorted)
+        words, counts, l = self._two_calls(_lib.lib().msbwt_rle_enumerate_kmers_by_source, args, 3,
+                                           lambda n: [np.empty(n, dtype=np.uint64), np.empty((n, S), dtype=np.uint64), np.empty(n, dtype=np.uint64) if ranges else None])
         return (words, counts, l) if ranges else (words, counts)
 
     def enumerate_kmers_by_source_device(self, k, d_words, d_counts, d_l, capacity, min_counts=None, max_counts=None, min_total=1, max_total=None, sorted=True,
@@ -478,18 +465,8 @@ class RleBWT(BWT):
         """msbwt_rle_enumerate_kmers_by_source_device: device pointers (ints; d_counts -- capacity x S u64 -- and d_l may be None) -> n,
         the k-mers that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  The limits are host arrays, as in
         enumerate_kmers_by_source.  Synchronises `stream`."""
-        n = C.c_uint64(0)
-        lo, hi = self._source_limits(min_counts, max_counts) if self.source_count() else (None, None)
-        rc = _lib.lib().msbwt_rle_enumerate_kmers_by_source_device(self._h, int(k), lo.ctypes.data_as(C.c_void_p) if lo is not None else None,
-                                                                   hi.ctypes.data_as(C.c_void_p) if hi is not None else None, int(min_total), int(max_total or 0),
-                                                                   1 if sorted else 0, d_words, d_counts, d_l, int(capacity), C.byref(n), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n = n.value
-                raise
-        return n.value
+        args, _limits = self._by_source_args(k, min_counts, max_counts, min_total, max_total, sorted)
+        return self._device_dump(_lib.lib().msbwt_rle_enumerate_kmers_by_source_device, *args, d_words, d_counts, d_l, int(capacity), stream=stream)
 
     # ---- the k-mer graph: an edge byte per k-mer of the sorted dump, and the table of (in, out) degrees ----
     def enumerate_kmer_graph(self, k, min_count=1, min_edge=None, ranges=False):
@@ -497,34 +474,15 @@ class RleBWT(BWT):
         least min_count times, ascending, as enumerate_kmers gives them, and per k-mer q one uint8: bit j (A C G T -> 0..3) = the
         (k+1)-mer j.q occurs at least min_edge times (None: min_count) -- a predecessor --, bit 4 + j = q.j does -- a successor.
         graph_successors / graph_predecessors turn the bits into neighbour words."""
-        lib, n = _lib.lib(), C.c_uint64(0)
-        args = (self._h, int(k), int(min_count), int(min_edge or 0))
-        rc = lib.msbwt_rle_enumerate_kmer_graph(*args, None, None, None, None, 0, C.byref(n))
-        if rc:
-            _raise(rc, self._h)
-        words, counts = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.uint64)
-        edges = np.zeros(n.value, dtype=np.uint8)
-        l = np.empty(n.value, dtype=np.uint64) if ranges else None
-        if n.value:
-            rc = lib.msbwt_rle_enumerate_kmer_graph(*args, words.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
-                                                    l.ctypes.data_as(C.c_void_p) if ranges else None, edges.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
-            if rc:
-                _raise(rc, self._h)
+        words, counts, l, edges = self._two_calls(_lib.lib().msbwt_rle_enumerate_kmer_graph, (int(k), int(min_count), int(min_edge or 0)), 4,
+                                                  lambda n: [np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64) if ranges else None, np.zeros(n, dtype=np.uint8)])
         return (words, counts, edges, l) if ranges else (words, counts, edges)
 
     def enumerate_kmer_graph_device(self, k, d_words, d_counts, d_l, d_edges, capacity, min_count=1, min_edge=None, stream=0):
         """msbwt_rle_enumerate_kmer_graph_device: device pointers (ints, each may be None) of `capacity` u64 -- d_edges: bytes, any
         alignment -- -> n, the k-mers that qualify; capacity 0 only counts, 0 < capacity < n raises (nothing written).  Synchronises `stream`."""
-        n = C.c_uint64(0)
-        rc = _lib.lib().msbwt_rle_enumerate_kmer_graph_device(self._h, int(k), int(min_count), int(min_edge or 0), d_words, d_counts, d_l, d_edges, int(capacity),
-                                                              C.byref(n), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n = n.value
-                raise
-        return n.value
+        return self._device_dump(_lib.lib().msbwt_rle_enumerate_kmer_graph_device, int(k), int(min_count), int(min_edge or 0), d_words, d_counts, d_l, d_edges,
+                                 int(capacity), stream=stream)
 
     def kmer_graph_degrees(self, k, min_count=1, min_edge=None):
         """msbwt_rle_kmer_graph_degrees -> (table, nodes, edges): table[i, o] (uint64, 5 x 5) = the k-mers with i predecessors and o
