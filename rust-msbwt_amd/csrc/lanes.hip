@@ -2,6 +2,7 @@
 // instantiations (kDirectTable) and those of the 24-bit-tag sparse table (kSparseComplete); the other layouts live in lanes_wide.hip,
 // lanes_xwide.hip and lanes_tier.hip.
 #include "lanes_kernel.hpp"
+#include "lookup_kernel.hpp"
 
 namespace msbwt {
 namespace {
@@ -32,6 +33,8 @@ hipError_t launch_lanes(const IndexView &ix, const QuerySource &src, bool reads,
     if (src.n == 0) return hipSuccess;
     pair = pair && ix.pair_blocks != nullptr && ix.block_format == kBlocksPlanes;
     if (ix.block_format != kBlocksPlanes && src.packed) return hipErrorInvalidValue;  // (packed queries on run blocks are unpacked by the caller)
+    // k == the depth of a complete sparse table: the table's range is the count, served by the lookup-only kernel (lookup_kernel.hip)
+    if (lookup_serves(ix, src, reads)) return launch_lookup(ix, src, flags, stream);
     const bool longk = src.k > uint32_t(kMaxShortK);
     if (reads) return (src.packed || src.range_stride != 0u) ? hipErrorInvalidValue : launch_shape<true, false>(pair, longk, stream, ix, src, flags);
     if ((src.out_index != nullptr || src.place_inline != 0u) && !src.packed) return hipErrorInvalidValue;  // (counts are placed for packed queries only)
