@@ -497,6 +497,77 @@ int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_co
  * may be NULL. */
 int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes);
 
+/* ---- unitigs ---- the k-mer graph compacted into its non-branching paths, on the device (no reference counterpart)
+ * THE GRAPH is G(k, m, me) exactly as the section above defines it: nodes = the k-mers with count_kmer >= m = max(min_count, 1), edges =
+ * the (k+1)-mers with count_kmer >= me (min_edge == 0: me = m; 0 < min_edge < m: MSBWT_ERR_INVALID_ARG), 1 <= k <= 32; in(q) = the
+ * population of the low nibble of q's edge byte, out(q) that of the high nibble.
+ * LINKS: an edge p -> q is a link when out(p) = 1 and in(q) = 1.  A node has at most one link in and one link out, so the links cut
+ * the node set into disjoint simple paths and simple cycles; a node without links is a path of one.
+ * UNITIGS: each such path or cycle is one unitig; every node belongs to exactly one.
+ * CYCLES: a cycle (every edge around it a link: an isolated cycle) is opened at its smallest k-mer word: that node is the unitig's
+ * first, the node whose link leads into it is its last, and the unitig is CIRCULAR.  A node whose only in-edge and only out-edge is
+ * its self-loop (A^k with A^(k+1) and nothing else) is a circular unitig of one node.
+ * SEQUENCE: a unitig of v nodes has k + v - 1 symbols: the first node's k symbols, then the last symbol of every following node.
+ * ORDER: ascending by the first node's packed word; the same from run to run and under every knob.
+ * TOTALS: with n nodes and U unitigs the symbols total S = n + U (k - 1).
+ * The graph is the strand-specific, directed one: a read set from both strands yields each unitig once per strand.  The bidirected
+ * (canonical) compaction is out of scope.
+ *
+ * Outputs (every buffer may be NULL):
+ *   out_offsets     U + 1 words: unitig u is out_symbols[out_offsets[u] .. out_offsets[u + 1]); out_offsets[0] = 0, out_offsets[U] = S
+ *   out_symbols     S bytes in the library's symbol codes (A C G T = 1 2 3 5): with the offsets a ragged read set, as it is, for
+ *                   msbwt_rle_count_ragged_read_kmers and msbwt_rle_build_from_reads(ascii = 0)
+ *   out_count_sums  U words: the sum of count_kmer over the unitig's nodes (mean abundance = the sum / the nodes)
+ *   out_ends        U bytes: low nibble = the predecessor bits of the first node, high nibble = the successor bits of the last node: the
+ *                   compacted graph's adjacency.  For a circular unitig both nibbles hold exactly the closing edge.
+ *   out_flags       U bytes: bit 0 = circular
+ * Capacity, as for the dumps: *out_unitigs (NULL: MSBWT_ERR_INVALID_ARG) and *out_symbol_total (may be NULL) are always set; both
+ * capacities 0 only counts; otherwise capacity_unitigs < U, or capacity_symbols < S with out_symbols wanted, writes NOTHING, returns
+ * MSBWT_ERR_INVALID_ARG and names U and S in the message.  A capacity above need leaves everything past U (U + 1 for the offsets) and
+ * past S untouched.  The _device form writes to device buffers on the handle's device -- the byte arrays need no alignment --,
+ * synchronises the stream and reports a device fault through msbwt_rle_device_status.
+ * A call that fills buffers does the whole work of the counting call again (graph and ranking; no state is kept between calls): a
+ * caller who knows bounds -- U <= n, S <= n k -- can make ONE call.
+ *
+ * How ("Unitigs"): the graph's two walks, the edge pass also keeping each node's predecessor slot; then over the n slots
+ * the links, the ranking by pointer jumping over {head, distance} -- double-buffered, stopped when a round leaves nothing unfinished,
+ * ceil(log2 n) + 1 rounds at the most --, the opening of isolated cycles by min-label jumping, one scan that numbers the unitigs, and
+ * the emission.  Every device loop is bounded by a round count fixed on the host.  Results depend on no knob.
+ * Guards, before the first HIP call: NULL handle MSBWT_ERR_INVALID_ARG; nothing loaded MSBWT_ERR_NOT_LOADED ("no BWT loaded"); k
+ * outside 1..32 MSBWT_ERR_INVALID_ARG; min_edge below the node threshold and not 0 MSBWT_ERR_INVALID_ARG.  An empty index: U = S = 0.
+ * Scratch per call, freed on return (msbwt_rle_device_bytes unchanged); scratch that does not fit: MSBWT_ERR_HIP naming the bytes.
+ * msbwt_rle_spectrum_info and msbwt_rle_spectrum_scratch_bytes report the call's writing walk and its scratch as for the graph. */
+int msbwt_rle_enumerate_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols,
+                                uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags,
+                                uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total);
+int msbwt_rle_enumerate_unitigs_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols,
+                                       void *d_out_offsets, void *d_out_count_sums, void *d_out_ends, void *d_out_flags,
+                                       uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs,
+                                       uint64_t *out_symbol_total, void *hip_stream);
+/* The handle's last unitig call (zeros before the first and after an empty index; a call refused by a guard leaves the words as they
+ * were, one refused for its capacities has filled them): [0] nodes, [1] edges, [2] links
+ * (closing links of cycles and self-loops included: U + links - circular = nodes), [3] unitigs, [4] symbols, [5] circular unitigs,
+ * [6] nodes of the longest unitig, [7] pointer-jumping rounds run (ranking, cycle labels and the ranking of opened cycles together).
+ * NULL handle or pointer: MSBWT_ERR_INVALID_ARG. */
+#define MSBWT_UNITIG_INFO_WORDS 8
+int msbwt_rle_unitig_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_UNITIG_INFO_WORDS */);
+/* Pure function, no device: bytes of HBM a host call over `nodes` nodes that fills all five buffers with `unitigs` unitigs of `symbols`
+ * symbols allocates and frees again with the automatic frontier, EXACTLY
+ *     msbwt_spectrum_plan(total_rows, free_hbm_bytes, 0, 1)   the walk, the bit per row and the rank checkpoints
+ *     + 56 nodes                                              two {head, distance} states of 16 bytes; word, count, predecessor slot
+ *     + 16 ceil(nodes / 2048)                                 the numbering scan's two sums per tile of 2048 slots
+ *     + 256                                                   the counters, padded
+ *     + 8 ceil(nodes / 4)                                     the edge bytes and the link bytes, one each per node, as whole 32-bit words
+ *     + 8 unitigs + 256                                       the offsets, U + 1 words, in an allocation of their own, padded
+ *     + 8 unitigs                                             the count sums staged for the host
+ *     + 8 ceil(symbols / 8)                                   the symbols staged
+ *     + 16 ceil(unitigs / 8)                                  the ends and the flags staged
+ * Each NULL buffer of the host form takes its staging term less (out_offsets none); the _device form stages nothing: the last three
+ * lines less.  A counting call (both capacities 0) allocates the first five lines only, which is what unitigs = symbols = 0 says.
+ * MSBWT_ERR_TOO_LARGE from 2^40 rows (or nodes, or unitigs) on; device_bytes may be NULL. */
+int msbwt_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols,
+                       uint64_t *device_bytes);
+
 /* The bytes of scratch the handle's last k-mer walk call (any call of the four sections above that walks) allocated in HBM and freed
  * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves
  * it as it was).  Every allocation counts with its size, 256 bytes at the least.  For the by-source calls this is what

@@ -424,6 +424,60 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_kmer_graph_plan");
         return bytes;
     }
+    /// What enumerate_unitigs returns: unitig u is symbols[offsets[u] .. offsets[u + 1]) in symbol codes (A C G T = 1 2 3 5), ascending
+    /// by first k-mer; count_sums[u] = the sum of its nodes' counts; ends[u]: low nibble = predecessor bits of its first node, high
+    /// nibble = successor bits of its last; flags[u] bit 0 = circular.
+    struct Unitigs {
+        std::vector<std::uint8_t> symbols;
+        std::vector<std::uint64_t> offsets, count_sums;
+        std::vector<std::uint8_t> ends, flags;
+        std::size_t size() const { return count_sums.size(); }
+    };
+    /// The non-branching paths of the k-mer graph (nodes: count >= max(min_count, 1); edges: count >= min_edge, 0: the node threshold).
+    Unitigs enumerate_unitigs(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0) const {
+        std::uint64_t n = 0, s = 0;
+        check(msbwt_rle_enumerate_unitigs(raw_, k, min_count, min_edge, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, &n, &s));
+        Unitigs u;
+        u.symbols.resize(s);
+        u.offsets.resize(n + 1);
+        u.count_sums.resize(n);
+        u.ends.resize(n);
+        u.flags.resize(n);
+        if (n)
+            check(msbwt_rle_enumerate_unitigs(raw_, k, min_count, min_edge, u.symbols.data(), u.offsets.data(), u.count_sums.data(), u.ends.data(), u.flags.data(), n, s,
+                                              &n, &s));
+        return u;
+    }
+    /// Device buffers (each may be null; the byte arrays at any alignment) -> the unitigs; *symbol_total (may be null) = their symbols.
+    /// Both capacities 0 only counts.
+    std::uint64_t enumerate_unitigs_device(std::size_t k, std::uint64_t min_count, std::uint64_t min_edge, void *d_symbols, void *d_offsets, void *d_count_sums,
+                                           void *d_ends, void *d_flags, std::uint64_t capacity_unitigs, std::uint64_t capacity_symbols, std::uint64_t *symbol_total,
+                                           void *hip_stream) const {
+        std::uint64_t n = 0;
+        check(msbwt_rle_enumerate_unitigs_device(raw_, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols,
+                                                 &n, symbol_total, hip_stream));
+        return n;
+    }
+    /// The last unitig call: nodes, edges, links, unitigs, symbols, circular unitigs, nodes of the longest unitig, jumping rounds.
+    struct UnitigInfo {
+        std::uint64_t nodes = 0, edges = 0, links = 0, unitigs = 0, symbols = 0, circular = 0, longest = 0, rounds = 0;
+    };
+    UnitigInfo unitig_info() const {
+        std::uint64_t w[MSBWT_UNITIG_INFO_WORDS] = {};
+        check(msbwt_rle_unitig_info(raw_, w));
+        UnitigInfo i;
+        i.nodes = w[0], i.edges = w[1], i.links = w[2], i.unitigs = w[3], i.symbols = w[4], i.circular = w[5], i.longest = w[6], i.rounds = w[7];
+        return i;
+    }
+    /// HBM bytes a host unitig call over `nodes` nodes that fills every buffer allocates (and frees again) with the automatic frontier;
+    /// unitigs = symbols = 0: the counting call.
+    static std::uint64_t unitigs_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t nodes = 0, std::uint64_t unitigs = 0,
+                                      std::uint64_t symbols = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_unitigs_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, &bytes);
+        if (rc) throw Panic(rc, "msbwt_unitigs_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

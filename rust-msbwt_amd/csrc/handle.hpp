@@ -194,6 +194,7 @@ struct msbwt_rle : Settings {
     uint64_t spectrum_frontier = 0;           // most nodes per frontier buffer of the k-mer walks (0 = automatic): msbwt_rle_set_spectrum_frontier
     uint64_t spectrum_info[MSBWT_SPECTRUM_INFO_WORDS] = {};  // what the last of them did
     uint64_t spectrum_scratch = 0;            // and the bytes of scratch it allocated (and freed again): msbwt_rle_spectrum_scratch_bytes
+    uint64_t unitig_info[MSBWT_UNITIG_INFO_WORDS] = {};  // what the last unitig call found: msbwt_rle_unitig_info
     std::mutex mu;
     std::string err;
 };

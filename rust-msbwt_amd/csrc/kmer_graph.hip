@@ -10,6 +10,9 @@
 //                   rank(e.l + 1) - 1 -- the last mark at or below e.l is the l of e's prefix p, whose range holds e's
 // Four records share a 32-bit word of edge bytes and p's record usually belongs to another chunk, so bits are ORed in by vector
 // atomics on that word (zeroed before the walk): a node's predecessor bits in one atomic, each successor bit in one of its own.
+// With sink.pred_slot set (the unitig call), every in-edge also stores its predecessor's slot, marks - 1, at the node's own slot, from
+// the lane that holds the edge: the word is only ever read for a node with ONE in-edge, which has one writer; where several edges store
+// (one thread in turn on plane blocks, lanes of a group on run blocks) whichever value stays is a valid slot below n that nobody reads.
 // No address is formed from a range that is not inside [0, total], nor from a slot at or beyond n: kFlagInternal instead.
 // Traffic per node: the 24-byte staged record, two plane-block lines (one when l and h share a block), and per rank lookup one
 // checkpoint and up to one 128-byte line of the bitmap -- five lookups at most; three 8-byte stores and up to five atomics.
@@ -87,6 +90,7 @@ __global__ __launch_bounds__(kThreads) void k_graph_edges(const Node *__restrict
                 continue;
             }
             pred |= 1u << c;
+            if (sink.pred_slot) sink.pred_slot[slot] = marks - 1u;
             or_edge_bits(sink.edge_words, marks - 1u, 16u << last);
         }
         if (pred) or_edge_bits(sink.edge_words, slot, pred);

@@ -31,6 +31,7 @@ struct GraphSink {
     uint64_t min_edge;             // >= 1: a (k+1)-mer narrower than this is no edge
     uint64_t *kmers, *counts, *l;  // the records, each at the rank of its l (every one optional)
     uint32_t *flags;
+    uint64_t *pred_slot;           // optional, n words (unitigs.hpp): per in-edge of a node, the slot of the predecessor, at the node's own slot
 };
 
 // the m staged nodes {word, l, h} of a chunk (spectrum_stage) -> their records and the edge bits of their in-edges, at both ends

@@ -1,7 +1,8 @@
 // The k-mer walk calls of a loaded index, four families of three: the abundance spectrum, the k-mer dump in its host and its device
 // form (the graph: and the degree table) of the plain k-mers (spectrum.hpp), of a k-mer and its reverse complement as one class
 // (canonical.hpp; the other strand is counted by query.cpp's packed search), of the k-mers by source of a merged index
-// (source_spectrum.hpp) and of the k-mer graph (kmer_graph.hpp).  The kernels are behind those headers; this file is the host side, and
+// (source_spectrum.hpp) and of the k-mer graph (kmer_graph.hpp) -- and the unitigs that graph compacts into (unitigs.hpp: the graph's
+// walks into scratch, then kernels over its slots).  The kernels are behind those headers; this file is the host side, and
 // what the calls share is written once:
 //   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
 //                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
@@ -22,6 +23,7 @@
 #include "run_encode.hpp"
 #include "source_spectrum.hpp"
 #include "spectrum.hpp"
+#include "unitigs.hpp"
 
 namespace {
 
@@ -531,6 +533,165 @@ int kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_
         });
 }
 
+// ---- unitigs ----
+
+constexpr uint64_t kUnitigNodeBytes = 2 * sizeof(UnitigState) + 3 * sizeof(uint64_t);  // two states; word, count and predecessor slot
+constexpr Shape kUnitigShape{true, false, 0, kUnitigNodeBytes};
+static_assert(kUnitigNodeBytes == 56 && kUnitigCounterWords * 8 <= kUnitigFixedBytes && MSBWT_UNITIG_INFO_WORDS == 8, "the header's plan and constants");
+
+uint64_t pad8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
+// what the compaction keeps beside the 56 bytes per node: the scan's tiles, the counters, the edge bytes and the link bytes
+uint64_t unitig_fixed_bytes(uint64_t n) { return unitig_tiles(n) * kUnitigTileBytes + kUnitigFixedBytes + 2 * graph_edge_words(n) * 4; }
+// the second allocation of a call that fills buffers: the offsets, and what a host form stages of sums, symbols, ends and flags
+uint64_t unitig_out_bytes(uint64_t U, uint64_t S, bool sums, bool symbols, bool ends, bool flags) {
+    return 8 * U + 256 + (sums ? 8 * U : 0) + (symbols ? pad8(S) : 0) + (ends ? pad8(U) : 0) + (flags ? pad8(U) : 0);
+}
+uint64_t ceil_log2(uint64_t x) {
+    uint64_t r = 0;
+    while (r < 63 && (1ull << r) < x) ++r;
+    return r;
+}
+
+// Both forms: the sorted dump's counting walk, the staged walk with the edge pass behind it (into scratch: words, counts, edge bytes
+// and predecessor slots), then links, ranking, cycles, numbering and emission over the slots (unitigs.hpp).
+int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums, void *out_ends,
+            void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total, hipStream_t stream) {
+    Frame f(bwt, "enumerate_unitigs", k, host, stream);
+    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
+    if (int rc = f.open(false, [&] {
+            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
+            return !out_unitigs ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
+        }))
+        return rc;
+    msbwt_rle *h = f.h;
+    *out_unitigs = 0;
+    if (out_symbol_total) *out_symbol_total = 0;
+    std::fill(h->unitig_info, h->unitig_info + MSBWT_UNITIG_INFO_WORDS, 0ull);
+    const IndexView v = view_of(h);
+    Column none[] = {{nullptr}};  // (both allocations are all tail)
+    uint64_t unused = 0, U = 0, S = 0;
+    bool filled = false;
+    uint64_t *d_offsets = nullptr, *d_sums = nullptr;
+    uint8_t *d_symbols = nullptr, *d_ends = nullptr, *d_flags = nullptr;
+    return two_pass(
+        f, ~0ull, nullptr, "k-mers", false,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, kUnitigShape)) return rc;
+            HIP_TRY(h, spectrum_count(v, seeds_of(f), uint32_t(k), m, 0, f.work, f.frontier, f.rank, n, &f.info, f.stream));
+            return MSBWT_OK;
+        },
+        [&](uint64_t n) -> int {
+            // one allocation: state | state | words | counts | predecessor slots | tiles | counters | edge words | link words
+            char *at = nullptr;
+            if (int rc = stage_records(f, none, n, &unused, "for the nodes of the graph", n * kUnitigNodeBytes + unitig_fixed_bytes(n), &at)) return rc;
+            UnitigState *cur = reinterpret_cast<UnitigState *>(at), *other = cur + n;
+            uint64_t *kmers = reinterpret_cast<uint64_t *>(other + n), *counts = kmers + n, *pred = counts + n;
+            char *tiles = reinterpret_cast<char *>(pred + n);
+            unsigned long long *counters = reinterpret_cast<unsigned long long *>(tiles + unitig_tiles(n) * kUnitigTileBytes);
+            uint32_t *edge_words = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(counters) + kUnitigFixedBytes), *link_words = edge_words + graph_edge_words(n);
+            HIP_TRY(h, hipMemsetAsync(counters, 0, kUnitigFixedBytes + 2 * graph_edge_words(n) * 4, f.stream));
+            HIP_TRY(h, hipMemsetAsync(pred, 0xFF, n * 8, f.stream));  // (no slot)
+            const SpectrumRank r = spectrum_rank_view(f.rank, h->totals.total);
+            GraphSink sink{};
+            sink.bitmap = r.bitmap;
+            sink.prefix = r.prefix;
+            sink.edge_words = edge_words;
+            sink.n = n;
+            sink.min_edge = me;
+            sink.flags = h->d_flags + f.which;
+            sink.kmers = kmers;
+            sink.counts = counts;
+            sink.pred_slot = pred;
+            if (int rc = staged_walk(f, m, nullptr, 0, nullptr, [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, f.stream); }))
+                return rc;
+
+            const UnitigNodes g{n, kmers, counts, pred, edge_words, link_words, counters, sink.flags};
+            uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
+            const auto read_counters = [&]() -> int {  // synchronises
+                HIP_TRY(h, hipMemcpyAsync(c, counters, sizeof c, hipMemcpyDeviceToHost, f.stream));
+                HIP_TRY(h, hipStreamSynchronize(f.stream));
+                return MSBWT_OK;
+            };
+            // Ranking rounds until none is unfinished, `cap` at the most.  A round that finishes nobody ends them too: on every path
+            // the unfinished node nearest the head has a finished ancestor, so what is left then lies on cycles.
+            const auto rank = [&](uint64_t cap) -> int {
+                for (uint64_t round = 0; c[kUnitigUnfinished] && round < cap; ++round) {
+                    const uint64_t before = c[kUnitigUnfinished];
+                    HIP_TRY(h, hipMemsetAsync(counters + kUnitigUnfinished, 0, 8, f.stream));
+                    HIP_TRY(h, launch_unitig_jump(g, cur, other, f.stream));
+                    std::swap(cur, other);
+                    ++rounds;
+                    if (int rc = read_counters()) return rc;
+                    if (c[kUnitigUnfinished] == before) break;
+                }
+                return MSBWT_OK;
+            };
+            HIP_TRY(h, launch_unitig_links(g, cur, f.stream));
+            if (int rc = read_counters()) return rc;
+            if (int rc = rank(ceil_log2(n) + 1)) return rc;
+            if (const uint64_t on_cycles = c[kUnitigUnfinished]) {
+                // a cycle has at most on_cycles nodes: after ceil(log2) rounds every label is its cycle's smallest slot
+                HIP_TRY(h, launch_unitig_cycle_seed(g, cur, f.stream));
+                for (uint64_t round = 0; round < ceil_log2(on_cycles); ++round, ++rounds) {
+                    HIP_TRY(h, launch_unitig_cycle_jump(g, cur, other, f.stream));
+                    std::swap(cur, other);
+                }
+                HIP_TRY(h, hipMemsetAsync(counters + kUnitigUnfinished, 0, 8, f.stream));
+                HIP_TRY(h, launch_unitig_cycle_cut(g, cur, f.stream));
+                if (int rc = read_counters()) return rc;
+                if (int rc = rank(ceil_log2(on_cycles) + 1)) return rc;
+            }
+            HIP_TRY(h, launch_unitig_tails(g, cur, other, f.stream));
+            if (int rc = read_counters()) return rc;
+            if (c[kUnitigUnfinished] || c[kUnitigLinks] > n + c[kUnitigCircular] || c[kUnitigCircular] > n)
+                return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the ranking left " + std::to_string(c[kUnitigUnfinished]) + " nodes without a head");
+            U = n - c[kUnitigLinks] + c[kUnitigCircular];
+            S = n + U * (k - 1);
+            *out_unitigs = U;
+            if (out_symbol_total) *out_symbol_total = S;
+            const uint64_t info[MSBWT_UNITIG_INFO_WORDS] = {n, c[kUnitigEdges], c[kUnitigLinks], U, S, c[kUnitigCircular], c[kUnitigLongest], rounds};
+            std::copy(info, info + MSBWT_UNITIG_INFO_WORDS, h->unitig_info);
+            if (capacity_unitigs == 0 && capacity_symbols == 0) return MSBWT_OK;
+            if (capacity_unitigs < U || (out_symbols && capacity_symbols < S))
+                return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the U = " +
+                                std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols");
+
+            // the other allocation: offsets | sums | symbols | ends | flags, the last four only where a host form stages them
+            const bool stage_sums = host && out_sums, stage_symbols = host && out_symbols, stage_ends = host && out_ends, stage_flags = host && out_flags;
+            if (int rc = stage_records(f, none, 0, &unused, "for the unitigs", unitig_out_bytes(U, S, stage_sums, stage_symbols, stage_ends, stage_flags), &at)) return rc;
+            // a device form's outputs are the caller's own; a staged one is carved off `at`
+            const auto carve = [&](void *out, bool stage, uint64_t bytes) -> void * {
+                if (!stage) return out;
+                char *here = at;
+                at += bytes;
+                return here;
+            };
+            d_offsets = static_cast<uint64_t *>(carve(nullptr, true, 8 * U + 256));
+            d_sums = static_cast<uint64_t *>(carve(out_sums, stage_sums, 8 * U));
+            d_symbols = static_cast<uint8_t *>(carve(out_symbols, stage_symbols, pad8(S)));
+            d_ends = static_cast<uint8_t *>(carve(out_ends, stage_ends, pad8(U)));
+            d_flags = static_cast<uint8_t *>(carve(out_flags, stage_flags, pad8(U)));
+            if (d_sums) HIP_TRY(h, hipMemsetAsync(d_sums, 0, 8 * U, f.stream));
+            HIP_TRY(h, launch_unitig_number(g, other, tiles, uint32_t(k), U, S, d_offsets, f.stream));
+            HIP_TRY(h, launch_unitig_emit(g, cur, other, uint32_t(k), U, S, d_symbols, d_sums, d_ends, d_flags, f.stream));
+            filled = true;
+            return MSBWT_OK;
+        },
+        [&](uint64_t) -> int {
+            if (filled) {
+                const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+                if (out_offsets) HIP_TRY(h, hipMemcpyAsync(out_offsets, d_offsets, 8 * (U + 1), kind, f.stream));
+                if (host && out_sums) HIP_TRY(h, hipMemcpyAsync(out_sums, d_sums, 8 * U, kind, f.stream));
+                if (host && out_symbols) HIP_TRY(h, hipMemcpyAsync(out_symbols, d_symbols, S, kind, f.stream));
+                if (host && out_ends) HIP_TRY(h, hipMemcpyAsync(out_ends, d_ends, U, kind, f.stream));
+                if (host && out_flags) HIP_TRY(h, hipMemcpyAsync(out_flags, d_flags, U, kind, f.stream));
+            }
+            if (host) return status_of(h, f.stream, f.which);  // synchronises
+            HIP_TRY(h, hipStreamSynchronize(f.stream));         // (the scratch is freed on return)
+            return MSBWT_OK;
+        });
+}
+
 }  // namespace
 
 extern "C" {
@@ -697,6 +858,36 @@ int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_co
 // the host dump of `records` nodes with words, counts and l
 int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
     return plan(graph_shape(true), total_rows, free_hbm_bytes, records, graph_edge_words(records) * 4, device_bytes);
+}
+
+// ---- unitigs: the non-branching paths of the k-mer graph as ragged sequences ----
+
+int msbwt_rle_enumerate_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols, uint64_t *out_offsets, uint64_t *out_count_sums,
+                                uint8_t *out_ends, uint8_t *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs,
+                                uint64_t *out_symbol_total) {
+    return unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs,
+                   out_symbol_total, nullptr);
+}
+
+int msbwt_rle_enumerate_unitigs_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols, void *d_out_offsets,
+                                       void *d_out_count_sums, void *d_out_ends, void *d_out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                       uint64_t *out_unitigs, uint64_t *out_symbol_total, void *hip_stream) {
+    return unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs, capacity_symbols,
+                   out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream));
+}
+
+int msbwt_rle_unitig_info(const msbwt_rle *bwt, uint64_t *out) {
+    Call c(bwt);
+    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
+    std::copy(c.h->unitig_info, c.h->unitig_info + MSBWT_UNITIG_INFO_WORDS, out);
+    return MSBWT_OK;
+}
+
+// the host call of `nodes` nodes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)
+int msbwt_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {
+    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 32 n + n)
+    const uint64_t out = unitigs || symbols ? unitig_out_bytes(unitigs, symbols, true, true, true, true) : 0;
+    return plan(kUnitigShape, total_rows, free_hbm_bytes, nodes, unitig_fixed_bytes(nodes) + out, device_bytes);
 }
 
 }  // extern "C"

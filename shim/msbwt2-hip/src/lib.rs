@@ -100,6 +100,16 @@ extern "C" {
     fn msbwt_rle_kmer_graph_degrees(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_table: *mut u64,
                                     out_nodes: *mut u64, out_edges: *mut u64) -> c_int;
     fn msbwt_kmer_graph_plan(total_rows: u64, free_hbm_bytes: u64, records: u64, device_bytes: *mut u64) -> c_int;
+    // unitigs: the non-branching paths of the k-mer graph as ragged sequences in symbol codes, ascending by first k-mer
+    fn msbwt_rle_enumerate_unitigs(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_symbols: *mut u8,
+                                   out_offsets: *mut u64, out_count_sums: *mut u64, out_ends: *mut u8, out_flags: *mut u8,
+                                   capacity_unitigs: u64, capacity_symbols: u64, out_unitigs: *mut u64, out_symbol_total: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_unitigs_device(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, d_out_symbols: *mut c_void,
+                                          d_out_offsets: *mut c_void, d_out_count_sums: *mut c_void, d_out_ends: *mut c_void,
+                                          d_out_flags: *mut c_void, capacity_unitigs: u64, capacity_symbols: u64, out_unitigs: *mut u64,
+                                          out_symbol_total: *mut u64, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_unitig_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_unitigs_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
@@ -517,6 +527,54 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_kmer_graph_plan(total_rows, free_hbm_bytes, records, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "kmer_graph_plan: {} rows, {} records", total_rows, records);
+        bytes
+    }
+
+    /// Unitigs of the k-mer graph (nodes: count >= `min_count`; edges: count >= `min_edge`, 0: `min_count`), ascending by first k-mer:
+    /// (symbols, offsets, count sums, ends, flags).  Unitig u is symbols[offsets[u]..offsets[u + 1]] in symbol codes (A C G T = 1 2 3 5);
+    /// ends[u]: low nibble = predecessor bits of its first node, high nibble = successor bits of its last; flags[u] bit 0 = circular.
+    pub fn enumerate_unitigs(&self, k: usize, min_count: u64, min_edge: u64) -> (Vec<u8>, Vec<u64>, Vec<u64>, Vec<u8>, Vec<u8>) {
+        let (mut u, mut s) = (0u64, 0u64);
+        let null8 = std::ptr::null_mut::<u8>();
+        let null64 = std::ptr::null_mut::<u64>();
+        let rc = unsafe { msbwt_rle_enumerate_unitigs(self.raw, k, min_count, min_edge, null8, null64, null64, null8, null8, 0, 0, &mut u, &mut s) };
+        if rc != MSBWT_OK { panic!("enumerate_unitigs: {}", self.last_error()); }
+        let (mut symbols, mut offsets) = (vec![0u8; s as usize], vec![0u64; u as usize + 1]);
+        let (mut sums, mut ends, mut flags) = (vec![0u64; u as usize], vec![0u8; u as usize], vec![0u8; u as usize]);
+        if u > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_unitigs(self.raw, k, min_count, min_edge, symbols.as_mut_ptr(), offsets.as_mut_ptr(), sums.as_mut_ptr(),
+                                            ends.as_mut_ptr(), flags.as_mut_ptr(), u, s, &mut u, &mut s)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_unitigs: {}", self.last_error()); }
+        }
+        (symbols, offsets, sums, ends, flags)
+    }
+
+    /// The same into device buffers (each may be null; the byte arrays at any alignment) -> (unitigs, symbols); both capacities 0 only counts.
+    pub unsafe fn enumerate_unitigs_device(&self, k: usize, min_count: u64, min_edge: u64, d_symbols: *mut c_void, d_offsets: *mut c_void,
+                                           d_count_sums: *mut c_void, d_ends: *mut c_void, d_flags: *mut c_void, capacity_unitigs: u64,
+                                           capacity_symbols: u64, hip_stream: *mut c_void) -> (u64, u64) {
+        let (mut u, mut s) = (0u64, 0u64);
+        let rc = msbwt_rle_enumerate_unitigs_device(self.raw, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
+                                                    capacity_unitigs, capacity_symbols, &mut u, &mut s, hip_stream);
+        if rc != MSBWT_OK { panic!("enumerate_unitigs_device: {}", self.last_error()); }
+        (u, s)
+    }
+
+    /// The last unitig call: [nodes, edges, links, unitigs, symbols, circular unitigs, nodes of the longest unitig, jumping rounds].
+    pub fn unitig_info(&self) -> [u64; 8] {
+        let mut words = [0u64; 8];
+        let rc = unsafe { msbwt_rle_unitig_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("unitig_info: {}", self.last_error()); }
+        words
+    }
+
+    /// HBM bytes a host unitig call over `nodes` nodes that fills every buffer allocates and frees again (pure function).
+    pub fn unitigs_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_unitigs_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "unitigs_plan: {} rows, {} nodes", total_rows, nodes);
         bytes
     }
 
