@@ -511,7 +511,7 @@ int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t
  * ORDER: ascending by the first node's packed word; the same from run to run and under every knob.
  * TOTALS: with n nodes and U unitigs the symbols total S = n + U (k - 1).
  * The graph is the strand-specific, directed one: a read set from both strands yields each unitig once per strand.  The bidirected
- * (canonical) compaction is out of scope.
+ * (canonical) compaction is out of scope of THIS call: see the canonical unitigs below.
  *
  * Outputs (every buffer may be NULL):
  *   out_offsets     U + 1 words: unitig u is out_symbols[out_offsets[u] .. out_offsets[u + 1]); out_offsets[0] = 0, out_offsets[U] = S
@@ -567,6 +567,75 @@ int msbwt_rle_unitig_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_UNITIG_IN
  * MSBWT_ERR_TOO_LARGE from 2^40 rows (or nodes, or unitigs) on; device_bytes may be NULL. */
 int msbwt_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols,
                        uint64_t *device_bytes);
+
+/* ---- canonical unitigs ---- the strand-merged k-mer graph compacted into its non-branching paths, on the device (no reference
+ * counterpart).  Everything follows from count_kmer; rc(x) is the reverse complement of x.
+ * CLASSES: for a word x of any length cc(x) = count_kmer(x) + count_kmer(rc(x)), and cc(x) = count_kmer(x) for a palindrome (x = rc(x)):
+ * exactly own + other of msbwt_rle_enumerate_canonical_kmers.
+ * NODES: all k-mers q with cc(q) >= m = max(min_count, 1) -- both members of every class, a member the index does not hold included.
+ * This graph D is closed under rc; with n classes it has N = 2 n - (palindromic nodes) nodes.
+ * EDGES: q -> q' (q' = q[1:].c) is an edge when cc(q.c) >= me (min_edge == 0: me = m; 0 < min_edge < m: MSBWT_ERR_INVALID_ARG) AND both
+ * q and q' are nodes.  The second clause matters at a palindromic end p, where cc(p) = count_kmer(p) can be below cc(p.c): reads
+ * {"CATG"}, k = 2, m = 2 have cc(ATG) = 2 and cc(AT) = 1, so ATG is no edge (even k and m >= 2 only).  D is symmetric: q -> q' exists
+ * exactly when rc(q') -> rc(q) does, so in-bit j of q equals out-bit 3 - j of rc(q).
+ * LINKS: as above (out(p) = 1 and in(q) = 1), with two cuts: a palindromic node has no links, and an edge whose (k+1)-mer is its own
+ * reverse complement (q -> rc(q), odd k) is never a link.  The cuts change links only; edge bits and out_ends keep the real adjacency.
+ * With them no path or cycle of D is its own mirror, so the unitigs of D come in pairs {U, rc(U)} of distinct unitigs -- but for a
+ * palindromic node, a unitig of one that is its own mirror -- and every class lies in exactly one unitig of a pair exactly once.
+ * CHOICE: of a pair, the unitig whose first node's word is smaller is emitted.  A cycle is opened at its smallest word as above; of C and
+ * rc(C) the one that holds the smallest word of both is emitted.
+ * OUTPUTS: the five arrays of msbwt_rle_enumerate_unitigs with the same meaning, except that out_count_sums holds sums of CLASS counts
+ * cc over the unitig's nodes and out_ends is the adjacency in D of the emitted orientation.  ORDER: ascending by first word.
+ * TOTALS: S = n + U (k - 1) with n the number of CLASSES.  Results depend on no knob.
+ * 1 <= k <= 31, because an edge is a packed (k+1)-mer: k = 32 is MSBWT_ERR_INVALID_ARG.
+ *
+ * Capacity, NULL buffers, untouched tails, the _device form and its stream, the guards before the first HIP call (with k outside 1..31
+ * in place of 1..32), the empty index (U = S = 0) and the scratch (per call, freed on return; one that does not fit: MSBWT_ERR_HIP
+ * naming the bytes) are those of msbwt_rle_enumerate_unitigs[_device]; a device fault is reported through msbwt_rle_device_status.
+ *
+ * How ("Canonical unitigs"): the canonical walk with the window [m, inf) counts and then writes the classes; a kernel
+ * writes both member words of every class (a palindrome once) with the class count as the payload, and stable 8-bit radix passes over
+ * the low ceil(2k / 8) bytes put the N nodes in word order; word -> slot is a binary search over them.  The four (k+1)-mers out of every
+ * node are counted by the packed search, 2^20 nodes a batch, and folded into edge bytes -- cc(q.c) = count(q.c) + count(rc(q.c)), the
+ * second read from the mirror node's counts, so every (k+1)-mer word is searched once.  Then the compaction of the unitig call over the
+ * N slots, with one kernel behind the links that takes the cut links back and one behind the ranking that marks, of every pair, the
+ * unitig that is not emitted; numbering and emission skip those.  Every device loop is bounded by a count fixed on the host. */
+int msbwt_rle_enumerate_canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols,
+                                          uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags,
+                                          uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs,
+                                          uint64_t *out_symbol_total);
+int msbwt_rle_enumerate_canonical_unitigs_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                                 void *d_out_symbols, void *d_out_offsets, void *d_out_count_sums, void *d_out_ends,
+                                                 void *d_out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                                 uint64_t *out_unitigs, uint64_t *out_symbol_total, void *hip_stream);
+/* The handle's last canonical unitig call (zeros before the first and after an empty index; a call refused by a guard leaves the words
+ * as they were, one refused for its capacities has filled them), for the EMITTED set: [0] classes n, [1] edge classes (the (k+1)-mer
+ * classes that are edges of D), [2] links among the emitted unitigs (closing links included: U + links - circular = classes), [3]
+ * unitigs U, [4] symbols S, [5] circular unitigs, [6] nodes of the longest unitig, [7] pointer-jumping rounds run; and two words more
+ * than msbwt_rle_unitig_info has: [8] palindromic nodes (N = 2 n - [8]), [9] links of D the two cuts took back (both strands counted).
+ * NULL handle or pointer: MSBWT_ERR_INVALID_ARG. */
+#define MSBWT_CANONICAL_UNITIG_INFO_WORDS 10
+int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_CANONICAL_UNITIG_INFO_WORDS */);
+/* Pure function, no device: bytes of HBM a host call over `classes` classes that fills all five buffers with `unitigs` unitigs of
+ * `symbols` symbols allocates and frees again with the automatic frontier, EXACTLY, with slots = 2 classes (the allocation does not
+ * wait for the palindromes to be counted):
+ *     msbwt_canonical_plan(total_rows, free_hbm_bytes, 0)     the canonical walk: its frontiers and the other strand of a chunk
+ *     + 256                                                   the walk's totals, which that plan leaves out
+ *     + 128 classes                                           per slot 32 bytes of (k+1)-mer counts -- first the walk's records, later the
+ *                                                             two {head, distance} states -- and 32 of (word, class count) twice for the
+ *                                                             sort, the free pair of which holds the predecessor slots
+ *     + 32 min(slots, 2^20)                                   the (k+1)-mer words of a batch of nodes
+ *     + 2048 ceil(slots / 4096)                               the sort's digit histogram per tile of 4096 keys
+ *     + 8 (ceil(ceil(slots / 4096) / 4) + 8)                  the levels of its scan
+ *     + 16 ceil(slots / 2048)                                 the numbering scan's two sums per tile of 2048 slots
+ *     + 512                                                   the counters of the compaction and of this call, padded
+ *     + 8 ceil(slots / 4)                                     the edge bytes and the link bytes, one each per slot, as whole 32-bit words
+ *     + 8 unitigs + 256 + 8 unitigs + 8 ceil(symbols / 8) + 16 ceil(unitigs / 8)      the second allocation, as in msbwt_unitigs_plan
+ * Each NULL buffer of the host form takes its staging term less (out_offsets none); the _device form stages nothing: 8 unitigs + 256
+ * is all of the last line.  A counting call (both capacities 0) allocates all but the last line: unitigs = symbols = 0.
+ * MSBWT_ERR_TOO_LARGE from 2^40 rows (or classes, or unitigs) on; device_bytes may be NULL. */
+int msbwt_canonical_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols,
+                                 uint64_t *device_bytes);
 
 /* The bytes of scratch the handle's last k-mer walk call (any call of the four sections above that walks) allocated in HBM and freed
  * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves

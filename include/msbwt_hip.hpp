@@ -478,6 +478,53 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_unitigs_plan");
         return bytes;
     }
+
+    /// Canonical unitigs: the unitigs of the strand-merged graph (1 <= k <= 31), every class {q, rc(q)} in exactly one of them once; of a
+    /// unitig and its mirror the one with the smaller first k-mer.  count_sums: sums of class counts.
+    Unitigs enumerate_canonical_unitigs(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0) const {
+        std::uint64_t n = 0, s = 0;
+        check(msbwt_rle_enumerate_canonical_unitigs(raw_, k, min_count, min_edge, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, &n, &s));
+        Unitigs u;
+        u.symbols.resize(s);
+        u.offsets.resize(n + 1);
+        u.count_sums.resize(n);
+        u.ends.resize(n);
+        u.flags.resize(n);
+        if (n)
+            check(msbwt_rle_enumerate_canonical_unitigs(raw_, k, min_count, min_edge, u.symbols.data(), u.offsets.data(), u.count_sums.data(), u.ends.data(),
+                                                        u.flags.data(), n, s, &n, &s));
+        return u;
+    }
+    /// Device buffers (each may be null; the byte arrays at any alignment) -> the unitigs; *symbol_total (may be null) = their symbols.
+    std::uint64_t enumerate_canonical_unitigs_device(std::size_t k, std::uint64_t min_count, std::uint64_t min_edge, void *d_symbols, void *d_offsets,
+                                                     void *d_count_sums, void *d_ends, void *d_flags, std::uint64_t capacity_unitigs,
+                                                     std::uint64_t capacity_symbols, std::uint64_t *symbol_total, void *hip_stream = nullptr) const {
+        std::uint64_t n = 0, s = 0;
+        check(msbwt_rle_enumerate_canonical_unitigs_device(raw_, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs,
+                                                           capacity_symbols, &n, &s, hip_stream));
+        if (symbol_total) *symbol_total = s;
+        return n;
+    }
+    /// The last canonical unitig call, for the emitted set.
+    struct CanonicalUnitigInfo {
+        std::uint64_t classes = 0, edge_classes = 0, links = 0, unitigs = 0, symbols = 0, circular = 0, longest = 0, rounds = 0, palindromes = 0, cut_links = 0;
+    };
+    CanonicalUnitigInfo canonical_unitig_info() const {
+        std::uint64_t w[MSBWT_CANONICAL_UNITIG_INFO_WORDS] = {};
+        check(msbwt_rle_canonical_unitig_info(raw_, w));
+        CanonicalUnitigInfo i;
+        i.classes = w[0], i.edge_classes = w[1], i.links = w[2], i.unitigs = w[3], i.symbols = w[4], i.circular = w[5], i.longest = w[6], i.rounds = w[7];
+        i.palindromes = w[8], i.cut_links = w[9];
+        return i;
+    }
+    /// HBM bytes a host canonical unitig call over `classes` classes that fills every buffer allocates (and frees again).
+    static std::uint64_t canonical_unitigs_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t classes = 0, std::uint64_t unitigs = 0,
+                                                std::uint64_t symbols = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_canonical_unitigs_plan(total_rows, free_hbm_bytes, classes, unitigs, symbols, &bytes);
+        if (rc) throw Panic(rc, "msbwt_canonical_unitigs_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

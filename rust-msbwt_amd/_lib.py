@@ -17,6 +17,7 @@ MERGE_MAX_INPUTS = 32  # MSBWT_MERGE_MAX_INPUTS
 SOURCE_INDEX_SLACK = 1024  # MSBWT_SOURCE_INDEX_SLACK
 SPECTRUM_INFO_WORDS = 40  # MSBWT_SPECTRUM_INFO_WORDS
 UNITIG_INFO_WORDS = 8  # MSBWT_UNITIG_INFO_WORDS
+CANONICAL_UNITIG_INFO_WORDS = 10  # MSBWT_CANONICAL_UNITIG_INFO_WORDS
 SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
@@ -95,6 +96,10 @@ SIGNATURES = {
     "msbwt_rle_enumerate_unitigs_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _pu64, _pu64, _vp]),
     "msbwt_rle_unitig_info": (_int, [_vp, _vp]),
     "msbwt_unitigs_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _pu64]),
+    "msbwt_rle_enumerate_canonical_unitigs": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _pu64, _pu64]),
+    "msbwt_rle_enumerate_canonical_unitigs_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _pu64, _pu64, _vp]),
+    "msbwt_rle_canonical_unitig_info": (_int, [_vp, _vp]),
+    "msbwt_canonical_unitigs_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _pu64]),
     "msbwt_rle_spectrum_scratch_bytes": (_int, [_vp, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),

@@ -195,6 +195,7 @@ struct msbwt_rle : Settings {
     uint64_t spectrum_info[MSBWT_SPECTRUM_INFO_WORDS] = {};  // what the last of them did
     uint64_t spectrum_scratch = 0;            // and the bytes of scratch it allocated (and freed again): msbwt_rle_spectrum_scratch_bytes
     uint64_t unitig_info[MSBWT_UNITIG_INFO_WORDS] = {};  // what the last unitig call found: msbwt_rle_unitig_info
+    uint64_t canonical_unitig_info[MSBWT_CANONICAL_UNITIG_INFO_WORDS] = {};  // and the last canonical one: msbwt_rle_canonical_unitig_info
     std::mutex mu;
     std::string err;
 };

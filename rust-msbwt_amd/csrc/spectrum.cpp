@@ -2,7 +2,8 @@
 // form (the graph: and the degree table) of the plain k-mers (spectrum.hpp), of a k-mer and its reverse complement as one class
 // (canonical.hpp; the other strand is counted by query.cpp's packed search), of the k-mers by source of a merged index
 // (source_spectrum.hpp) and of the k-mer graph (kmer_graph.hpp) -- and the unitigs that graph compacts into (unitigs.hpp: the graph's
-// walks into scratch, then kernels over its slots).  The kernels are behind those headers; this file is the host side, and
+// walks into scratch, then kernels over its slots; canonical_unitigs.hpp: the same compaction over both members of every canonical
+// class).  The kernels are behind those headers; this file is the host side, and
 // what the calls share is written once:
 //   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
 //                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
@@ -18,6 +19,7 @@
 #include <string>
 
 #include "canonical.hpp"
+#include "canonical_unitigs.hpp"
 #include "handle.hpp"
 #include "kmer_graph.hpp"
 #include "run_encode.hpp"
@@ -552,6 +554,114 @@ uint64_t ceil_log2(uint64_t x) {
     return r;
 }
 
+// Links, ranking, cycles and tails over the slots of g (unitigs.hpp): every node of `cur` ends with its head and its distance,
+// heads[h].x in `other` with the nodes of the unitig that starts at h, c[] with the counters and *rounds with the jumping rounds run.
+// after_links() runs between the links and the first look at the counters (the canonical call takes links back there).
+template <class AfterLinks>
+int rank_unitigs(Frame &f, const UnitigNodes &g, UnitigState *&cur, UnitigState *&other, uint64_t (&c)[kUnitigCounterWords], uint64_t *rounds, AfterLinks &&after_links) {
+    msbwt_rle *h = f.h;
+    const auto read_counters = [&]() -> int {  // synchronises
+        HIP_TRY(h, hipMemcpyAsync(c, g.counters, sizeof c, hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(h, hipStreamSynchronize(f.stream));
+        return MSBWT_OK;
+    };
+    // Ranking rounds until none is unfinished, `cap` at the most.  A round that finishes nobody ends them too: on every path
+    // the unfinished node nearest the head has a finished ancestor, so what is left then lies on cycles.
+    const auto rank = [&](uint64_t cap) -> int {
+        for (uint64_t round = 0; c[kUnitigUnfinished] && round < cap; ++round) {
+            const uint64_t before = c[kUnitigUnfinished];
+            HIP_TRY(h, hipMemsetAsync(g.counters + kUnitigUnfinished, 0, 8, f.stream));
+            HIP_TRY(h, launch_unitig_jump(g, cur, other, f.stream));
+            std::swap(cur, other);
+            ++*rounds;
+            if (int rc = read_counters()) return rc;
+            if (c[kUnitigUnfinished] == before) break;
+        }
+        return MSBWT_OK;
+    };
+    HIP_TRY(h, launch_unitig_links(g, cur, f.stream));
+    if (int rc = after_links()) return rc;
+    if (int rc = read_counters()) return rc;
+    if (int rc = rank(ceil_log2(g.n) + 1)) return rc;
+    if (const uint64_t on_cycles = c[kUnitigUnfinished]) {
+        // a cycle has at most on_cycles nodes: after ceil(log2) rounds every label is its cycle's smallest slot
+        HIP_TRY(h, launch_unitig_cycle_seed(g, cur, f.stream));
+        for (uint64_t round = 0; round < ceil_log2(on_cycles); ++round, ++*rounds) {
+            HIP_TRY(h, launch_unitig_cycle_jump(g, cur, other, f.stream));
+            std::swap(cur, other);
+        }
+        HIP_TRY(h, hipMemsetAsync(g.counters + kUnitigUnfinished, 0, 8, f.stream));
+        HIP_TRY(h, launch_unitig_cycle_cut(g, cur, f.stream));
+        if (int rc = read_counters()) return rc;
+        if (int rc = rank(ceil_log2(on_cycles) + 1)) return rc;
+    }
+    HIP_TRY(h, launch_unitig_tails(g, cur, other, f.stream));
+    return read_counters();
+}
+
+// The outputs of a unitig call, plain or canonical, once U and S are known: *out_unitigs and *out_symbol_total, the capacity contract,
+// the second allocation -- offsets | sums | symbols | ends | flags, the last four only where a host form stages them --, numbering and
+// emission (skip_marked: heads carry kUnitigSkip), and the delivery.
+struct UnitigOutputs {
+    void *symbols, *offsets, *sums, *ends, *flags;
+    uint64_t capacity_unitigs, capacity_symbols;
+    uint64_t *out_unitigs, *out_symbol_total;
+    uint64_t U = 0, S = 0;
+    bool filled = false;
+    uint64_t *d_offsets = nullptr, *d_sums = nullptr;
+    uint8_t *d_symbols = nullptr, *d_ends = nullptr, *d_flags = nullptr;
+
+    int emit(Frame &f, const UnitigNodes &g, const UnitigState *state, UnitigState *heads, void *tiles, uint64_t unitigs, uint64_t total, bool skip_marked) {
+        msbwt_rle *h = f.h;
+        const bool host = f.host;
+        U = unitigs;
+        S = total;
+        *out_unitigs = U;
+        if (out_symbol_total) *out_symbol_total = S;
+        if (capacity_unitigs == 0 && capacity_symbols == 0) return MSBWT_OK;
+        if (capacity_unitigs < U || (symbols && capacity_symbols < S))
+            return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the U = " +
+                            std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols");
+        const bool stage_sums = host && sums, stage_symbols = host && symbols, stage_ends = host && ends, stage_flags = host && flags;
+        Column none[] = {{nullptr}};
+        uint64_t unused = 0;
+        char *at = nullptr;
+        if (int rc = stage_records(f, none, 0, &unused, "for the unitigs", unitig_out_bytes(U, S, stage_sums, stage_symbols, stage_ends, stage_flags), &at)) return rc;
+        // a device form's outputs are the caller's own; a staged one is carved off `at`
+        const auto carve = [&](void *out, bool stage, uint64_t bytes) -> void * {
+            if (!stage) return out;
+            char *here = at;
+            at += bytes;
+            return here;
+        };
+        d_offsets = static_cast<uint64_t *>(carve(nullptr, true, 8 * U + 256));
+        d_sums = static_cast<uint64_t *>(carve(sums, stage_sums, 8 * U));
+        d_symbols = static_cast<uint8_t *>(carve(symbols, stage_symbols, pad8(S)));
+        d_ends = static_cast<uint8_t *>(carve(ends, stage_ends, pad8(U)));
+        d_flags = static_cast<uint8_t *>(carve(flags, stage_flags, pad8(U)));
+        if (d_sums) HIP_TRY(h, hipMemsetAsync(d_sums, 0, 8 * U, f.stream));
+        HIP_TRY(h, launch_unitig_number(g, heads, tiles, uint32_t(f.k), U, S, d_offsets, f.stream));
+        HIP_TRY(h, launch_unitig_emit(g, state, heads, uint32_t(f.k), U, S, d_symbols, d_sums, d_ends, d_flags, f.stream, skip_marked));
+        filled = true;
+        return MSBWT_OK;
+    }
+
+    int deliver(Frame &f) {
+        msbwt_rle *h = f.h;
+        if (filled) {
+            const hipMemcpyKind kind = f.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+            if (offsets) HIP_TRY(h, hipMemcpyAsync(offsets, d_offsets, 8 * (U + 1), kind, f.stream));
+            if (f.host && sums) HIP_TRY(h, hipMemcpyAsync(sums, d_sums, 8 * U, kind, f.stream));
+            if (f.host && symbols) HIP_TRY(h, hipMemcpyAsync(symbols, d_symbols, S, kind, f.stream));
+            if (f.host && ends) HIP_TRY(h, hipMemcpyAsync(ends, d_ends, U, kind, f.stream));
+            if (f.host && flags) HIP_TRY(h, hipMemcpyAsync(flags, d_flags, U, kind, f.stream));
+        }
+        if (f.host) return status_of(h, f.stream, f.which);  // synchronises
+        HIP_TRY(h, hipStreamSynchronize(f.stream));           // (the scratch is freed on return)
+        return MSBWT_OK;
+    }
+};
+
 // Both forms: the sorted dump's counting walk, the staged walk with the edge pass behind it (into scratch: words, counts, edge bytes
 // and predecessor slots), then links, ranking, cycles, numbering and emission over the slots (unitigs.hpp).
 int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums, void *out_ends,
@@ -570,9 +680,7 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
     const IndexView v = view_of(h);
     Column none[] = {{nullptr}};  // (both allocations are all tail)
     uint64_t unused = 0, U = 0, S = 0;
-    bool filled = false;
-    uint64_t *d_offsets = nullptr, *d_sums = nullptr;
-    uint8_t *d_symbols = nullptr, *d_ends = nullptr, *d_flags = nullptr;
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
     return two_pass(
         f, ~0ull, nullptr, "k-mers", false,
         [&](uint64_t *n) -> int {
@@ -607,89 +715,145 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
 
             const UnitigNodes g{n, kmers, counts, pred, edge_words, link_words, counters, sink.flags};
             uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
-            const auto read_counters = [&]() -> int {  // synchronises
-                HIP_TRY(h, hipMemcpyAsync(c, counters, sizeof c, hipMemcpyDeviceToHost, f.stream));
-                HIP_TRY(h, hipStreamSynchronize(f.stream));
-                return MSBWT_OK;
-            };
-            // Ranking rounds until none is unfinished, `cap` at the most.  A round that finishes nobody ends them too: on every path
-            // the unfinished node nearest the head has a finished ancestor, so what is left then lies on cycles.
-            const auto rank = [&](uint64_t cap) -> int {
-                for (uint64_t round = 0; c[kUnitigUnfinished] && round < cap; ++round) {
-                    const uint64_t before = c[kUnitigUnfinished];
-                    HIP_TRY(h, hipMemsetAsync(counters + kUnitigUnfinished, 0, 8, f.stream));
-                    HIP_TRY(h, launch_unitig_jump(g, cur, other, f.stream));
-                    std::swap(cur, other);
-                    ++rounds;
-                    if (int rc = read_counters()) return rc;
-                    if (c[kUnitigUnfinished] == before) break;
-                }
-                return MSBWT_OK;
-            };
-            HIP_TRY(h, launch_unitig_links(g, cur, f.stream));
-            if (int rc = read_counters()) return rc;
-            if (int rc = rank(ceil_log2(n) + 1)) return rc;
-            if (const uint64_t on_cycles = c[kUnitigUnfinished]) {
-                // a cycle has at most on_cycles nodes: after ceil(log2) rounds every label is its cycle's smallest slot
-                HIP_TRY(h, launch_unitig_cycle_seed(g, cur, f.stream));
-                for (uint64_t round = 0; round < ceil_log2(on_cycles); ++round, ++rounds) {
-                    HIP_TRY(h, launch_unitig_cycle_jump(g, cur, other, f.stream));
-                    std::swap(cur, other);
-                }
-                HIP_TRY(h, hipMemsetAsync(counters + kUnitigUnfinished, 0, 8, f.stream));
-                HIP_TRY(h, launch_unitig_cycle_cut(g, cur, f.stream));
-                if (int rc = read_counters()) return rc;
-                if (int rc = rank(ceil_log2(on_cycles) + 1)) return rc;
-            }
-            HIP_TRY(h, launch_unitig_tails(g, cur, other, f.stream));
-            if (int rc = read_counters()) return rc;
+            if (int rc = rank_unitigs(f, g, cur, other, c, &rounds, [] { return int(MSBWT_OK); })) return rc;
             if (c[kUnitigUnfinished] || c[kUnitigLinks] > n + c[kUnitigCircular] || c[kUnitigCircular] > n)
                 return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the ranking left " + std::to_string(c[kUnitigUnfinished]) + " nodes without a head");
             U = n - c[kUnitigLinks] + c[kUnitigCircular];
             S = n + U * (k - 1);
-            *out_unitigs = U;
-            if (out_symbol_total) *out_symbol_total = S;
             const uint64_t info[MSBWT_UNITIG_INFO_WORDS] = {n, c[kUnitigEdges], c[kUnitigLinks], U, S, c[kUnitigCircular], c[kUnitigLongest], rounds};
             std::copy(info, info + MSBWT_UNITIG_INFO_WORDS, h->unitig_info);
-            if (capacity_unitigs == 0 && capacity_symbols == 0) return MSBWT_OK;
-            if (capacity_unitigs < U || (out_symbols && capacity_symbols < S))
-                return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the U = " +
-                                std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols");
+            return out.emit(f, g, cur, other, tiles, U, S, false);
+        },
+        [&](uint64_t) { return out.deliver(f); });
+}
 
-            // the other allocation: offsets | sums | symbols | ends | flags, the last four only where a host form stages them
-            const bool stage_sums = host && out_sums, stage_symbols = host && out_symbols, stage_ends = host && out_ends, stage_flags = host && out_flags;
-            if (int rc = stage_records(f, none, 0, &unused, "for the unitigs", unitig_out_bytes(U, S, stage_sums, stage_symbols, stage_ends, stage_flags), &at)) return rc;
-            // a device form's outputs are the caller's own; a staged one is carved off `at`
-            const auto carve = [&](void *out, bool stage, uint64_t bytes) -> void * {
-                if (!stage) return out;
-                char *here = at;
-                at += bytes;
-                return here;
-            };
-            d_offsets = static_cast<uint64_t *>(carve(nullptr, true, 8 * U + 256));
-            d_sums = static_cast<uint64_t *>(carve(out_sums, stage_sums, 8 * U));
-            d_symbols = static_cast<uint8_t *>(carve(out_symbols, stage_symbols, pad8(S)));
-            d_ends = static_cast<uint8_t *>(carve(out_ends, stage_ends, pad8(U)));
-            d_flags = static_cast<uint8_t *>(carve(out_flags, stage_flags, pad8(U)));
-            if (d_sums) HIP_TRY(h, hipMemsetAsync(d_sums, 0, 8 * U, f.stream));
-            HIP_TRY(h, launch_unitig_number(g, other, tiles, uint32_t(k), U, S, d_offsets, f.stream));
-            HIP_TRY(h, launch_unitig_emit(g, cur, other, uint32_t(k), U, S, d_symbols, d_sums, d_ends, d_flags, f.stream));
-            filled = true;
+// ---- canonical unitigs ----
+
+// per class: two slots of (four counts, later two states) and of the sort's (key, payload) twice over: 2 x (32 + 32) bytes
+constexpr uint64_t kCanonicalUnitigClassBytes = 128;
+constexpr uint64_t kCanonicalUnitigInfoWords = MSBWT_CANONICAL_UNITIG_INFO_WORDS;
+constexpr Shape kCanonicalUnitigShape{false, true, kCanonicalTotalWords * 8 < 256 ? 256 : kCanonicalTotalWords * 8, kCanonicalUnitigClassBytes};  // (fixed: the walk's totals)
+static_assert(4 * sizeof(uint64_t) == 2 * sizeof(UnitigState) && kCanonicalUnitigCounterWords * 8 <= kCanonicalUnitigFixedBytes && kCanonicalUnitigInfoWords == 10,
+              "the header's plan and constants");
+
+uint64_t canonical_unitig_chunk_slots(uint64_t slots) { return std::min(slots, kCanonicalUnitigChunkSlots); }
+// what the call keeps beside the 128 bytes per class, over 2 n slots: the (k+1)-mer words of a chunk, the sort's histogram and scan,
+// the numbering's tiles, both sets of counters, the edge bytes and the link bytes
+uint64_t canonical_unitig_fixed_bytes(uint64_t n) {
+    const uint64_t slots = 2 * n;
+    return 32 * canonical_unitig_chunk_slots(slots) + 8 * canonical_unitig_hist_words(slots) + 8 * canonical_unitig_scan_words(slots) + unitig_tiles(slots) * kUnitigTileBytes +
+           kUnitigFixedBytes + kCanonicalUnitigFixedBytes + 2 * graph_edge_words(slots) * 4;
+}
+
+// Both forms: the canonical walk counts the classes and then appends them; both members of every class become nodes in word order;
+// the (k+1)-mers out of every node are counted and folded into D's edge bytes; then the compaction of the plain call over the N
+// slots, with the cuts behind the links and the choice between a unitig and its mirror behind the ranking (canonical_unitigs.hpp).
+int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums,
+                      void *out_ends, void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                      hipStream_t stream) {
+    Frame f(bwt, "enumerate_canonical_unitigs", k, host, stream);
+    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
+    if (int rc = f.open(false, [&] {
+            if (k > 31) return f.refuse(" needs 1 <= k <= 31 (an edge is a packed (k+1)-mer)");
+            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
+            return !out_unitigs ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
+        }))
+        return rc;
+    msbwt_rle *h = f.h;
+    *out_unitigs = 0;
+    if (out_symbol_total) *out_symbol_total = 0;
+    std::fill(h->canonical_unitig_info, h->canonical_unitig_info + kCanonicalUnitigInfoWords, 0ull);
+    CanonicalSink classes{};
+    classes.mode = kCanonicalCount;
+    classes.min = m;
+    classes.max = ~0ull;
+    const uint64_t prune = m / 2 + m % 2;  // (enumerate_canonical: the member that emits a class has at least half of its count)
+    uint64_t totals[kCanonicalTotalWords] = {};
+    Column none[] = {{nullptr}};
+    uint64_t unused = 0;
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
+    return two_pass(
+        f, ~0ull, nullptr, "classes", true,
+        [&](uint64_t *n) -> int {
+            if (int rc = take_scratch(f, kCanonicalUnitigShape)) return rc;
+            if (int rc = canonical_walk(f, prune, classes, totals)) return rc;
+            *n = totals[kCanonicalClasses];
             return MSBWT_OK;
         },
-        [&](uint64_t) -> int {
-            if (filled) {
-                const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-                if (out_offsets) HIP_TRY(h, hipMemcpyAsync(out_offsets, d_offsets, 8 * (U + 1), kind, f.stream));
-                if (host && out_sums) HIP_TRY(h, hipMemcpyAsync(out_sums, d_sums, 8 * U, kind, f.stream));
-                if (host && out_symbols) HIP_TRY(h, hipMemcpyAsync(out_symbols, d_symbols, S, kind, f.stream));
-                if (host && out_ends) HIP_TRY(h, hipMemcpyAsync(out_ends, d_ends, U, kind, f.stream));
-                if (host && out_flags) HIP_TRY(h, hipMemcpyAsync(out_flags, d_flags, U, kind, f.stream));
+        [&](uint64_t n) -> int {
+            // one allocation over M = 2 n slots:
+            //   counts   4 M words: cnt[4 slot + c]; before them the walk's records (word, own, other: 3 n words), after them the two states
+            //   sort     4 M words: (keys, payloads) twice; the pair the sort leaves free holds the predecessor slots
+            //   chunk | histogram | scan | tiles | counters | counters | edge words | link words
+            const uint64_t M = 2 * n, chunk_slots = canonical_unitig_chunk_slots(M);
+            char *at = nullptr;
+            if (int rc = stage_records(f, none, n, &unused, "for the nodes of the graph", n * kCanonicalUnitigClassBytes + canonical_unitig_fixed_bytes(n), &at)) return rc;
+            uint64_t *cnt = reinterpret_cast<uint64_t *>(at), *keys_a = cnt + 4 * M, *vals_a = keys_a + M, *keys_b = vals_a + M, *vals_b = keys_b + M;
+            uint64_t *chunk = vals_b + M, *hist = chunk + 4 * chunk_slots, *scan = hist + canonical_unitig_hist_words(M);
+            char *tiles = reinterpret_cast<char *>(scan + canonical_unitig_scan_words(M));
+            unsigned long long *counters = reinterpret_cast<unsigned long long *>(tiles + unitig_tiles(M) * kUnitigTileBytes);
+            unsigned long long *own_counters = counters + kUnitigFixedBytes / 8;
+            uint32_t *edge_words = reinterpret_cast<uint32_t *>(own_counters + kCanonicalUnitigFixedBytes / 8), *link_words = edge_words + graph_edge_words(M);
+            uint32_t *flags = h->d_flags + f.which;
+            HIP_TRY(h, hipMemsetAsync(counters, 0, kUnitigFixedBytes + kCanonicalUnitigFixedBytes + 2 * graph_edge_words(M) * 4, f.stream));
+
+            // the classes, in walk order
+            classes.mode = kCanonicalAppend;
+            classes.kmers = cnt;
+            classes.own = cnt + n;
+            classes.other = cnt + 2 * n;
+            classes.capacity = n;
+            classes.flags = flags;
+            if (int rc = canonical_walk(f, prune, classes, totals)) return rc;
+            if (totals[kCanonicalOut] != n) return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the second walk found another number of classes");
+
+            // the nodes, in word order
+            uint64_t own[kCanonicalUnitigCounterWords] = {};
+            const auto read_own = [&]() -> int {  // synchronises
+                HIP_TRY(h, hipMemcpyAsync(own, own_counters, sizeof own, hipMemcpyDeviceToHost, f.stream));
+                HIP_TRY(h, hipStreamSynchronize(f.stream));
+                return MSBWT_OK;
+            };
+            HIP_TRY(h, launch_canonical_unitig_double(classes.kmers, classes.own, classes.other, n, uint32_t(k), keys_a, vals_a, own_counters, flags, f.stream));
+            if (int rc = read_own()) return rc;
+            if (own[kCanonicalUnitigSeconds] > n) return fail(h, MSBWT_ERR_INTERNAL, f.name + ": more second members than classes");
+            const uint64_t N = n + own[kCanonicalUnitigSeconds];
+            bool in_b = false;
+            HIP_TRY(h, canonical_unitig_sort(keys_a, vals_a, keys_b, vals_b, N, uint32_t(k), hist, scan, flags, f.stream, &in_b));
+            const uint64_t *keys = in_b ? keys_b : keys_a, *vals = in_b ? vals_b : vals_a;
+            uint64_t *pred = in_b ? keys_a : keys_b;
+            HIP_TRY(h, hipMemsetAsync(pred, 0xFF, N * 8, f.stream));  // (no slot)
+
+            // the edges: count_kmer of the four (k+1)-mers out of every node, a chunk of nodes at a time, then the fold
+            for (uint64_t first = 0; first < N; first += chunk_slots) {
+                const uint64_t nodes = std::min(chunk_slots, N - first);
+                HIP_TRY(h, launch_canonical_unitig_edge_words(keys, first, nodes, chunk, f.stream));
+                if (int rc = launch_count_2bit(h, chunk, k + 1, size_t(4 * nodes), cnt + 4 * first, f.stream, f.which)) return rc;
             }
-            if (host) return status_of(h, f.stream, f.which);  // synchronises
-            HIP_TRY(h, hipStreamSynchronize(f.stream));         // (the scratch is freed on return)
-            return MSBWT_OK;
-        });
+            HIP_TRY(h, launch_canonical_unitig_fold(keys, N, uint32_t(k), me, cnt, edge_words, pred, own_counters, flags, f.stream));
+
+            // the compaction over the N slots (the counts are folded: their place is the states')
+            UnitigState *cur = reinterpret_cast<UnitigState *>(cnt), *other = cur + N;
+            const UnitigNodes g{N, keys, vals, pred, edge_words, link_words, counters, flags};
+            uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
+            if (int rc = rank_unitigs(f, g, cur, other, c, &rounds, [&]() -> int {
+                    HIP_TRY(h, launch_canonical_unitig_cut(g, uint32_t(k), cur, own_counters, f.stream));
+                    return MSBWT_OK;
+                }))
+                return rc;
+            HIP_TRY(h, launch_canonical_unitig_choose(g, uint32_t(k), cur, own_counters, f.stream));
+            if (int rc = read_own()) return rc;
+            const uint64_t U = own[kCanonicalUnitigEmitted], circular = own[kCanonicalUnitigEmittedCircular];
+            if (c[kUnitigUnfinished] || own[kCanonicalUnitigEmittedNodes] != n || U > n || circular > U)
+                return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the ranking left " + std::to_string(c[kUnitigUnfinished]) + " nodes without a head, and the emitted unitigs hold " +
+                                                       std::to_string(own[kCanonicalUnitigEmittedNodes]) + " of " + std::to_string(n) + " classes");
+            const uint64_t S = n + U * (k - 1);
+            const uint64_t info[kCanonicalUnitigInfoWords] = {n, (c[kUnitigEdges] + own[kCanonicalUnitigHairpins]) / 2, n + circular - U, U, S, circular, c[kUnitigLongest], rounds,
+                                                              2 * n - N, own[kCanonicalUnitigCut]};
+            std::copy(info, info + kCanonicalUnitigInfoWords, h->canonical_unitig_info);
+            return out.emit(f, g, cur, other, tiles, U, S, true);
+        },
+        [&](uint64_t) { return out.deliver(f); });
 }
 
 }  // namespace
@@ -888,6 +1052,36 @@ int msbwt_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t no
     if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 32 n + n)
     const uint64_t out = unitigs || symbols ? unitig_out_bytes(unitigs, symbols, true, true, true, true) : 0;
     return plan(kUnitigShape, total_rows, free_hbm_bytes, nodes, unitig_fixed_bytes(nodes) + out, device_bytes);
+}
+
+// ---- canonical unitigs: the non-branching paths of the strand-merged k-mer graph ----
+
+int msbwt_rle_enumerate_canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols, uint64_t *out_offsets,
+                                          uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                          uint64_t *out_unitigs, uint64_t *out_symbol_total) {
+    return canonical_unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols,
+                             out_unitigs, out_symbol_total, nullptr);
+}
+
+int msbwt_rle_enumerate_canonical_unitigs_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols, void *d_out_offsets,
+                                                 void *d_out_count_sums, void *d_out_ends, void *d_out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                                 uint64_t *out_unitigs, uint64_t *out_symbol_total, void *hip_stream) {
+    return canonical_unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs,
+                             capacity_symbols, out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream));
+}
+
+int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out) {
+    Call c(bwt);
+    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
+    std::copy(c.h->canonical_unitig_info, c.h->canonical_unitig_info + MSBWT_CANONICAL_UNITIG_INFO_WORDS, out);
+    return MSBWT_OK;
+}
+
+// the host call over `classes` classes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)
+int msbwt_canonical_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {
+    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 31 n + n)
+    const uint64_t out = unitigs || symbols ? unitig_out_bytes(unitigs, symbols, true, true, true, true) : 0;
+    return plan(kCanonicalUnitigShape, total_rows, free_hbm_bytes, classes, canonical_unitig_fixed_bytes(classes) + out, device_bytes);
 }
 
 }  // extern "C"

@@ -144,7 +144,7 @@ __device__ __forceinline__ void tile_thread_sums(const UnitigNodes &g, const Uni
 #pragma unroll
     for (uint32_t j = 0; j < kPerThread; ++j) {
         const uint64_t i = first + j;
-        if (i < g.n && !(byte_of(g.link_words, i) & kUnitigLinkUp)) {
+        if (i < g.n && !(byte_of(g.link_words, i) & (kUnitigLinkUp | kUnitigSkip))) {
             v[0] += 1;
             v[1] += heads[i].x;
         }
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void k_unitig_number(UnitigNodes g, Uniti
 #pragma unroll
         for (uint32_t j = 0; j < kPerThread; ++j) {
             const uint64_t i = first + j;
-            if (i >= g.n || (byte_of(g.link_words, i) & kUnitigLinkUp)) continue;
+            if (i >= g.n || (byte_of(g.link_words, i) & (kUnitigLinkUp | kUnitigSkip))) continue;
             const uint64_t nodes = heads[i].x;
             if (number >= U || before + number * (k - 1u) >= S) {  // (U and S are what the counters said)
                 atomicOr(g.flags, kFlagInternal);
@@ -188,6 +188,8 @@ __global__ __launch_bounds__(kThreads) void k_unitig_number(UnitigNodes g, Uniti
     }
 }
 
+// kSkip: the nodes of a unitig whose head carries kUnitigSkip emit nothing (canonical_unitigs.hpp; the plain call sets no such bit)
+template <bool kSkip>
 __global__ __launch_bounds__(kThreads) void k_unitig_emit(UnitigNodes g, const UnitigState *__restrict__ state, const UnitigState *__restrict__ heads, uint32_t k, uint64_t U,
                                                          uint64_t S, uint8_t *__restrict__ symbols, unsigned long long *__restrict__ count_sums, uint8_t *__restrict__ ends,
                                                          uint8_t *__restrict__ out_flags) {
@@ -198,6 +200,8 @@ __global__ __launch_bounds__(kThreads) void k_unitig_emit(UnitigNodes g, const U
             atomicOr(g.flags, kFlagInternal);
             continue;
         }
+        if constexpr (kSkip)
+            if (byte_of(g.link_words, head) & kUnitigSkip) continue;
         const UnitigState h = heads[head];
         const uint64_t u = h.y, offset = h.x + u * (k - 1u), at = offset + (k - 1u) + distance;
         if (u >= U || at >= S) {
@@ -279,11 +283,14 @@ hipError_t launch_unitig_number(const UnitigNodes &g, UnitigState *heads, void *
 }
 
 hipError_t launch_unitig_emit(const UnitigNodes &g, const UnitigState *state, const UnitigState *heads, uint32_t k, uint64_t U, uint64_t S, uint8_t *symbols,
-                              uint64_t *count_sums, uint8_t *ends, uint8_t *out_flags, hipStream_t stream) {
+                              uint64_t *count_sums, uint8_t *ends, uint8_t *out_flags, hipStream_t stream, bool skip_marked) {
     if (!usable(g) || !state || !heads || k < 1) return hipErrorInvalidValue;
     if (g.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_unitig_emit, slots_grid(g), dim3(kThreads), 0, stream, g, state, heads, k, U, S, symbols, reinterpret_cast<unsigned long long *>(count_sums), ends,
-                       out_flags);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(count_sums);
+    if (skip_marked)
+        hipLaunchKernelGGL(k_unitig_emit<true>, slots_grid(g), dim3(kThreads), 0, stream, g, state, heads, k, U, S, symbols, sums, ends, out_flags);
+    else
+        hipLaunchKernelGGL(k_unitig_emit<false>, slots_grid(g), dim3(kThreads), 0, stream, g, state, heads, k, U, S, symbols, sums, ends, out_flags);
     return hipGetLastError();
 }
 

@@ -29,7 +29,9 @@ enum : uint32_t {                             // words of the counters
     kUnitigUnfinished,   // nodes a jumping round (or launch_unitig_links) left short of their head: zeroed by the caller before each
     kUnitigCounterWords
 };
-enum : uint32_t { kUnitigLinkUp = 1, kUnitigLinkDown = 2, kUnitigOnCycle = 4 };  // bits of a node's link byte (kOnCycle: at the unitig's first node)
+// bits of a node's link byte (kOnCycle: at the unitig's first node).  kUnitigSkip, at a first node: the unitig is neither numbered nor
+// emitted -- set by the canonical call alone (canonical_unitigs.hpp) between the ranking and the numbering; the plain call never sets it.
+enum : uint32_t { kUnitigLinkUp = 1, kUnitigLinkDown = 2, kUnitigOnCycle = 4, kUnitigSkip = 8 };
 
 // {ancestor, distance | kUnitigDone} while ranking; {slot 2^r links up, smallest slot of the 2^r nodes from here up} while a cycle
 // looks for its opening; in the other buffer, after the ranking, at a head's slot {nodes of all unitigs before, unitig number}
@@ -67,8 +69,8 @@ hipError_t launch_unitig_tails(const UnitigNodes &g, const UnitigState *state, U
 // heads[h] = {nodes before, number} at every head h, in slot order; offsets[u] = nodes before + u (k - 1) for u < U, offsets[U] = S.
 // tiles: unitig_tiles(n) x kUnitigTileBytes of scratch.
 hipError_t launch_unitig_number(const UnitigNodes &g, UnitigState *heads, void *tiles, uint32_t k, uint64_t U, uint64_t S, uint64_t *offsets, hipStream_t stream);
-// the outputs (each may be nullptr; count_sums zeroed by the caller: the counts are added)
+// the outputs (each may be nullptr; count_sums zeroed by the caller: the counts are added).  skip_marked: heads carry kUnitigSkip
 hipError_t launch_unitig_emit(const UnitigNodes &g, const UnitigState *state, const UnitigState *heads, uint32_t k, uint64_t U, uint64_t S, uint8_t *symbols,
-                              uint64_t *count_sums, uint8_t *ends, uint8_t *out_flags, hipStream_t stream);
+                              uint64_t *count_sums, uint8_t *ends, uint8_t *out_flags, hipStream_t stream, bool skip_marked = false);
 
 }  // namespace msbwt

@@ -496,13 +496,10 @@ class RleBWT(BWT):
         return table, nodes.value, edges.value
 
     # ---- unitigs: the non-branching paths of the k-mer graph as ragged sequences ----
-    def enumerate_unitigs(self, k, min_count=1, min_edge=None, text=False):
-        """msbwt_rle_enumerate_unitigs, both calls of the two-call pattern -> (symbols, offsets, count_sums, ends, flags): unitig u is
-        symbols[offsets[u]:offsets[u + 1]] in symbol codes (A C G T = 1 2 3 5; uint8), of offsets[u + 1] - offsets[u] - k + 1 nodes whose
-        counts sum to count_sums[u]; ends[u]: low nibble = predecessor bits of its first node, high nibble = successor bits of its last;
-        flags[u] bit 0 = circular.  Ascending by first k-mer.  text=True: the sequences as a list of str in place of (symbols, offsets),
-        that is (sequences, count_sums, ends, flags)."""
-        fn, args = _lib.lib().msbwt_rle_enumerate_unitigs, (int(k), int(min_count), int(min_edge or 0))
+    def _unitigs(self, fn, k, min_count, min_edge, text):
+        """Both calls of the two-call pattern of a unitig entry point -> (symbols, offsets, count_sums, ends, flags), or with text=True
+        (sequences, count_sums, ends, flags)."""
+        args = (int(k), int(min_count), int(min_edge or 0))
         U, S = C.c_uint64(0), C.c_uint64(0)
         rc = fn(self._h, *args, None, None, None, None, None, 0, 0, C.byref(U), C.byref(S))
         if rc:
@@ -518,14 +515,10 @@ class RleBWT(BWT):
         letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
         return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags
 
-    def enumerate_unitigs_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count=1, min_edge=None,
-                                 stream=0):
-        """msbwt_rle_enumerate_unitigs_device: device pointers (ints, each may be None; the byte arrays at any alignment) -> (U, S);
-        both capacities 0 only counts, a capacity too small raises (nothing written; the error carries .n = U and .symbols = S).
-        Synchronises `stream`."""
+    def _unitigs_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count, min_edge, stream):
         U, S = C.c_uint64(0), C.c_uint64(0)
-        rc = _lib.lib().msbwt_rle_enumerate_unitigs_device(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
-                                                           int(capacity_unitigs), int(capacity_symbols), C.byref(U), C.byref(S), stream)
+        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, int(capacity_unitigs), int(capacity_symbols),
+                C.byref(U), C.byref(S), stream)
         if rc:
             try:
                 _raise(rc, self._h)
@@ -534,13 +527,51 @@ class RleBWT(BWT):
                 raise
         return U.value, S.value
 
-    def unitig_info(self):
-        """What the last unitig call found: {"nodes", "edges", "links", "unitigs", "symbols", "circular", "longest", "rounds"}."""
-        w = np.zeros(_lib.UNITIG_INFO_WORDS, dtype=np.uint64)
-        rc = _lib.lib().msbwt_rle_unitig_info(self._h, w.ctypes.data_as(C.c_void_p))
+    def _info(self, fn, names):
+        w = np.zeros(len(names), dtype=np.uint64)
+        rc = fn(self._h, w.ctypes.data_as(C.c_void_p))
         if rc:
             _raise(rc, self._h)
-        return dict(zip(("nodes", "edges", "links", "unitigs", "symbols", "circular", "longest", "rounds"), (int(x) for x in w)))
+        return dict(zip(names, (int(x) for x in w)))
+
+    def enumerate_unitigs(self, k, min_count=1, min_edge=None, text=False):
+        """msbwt_rle_enumerate_unitigs, both calls of the two-call pattern -> (symbols, offsets, count_sums, ends, flags): unitig u is
+        symbols[offsets[u]:offsets[u + 1]] in symbol codes (A C G T = 1 2 3 5; uint8), of offsets[u + 1] - offsets[u] - k + 1 nodes whose
+        counts sum to count_sums[u]; ends[u]: low nibble = predecessor bits of its first node, high nibble = successor bits of its last;
+        flags[u] bit 0 = circular.  Ascending by first k-mer.  text=True: the sequences as a list of str in place of (symbols, offsets),
+        that is (sequences, count_sums, ends, flags)."""
+        return self._unitigs(_lib.lib().msbwt_rle_enumerate_unitigs, k, min_count, min_edge, text)
+
+    def enumerate_unitigs_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count=1, min_edge=None,
+                                 stream=0):
+        """msbwt_rle_enumerate_unitigs_device: device pointers (ints, each may be None; the byte arrays at any alignment) -> (U, S);
+        both capacities 0 only counts, a capacity too small raises (nothing written; the error carries .n = U and .symbols = S).
+        Synchronises `stream`."""
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_unitigs_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs,
+                                    capacity_symbols, min_count, min_edge, stream)
+
+    def unitig_info(self):
+        """What the last unitig call found: {"nodes", "edges", "links", "unitigs", "symbols", "circular", "longest", "rounds"}."""
+        return self._info(_lib.lib().msbwt_rle_unitig_info, ("nodes", "edges", "links", "unitigs", "symbols", "circular", "longest", "rounds"))
+
+    # ---- canonical unitigs: the same over the strand-merged graph, every class of {q, rc(q)} in one unitig once ----
+    def enumerate_canonical_unitigs(self, k, min_count=1, min_edge=None, text=False):
+        """msbwt_rle_enumerate_canonical_unitigs, both calls of the two-call pattern -> what enumerate_unitigs returns, for the
+        strand-merged graph (1 <= k <= 31): count_sums are sums of class counts, ends the adjacency of the emitted orientation; of a
+        unitig and its reverse complement the one with the smaller first k-mer is returned."""
+        return self._unitigs(_lib.lib().msbwt_rle_enumerate_canonical_unitigs, k, min_count, min_edge, text)
+
+    def enumerate_canonical_unitigs_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count=1,
+                                           min_edge=None, stream=0):
+        """msbwt_rle_enumerate_canonical_unitigs_device: as enumerate_unitigs_device."""
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_canonical_unitigs_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs,
+                                    capacity_symbols, min_count, min_edge, stream)
+
+    def canonical_unitig_info(self):
+        """What the last canonical unitig call found, for the emitted set: {"classes", "edge_classes", "links", "unitigs", "symbols",
+        "circular", "longest", "rounds", "palindromes", "cut_links"}."""
+        return self._info(_lib.lib().msbwt_rle_canonical_unitig_info,
+                          ("classes", "edge_classes", "links", "unitigs", "symbols", "circular", "longest", "rounds", "palindromes", "cut_links"))
 
     def spectrum_scratch_bytes(self):
         """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""

@@ -110,6 +110,16 @@ extern "C" {
                                           out_symbol_total: *mut u64, hip_stream: *mut c_void) -> c_int;
     fn msbwt_rle_unitig_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
     fn msbwt_unitigs_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64, device_bytes: *mut u64) -> c_int;
+    // canonical unitigs: the same over the strand-merged graph, every class of {q, rc(q)} in one unitig once (1 <= k <= 31)
+    fn msbwt_rle_enumerate_canonical_unitigs(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_symbols: *mut u8,
+                                             out_offsets: *mut u64, out_count_sums: *mut u64, out_ends: *mut u8, out_flags: *mut u8,
+                                             capacity_unitigs: u64, capacity_symbols: u64, out_unitigs: *mut u64, out_symbol_total: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_canonical_unitigs_device(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, d_out_symbols: *mut c_void,
+                                                    d_out_offsets: *mut c_void, d_out_count_sums: *mut c_void, d_out_ends: *mut c_void,
+                                                    d_out_flags: *mut c_void, capacity_unitigs: u64, capacity_symbols: u64, out_unitigs: *mut u64,
+                                                    out_symbol_total: *mut u64, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_canonical_unitig_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_canonical_unitigs_plan(total_rows: u64, free_hbm_bytes: u64, classes: u64, unitigs: u64, symbols: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
@@ -575,6 +585,55 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_unitigs_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "unitigs_plan: {} rows, {} nodes", total_rows, nodes);
+        bytes
+    }
+
+    /// Canonical unitigs: the unitigs of the strand-merged graph (1 <= k <= 31), every class of a k-mer and its reverse complement in
+    /// exactly one of them; of a unitig and its mirror the one with the smaller first k-mer.  The arrays of `enumerate_unitigs`, the
+    /// count sums over class counts.
+    pub fn enumerate_canonical_unitigs(&self, k: usize, min_count: u64, min_edge: u64) -> (Vec<u8>, Vec<u64>, Vec<u64>, Vec<u8>, Vec<u8>) {
+        let (mut u, mut s) = (0u64, 0u64);
+        let null8 = std::ptr::null_mut::<u8>();
+        let null64 = std::ptr::null_mut::<u64>();
+        let rc = unsafe { msbwt_rle_enumerate_canonical_unitigs(self.raw, k, min_count, min_edge, null8, null64, null64, null8, null8, 0, 0, &mut u, &mut s) };
+        if rc != MSBWT_OK { panic!("enumerate_canonical_unitigs: {}", self.last_error()); }
+        let (mut symbols, mut offsets) = (vec![0u8; s as usize], vec![0u64; u as usize + 1]);
+        let (mut sums, mut ends, mut flags) = (vec![0u64; u as usize], vec![0u8; u as usize], vec![0u8; u as usize]);
+        if u > 0 {
+            let rc = unsafe {
+                msbwt_rle_enumerate_canonical_unitigs(self.raw, k, min_count, min_edge, symbols.as_mut_ptr(), offsets.as_mut_ptr(), sums.as_mut_ptr(),
+                                                      ends.as_mut_ptr(), flags.as_mut_ptr(), u, s, &mut u, &mut s)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_canonical_unitigs: {}", self.last_error()); }
+        }
+        (symbols, offsets, sums, ends, flags)
+    }
+
+    /// The same into device buffers (each may be null; the byte arrays at any alignment) -> (unitigs, symbols); both capacities 0 only counts.
+    pub unsafe fn enumerate_canonical_unitigs_device(&self, k: usize, min_count: u64, min_edge: u64, d_symbols: *mut c_void, d_offsets: *mut c_void,
+                                                     d_count_sums: *mut c_void, d_ends: *mut c_void, d_flags: *mut c_void, capacity_unitigs: u64,
+                                                     capacity_symbols: u64, hip_stream: *mut c_void) -> (u64, u64) {
+        let (mut u, mut s) = (0u64, 0u64);
+        let rc = msbwt_rle_enumerate_canonical_unitigs_device(self.raw, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
+                                                              capacity_unitigs, capacity_symbols, &mut u, &mut s, hip_stream);
+        if rc != MSBWT_OK { panic!("enumerate_canonical_unitigs_device: {}", self.last_error()); }
+        (u, s)
+    }
+
+    /// The last canonical unitig call: [classes, edge classes, links, unitigs, symbols, circular unitigs, nodes of the longest unitig,
+    /// jumping rounds, palindromic nodes, cut links].
+    pub fn canonical_unitig_info(&self) -> [u64; 10] {
+        let mut words = [0u64; 10];
+        let rc = unsafe { msbwt_rle_canonical_unitig_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("canonical_unitig_info: {}", self.last_error()); }
+        words
+    }
+
+    /// HBM bytes a host canonical unitig call over `classes` classes that fills every buffer allocates and frees again (pure function).
+    pub fn canonical_unitigs_plan(total_rows: u64, free_hbm_bytes: u64, classes: u64, unitigs: u64, symbols: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_canonical_unitigs_plan(total_rows, free_hbm_bytes, classes, unitigs, symbols, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "canonical_unitigs_plan: {} rows, {} classes", total_rows, classes);
         bytes
     }
 
