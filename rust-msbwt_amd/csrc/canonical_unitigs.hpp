@@ -3,7 +3,7 @@
 // what the kernels do between the canonical walk (canonical.hpp), which leaves the n classes (canonical word, own, other) in walk
 // order, and the compaction of unitigs.hpp, which works over slots whatever they came from:
 //   doubling   both member words of every class into one array of N = 2n - palindromes keys, the class count as the payload
-//   order      stable 8-bit radix passes (per-tile digit histogram, scan, scatter) over the low ceil(2k / 8) bytes of the keys: slot
+//   order      the stable 8-bit radix passes of radix_sort.hpp over the low ceil(2k / 8) bytes of the keys (spectrum.cpp calls them): slot
 //              order is word order from here on.  WORD -> SLOT is a binary search over the sorted keys, ceil(log2 N) + 1 probes at the
 //              most; a word that is no node comes back as N, never as a slot.
 //   edges      the four (k+1)-mers q.c of every node are written as packed words chunk by chunk, counted by the library's packed
@@ -23,7 +23,6 @@
 
 namespace msbwt {
 
-constexpr uint64_t kCanonicalUnitigSortTile = 4096;        // keys a workgroup ranks and scatters per radix pass
 constexpr uint64_t kCanonicalUnitigChunkSlots = 1u << 20;  // nodes whose four (k+1)-mers are searched per batch
 constexpr uint64_t kCanonicalUnitigFixedBytes = 256;       // the counters below, padded: zeroed by the caller
 enum : uint32_t {                                          // words of the counters
@@ -36,18 +35,10 @@ enum : uint32_t {                                          // words of the count
     kCanonicalUnitigCounterWords
 };
 
-inline uint64_t canonical_unitig_sort_tiles(uint64_t slots) { return (slots + kCanonicalUnitigSortTile - 1) / kCanonicalUnitigSortTile; }
-inline uint64_t canonical_unitig_hist_words(uint64_t slots) { return 256 * canonical_unitig_sort_tiles(slots); }
-inline uint64_t canonical_unitig_scan_words(uint64_t slots) { return (canonical_unitig_sort_tiles(slots) + 3) / 4 + 8; }  // (>= scan_scratch_words of the histogram)
-
 // keys[i] = words[i], vals[i] = own[i] + other[i] for i < n; the reverse complement of every word that is not its own, with the same
 // payload, appended from n on in no particular order (counters[kCanonicalUnitigSeconds] counts them).  keys, vals: 2 n words.
 hipError_t launch_canonical_unitig_double(const uint64_t *words, const uint64_t *own, const uint64_t *other, uint64_t n, uint32_t k, uint64_t *keys, uint64_t *vals,
                                           unsigned long long *counters, uint32_t *flags, hipStream_t stream);
-// (keys_a, vals_a)[0 .. N) sorted by the low 2k bits of the keys, through (keys_b, vals_b); *in_b: the result is in the b pair.
-// hist: canonical_unitig_hist_words(N) words, scan: canonical_unitig_scan_words(N) words.
-hipError_t canonical_unitig_sort(uint64_t *keys_a, uint64_t *vals_a, uint64_t *keys_b, uint64_t *vals_b, uint64_t N, uint32_t k, uint64_t *hist, uint64_t *scan,
-                                 uint32_t *flags, hipStream_t stream, bool *in_b);
 // out[4 j + c] = the (k+1)-mer keys[first + j].c as a packed word, j < m, c < 4
 hipError_t launch_canonical_unitig_edge_words(const uint64_t *keys, uint64_t first, uint64_t m, uint64_t *out, hipStream_t stream);
 // the edge bytes (zeroed by the caller) and pred[] (as GraphSink::pred_slot) of D from cnt[4 slot + c] = count_kmer(keys[slot].c)

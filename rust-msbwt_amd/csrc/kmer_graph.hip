@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "kmer_graph.hpp"
 #include "rank_ops.hpp"
+#include "slot_bytes.hpp"
 #include "spectrum.hpp"
 #include "workgroup.hpp"
 
@@ -37,10 +38,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr uint32_t kGridCap = 256u * 8u;
-
-__device__ __forceinline__ void or_edge_bits(uint32_t *__restrict__ edge_words, uint64_t slot, uint32_t bits) {
-    atomicOr(edge_words + (slot >> 2), bits << (8u * (uint32_t(slot) & 3u)));
-}
 
 template <bool kRuns>
 __global__ __launch_bounds__(kThreads) void k_graph_edges(const Node *__restrict__ staged, uint64_t m, const uint4 *__restrict__ blocks, const uint4 *__restrict__ overflow,
@@ -91,9 +88,9 @@ __global__ __launch_bounds__(kThreads) void k_graph_edges(const Node *__restrict
             }
             pred |= 1u << c;
             if (sink.pred_slot) sink.pred_slot[slot] = marks - 1u;
-            or_edge_bits(sink.edge_words, marks - 1u, 16u << last);
+            or_slot_bits(sink.edge_words, marks - 1u, 16u << last);
         }
-        if (pred) or_edge_bits(sink.edge_words, slot, pred);
+        if (pred) or_slot_bits(sink.edge_words, slot, pred);
     }
 }
 

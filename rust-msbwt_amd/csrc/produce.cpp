@@ -11,6 +11,7 @@
 
 #include "handle.hpp"
 #include "index_build.hpp"
+#include "radix_sort.hpp"
 
 namespace {
 
@@ -315,7 +316,7 @@ int msbwt_build_reads_plan(uint64_t total_symbols, uint64_t free_hbm_bytes, uint
     return MSBWT_OK;
 }
 
-size_t msbwt_build_reads_sort_tile(void) { return kReadsSortTile; }
+size_t msbwt_build_reads_sort_tile(void) { return kRadixSortTile; }
 
 int msbwt_rle_build_stage_ms(const msbwt_rle *ch, double *out_ms, uint64_t *out_pieces) {
     Call c(ch);

@@ -11,13 +11,13 @@
 //   3. sort         a piece's positions are collected in text order (count, scan, compact), then sorted by 63-bit key words of
 //                   21 symbols at 3 bits, zero after the suffix's own '$', from the last word the longest read reaches down to
 //                   word 0.  A word is gathered from the text for the current permutation and sorted by 8 stable 8-bit
-//                   radix passes: per-tile digit histogram, scan, scatter.  Stable passes over keys that are equal exactly
-//                   where the suffixes are leave equal suffixes in text order.
+//                   radix passes (radix_sort.hip: per-tile digit histogram, scan, scatter).  Stable passes over keys that are
+//                   equal exactly where the suffixes are leave equal suffixes in text order.
 //   4. emit         text[p - 1] for every sorted position p, into the piece's slot of the symbol array.
 //   5. encode       the symbol array's runs -> RLE bytes (run_encode.hip, shared with the merge).
 //
 // Integer only; every kernel runs without scratch memory.  64-bit: every text position, offset into the symbol and
-// RLE arrays, histogram bin and scanned rank.  32-bit: a suffix's rank inside its tile (< kReadsSortTile), a tile's digit
+// RLE arrays, histogram bin and scanned rank.  32-bit: a suffix's rank inside its tile (< kRadixSortTile), a tile's digit
 // counts, and -- while the text is below 2^32 symbols -- the stored positions themselves.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "radix_sort.hpp"
 #include "reads_build.hpp"
 #include "rle_codec.hpp"
 #include "run_encode.hpp"
@@ -36,13 +37,12 @@ namespace msbwt {
 namespace {
 
 constexpr uint32_t kThreads = kScanThreads, kWaves = kScanWaves;
-constexpr uint32_t kRounds = kReadsSortTile / kThreads;  // elements per lane in a sort tile
-constexpr uint32_t kDigitBits = 8, kDigits = 1u << kDigitBits, kPassesPerWord = 8;  // 8 x 8 bits cover the 63 key bits
+constexpr uint32_t kPassesPerWord = 8;  // 8 x 8 bits cover the 63 key bits; an even number: a word's result is back where it started
 constexpr uint32_t kWordSymbols = 21;
 constexpr uint32_t kCollectPer = 8, kCollectTile = kThreads * kCollectPer;  // collect: text positions per thread / workgroup
 constexpr uint32_t kBins = 4096;
 constexpr uint32_t kPad = 128;  // zero bytes after the reads and after the text: wide loads past the last symbol stay inside
-static_assert(kRounds * kThreads == kReadsSortTile && kThreads == kDigits, "one thread per digit when a tile's counts are laid out");
+static_assert(kPassesPerWord % 2 == 0 && kPassesPerWord * kRadixDigitBits == 64, "a key word's passes");
 
 // ---- keys ----
 
@@ -107,88 +107,6 @@ template <class Pos>
 __global__ __launch_bounds__(256) void k_iota(Pos *__restrict__ pos, uint64_t n) {
     const uint64_t stride = uint64_t(gridDim.x) * kThreads;
     for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < n; i += stride) pos[i] = Pos(i);
-}
-
-// ---- one stable radix pass over a piece: tile t = elements [t * kReadsSortTile, ...) ----
-
-// hist[digit * ntiles + tile] = the tile's elements with that digit
-__global__ __launch_bounds__(256) void k_sort_histogram(const uint64_t *__restrict__ keys, uint64_t n, uint32_t shift, uint64_t ntiles,
-                                                        uint64_t *__restrict__ hist) {
-    __shared__ uint32_t counts[kDigits];
-    counts[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint64_t base = uint64_t(blockIdx.x) * kReadsSortTile;
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const uint64_t i = base + r * kThreads + threadIdx.x;
-        if (i < n) atomicAdd(&counts[uint32_t(keys[i] >> shift) & (kDigits - 1u)], 1u);
-    }
-    __syncthreads();
-    hist[uint64_t(threadIdx.x) * ntiles + blockIdx.x] = counts[threadIdx.x];
-}
-
-// hist: scanned.  A wave takes kRounds rows of 64 consecutive elements; a lane's rank among the tile's elements of its digit is
-// (what earlier waves hold) + (what the wave's earlier rows hold) + (the lanes before it in its row with the same digit).
-template <class Pos>
-__global__ __launch_bounds__(256) void k_sort_scatter(const uint64_t *__restrict__ keys_in, const Pos *__restrict__ pos_in, uint64_t n, uint32_t shift,
-                                                      uint64_t ntiles, const uint64_t *__restrict__ hist, uint64_t *__restrict__ keys_out,
-                                                      Pos *__restrict__ pos_out) {
-    __shared__ uint32_t wave_counts[kWaves][kDigits];
-    __shared__ uint64_t digit_base[kDigits];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (uint32_t w = 0; w < kWaves; ++w) wave_counts[w][threadIdx.x] = 0u;
-    __syncthreads();
-    volatile uint32_t *mine = wave_counts[wave];
-    const uint64_t first = uint64_t(blockIdx.x) * kReadsSortTile + uint64_t(wave) * (kRounds * 64u) + lane;
-    uint64_t key[kRounds];
-    Pos pos[kRounds];
-    uint32_t rank[kRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const uint64_t i = first + r * 64u;
-        const bool live = i < n;
-        key[r] = live ? keys_in[i] : 0ull;
-        pos[r] = live ? pos_in[i] : Pos(0);
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const bool live = first + r * 64u < n;
-        const uint32_t d = uint32_t(key[r] >> shift) & (kDigits - 1u);
-        uint64_t peers = __ballot(live);  // the live lanes of the row with this lane's digit
-#pragma unroll
-        for (uint32_t b = 0; b < kDigitBits; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const uint64_t with = __ballot(live && bit);
-            peers &= bit ? with : ~with;
-        }
-        const uint32_t before = uint32_t(__popcll(peers & ((1ull << lane) - 1ull)));
-        const uint32_t held = live ? mine[d] : 0u;
-        __builtin_amdgcn_wave_barrier();
-        if (live && before == 0u) mine[d] = held + uint32_t(__popcll(peers));
-        __builtin_amdgcn_wave_barrier();
-        rank[r] = held + before;
-    }
-    __syncthreads();
-    {   // thread d: the digit's place in the output, and where each wave's share of it starts inside the tile's
-        uint32_t acc = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kWaves; ++w) {
-            const uint32_t c = wave_counts[w][threadIdx.x];
-            wave_counts[w][threadIdx.x] = acc;
-            acc += c;
-        }
-        digit_base[threadIdx.x] = hist[uint64_t(threadIdx.x) * ntiles + blockIdx.x];
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        if (first + r * 64u >= n) continue;
-        const uint32_t d = uint32_t(key[r] >> shift) & (kDigits - 1u);
-        const uint64_t to = digit_base[d] + wave_counts[wave][d] + rank[r];  // < n: the scanned histogram counts exactly n elements
-        keys_out[to] = key[r];
-        pos_out[to] = pos[r];
-    }
 }
 
 // ---- step 1: the text ----
@@ -324,15 +242,14 @@ struct SortBuffers {
     uint64_t capacity = 0;
     uint64_t *keys_a = nullptr, *keys_b = nullptr, *hist = nullptr, *scan = nullptr;
     Pos *pos_a = nullptr, *pos_b = nullptr;
-    static uint64_t hist_words(uint64_t n) { return uint64_t(kDigits) * ceil_div(std::max<uint64_t>(n, 1), kReadsSortTile); }
     hipError_t take(Arena &arena, uint64_t n) {
         capacity = n;
         hipError_t e = arena.take(&keys_a, n * 8);
         if (e == hipSuccess) e = arena.take(&keys_b, n * 8);
         if (e == hipSuccess) e = arena.take(&pos_a, n * sizeof(Pos));
         if (e == hipSuccess) e = arena.take(&pos_b, n * sizeof(Pos));
-        if (e == hipSuccess) e = arena.take(&hist, hist_words(n) * 8);
-        if (e == hipSuccess) e = arena.take(&scan, scan_scratch_words(hist_words(n)) * 8);
+        if (e == hipSuccess) e = arena.take(&hist, radix_sort_hist_words(n) * 8);
+        if (e == hipSuccess) e = arena.take(&scan, radix_sort_scan_words(n) * 8);
         return e;
     }
     void give_back(Arena &arena) {
@@ -350,20 +267,10 @@ struct SortBuffers {
 template <class Pos, class Source>
 hipError_t sort_elements(const Source &src, SortBuffers<Pos> &b, uint64_t n, uint32_t nwords, hipStream_t stream) {
     if (n < 2) return hipSuccess;
-    const uint64_t ntiles = ceil_div(n, kReadsSortTile);
     for (uint32_t w = nwords; w-- > 0;) {
         hipLaunchKernelGGL((k_gather_keys<Pos, Source>), dim3(capped_grid(n, kThreads)), dim3(kThreads), 0, stream, src, b.pos_a, n, w, b.keys_a);
-        for (uint32_t pass = 0; pass < kPassesPerWord; ++pass) {
-            const uint32_t shift = pass * kDigitBits;
-            hipLaunchKernelGGL(k_sort_histogram, dim3(uint32_t(ntiles)), dim3(kThreads), 0, stream, b.keys_a, n, shift, ntiles, b.hist);
-            hipError_t e = exclusive_scan(b.hist, kDigits * ntiles, b.scan, stream);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_sort_scatter<Pos>), dim3(uint32_t(ntiles)), dim3(kThreads), 0, stream, b.keys_a, b.pos_a, n, shift, ntiles, b.hist, b.keys_b,
-                               b.pos_b);
-            std::swap(b.keys_a, b.keys_b);
-            std::swap(b.pos_a, b.pos_b);
-        }
-        const hipError_t e = hipGetLastError();
+        bool in_b = false;  // (never: an even number of passes)
+        const hipError_t e = radix_sort_passes(b.keys_a, b.pos_a, b.keys_b, b.pos_b, n, 0, kPassesPerWord, b.hist, b.scan, nullptr, stream, &in_b);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -457,7 +364,7 @@ hipError_t build(const uint8_t *reads, const uint64_t *offsets, uint64_t n, bool
     std::vector<uint64_t> bins(kBins);
     hipLaunchKernelGGL(k_terminator_bits, dim3(capped_grid(bitmap_words, kThreads)), dim3(kThreads), 0, stream, d_text, bitmap_words, d_terminators);
     if ((e = hipMemsetAsync(d_bins, 0, kBins * 8, stream)) != hipSuccess) return failed("clearing the histogram");
-    hipLaunchKernelGGL(k_bin_histogram, dim3(capped_grid(total, kReadsSortTile, 1024)), dim3(kThreads), 0, stream, d_text, total, d_bins);
+    hipLaunchKernelGGL(k_bin_histogram, dim3(capped_grid(total, kBins, 1024)), dim3(kThreads), 0, stream, d_text, total, d_bins);
     if ((e = hipMemcpyAsync(bins.data(), d_bins, kBins * 8, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = lap(kStageHistogram)) != hipSuccess)
         return failed("the histogram of the suffixes");
     arena.give_back(d_bins);

@@ -8,8 +8,6 @@
 
 namespace msbwt {
 
-constexpr uint32_t kReadsSortTile = 4096;  // suffixes one workgroup ranks and scatters per radix pass
-
 // stages the builder times (host clock around a stream synchronisation at every stage border)
 enum ReadsBuildStage {
     kStageCopyIn = 0,   // reads and offsets to HBM

@@ -22,6 +22,7 @@
 #include "canonical_unitigs.hpp"
 #include "handle.hpp"
 #include "kmer_graph.hpp"
+#include "radix_sort.hpp"
 #include "run_encode.hpp"
 #include "source_spectrum.hpp"
 #include "spectrum.hpp"
@@ -741,7 +742,7 @@ uint64_t canonical_unitig_chunk_slots(uint64_t slots) { return std::min(slots, k
 // the numbering's tiles, both sets of counters, the edge bytes and the link bytes
 uint64_t canonical_unitig_fixed_bytes(uint64_t n) {
     const uint64_t slots = 2 * n;
-    return 32 * canonical_unitig_chunk_slots(slots) + 8 * canonical_unitig_hist_words(slots) + 8 * canonical_unitig_scan_words(slots) + unitig_tiles(slots) * kUnitigTileBytes +
+    return 32 * canonical_unitig_chunk_slots(slots) + 8 * radix_sort_hist_words(slots) + 8 * radix_sort_scan_words(slots) + unitig_tiles(slots) * kUnitigTileBytes +
            kUnitigFixedBytes + kCanonicalUnitigFixedBytes + 2 * graph_edge_words(slots) * 4;
 }
 
@@ -789,8 +790,8 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
             char *at = nullptr;
             if (int rc = stage_records(f, none, n, &unused, "for the nodes of the graph", n * kCanonicalUnitigClassBytes + canonical_unitig_fixed_bytes(n), &at)) return rc;
             uint64_t *cnt = reinterpret_cast<uint64_t *>(at), *keys_a = cnt + 4 * M, *vals_a = keys_a + M, *keys_b = vals_a + M, *vals_b = keys_b + M;
-            uint64_t *chunk = vals_b + M, *hist = chunk + 4 * chunk_slots, *scan = hist + canonical_unitig_hist_words(M);
-            char *tiles = reinterpret_cast<char *>(scan + canonical_unitig_scan_words(M));
+            uint64_t *chunk = vals_b + M, *hist = chunk + 4 * chunk_slots, *scan = hist + radix_sort_hist_words(M);
+            char *tiles = reinterpret_cast<char *>(scan + radix_sort_scan_words(M));
             unsigned long long *counters = reinterpret_cast<unsigned long long *>(tiles + unitig_tiles(M) * kUnitigTileBytes);
             unsigned long long *own_counters = counters + kUnitigFixedBytes / 8;
             uint32_t *edge_words = reinterpret_cast<uint32_t *>(own_counters + kCanonicalUnitigFixedBytes / 8), *link_words = edge_words + graph_edge_words(M);
@@ -819,7 +820,8 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
             if (own[kCanonicalUnitigSeconds] > n) return fail(h, MSBWT_ERR_INTERNAL, f.name + ": more second members than classes");
             const uint64_t N = n + own[kCanonicalUnitigSeconds];
             bool in_b = false;
-            HIP_TRY(h, canonical_unitig_sort(keys_a, vals_a, keys_b, vals_b, N, uint32_t(k), hist, scan, flags, f.stream, &in_b));
+            const uint32_t passes = (2 * uint32_t(k) + kRadixDigitBits - 1) / kRadixDigitBits;  // the bytes above 2k bits are zero in every key
+            HIP_TRY(h, radix_sort_passes(keys_a, vals_a, keys_b, vals_b, N, 0, passes, hist, scan, flags, f.stream, &in_b));
             const uint64_t *keys = in_b ? keys_b : keys_a, *vals = in_b ? vals_b : vals_a;
             uint64_t *pred = in_b ? keys_a : keys_b;
             HIP_TRY(h, hipMemsetAsync(pred, 0xFF, N * 8, f.stream));  // (no slot)

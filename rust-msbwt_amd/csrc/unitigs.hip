@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "slot_bytes.hpp"
 #include "unitigs.hpp"
 #include "workgroup.hpp"
 
@@ -20,20 +21,9 @@ namespace {
 constexpr int kThreads = 256;
 constexpr uint32_t kGridCap = 256u * 8u;
 constexpr uint32_t kPerThread = uint32_t(kUnitigTileSlots) / uint32_t(kThreads);
-constexpr unsigned long long kDistance = ~kUnitigDone;
 
-__device__ __forceinline__ uint32_t byte_of(const uint32_t *__restrict__ words, uint64_t slot) { return (words[slot >> 2] >> (8u * (uint32_t(slot) & 3u))) & 0xFFu; }
-__device__ __forceinline__ void set_link_bits(uint32_t *__restrict__ words, uint64_t slot, uint32_t bits) { atomicOr(words + (slot >> 2), bits << (8u * (uint32_t(slot) & 3u))); }
-__device__ __forceinline__ void clear_link_bits(uint32_t *__restrict__ words, uint64_t slot, uint32_t bits) { atomicAnd(words + (slot >> 2), ~(bits << (8u * (uint32_t(slot) & 3u)))); }
 // A C G T (0..3) -> the library's symbol codes 1 2 3 5
 __device__ __forceinline__ uint8_t code_of(uint64_t two_bits) { return uint8_t(two_bits == 3u ? 5u : two_bits + 1u); }
-
-// counters[at + j] += the workgroup's sum of v[j]; the whole workgroup calls it
-template <uint32_t N>
-__device__ __forceinline__ void add_to_counters(unsigned long long *__restrict__ counters, uint32_t at, const uint64_t (&v)[N]) {
-    const uint64_t s = block_vector_sum(v);
-    if (threadIdx.x < N && s) atomicAdd(counters + at + threadIdx.x, (unsigned long long)s);
-}
 
 __global__ __launch_bounds__(kThreads) void k_unitig_links(UnitigNodes g, UnitigState *__restrict__ state) {
     uint64_t sums[3] = {0, 0, 0}, unfinished[1] = {0};  // edges, links, circular: kUnitigEdges ..
@@ -48,11 +38,11 @@ __global__ __launch_bounds__(kThreads) void k_unitig_links(UnitigNodes g, Unitig
             } else if (__popc(byte_of(g.edge_words, p) >> 4) == 1) {
                 sums[1] += 1;
                 if (p == i) {  // A^k with A^(k+1) and nothing else: a cycle of one
-                    set_link_bits(g.link_words, i, kUnitigOnCycle);
+                    or_slot_bits(g.link_words, i, kUnitigOnCycle);
                     sums[2] += 1;
                 } else {
-                    set_link_bits(g.link_words, i, kUnitigLinkUp);
-                    set_link_bits(g.link_words, p, kUnitigLinkDown);
+                    or_slot_bits(g.link_words, i, kUnitigLinkUp);
+                    or_slot_bits(g.link_words, p, kUnitigLinkDown);
                     s = UnitigState{p, 1ull};
                     unfinished[0] += 1;
                 }
@@ -102,9 +92,9 @@ __global__ __launch_bounds__(kThreads) void k_unitig_cycle_cut(UnitigNodes g, Un
         if (s.y > i || p >= g.n) {  // (the smallest slot of a cycle is at most one's own)
             atomicOr(g.flags, kFlagInternal);
         } else if (s.y == i) {
-            clear_link_bits(g.link_words, i, kUnitigLinkUp);
-            clear_link_bits(g.link_words, p, kUnitigLinkDown);
-            set_link_bits(g.link_words, i, kUnitigOnCycle);
+            clear_slot_bits(g.link_words, i, kUnitigLinkUp);
+            clear_slot_bits(g.link_words, p, kUnitigLinkDown);
+            or_slot_bits(g.link_words, i, kUnitigOnCycle);
             state[i] = UnitigState{i, kUnitigDone};
             circular[0] += 1;
         } else {
@@ -129,11 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_unitig_tails(UnitigNodes g, const 
         heads[s.x].x = nodes;
         longest = nodes > longest ? nodes : longest;
     }
-#pragma unroll
-    for (uint32_t d = 32; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(longest, d);
-        longest = other > longest ? other : longest;
-    }
+    longest = wave_max(longest);
     if ((threadIdx.x & 63u) == 0u && longest) atomicMax(g.counters + kUnitigLongest, longest);
 }
 

@@ -21,6 +21,7 @@ namespace msbwt {
 constexpr uint64_t kUnitigTileSlots = 2048;   // slots a workgroup numbers at a time: 256 threads, 8 consecutive slots each
 constexpr uint64_t kUnitigFixedBytes = 256;   // the counters below, padded: zeroed by the caller
 constexpr uint64_t kUnitigDone = 1ull << 63;  // in a state's distance: the ancestor is the head
+constexpr uint64_t kDistance = ~kUnitigDone;  // the distance itself
 enum : uint32_t {                             // words of the counters
     kUnitigEdges = 0,    // in-edges of all nodes
     kUnitigLinks,        // edges p -> q with out(p) = 1 and in(q) = 1, a cycle's closing link and a self-loop included

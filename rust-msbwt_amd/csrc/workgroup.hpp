@@ -1,6 +1,6 @@
 // The wave and workgroup primitives of the device builders (loader, merges, encoder, builder from reads) and of the frontier
-// walks: launch arithmetic, wave sums, the workgroup prefix sum, the workgroup sum of a small vector, and the one-workgroup scan
-// of per-tile vectors.  Include from HIP translation units only (the names are per translation unit, as in frontier.hpp).
+// walks: launch arithmetic, wave sums and maxima, the workgroup prefix sum, the workgroup sum of a small vector (and its addition
+// to counters in HBM), and the one-workgroup scan of per-tile vectors.  Include from HIP translation units only (the names are per translation unit, as in frontier.hpp).
 // Integer only, and no instantiation needs scratch memory: every loop over waves or elements has a constant bound.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +35,17 @@ template <class T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (uint32_t d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// the largest v of the wave, in every lane
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (uint32_t d = 32; d > 0; d >>= 1) {
+        const T other = __shfl_xor(v, d);
+        v = other > v ? other : v;
+    }
     return v;
 }
 
@@ -75,6 +86,14 @@ __device__ __forceinline__ uint64_t block_vector_sum(const T (&v)[N]) {
 #pragma unroll
         for (uint32_t w = 0; w < kWaves; ++w) s += part[threadIdx.x][w];
     }
+    return s;
+}
+
+// counters[at + j] += the workgroup's sum of v[j], which thread j < N returns as block_vector_sum does; the whole workgroup calls it
+template <uint32_t N>
+__device__ __forceinline__ uint64_t add_to_counters(unsigned long long *__restrict__ counters, uint32_t at, const uint64_t (&v)[N]) {
+    const uint64_t s = block_vector_sum(v);
+    if (threadIdx.x < N && s) atomicAdd(counters + at + threadIdx.x, (unsigned long long)s);
     return s;
 }
 

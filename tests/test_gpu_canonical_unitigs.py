@@ -379,6 +379,24 @@ def test_read_sets_with_errors(k):
         assert err.value.code == _lib.ERR_INVALID_ARG and "min_edge" in str(err.value)
 
 
+@pytest.mark.parametrize("grid", [1, 3])
+@pytest.mark.parametrize("k", [17, 21, 31])  # 5, 6 and 8 radix passes: the sorted nodes end in the second pair of buffers (17) and in the first
+def test_sort_grid_cap_gives_the_same_unitigs(monkeypatch, k, grid):
+    """MSBWT_SORT_GRID caps the grids of the order step's passes (csrc/radix_sort.hip): a workgroup takes several tiles of 4096 slots"""
+    name = "plain_100"
+    _, rle, _ = both_strands(name)
+    want = both_strands_unitigs(name, k)
+    slots = 2 * want["info"]["classes"] - want["info"]["palindromes"]
+    assert slots > 4 * 4096  # more tiles than workgroups
+    b = loaded(rle)
+    monkeypatch.delenv("MSBWT_SORT_GRID", raising=False)
+    check_canonical(b, k, want)
+    unset = b.canonical_unitig_info()
+    monkeypatch.setenv("MSBWT_SORT_GRID", str(grid))
+    check_canonical(b, k, want)
+    assert b.canonical_unitig_info() == unset
+
+
 # ---- 5. chunks of the walk, and every index form ----
 
 def test_a_frontier_at_its_minimum_gives_the_same_bytes():

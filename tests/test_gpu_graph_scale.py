@@ -11,8 +11,9 @@ tests/test_graph_oracle.py holds to the string oracles of the neighbouring files
    524 288 slots (the second grid-stride trip of every slot-strided kernel), 1 048 576 canonical slots (the second chunk of the edge
    counting), 2 097 152 slots (the second round of k_scan_tile_sums<2>) and 4 194 304 slots (the second trip of k_unitig_tile_sums and
    k_unitig_number), a unitig of more than 524 288 nodes (20 rounds of pointer jumping and more), more than 1000 unitigs of several
-   nodes, more than 1000 branching nodes and a circular unitig.  The tile loops of k_sort_histogram and k_sort_scatter go round only
-   beyond 65 536 tiles, 2.7e8 slots: out of reach of a test of a few seconds, and not reached here.
+   nodes, more than 1000 branching nodes and a circular unitig.  The tile loops of k_sort_histogram and k_sort_scatter (csrc/radix_sort.hip) go
+   round only beyond 2^20 tiles, 4.3e9 slots; they are reached at toy sizes under MSBWT_SORT_GRID, by
+   test_gpu_canonical_unitigs.test_sort_grid_cap_gives_the_same_unitigs and test_gpu_reads_build.test_sort_grid_cap_*, not here.
 2. S x 4096 for S = copy_set(1 100 000, 11, ...), the "past it" set of tests/test_gpu_scaled_copies.py with a few reads put in (below):
    4 505 600 000 rows.  The graph of S x c under thresholds times c is the graph of S with the counts, count sums and range starts
    times c (tests/test_graph_oracle.py and tests/test_scaled_copies.py prove it), so the oracle runs on 1.1e6 rows.  In

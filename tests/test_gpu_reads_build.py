@@ -152,6 +152,40 @@ def test_wide_positions_give_the_same_bytes(monkeypatch):
     assert np.array_equal(b.build_from_reads(reads), expected)
 
 
+# ---- the sort's loop over tiles (csrc/radix_sort.hip): MSBWT_SORT_GRID caps its grids, so a workgroup takes several tiles ----
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("grid", [1, 7])  # plain_100: 404 000 suffixes, 99 tiles -- all in one workgroup; 14 or 15 a workgroup, the last one partial
+def test_sort_grid_cap_gives_the_same_bytes(monkeypatch, grid, wide):
+    reads, expected = read_set("plain_100")
+    assert -(-(reads[0].size + reads[1].size - 1) // msbwt.build_reads_sort_tile()) == 99
+    monkeypatch.setenv("MSBWT_SORT_GRID", str(grid))
+    if wide:
+        monkeypatch.setenv("MSBWT_BUILD_WIDE", "1")
+    b = msbwt.RleBWT(device=0)
+    assert np.array_equal(b.build_from_reads(reads), expected)
+    assert b.build_stage_ms()["pieces"] == 1
+
+
+def test_sort_grid_cap_over_many_small_pieces(monkeypatch):
+    reads, expected = read_set("plain_100")
+    monkeypatch.setenv("MSBWT_SORT_GRID", "1")
+    b = msbwt.RleBWT(device=0)
+    b.set_build_piece(1000)  # most pieces below one tile, the large bins a few tiles
+    assert np.array_equal(b.build_from_reads(reads), expected)
+    assert b.build_stage_ms()["pieces"] > 100
+
+
+@pytest.mark.parametrize("value", ["0", "abc"])
+def test_sort_grid_cap_that_does_not_parse_is_no_cap(monkeypatch, value):
+    reads, expected = read_set("plain_100")
+    monkeypatch.delenv("MSBWT_SORT_GRID", raising=False)
+    b = msbwt.RleBWT(device=0)
+    unset = b.build_from_reads(reads)
+    monkeypatch.setenv("MSBWT_SORT_GRID", value)
+    assert np.array_equal(b.build_from_reads(reads), unset) and np.array_equal(unset, expected)
+
+
 @pytest.mark.parametrize("delta", [-1, 0, 1])
 def test_suffix_counts_at_the_tile_border(bwt, delta):
     import synth
