@@ -1,0 +1,87 @@
+// Where the arrays of a graph or unitig call lie in its HBM blocks (spectrum.cpp, and nothing else, includes this).  One function per
+// block returns the byte offset of every array, the block's bytes and -- where the kernels want a tail of it zeroed -- where that tail
+// starts: a msbwt_*_plan and the hipMalloc take `bytes`, the call carves `base + field`, the memset runs from `zero_from` to `bytes`.
+// A struct lists its arrays in their order in HBM, and its function puts their extents down in that order: the n-th put() is the n-th
+// field.  hipMalloc aligns a block to 256 bytes; what precedes a 16-byte array is a multiple of 16, what precedes a 64-bit one of 8
+// (tests/cpp/graph_layouts.cpp holds every layout to that, and to no array reaching into the next).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+#include "canonical_unitigs.hpp"
+#include "kmer_graph.hpp"
+#include "radix_sort.hpp"
+#include "unitigs.hpp"
+
+namespace msbwt {
+
+static_assert(kGraphTableWords * 8 <= kGraphFixedBytes && kUnitigCounterWords * 8 <= kUnitigFixedBytes && kCanonicalUnitigCounterWords * 8 <= kCanonicalUnitigFixedBytes,
+              "the counters fit their padded sizes");
+static_assert(sizeof(UnitigState) == 16 && kUnitigTileBytes == 16, "two words a state, and a tile");
+
+struct LayoutCursor {
+    uint64_t bytes = 0;  // laid out so far
+    uint64_t put(uint64_t extent) { return (bytes += extent) - extent; }
+};
+
+// The tail of the graph call's block, behind the records a host dump stages: the degree counters, padded, and the edge words of n records.
+struct GraphTailLayout {
+    uint64_t table, edge_words, bytes, zero_from = table;
+};
+inline GraphTailLayout graph_tail_layout(uint64_t n) {
+    LayoutCursor c;
+    return {c.put(kGraphFixedBytes), c.put(4 * graph_edge_words(n)), c.bytes};
+}
+
+// The nodes of the unitig call, n slots: the ranking's two buffers of states, the edge pass's words, counts and predecessor slots, the
+// numbering's tiles, the counters, padded, and a byte a slot of edges and of links.
+struct UnitigNodeLayout {
+    uint64_t states[2], kmers, counts, pred, tiles, counters, edge_words, link_words, bytes, zero_from = counters;
+};
+inline UnitigNodeLayout unitig_node_layout(uint64_t n) {
+    LayoutCursor c;
+    return {{c.put(16 * n), c.put(16 * n)}, c.put(8 * n), c.put(8 * n), c.put(8 * n), c.put(unitig_tiles(n) * kUnitigTileBytes), c.put(kUnitigFixedBytes),
+            c.put(4 * graph_edge_words(n)), c.put(4 * graph_edge_words(n)), c.bytes};
+}
+
+// The nodes of the canonical unitig call: n classes, M = 2 n slots of which the N <= M that doubling fills are used.
+//   cnt                 4 M words: cnt[4 slot + c]
+//   pairs               the sort's two (keys, payloads), M words an array
+//   chunk               the four (k+1)-mer words of chunk_slots nodes at a time
+//   hist .. link_words  the sort's histogram and scan, the numbering's tiles, the compaction's counters and this call's own, both
+//                       padded, a byte a slot of edges and of links
+// and, each inside what it is written over:
+//   classes[3]          the walk's records (word, own, other), n words a column, at the start of cnt until doubling has read them
+//   states              2 M states over cnt once the fold has read it; the ranking's second buffer starts N states in
+//   pred[p]             M words, where the sort left its result in pair p: the keys of the other pair
+struct CanonicalUnitigLayout {
+    struct Pair {
+        uint64_t keys, vals;
+    };
+    uint64_t cnt;
+    Pair pairs[2];
+    uint64_t chunk, hist, scan, tiles, counters, own_counters, edge_words, link_words, bytes, zero_from = counters;
+    uint64_t chunk_slots = 0, classes[3] = {}, states = cnt, pred[2] = {pairs[1].keys, pairs[0].keys};
+};
+inline CanonicalUnitigLayout canonical_unitig_layout(uint64_t n) {
+    const uint64_t M = 2 * n, chunk_slots = std::min(M, kCanonicalUnitigChunkSlots);
+    LayoutCursor c;
+    CanonicalUnitigLayout l{c.put(32 * M), {{c.put(8 * M), c.put(8 * M)}, {c.put(8 * M), c.put(8 * M)}}, c.put(32 * chunk_slots), c.put(8 * radix_sort_hist_words(M)),
+                            c.put(8 * radix_sort_scan_words(M)), c.put(unitig_tiles(M) * kUnitigTileBytes), c.put(kUnitigFixedBytes), c.put(kCanonicalUnitigFixedBytes),
+                            c.put(4 * graph_edge_words(M)), c.put(4 * graph_edge_words(M)), c.bytes};
+    l.chunk_slots = chunk_slots;
+    for (uint64_t column = 0; column < 3; ++column) l.classes[column] = l.cnt + column * 8 * n;
+    return l;
+}
+
+// The outputs of either unitig call, U unitigs of S symbols: the offsets (U + 1 words, padded), then whichever of the other four
+// columns a host form stages, a byte column padded to whole words -- a column that is not staged takes no room.
+struct UnitigOutputLayout {
+    uint64_t offsets, sums, symbols, ends, flags, bytes;
+};
+inline UnitigOutputLayout unitig_output_layout(uint64_t U, uint64_t S, bool sums, bool symbols, bool ends, bool flags) {
+    LayoutCursor c;
+    return {c.put(8 * U + 256), c.put(sums ? 8 * U : 0), c.put(symbols ? (S + 7) / 8 * 8 : 0), c.put(ends ? (U + 7) / 8 * 8 : 0), c.put(flags ? (U + 7) / 8 * 8 : 0), c.bytes};
+}
+
+}  // namespace msbwt

@@ -1,18 +1,22 @@
-// The k-mer walk calls of a loaded index, four families of three: the abundance spectrum, the k-mer dump in its host and its device
-// form (the graph: and the degree table) of the plain k-mers (spectrum.hpp), of a k-mer and its reverse complement as one class
-// (canonical.hpp; the other strand is counted by query.cpp's packed search), of the k-mers by source of a merged index
-// (source_spectrum.hpp) and of the k-mer graph (kmer_graph.hpp) -- and the unitigs that graph compacts into (unitigs.hpp: the graph's
-// walks into scratch, then kernels over its slots; canonical_unitigs.hpp: the same compaction over both members of every canonical
-// class).  The kernels are behind those headers; this file is the host side, and
+// The k-mer walk calls of a loaded index, six families.  Four of three calls each -- the abundance spectrum, the k-mer dump in its host
+// and its device form (the graph: and the degree table): the plain k-mers (spectrum.hpp), a k-mer and its reverse complement as one
+// class (canonical.hpp; the other strand is counted by query.cpp's packed search), the k-mers by source of a merged index
+// (source_spectrum.hpp) and the k-mer graph (kmer_graph.hpp).  Two of two, a host and a device form: the unitigs that graph compacts
+// into (unitigs.hpp: the graph's walks into scratch, then kernels over its slots) and the canonical unitigs (canonical_unitigs.hpp: the
+// same compaction over both members of every canonical class).  The kernels are behind those headers; this file is the host side, and
 // what the calls share is written once:
 //   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
 //                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
 //                 the one name the call passes, every text it can say
 //   Shape         what a family allocates: its msbwt_*_plan and the sufficiency check of take_scratch are the same sum over it
+//   layouts       graph_layouts.hpp: where the arrays of the graph's and the unitigs' blocks lie -- the plan takes a layout's bytes, the
+//                 call carves base + field, the memset runs over the span it names; nothing here adds up a block of its own
 //   two_pass      a dump: the counting pass, *out_n, the capacity pattern, the filling pass, the record after either
 //   stage_records / copy_out   the columns of a dump: the caller's device arrays, or one staged block carved up and copied out
 //   staged_walk   a walk whose chunks go to a sink behind it (canonical, by source, the graph's edge pass)
 //   spectrum      a spectrum: the histograms zeroed, taken, walked into and copied out
+//   GraphCut / graph_edge_walk   the thresholds of the three graph calls and their staged walk with the edge pass behind it
+//   rank_unitigs / UnitigOutputs   the compaction both unitig calls run over their slots, and their outputs from guard to delivery
 // A body below is what is left: its argument checks, its sink, and the order of its passes.
 #include <algorithm>
 #include <chrono>
@@ -20,6 +24,7 @@
 
 #include "canonical.hpp"
 #include "canonical_unitigs.hpp"
+#include "graph_layouts.hpp"
 #include "handle.hpp"
 #include "kmer_graph.hpp"
 #include "radix_sort.hpp"
@@ -47,7 +52,7 @@ struct Shape {
 Shape plain_shape(bool rank) { return Shape{rank, false, 0, kRecordBytes}; }
 constexpr Shape kCanonicalShape{false, true, 0, kRecordBytes};  // (its totals, 256 bytes more, are in no plan)
 Shape by_source_shape(bool rank, uint64_t n_sources) { return Shape{rank, false, kSourceSinkFixedBytes, (2 + n_sources) * sizeof(uint64_t)}; }
-Shape graph_shape(bool fill) { return Shape{fill, false, fill ? kGraphFixedBytes : 0, kRecordBytes}; }  // (and the edge words of its records)
+Shape graph_shape(bool fill) { return Shape{fill, false, fill ? graph_tail_layout(0).bytes : 0, kRecordBytes}; }  // (fixed: the tail of no records)
 
 uint64_t shape_bytes(const Shape &p, uint64_t total_rows, uint64_t frontier, uint64_t records) {
     return spectrum_work_bytes(frontier) + (p.rank ? spectrum_rank_bytes(total_rows) : 0) + (p.canonical ? frontier * kCanonicalStageBytes : 0) + p.fixed +
@@ -149,6 +154,8 @@ struct Frame {
         }
         return MSBWT_OK;
     }
+    // a block on top of the scratch, asked for only where the device says it has that much free
+    int take_more(char **block, uint64_t bytes, const char *for_what) { return take(block, bytes, needs(bytes, true, for_what), true); }
 };
 
 // where the walk starts: the flat direct table when it is shallower than k, else the root
@@ -209,7 +216,7 @@ int stage_records(Frame &f, Column (&cols)[N], uint64_t n, uint64_t *capacity, c
     const uint64_t bytes = n * words * 8 + tail_bytes;
     if (bytes == 0) return MSBWT_OK;
     char *block = nullptr;
-    if (int rc = f.take(&block, bytes, f.needs(bytes, true, for_what), true)) return rc;
+    if (int rc = f.take_more(&block, bytes, for_what)) return rc;
     if (tail) *tail = block + n * words * 8;
     if (!f.host) return MSBWT_OK;
     uint64_t *next = reinterpret_cast<uint64_t *>(block);
@@ -472,56 +479,67 @@ int enumerate_by_source(const msbwt_rle *bwt, size_t k, const uint64_t *min_coun
 
 // ---- the k-mer graph ----
 
+// What the graph and both unitig calls take for a node and for an edge: a k-mer at least m wide, a (k+1)-mer at least me.
+struct GraphCut {
+    uint64_t m, me;
+    GraphCut(uint64_t min_count, uint64_t min_edge) : m(std::max<uint64_t>(min_count, 1)), me(min_edge ? min_edge : m) {}
+    // the calls' own rung of the guard ladder: the thresholds, then the output no call can do without
+    int check(const Frame &f, const void *needed) const {
+        if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
+        return !needed ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
+    }
+};
+
+// an array of a block, at the offset its layout gives (graph_layouts.hpp)
+template <class T>
+T *in(char *block, uint64_t offset) {
+    return reinterpret_cast<T *>(block + offset);
+}
+
+// the sorted dump's counting walk: the scratch of `p`, *n = the nodes, and with p.rank the bit of every node's l
+int count_nodes(Frame &f, const Shape &p, const GraphCut &cut, uint64_t *n) {
+    if (int rc = take_scratch(f, p)) return rc;
+    HIP_TRY(f.h, spectrum_count(view_of(f.h), seeds_of(f), uint32_t(f.k), cut.m, 0, f.work, f.frontier, f.rank, n, &f.info, f.stream));
+    return MSBWT_OK;
+}
+
+// The staged walk with the edge pass behind it: the n nodes' columns (each optional) at the rank of their l, their edge bytes ORed into
+// edge_words (zeroed by the caller) and, where pred is given, the slot of a predecessor.
+int graph_edge_walk(Frame &f, const GraphCut &cut, uint64_t n, uint32_t *edge_words, uint64_t *kmers, uint64_t *counts, uint64_t *l, uint64_t *pred) {
+    const IndexView v = view_of(f.h);
+    const SpectrumRank r = spectrum_rank_view(f.rank, f.h->totals.total);
+    const GraphSink sink{r.bitmap, r.prefix, edge_words, n, cut.me, kmers, counts, l, f.h->d_flags + f.which, pred};
+    return staged_walk(f, cut.m, nullptr, 0, nullptr, [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, f.stream); });
+}
+
 // The dump (both forms) and the degree table (table != nullptr: no record outputs, *out_n = the nodes, *out_edge_count = the edges):
 // the sorted dump's counting walk, then the staged walk with the edge pass behind it.
 int kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_kmers, void *out_counts, void *out_l, void *out_edges,
                uint64_t capacity, uint64_t *out_n, uint64_t *table, uint64_t *out_edge_count, hipStream_t stream) {
     const bool degrees = table != nullptr;
     Frame f(bwt, degrees ? "kmer_graph_degrees" : "enumerate_kmer_graph", k, host, stream);
-    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
-    if (int rc = f.open(false, [&] {
-            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
-            return !degrees && !out_n ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
-        }))
-        return rc;
+    const GraphCut cut(min_count, min_edge);
+    if (int rc = f.open(false, [&] { return cut.check(f, degrees ? table : out_n); })) return rc;
     msbwt_rle *h = f.h;
     if (out_edge_count) *out_edge_count = 0;
     if (degrees) std::fill(table, table + kGraphTableWords, 0ull);
     const bool fill = degrees || capacity != 0;  // (the degree table has no capacity to fall short)
-    const IndexView v = view_of(h);
     Column cols[] = {{out_kmers}, {out_counts}, {out_l}};
-    uint64_t *d_table = nullptr;
-    uint32_t *edge_words = nullptr;
+    GraphTailLayout at{};
+    char *tail = nullptr;
     return two_pass(
-        f, degrees ? ~0ull : capacity, out_n, "k-mers", false,
-        [&](uint64_t *n) -> int {
-            if (int rc = take_scratch(f, graph_shape(fill))) return rc;
-            HIP_TRY(h, spectrum_count(v, seeds_of(f), uint32_t(k), m, 0, f.work, f.frontier, f.rank, n, &f.info, f.stream));
-            return MSBWT_OK;
+        f, degrees ? ~0ull : capacity, out_n, "k-mers", false, [&](uint64_t *n) { return count_nodes(f, graph_shape(fill), cut, n); },
+        [&](uint64_t n) -> int {
+            // one allocation: the records staged for a host dump, and graph_tail_layout behind them
+            at = graph_tail_layout(n);
+            if (int rc = stage_records(f, cols, n, &capacity, "for the edge bytes and the records", at.bytes, &tail)) return rc;
+            HIP_TRY(h, hipMemsetAsync(tail + at.zero_from, 0, at.bytes - at.zero_from, f.stream));
+            return graph_edge_walk(f, cut, n, in<uint32_t>(tail, at.edge_words), cols[0].at, cols[1].at, cols[2].at, nullptr);
         },
         [&](uint64_t n) -> int {
-            // one allocation: the records staged for a host dump | the degree counters | the edge words
-            const uint64_t edge_bytes = graph_edge_words(n) * 4;
-            char *tail = nullptr;
-            if (int rc = stage_records(f, cols, n, &capacity, "for the edge bytes and the records", kGraphFixedBytes + edge_bytes, &tail)) return rc;
-            d_table = reinterpret_cast<uint64_t *>(tail);
-            edge_words = reinterpret_cast<uint32_t *>(tail + kGraphFixedBytes);
-            HIP_TRY(h, hipMemsetAsync(d_table, 0, kGraphFixedBytes + edge_bytes, f.stream));
-            const SpectrumRank r = spectrum_rank_view(f.rank, h->totals.total);
-            GraphSink sink{};
-            sink.bitmap = r.bitmap;
-            sink.prefix = r.prefix;
-            sink.edge_words = edge_words;
-            sink.n = n;
-            sink.min_edge = me;
-            sink.flags = h->d_flags + f.which;
-            sink.kmers = cols[0].at;
-            sink.counts = cols[1].at;
-            sink.l = cols[2].at;
-            return staged_walk(f, m, nullptr, 0, nullptr, [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, f.stream); });
-        },
-        [&](uint64_t n) -> int {
+            const uint32_t *edge_words = in<uint32_t>(tail, at.edge_words);
             if (degrees) {
+                uint64_t *d_table = in<uint64_t>(tail, at.table);
                 HIP_TRY(h, launch_graph_degrees(edge_words, n, d_table, f.stream));
                 HIP_TRY(h, hipMemcpyAsync(table, d_table, kGraphTableWords * 8, hipMemcpyDeviceToHost, f.stream));
                 if (int rc = status_of(h, f.stream, f.which)) return rc;  // synchronises
@@ -538,21 +556,31 @@ int kmer_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_
 
 // ---- unitigs ----
 
-constexpr uint64_t kUnitigNodeBytes = 2 * sizeof(UnitigState) + 3 * sizeof(uint64_t);  // two states; word, count and predecessor slot
-constexpr Shape kUnitigShape{true, false, 0, kUnitigNodeBytes};
-static_assert(kUnitigNodeBytes == 56 && kUnitigCounterWords * 8 <= kUnitigFixedBytes && MSBWT_UNITIG_INFO_WORDS == 8, "the header's plan and constants");
+// the walks of either call; its nodes (unitig_node_layout, canonical_unitig_layout) and outputs (unitig_output_layout) come on top
+constexpr Shape kUnitigShape{true, false, 0, 0};
+constexpr Shape kCanonicalUnitigShape{false, true, kCanonicalTotalWords * 8 < 256 ? 256 : kCanonicalTotalWords * 8, 0};  // (fixed: the walk's totals)
+static_assert(MSBWT_UNITIG_INFO_WORDS == 8 && MSBWT_CANONICAL_UNITIG_INFO_WORDS == 10, "the header's constants");
 
-uint64_t pad8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
-// what the compaction keeps beside the 56 bytes per node: the scan's tiles, the counters, the edge bytes and the link bytes
-uint64_t unitig_fixed_bytes(uint64_t n) { return unitig_tiles(n) * kUnitigTileBytes + kUnitigFixedBytes + 2 * graph_edge_words(n) * 4; }
-// the second allocation of a call that fills buffers: the offsets, and what a host form stages of sums, symbols, ends and flags
-uint64_t unitig_out_bytes(uint64_t U, uint64_t S, bool sums, bool symbols, bool ends, bool flags) {
-    return 8 * U + 256 + (sums ? 8 * U : 0) + (symbols ? pad8(S) : 0) + (ends ? pad8(U) : 0) + (flags ? pad8(U) : 0);
+// a msbwt_[canonical_]unitigs_plan: the walks of `p`, `node_bytes` over `nodes` nodes or classes and, unless it is the counting call
+// (unitigs = symbols = 0), the outputs with all four columns staged
+int unitigs_plan(const Shape &p, uint64_t node_bytes, uint64_t total_rows, uint64_t free_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {
+    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 32 n + n)
+    const uint64_t out = unitigs || symbols ? unitig_output_layout(unitigs, symbols, true, true, true, true).bytes : 0;
+    return plan(p, total_rows, free_bytes, nodes, node_bytes + out, device_bytes);
 }
+
 uint64_t ceil_log2(uint64_t x) {
     uint64_t r = 0;
     while (r < 63 && (1ull << r) < x) ++r;
     return r;
+}
+
+// a kernel's counters on the host (synchronises)
+template <size_t N>
+int read_counters(Frame &f, const unsigned long long *d_counters, uint64_t (&c)[N]) {
+    HIP_TRY(f.h, hipMemcpyAsync(c, d_counters, sizeof c, hipMemcpyDeviceToHost, f.stream));
+    HIP_TRY(f.h, hipStreamSynchronize(f.stream));
+    return MSBWT_OK;
 }
 
 // Links, ranking, cycles and tails over the slots of g (unitigs.hpp): every node of `cur` ends with its head and its distance,
@@ -561,11 +589,7 @@ uint64_t ceil_log2(uint64_t x) {
 template <class AfterLinks>
 int rank_unitigs(Frame &f, const UnitigNodes &g, UnitigState *&cur, UnitigState *&other, uint64_t (&c)[kUnitigCounterWords], uint64_t *rounds, AfterLinks &&after_links) {
     msbwt_rle *h = f.h;
-    const auto read_counters = [&]() -> int {  // synchronises
-        HIP_TRY(h, hipMemcpyAsync(c, g.counters, sizeof c, hipMemcpyDeviceToHost, f.stream));
-        HIP_TRY(h, hipStreamSynchronize(f.stream));
-        return MSBWT_OK;
-    };
+    const auto read = [&] { return read_counters(f, g.counters, c); };
     // Ranking rounds until none is unfinished, `cap` at the most.  A round that finishes nobody ends them too: on every path
     // the unfinished node nearest the head has a finished ancestor, so what is left then lies on cycles.
     const auto rank = [&](uint64_t cap) -> int {
@@ -575,14 +599,14 @@ int rank_unitigs(Frame &f, const UnitigNodes &g, UnitigState *&cur, UnitigState 
             HIP_TRY(h, launch_unitig_jump(g, cur, other, f.stream));
             std::swap(cur, other);
             ++*rounds;
-            if (int rc = read_counters()) return rc;
+            if (int rc = read()) return rc;
             if (c[kUnitigUnfinished] == before) break;
         }
         return MSBWT_OK;
     };
     HIP_TRY(h, launch_unitig_links(g, cur, f.stream));
     if (int rc = after_links()) return rc;
-    if (int rc = read_counters()) return rc;
+    if (int rc = read()) return rc;
     if (int rc = rank(ceil_log2(g.n) + 1)) return rc;
     if (const uint64_t on_cycles = c[kUnitigUnfinished]) {
         // a cycle has at most on_cycles nodes: after ceil(log2) rounds every label is its cycle's smallest slot
@@ -593,16 +617,17 @@ int rank_unitigs(Frame &f, const UnitigNodes &g, UnitigState *&cur, UnitigState 
         }
         HIP_TRY(h, hipMemsetAsync(g.counters + kUnitigUnfinished, 0, 8, f.stream));
         HIP_TRY(h, launch_unitig_cycle_cut(g, cur, f.stream));
-        if (int rc = read_counters()) return rc;
+        if (int rc = read()) return rc;
         if (int rc = rank(ceil_log2(on_cycles) + 1)) return rc;
     }
     HIP_TRY(h, launch_unitig_tails(g, cur, other, f.stream));
-    return read_counters();
+    return read();
 }
 
-// The outputs of a unitig call, plain or canonical, once U and S are known: *out_unitigs and *out_symbol_total, the capacity contract,
-// the second allocation -- offsets | sums | symbols | ends | flags, the last four only where a host form stages them --, numbering and
-// emission (skip_marked: heads carry kUnitigSkip), and the delivery.
+// The outputs of a unitig call, plain or canonical.  open(): the frame's guard ladder with the call's own checks (args) and the
+// thresholds' in it, then zeros in *out_unitigs, *out_symbol_total and the handle's info words.  emit(), once U and S are known:
+// *out_unitigs and *out_symbol_total, the capacity contract, the second allocation (unitig_output_layout: the offsets, and the other
+// four columns where a host form stages them), numbering and emission (skip_marked: heads carry kUnitigSkip).  deliver(): the copies.
 struct UnitigOutputs {
     void *symbols, *offsets, *sums, *ends, *flags;
     uint64_t capacity_unitigs, capacity_symbols;
@@ -611,6 +636,16 @@ struct UnitigOutputs {
     bool filled = false;
     uint64_t *d_offsets = nullptr, *d_sums = nullptr;
     uint8_t *d_symbols = nullptr, *d_ends = nullptr, *d_flags = nullptr;
+
+    template <size_t W, class Args>
+    int open(Frame &f, const GraphCut &cut, uint64_t (msbwt_rle::*info)[W], Args &&args) const {
+        const auto checks = [&] { const int rc = args(); return rc ? rc : cut.check(f, out_unitigs); };
+        if (int rc = f.open(false, checks)) return rc;
+        *out_unitigs = 0;
+        if (out_symbol_total) *out_symbol_total = 0;
+        std::fill(f.h->*info, f.h->*info + W, 0ull);
+        return MSBWT_OK;
+    }
 
     int emit(Frame &f, const UnitigNodes &g, const UnitigState *state, UnitigState *heads, void *tiles, uint64_t unitigs, uint64_t total, bool skip_marked) {
         msbwt_rle *h = f.h;
@@ -624,22 +659,15 @@ struct UnitigOutputs {
             return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the U = " +
                             std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols");
         const bool stage_sums = host && sums, stage_symbols = host && symbols, stage_ends = host && ends, stage_flags = host && flags;
-        Column none[] = {{nullptr}};
-        uint64_t unused = 0;
-        char *at = nullptr;
-        if (int rc = stage_records(f, none, 0, &unused, "for the unitigs", unitig_out_bytes(U, S, stage_sums, stage_symbols, stage_ends, stage_flags), &at)) return rc;
-        // a device form's outputs are the caller's own; a staged one is carved off `at`
-        const auto carve = [&](void *out, bool stage, uint64_t bytes) -> void * {
-            if (!stage) return out;
-            char *here = at;
-            at += bytes;
-            return here;
-        };
-        d_offsets = static_cast<uint64_t *>(carve(nullptr, true, 8 * U + 256));
-        d_sums = static_cast<uint64_t *>(carve(sums, stage_sums, 8 * U));
-        d_symbols = static_cast<uint8_t *>(carve(symbols, stage_symbols, pad8(S)));
-        d_ends = static_cast<uint8_t *>(carve(ends, stage_ends, pad8(U)));
-        d_flags = static_cast<uint8_t *>(carve(flags, stage_flags, pad8(U)));
+        const UnitigOutputLayout at = unitig_output_layout(U, S, stage_sums, stage_symbols, stage_ends, stage_flags);
+        char *block = nullptr;
+        if (int rc = f.take_more(&block, at.bytes, "for the unitigs")) return rc;
+        // a device form's outputs are the caller's own; a staged one has its place in the block
+        d_offsets = in<uint64_t>(block, at.offsets);
+        d_sums = static_cast<uint64_t *>(stage_sums ? block + at.sums : sums);
+        d_symbols = static_cast<uint8_t *>(stage_symbols ? block + at.symbols : symbols);
+        d_ends = static_cast<uint8_t *>(stage_ends ? block + at.ends : ends);
+        d_flags = static_cast<uint8_t *>(stage_flags ? block + at.flags : flags);
         if (d_sums) HIP_TRY(h, hipMemsetAsync(d_sums, 0, 8 * U, f.stream));
         HIP_TRY(h, launch_unitig_number(g, heads, tiles, uint32_t(f.k), U, S, d_offsets, f.stream));
         HIP_TRY(h, launch_unitig_emit(g, state, heads, uint32_t(f.k), U, S, d_symbols, d_sums, d_ends, d_flags, f.stream, skip_marked));
@@ -668,83 +696,37 @@ struct UnitigOutputs {
 int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums, void *out_ends,
             void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total, hipStream_t stream) {
     Frame f(bwt, "enumerate_unitigs", k, host, stream);
-    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
-    if (int rc = f.open(false, [&] {
-            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
-            return !out_unitigs ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
-        }))
-        return rc;
-    msbwt_rle *h = f.h;
-    *out_unitigs = 0;
-    if (out_symbol_total) *out_symbol_total = 0;
-    std::fill(h->unitig_info, h->unitig_info + MSBWT_UNITIG_INFO_WORDS, 0ull);
-    const IndexView v = view_of(h);
-    Column none[] = {{nullptr}};  // (both allocations are all tail)
-    uint64_t unused = 0, U = 0, S = 0;
+    const GraphCut cut(min_count, min_edge);
     UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
+    if (int rc = out.open(f, cut, &msbwt_rle::unitig_info, [] { return int(MSBWT_OK); })) return rc;
+    msbwt_rle *h = f.h;
     return two_pass(
-        f, ~0ull, nullptr, "k-mers", false,
-        [&](uint64_t *n) -> int {
-            if (int rc = take_scratch(f, kUnitigShape)) return rc;
-            HIP_TRY(h, spectrum_count(v, seeds_of(f), uint32_t(k), m, 0, f.work, f.frontier, f.rank, n, &f.info, f.stream));
-            return MSBWT_OK;
-        },
+        f, ~0ull, nullptr, "k-mers", false, [&](uint64_t *n) { return count_nodes(f, kUnitigShape, cut, n); },
         [&](uint64_t n) -> int {
-            // one allocation: state | state | words | counts | predecessor slots | tiles | counters | edge words | link words
-            char *at = nullptr;
-            if (int rc = stage_records(f, none, n, &unused, "for the nodes of the graph", n * kUnitigNodeBytes + unitig_fixed_bytes(n), &at)) return rc;
-            UnitigState *cur = reinterpret_cast<UnitigState *>(at), *other = cur + n;
-            uint64_t *kmers = reinterpret_cast<uint64_t *>(other + n), *counts = kmers + n, *pred = counts + n;
-            char *tiles = reinterpret_cast<char *>(pred + n);
-            unsigned long long *counters = reinterpret_cast<unsigned long long *>(tiles + unitig_tiles(n) * kUnitigTileBytes);
-            uint32_t *edge_words = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(counters) + kUnitigFixedBytes), *link_words = edge_words + graph_edge_words(n);
-            HIP_TRY(h, hipMemsetAsync(counters, 0, kUnitigFixedBytes + 2 * graph_edge_words(n) * 4, f.stream));
+            const UnitigNodeLayout at = unitig_node_layout(n);
+            char *block = nullptr;
+            if (int rc = f.take_more(&block, at.bytes, "for the nodes of the graph")) return rc;
+            UnitigState *cur = in<UnitigState>(block, at.states[0]), *other = in<UnitigState>(block, at.states[1]);
+            uint64_t *kmers = in<uint64_t>(block, at.kmers), *counts = in<uint64_t>(block, at.counts), *pred = in<uint64_t>(block, at.pred);
+            uint32_t *edge_words = in<uint32_t>(block, at.edge_words);
+            HIP_TRY(h, hipMemsetAsync(block + at.zero_from, 0, at.bytes - at.zero_from, f.stream));
             HIP_TRY(h, hipMemsetAsync(pred, 0xFF, n * 8, f.stream));  // (no slot)
-            const SpectrumRank r = spectrum_rank_view(f.rank, h->totals.total);
-            GraphSink sink{};
-            sink.bitmap = r.bitmap;
-            sink.prefix = r.prefix;
-            sink.edge_words = edge_words;
-            sink.n = n;
-            sink.min_edge = me;
-            sink.flags = h->d_flags + f.which;
-            sink.kmers = kmers;
-            sink.counts = counts;
-            sink.pred_slot = pred;
-            if (int rc = staged_walk(f, m, nullptr, 0, nullptr, [&](const void *d_nodes, uint64_t nodes) { return launch_graph_edges(v, d_nodes, nodes, sink, f.stream); }))
-                return rc;
+            if (int rc = graph_edge_walk(f, cut, n, edge_words, kmers, counts, nullptr, pred)) return rc;
 
-            const UnitigNodes g{n, kmers, counts, pred, edge_words, link_words, counters, sink.flags};
+            const UnitigNodes g{n, kmers, counts, pred, edge_words, in<uint32_t>(block, at.link_words), in<unsigned long long>(block, at.counters), h->d_flags + f.which};
             uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
             if (int rc = rank_unitigs(f, g, cur, other, c, &rounds, [] { return int(MSBWT_OK); })) return rc;
             if (c[kUnitigUnfinished] || c[kUnitigLinks] > n + c[kUnitigCircular] || c[kUnitigCircular] > n)
                 return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the ranking left " + std::to_string(c[kUnitigUnfinished]) + " nodes without a head");
-            U = n - c[kUnitigLinks] + c[kUnitigCircular];
-            S = n + U * (k - 1);
+            const uint64_t U = n - c[kUnitigLinks] + c[kUnitigCircular], S = n + U * (k - 1);
             const uint64_t info[MSBWT_UNITIG_INFO_WORDS] = {n, c[kUnitigEdges], c[kUnitigLinks], U, S, c[kUnitigCircular], c[kUnitigLongest], rounds};
             std::copy(info, info + MSBWT_UNITIG_INFO_WORDS, h->unitig_info);
-            return out.emit(f, g, cur, other, tiles, U, S, false);
+            return out.emit(f, g, cur, other, block + at.tiles, U, S, false);
         },
         [&](uint64_t) { return out.deliver(f); });
 }
 
 // ---- canonical unitigs ----
-
-// per class: two slots of (four counts, later two states) and of the sort's (key, payload) twice over: 2 x (32 + 32) bytes
-constexpr uint64_t kCanonicalUnitigClassBytes = 128;
-constexpr uint64_t kCanonicalUnitigInfoWords = MSBWT_CANONICAL_UNITIG_INFO_WORDS;
-constexpr Shape kCanonicalUnitigShape{false, true, kCanonicalTotalWords * 8 < 256 ? 256 : kCanonicalTotalWords * 8, kCanonicalUnitigClassBytes};  // (fixed: the walk's totals)
-static_assert(4 * sizeof(uint64_t) == 2 * sizeof(UnitigState) && kCanonicalUnitigCounterWords * 8 <= kCanonicalUnitigFixedBytes && kCanonicalUnitigInfoWords == 10,
-              "the header's plan and constants");
-
-uint64_t canonical_unitig_chunk_slots(uint64_t slots) { return std::min(slots, kCanonicalUnitigChunkSlots); }
-// what the call keeps beside the 128 bytes per class, over 2 n slots: the (k+1)-mer words of a chunk, the sort's histogram and scan,
-// the numbering's tiles, both sets of counters, the edge bytes and the link bytes
-uint64_t canonical_unitig_fixed_bytes(uint64_t n) {
-    const uint64_t slots = 2 * n;
-    return 32 * canonical_unitig_chunk_slots(slots) + 8 * radix_sort_hist_words(slots) + 8 * radix_sort_scan_words(slots) + unitig_tiles(slots) * kUnitigTileBytes +
-           kUnitigFixedBytes + kCanonicalUnitigFixedBytes + 2 * graph_edge_words(slots) * 4;
-}
 
 // Both forms: the canonical walk counts the classes and then appends them; both members of every class become nodes in word order;
 // the (k+1)-mers out of every node are counted and folded into D's edge bytes; then the compaction of the plain call over the N
@@ -753,26 +735,18 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
                       void *out_ends, void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total,
                       hipStream_t stream) {
     Frame f(bwt, "enumerate_canonical_unitigs", k, host, stream);
-    const uint64_t m = std::max<uint64_t>(min_count, 1), me = min_edge ? min_edge : m;
-    if (int rc = f.open(false, [&] {
-            if (k > 31) return f.refuse(" needs 1 <= k <= 31 (an edge is a packed (k+1)-mer)");
-            if (me < m) return f.refuse(": min_edge is below the node threshold (0 = the node threshold)");
-            return !out_unitigs ? fail(f.h, MSBWT_ERR_INVALID_ARG, "null pointer") : int(MSBWT_OK);
-        }))
+    const GraphCut cut(min_count, min_edge);
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
+    if (int rc = out.open(f, cut, &msbwt_rle::canonical_unitig_info,
+                          [&] { return k > 31 ? f.refuse(" needs 1 <= k <= 31 (an edge is a packed (k+1)-mer)") : int(MSBWT_OK); }))
         return rc;
     msbwt_rle *h = f.h;
-    *out_unitigs = 0;
-    if (out_symbol_total) *out_symbol_total = 0;
-    std::fill(h->canonical_unitig_info, h->canonical_unitig_info + kCanonicalUnitigInfoWords, 0ull);
     CanonicalSink classes{};
     classes.mode = kCanonicalCount;
-    classes.min = m;
+    classes.min = cut.m;
     classes.max = ~0ull;
-    const uint64_t prune = m / 2 + m % 2;  // (enumerate_canonical: the member that emits a class has at least half of its count)
+    const uint64_t prune = cut.m / 2 + cut.m % 2;  // (enumerate_canonical: the member that emits a class has at least half of its count)
     uint64_t totals[kCanonicalTotalWords] = {};
-    Column none[] = {{nullptr}};
-    uint64_t unused = 0;
-    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
     return two_pass(
         f, ~0ull, nullptr, "classes", true,
         [&](uint64_t *n) -> int {
@@ -782,27 +756,19 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
             return MSBWT_OK;
         },
         [&](uint64_t n) -> int {
-            // one allocation over M = 2 n slots:
-            //   counts   4 M words: cnt[4 slot + c]; before them the walk's records (word, own, other: 3 n words), after them the two states
-            //   sort     4 M words: (keys, payloads) twice; the pair the sort leaves free holds the predecessor slots
-            //   chunk | histogram | scan | tiles | counters | counters | edge words | link words
-            const uint64_t M = 2 * n, chunk_slots = canonical_unitig_chunk_slots(M);
-            char *at = nullptr;
-            if (int rc = stage_records(f, none, n, &unused, "for the nodes of the graph", n * kCanonicalUnitigClassBytes + canonical_unitig_fixed_bytes(n), &at)) return rc;
-            uint64_t *cnt = reinterpret_cast<uint64_t *>(at), *keys_a = cnt + 4 * M, *vals_a = keys_a + M, *keys_b = vals_a + M, *vals_b = keys_b + M;
-            uint64_t *chunk = vals_b + M, *hist = chunk + 4 * chunk_slots, *scan = hist + radix_sort_hist_words(M);
-            char *tiles = reinterpret_cast<char *>(scan + radix_sort_scan_words(M));
-            unsigned long long *counters = reinterpret_cast<unsigned long long *>(tiles + unitig_tiles(M) * kUnitigTileBytes);
-            unsigned long long *own_counters = counters + kUnitigFixedBytes / 8;
-            uint32_t *edge_words = reinterpret_cast<uint32_t *>(own_counters + kCanonicalUnitigFixedBytes / 8), *link_words = edge_words + graph_edge_words(M);
-            uint32_t *flags = h->d_flags + f.which;
-            HIP_TRY(h, hipMemsetAsync(counters, 0, kUnitigFixedBytes + kCanonicalUnitigFixedBytes + 2 * graph_edge_words(M) * 4, f.stream));
+            const CanonicalUnitigLayout at = canonical_unitig_layout(n);  // over M = 2 n slots, with what lies over what
+            char *block = nullptr;
+            if (int rc = f.take_more(&block, at.bytes, "for the nodes of the graph")) return rc;
+            uint64_t *cnt = in<uint64_t>(block, at.cnt), *chunk = in<uint64_t>(block, at.chunk);
+            unsigned long long *own_counters = in<unsigned long long>(block, at.own_counters);
+            uint32_t *edge_words = in<uint32_t>(block, at.edge_words), *flags = h->d_flags + f.which;
+            HIP_TRY(h, hipMemsetAsync(block + at.zero_from, 0, at.bytes - at.zero_from, f.stream));
 
             // the classes, in walk order
             classes.mode = kCanonicalAppend;
-            classes.kmers = cnt;
-            classes.own = cnt + n;
-            classes.other = cnt + 2 * n;
+            classes.kmers = in<uint64_t>(block, at.classes[0]);
+            classes.own = in<uint64_t>(block, at.classes[1]);
+            classes.other = in<uint64_t>(block, at.classes[2]);
             classes.capacity = n;
             classes.flags = flags;
             if (int rc = canonical_walk(f, prune, classes, totals)) return rc;
@@ -810,33 +776,31 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
 
             // the nodes, in word order
             uint64_t own[kCanonicalUnitigCounterWords] = {};
-            const auto read_own = [&]() -> int {  // synchronises
-                HIP_TRY(h, hipMemcpyAsync(own, own_counters, sizeof own, hipMemcpyDeviceToHost, f.stream));
-                HIP_TRY(h, hipStreamSynchronize(f.stream));
-                return MSBWT_OK;
-            };
-            HIP_TRY(h, launch_canonical_unitig_double(classes.kmers, classes.own, classes.other, n, uint32_t(k), keys_a, vals_a, own_counters, flags, f.stream));
-            if (int rc = read_own()) return rc;
+            uint64_t *const sort_keys[2] = {in<uint64_t>(block, at.pairs[0].keys), in<uint64_t>(block, at.pairs[1].keys)};
+            uint64_t *const sort_vals[2] = {in<uint64_t>(block, at.pairs[0].vals), in<uint64_t>(block, at.pairs[1].vals)};
+            HIP_TRY(h, launch_canonical_unitig_double(classes.kmers, classes.own, classes.other, n, uint32_t(k), sort_keys[0], sort_vals[0], own_counters, flags, f.stream));
+            if (int rc = read_counters(f, own_counters, own)) return rc;
             if (own[kCanonicalUnitigSeconds] > n) return fail(h, MSBWT_ERR_INTERNAL, f.name + ": more second members than classes");
             const uint64_t N = n + own[kCanonicalUnitigSeconds];
             bool in_b = false;
             const uint32_t passes = (2 * uint32_t(k) + kRadixDigitBits - 1) / kRadixDigitBits;  // the bytes above 2k bits are zero in every key
-            HIP_TRY(h, radix_sort_passes(keys_a, vals_a, keys_b, vals_b, N, 0, passes, hist, scan, flags, f.stream, &in_b));
-            const uint64_t *keys = in_b ? keys_b : keys_a, *vals = in_b ? vals_b : vals_a;
-            uint64_t *pred = in_b ? keys_a : keys_b;
+            HIP_TRY(h, radix_sort_passes(sort_keys[0], sort_vals[0], sort_keys[1], sort_vals[1], N, 0, passes, in<uint64_t>(block, at.hist), in<uint64_t>(block, at.scan), flags,
+                                         f.stream, &in_b));
+            const uint64_t *keys = sort_keys[in_b], *vals = sort_vals[in_b];
+            uint64_t *pred = in<uint64_t>(block, at.pred[in_b]);  // (in the pair the sort left free)
             HIP_TRY(h, hipMemsetAsync(pred, 0xFF, N * 8, f.stream));  // (no slot)
 
             // the edges: count_kmer of the four (k+1)-mers out of every node, a chunk of nodes at a time, then the fold
-            for (uint64_t first = 0; first < N; first += chunk_slots) {
-                const uint64_t nodes = std::min(chunk_slots, N - first);
+            for (uint64_t first = 0; first < N; first += at.chunk_slots) {
+                const uint64_t nodes = std::min(at.chunk_slots, N - first);
                 HIP_TRY(h, launch_canonical_unitig_edge_words(keys, first, nodes, chunk, f.stream));
                 if (int rc = launch_count_2bit(h, chunk, k + 1, size_t(4 * nodes), cnt + 4 * first, f.stream, f.which)) return rc;
             }
-            HIP_TRY(h, launch_canonical_unitig_fold(keys, N, uint32_t(k), me, cnt, edge_words, pred, own_counters, flags, f.stream));
+            HIP_TRY(h, launch_canonical_unitig_fold(keys, N, uint32_t(k), cut.me, cnt, edge_words, pred, own_counters, flags, f.stream));
 
             // the compaction over the N slots (the counts are folded: their place is the states')
-            UnitigState *cur = reinterpret_cast<UnitigState *>(cnt), *other = cur + N;
-            const UnitigNodes g{N, keys, vals, pred, edge_words, link_words, counters, flags};
+            UnitigState *cur = in<UnitigState>(block, at.states), *other = cur + N;
+            const UnitigNodes g{N, keys, vals, pred, edge_words, in<uint32_t>(block, at.link_words), in<unsigned long long>(block, at.counters), flags};
             uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
             if (int rc = rank_unitigs(f, g, cur, other, c, &rounds, [&]() -> int {
                     HIP_TRY(h, launch_canonical_unitig_cut(g, uint32_t(k), cur, own_counters, f.stream));
@@ -844,18 +808,27 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
                 }))
                 return rc;
             HIP_TRY(h, launch_canonical_unitig_choose(g, uint32_t(k), cur, own_counters, f.stream));
-            if (int rc = read_own()) return rc;
+            if (int rc = read_counters(f, own_counters, own)) return rc;
             const uint64_t U = own[kCanonicalUnitigEmitted], circular = own[kCanonicalUnitigEmittedCircular];
             if (c[kUnitigUnfinished] || own[kCanonicalUnitigEmittedNodes] != n || U > n || circular > U)
                 return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the ranking left " + std::to_string(c[kUnitigUnfinished]) + " nodes without a head, and the emitted unitigs hold " +
                                                        std::to_string(own[kCanonicalUnitigEmittedNodes]) + " of " + std::to_string(n) + " classes");
             const uint64_t S = n + U * (k - 1);
-            const uint64_t info[kCanonicalUnitigInfoWords] = {n, (c[kUnitigEdges] + own[kCanonicalUnitigHairpins]) / 2, n + circular - U, U, S, circular, c[kUnitigLongest], rounds,
+            const uint64_t info[MSBWT_CANONICAL_UNITIG_INFO_WORDS] = {n, (c[kUnitigEdges] + own[kCanonicalUnitigHairpins]) / 2, n + circular - U, U, S, circular, c[kUnitigLongest], rounds,
                                                               2 * n - N, own[kCanonicalUnitigCut]};
-            std::copy(info, info + kCanonicalUnitigInfoWords, h->canonical_unitig_info);
-            return out.emit(f, g, cur, other, tiles, U, S, true);
+            std::copy(info, info + MSBWT_CANONICAL_UNITIG_INFO_WORDS, h->canonical_unitig_info);
+            return out.emit(f, g, cur, other, block + at.tiles, U, S, true);
         },
         [&](uint64_t) { return out.deliver(f); });
+}
+
+// what a family's last call on the handle left in its info words
+template <size_t W>
+int info_words(const msbwt_rle *bwt, uint64_t (msbwt_rle::*info)[W], uint64_t *out) {
+    Call c(bwt);
+    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
+    std::copy(c.h->*info, c.h->*info + W, out);
+    return MSBWT_OK;
 }
 
 }  // namespace
@@ -895,12 +868,7 @@ int msbwt_rle_set_spectrum_frontier(msbwt_rle *bwt, uint64_t nodes) {
     return set_locked(bwt, bwt->spectrum_frontier, nodes);
 }
 
-int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out) {
-    Call c(bwt);
-    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
-    std::copy(c.h->spectrum_info, c.h->spectrum_info + MSBWT_SPECTRUM_INFO_WORDS, out);
-    return MSBWT_OK;
-}
+int msbwt_rle_spectrum_info(const msbwt_rle *bwt, uint64_t *out) { return info_words(bwt, &msbwt_rle::spectrum_info, out); }
 
 int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes) {
     Call c(bwt);
@@ -1023,7 +991,7 @@ int msbwt_rle_kmer_graph_degrees(const msbwt_rle *bwt, size_t k, uint64_t min_co
 
 // the host dump of `records` nodes with words, counts and l
 int msbwt_kmer_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t records, uint64_t *device_bytes) {
-    return plan(graph_shape(true), total_rows, free_hbm_bytes, records, graph_edge_words(records) * 4, device_bytes);
+    return plan(graph_shape(true), total_rows, free_hbm_bytes, records, graph_tail_layout(records).bytes - graph_tail_layout(0).bytes, device_bytes);
 }
 
 // ---- unitigs: the non-branching paths of the k-mer graph as ragged sequences ----
@@ -1042,18 +1010,11 @@ int msbwt_rle_enumerate_unitigs_device(const msbwt_rle *bwt, size_t k, uint64_t 
                    out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream));
 }
 
-int msbwt_rle_unitig_info(const msbwt_rle *bwt, uint64_t *out) {
-    Call c(bwt);
-    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
-    std::copy(c.h->unitig_info, c.h->unitig_info + MSBWT_UNITIG_INFO_WORDS, out);
-    return MSBWT_OK;
-}
+int msbwt_rle_unitig_info(const msbwt_rle *bwt, uint64_t *out) { return info_words(bwt, &msbwt_rle::unitig_info, out); }
 
 // the host call of `nodes` nodes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)
 int msbwt_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {
-    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 32 n + n)
-    const uint64_t out = unitigs || symbols ? unitig_out_bytes(unitigs, symbols, true, true, true, true) : 0;
-    return plan(kUnitigShape, total_rows, free_hbm_bytes, nodes, unitig_fixed_bytes(nodes) + out, device_bytes);
+    return unitigs_plan(kUnitigShape, unitig_node_layout(nodes).bytes, total_rows, free_hbm_bytes, nodes, unitigs, symbols, device_bytes);
 }
 
 // ---- canonical unitigs: the non-branching paths of the strand-merged k-mer graph ----
@@ -1072,18 +1033,11 @@ int msbwt_rle_enumerate_canonical_unitigs_device(const msbwt_rle *bwt, size_t k,
                              capacity_symbols, out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream));
 }
 
-int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out) {
-    Call c(bwt);
-    if (!c.h || !out) return MSBWT_ERR_INVALID_ARG;
-    std::copy(c.h->canonical_unitig_info, c.h->canonical_unitig_info + MSBWT_CANONICAL_UNITIG_INFO_WORDS, out);
-    return MSBWT_OK;
-}
+int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out) { return info_words(bwt, &msbwt_rle::canonical_unitig_info, out); }
 
 // the host call over `classes` classes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)
 int msbwt_canonical_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {
-    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (S <= 31 n + n)
-    const uint64_t out = unitigs || symbols ? unitig_out_bytes(unitigs, symbols, true, true, true, true) : 0;
-    return plan(kCanonicalUnitigShape, total_rows, free_hbm_bytes, classes, canonical_unitig_fixed_bytes(classes) + out, device_bytes);
+    return unitigs_plan(kCanonicalUnitigShape, canonical_unitig_layout(classes).bytes, total_rows, free_hbm_bytes, classes, unitigs, symbols, device_bytes);
 }
 
 }  // extern "C"
