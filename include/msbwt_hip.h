@@ -637,6 +637,82 @@ int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT
 int msbwt_canonical_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols,
                                  uint64_t *device_bytes);
 
+/* ---- unitig links ---- the edges of the compacted graph: either unitig call with the LINK TABLE behind its five columns, on the device
+ * (no reference counterpart).  The five columns are byte for byte those of msbwt_rle_enumerate_unitigs / _canonical_unitigs (but for
+ * flag bit 1 below), and msbwt_rle_unitig_info / msbwt_rle_canonical_unitig_info are filled exactly as those calls fill them.
+ * SIDES: unitig u has two.  Side 2u leaves u forwards, out of its last node; side 2u + 1 leaves rc(u) forwards, out of the reverse
+ * complement of u's first node -- "backwards out of u".
+ * ENTRIES: let W be the sequence side a leaves (u or rc(u)).  For every symbol c in A C G T order for which the graph has the edge
+ * last(W) -> q' = last(W)[1:].c the side holds one entry 2v + o: v is the returned unitig with q' at an end, o = 0 when q' = first(v),
+ * o = 1 when q' = rc(last(v)), o = 0 when both hold.  The entries of a side ascend by c.  q' always lies at an end: an edge that is no
+ * link starts at a last node and ends at a first node, the only link that is an entry is the closing link of a circular unitig, and a
+ * cut link of the canonical graph is an edge that is no link.
+ * PLAIN CALL (the strand-specific graph; rc(u) is no part of it, and a side 2u + 1 is read through the mirrored edges): side 2u has
+ * popcount(out_ends[u] >> 4) entries, all even: the successors.  Side 2u + 1 has popcount(out_ends[u] & 15) entries, all odd: 2v + 1
+ * for every unitig v whose last node precedes first(u), by DESCENDING predecessor symbol (leaving rc(u) appends the complement).
+ * L = 2 (edges - links + circular) of msbwt_rle_unitig_info.  A circular unitig has exactly 2u on side 2u and 2u + 1 on side 2u + 1.
+ * CANONICAL CALL (the graph D above): side 2u has popcount(out_ends[u] >> 4) entries, side 2u + 1 popcount(out_ends[u] & 15) -- in-bit
+ * j of a node is out-bit 3 - j of its mirror.  A unitig that is its own reverse complement -- a single palindromic node, the only case
+ * in which both o apply -- has ONE side: its side 2u + 1 is empty, entries that reach it carry o = 0, and out_flags[u] has bit 1 set
+ * (bit 0 stays "circular"; the plain call never sets bit 1).
+ * MIRROR RECORDS: write (a, e) for "side a holds entry e", and c(x) = x & ~1 for a unitig that is its own reverse complement, else x.
+ * With every (a, e) the table holds (c(e ^ 1), c(a ^ 1)): the same bidirected edge from its other end.  A hairpin edge q -> rc(q) is
+ * its own mirror.  Keeping a record only when (a, e) <= its mirror, compared as pairs, keeps every edge once: edges - links + circular
+ * records of the plain call (as many as its even sides hold, though not those: the rule keeps (1, 3) and not its mirror (2, 0)),
+ * edge_classes - links + circular of the canonical call.
+ *
+ * Outputs beyond the five columns (every buffer may be NULL):
+ *   out_link_offsets  2 U + 1 words: side a is out_link_targets[out_link_offsets[a] .. out_link_offsets[a + 1]); [0] = 0, [2 U] = L
+ *   out_link_targets  L words
+ * Capacity: the contract of the unitig calls with one capacity more.  *out_unitigs (NULL: MSBWT_ERR_INVALID_ARG), *out_symbol_total and
+ * *out_links (each may be NULL) are always set; all three capacities 0 only counts, L included; otherwise capacity_unitigs < U, or
+ * capacity_symbols < S with out_symbols wanted, or capacity_links < L with out_link_targets wanted, writes NOTHING, returns
+ * MSBWT_ERR_INVALID_ARG and names U, S and L.  Tails past U, U + 1, 2 U + 1, S and L stay untouched.  The _device form writes to device
+ * buffers -- the byte arrays need no alignment --, synchronises the stream and reports a device fault through msbwt_rle_device_status.
+ * 1 <= k <= 32, canonical 1 <= k <= 31; the guards are those of the unitig calls, in their order, before the first HIP call.  An empty
+ * index, or one without a node: U = S = L = 0, and a call with a capacity writes out_link_offsets[0] = 0.  Results depend on no knob.
+ *
+ * How ("Unitig links"): behind the emission, over the arrays it used.  The tails' degrees are added up for L before a
+ * capacity is looked at; then every tail writes its two degrees, one scan (the numbering's helpers, tiles of 2048 words) turns them
+ * into offsets, and every tail and head fills its side: a neighbour's word is the node's shifted by a symbol (at k = 32 the successor
+ * shifts out of the 64 bits), its slot a binary search over the sorted words of ceil(log2 n) + 1 steps, fixed on the host, and its
+ * unitig the number at that slot's head -- or, where the canonical call did not emit that unitig, at the head of its mirror, one more
+ * search.  Scratch per call, freed on return; msbwt_rle_spectrum_scratch_bytes reports these calls too. */
+int msbwt_rle_enumerate_unitig_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols,
+                                     uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags,
+                                     uint64_t *out_link_offsets /* 2U + 1 */, uint64_t *out_link_targets /* L */,
+                                     uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links,
+                                     uint64_t *out_unitigs, uint64_t *out_symbol_total, uint64_t *out_links);
+int msbwt_rle_enumerate_unitig_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols,
+                                            void *d_out_offsets, void *d_out_count_sums, void *d_out_ends, void *d_out_flags,
+                                            void *d_out_link_offsets, void *d_out_link_targets, uint64_t capacity_unitigs,
+                                            uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs,
+                                            uint64_t *out_symbol_total, uint64_t *out_links, void *hip_stream);
+int msbwt_rle_enumerate_canonical_unitig_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                               uint8_t *out_symbols, uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends,
+                                               uint8_t *out_flags, uint64_t *out_link_offsets /* 2U + 1 */,
+                                               uint64_t *out_link_targets /* L */, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                               uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                               uint64_t *out_links);
+int msbwt_rle_enumerate_canonical_unitig_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                                      void *d_out_symbols, void *d_out_offsets, void *d_out_count_sums, void *d_out_ends,
+                                                      void *d_out_flags, void *d_out_link_offsets, void *d_out_link_targets,
+                                                      uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links,
+                                                      uint64_t *out_unitigs, uint64_t *out_symbol_total, uint64_t *out_links,
+                                                      void *hip_stream);
+/* Pure functions, no device: bytes of HBM a host call that fills all seven buffers allocates and frees again, EXACTLY
+ *     msbwt_unitigs_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols)   (msbwt_canonical_unitigs_plan for the canonical call)
+ *     + 16 unitigs + 256                                      the link offsets, 2 U + 1 words, in a third allocation, padded
+ *     + 16 ceil((2 unitigs + 1) / 2048)                       their scan's two sums per tile of 2048 words
+ *     + 8 links                                               the link targets staged for the host
+ * A NULL out_link_targets, and the _device form, take the last line less.  A counting call (all three capacities 0) allocates what the
+ * unitig call's counting call does: unitigs = symbols = links = 0 says so.  MSBWT_ERR_TOO_LARGE as for the unitig plans, and from
+ * 2^43 links on; device_bytes may be NULL. */
+int msbwt_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols,
+                            uint64_t links, uint64_t *device_bytes);
+int msbwt_canonical_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols,
+                                      uint64_t links, uint64_t *device_bytes);
+
 /* The bytes of scratch the handle's last k-mer walk call (any call of the four sections above that walks) allocated in HBM and freed
  * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves
  * it as it was).  Every allocation counts with its size, 256 bytes at the least.  For the by-source calls this is what

@@ -525,6 +525,52 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_canonical_unitigs_plan");
         return bytes;
     }
+    /// What enumerate_unitig_graph returns: the unitigs and the link table of the compacted graph.  Side 2u leaves unitig u forwards,
+    /// side 2u + 1 leaves its reverse complement forwards; side a holds link_targets[link_offsets[a] .. link_offsets[a + 1]), an
+    /// entry 2v + o per edge: it reaches the first node of v (o = 0) or the reverse complement of its last node (o = 1).  Canonical:
+    /// flags[u] bit 1 = the unitig is its own reverse complement and has one side.
+    struct UnitigGraph : Unitigs {
+        std::vector<std::uint64_t> link_offsets, link_targets;
+    };
+    /// Either unitig call with the link table behind its columns (canonical: the strand-merged graph, 1 <= k <= 31).
+    UnitigGraph enumerate_unitig_graph(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0, bool canonical = false) const {
+        const auto call = canonical ? msbwt_rle_enumerate_canonical_unitig_graph : msbwt_rle_enumerate_unitig_graph;
+        std::uint64_t n = 0, s = 0, l = 0;
+        check(call(raw_, k, min_count, min_edge, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, &n, &s, &l));
+        UnitigGraph u;
+        u.symbols.resize(s);
+        u.offsets.resize(n + 1);
+        u.count_sums.resize(n);
+        u.ends.resize(n);
+        u.flags.resize(n);
+        u.link_offsets.resize(2 * n + 1);
+        u.link_targets.resize(l);
+        if (n)
+            check(call(raw_, k, min_count, min_edge, u.symbols.data(), u.offsets.data(), u.count_sums.data(), u.ends.data(), u.flags.data(), u.link_offsets.data(),
+                       u.link_targets.data(), n, s, l, &n, &s, &l));
+        return u;
+    }
+    /// Device buffers (each may be null; the byte arrays at any alignment) -> the unitigs; *symbol_total and *links (each may be null)
+    /// = their symbols and link entries.  All three capacities 0 only counts.
+    std::uint64_t enumerate_unitig_graph_device(std::size_t k, std::uint64_t min_count, std::uint64_t min_edge, bool canonical, void *d_symbols, void *d_offsets,
+                                                void *d_count_sums, void *d_ends, void *d_flags, void *d_link_offsets, void *d_link_targets,
+                                                std::uint64_t capacity_unitigs, std::uint64_t capacity_symbols, std::uint64_t capacity_links,
+                                                std::uint64_t *symbol_total, std::uint64_t *links, void *hip_stream = nullptr) const {
+        const auto call = canonical ? msbwt_rle_enumerate_canonical_unitig_graph_device : msbwt_rle_enumerate_unitig_graph_device;
+        std::uint64_t n = 0;
+        check(call(raw_, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols,
+                   capacity_links, &n, symbol_total, links, hip_stream));
+        return n;
+    }
+    /// HBM bytes a host unitig graph call that fills every buffer allocates (and frees again): the unitig call's plan and the link table;
+    /// unitigs = symbols = links = 0: the counting call.
+    static std::uint64_t unitig_graph_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t nodes = 0, std::uint64_t unitigs = 0,
+                                           std::uint64_t symbols = 0, std::uint64_t links = 0, bool canonical = false) {
+        std::uint64_t bytes = 0;
+        const int rc = (canonical ? msbwt_canonical_unitig_graph_plan : msbwt_unitig_graph_plan)(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, &bytes);
+        if (rc) throw Panic(rc, canonical ? "msbwt_canonical_unitig_graph_plan" : "msbwt_unitig_graph_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

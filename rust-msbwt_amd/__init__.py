@@ -17,7 +17,7 @@ from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "unitig_graph_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -186,6 +186,20 @@ def canonical_unitigs_plan(total_rows, free_hbm_bytes, classes=0, unitigs=0, sym
     rc = _lib.lib().msbwt_canonical_unitigs_plan(int(total_rows), int(free_hbm_bytes), int(classes), int(unitigs), int(symbols), ctypes.byref(size))
     if rc:
         raise MsbwtError(rc, "msbwt_canonical_unitigs_plan")
+    return size.value
+
+
+def unitig_graph_plan(total_rows, free_hbm_bytes, nodes=0, unitigs=0, symbols=0, links=0, canonical=False):
+    """HBM bytes a RleBWT.enumerate_unitig_graph call over `nodes` nodes (canonical: classes) that fills every buffer with `unitigs`
+    unitigs of `symbols` symbols and `links` link entries allocates and frees again: unitigs_plan or canonical_unitigs_plan and the
+    link table (include/msbwt_hip.h writes the terms out); all three 0: the counting call.  The device form stages no targets either.
+    Pure host logic."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    name = "msbwt_canonical_unitig_graph_plan" if canonical else "msbwt_unitig_graph_plan"
+    rc = getattr(_lib.lib(), name)(int(total_rows), int(free_hbm_bytes), int(nodes), int(unitigs), int(symbols), int(links), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, name)
     return size.value
 
 

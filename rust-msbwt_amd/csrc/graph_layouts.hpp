@@ -3,7 +3,7 @@
 // starts: a msbwt_*_plan and the hipMalloc take `bytes`, the call carves `base + field`, the memset runs from `zero_from` to `bytes`.
 // A struct lists its arrays in their order in HBM, and its function puts their extents down in that order: the n-th put() is the n-th
 // field.  hipMalloc aligns a block to 256 bytes; what precedes a 16-byte array is a multiple of 16, what precedes a 64-bit one of 8
-// (tests/cpp/graph_layouts.cpp holds every layout to that, and to no array reaching into the next).
+// (tests/cpp/graph_layouts.cpp, and link_layouts.cpp for the link table, hold every layout to that, and to no array reaching into the next).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -11,6 +11,7 @@
 #include "canonical_unitigs.hpp"
 #include "kmer_graph.hpp"
 #include "radix_sort.hpp"
+#include "unitig_links.hpp"
 #include "unitigs.hpp"
 
 namespace msbwt {
@@ -82,6 +83,16 @@ struct UnitigOutputLayout {
 inline UnitigOutputLayout unitig_output_layout(uint64_t U, uint64_t S, bool sums, bool symbols, bool ends, bool flags) {
     LayoutCursor c;
     return {c.put(8 * U + 256), c.put(sums ? 8 * U : 0), c.put(symbols ? (S + 7) / 8 * 8 : 0), c.put(ends ? (U + 7) / 8 * 8 : 0), c.put(flags ? (U + 7) / 8 * 8 : 0), c.bytes};
+}
+
+// The link table of either unitig graph call, U unitigs with L entries: the offsets of the 2 U + 1 sides (padded), the tiles of their
+// scan, then the targets where a host form stages them -- a device form's are the caller's own and take no room.
+struct UnitigLinkLayout {
+    uint64_t offsets, tiles, targets, bytes;
+};
+inline UnitigLinkLayout unitig_link_layout(uint64_t U, uint64_t L, bool targets) {
+    LayoutCursor c;
+    return {c.put(16 * U + 256), c.put(unitig_tiles(unitig_link_sides(U)) * kUnitigTileBytes), c.put(targets ? 8 * L : 0), c.bytes};
 }
 
 }  // namespace msbwt

@@ -3,7 +3,8 @@
 // class (canonical.hpp; the other strand is counted by query.cpp's packed search), the k-mers by source of a merged index
 // (source_spectrum.hpp) and the k-mer graph (kmer_graph.hpp).  Two of two, a host and a device form: the unitigs that graph compacts
 // into (unitigs.hpp: the graph's walks into scratch, then kernels over its slots) and the canonical unitigs (canonical_unitigs.hpp: the
-// same compaction over both members of every canonical class).  The kernels are behind those headers; this file is the host side, and
+// same compaction over both members of every canonical class), each also as a unitig GRAPH call that adds the link table of the
+// compacted graph behind the emission (unitig_links.hpp).  The kernels are behind those headers; this file is the host side, and
 // what the calls share is written once:
 //   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
 //                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
@@ -16,7 +17,8 @@
 //   staged_walk   a walk whose chunks go to a sink behind it (canonical, by source, the graph's edge pass)
 //   spectrum      a spectrum: the histograms zeroed, taken, walked into and copied out
 //   GraphCut / graph_edge_walk   the thresholds of the three graph calls and their staged walk with the edge pass behind it
-//   rank_unitigs / UnitigOutputs   the compaction both unitig calls run over their slots, and their outputs from guard to delivery
+//   rank_unitigs / UnitigOutputs   the compaction both unitig calls run over their slots, and their outputs from guard to delivery;
+//                 UnitigLinkOutputs: the link table the unitig graph calls add behind the emission (unitig_links.hpp)
 // A body below is what is left: its argument checks, its sink, and the order of its passes.
 #include <algorithm>
 #include <chrono>
@@ -31,6 +33,7 @@
 #include "run_encode.hpp"
 #include "source_spectrum.hpp"
 #include "spectrum.hpp"
+#include "unitig_links.hpp"
 #include "unitigs.hpp"
 
 namespace {
@@ -569,6 +572,17 @@ int unitigs_plan(const Shape &p, uint64_t node_bytes, uint64_t total_rows, uint6
     return plan(p, total_rows, free_bytes, nodes, node_bytes + out, device_bytes);
 }
 
+// a msbwt_[canonical_]unitig_graph_plan: that plan and, unless it is the counting call (unitigs = symbols = links = 0), the link table
+// with its targets staged
+int unitig_graph_plan(const Shape &p, uint64_t node_bytes, uint64_t total_rows, uint64_t free_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t links,
+                      uint64_t *device_bytes) {
+    if (links / 8 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;  // (L <= 8 U)
+    const bool fills = unitigs || symbols || links;
+    const uint64_t out = fills ? unitig_output_layout(unitigs, symbols, true, true, true, true).bytes + unitig_link_layout(unitigs, links, true).bytes : 0;
+    if (unitigs >= kMaxSymbols || symbols / 33 >= kMaxSymbols) return MSBWT_ERR_TOO_LARGE;
+    return plan(p, total_rows, free_bytes, nodes, node_bytes + out, device_bytes);
+}
+
 uint64_t ceil_log2(uint64_t x) {
     uint64_t r = 0;
     while (r < 63 && (1ull << r) < x) ++r;
@@ -628,10 +642,24 @@ int rank_unitigs(Frame &f, const UnitigNodes &g, UnitigState *&cur, UnitigState 
 // thresholds' in it, then zeros in *out_unitigs, *out_symbol_total and the handle's info words.  emit(), once U and S are known:
 // *out_unitigs and *out_symbol_total, the capacity contract, the second allocation (unitig_output_layout: the offsets, and the other
 // four columns where a host form stages them), numbering and emission (skip_marked: heads carry kUnitigSkip).  deliver(): the copies.
+// With `links` (the unitig graph calls) the link table rides along: open() zeroes *out_links too; emit() counts L before it looks at
+// the capacities -- so that a capacity_links below L also writes nothing --, takes unitig_link_layout as a third allocation and
+// runs degrees, scan and targets behind the emission (unitig_links.hpp); deliver() copies the offsets and the staged targets.
+struct UnitigLinkOutputs {
+    void *offsets, *targets;  // the caller's: 2 U + 1 words and L words, each may be nullptr
+    uint64_t capacity;
+    uint64_t *out_links;  // may be nullptr
+    bool canonical;
+    uint64_t expect = ~0ull;  // what the counters say L is, where they say it (the plain call)
+    uint64_t L = 0;
+    uint64_t *d_offsets = nullptr, *d_targets = nullptr;
+};
+
 struct UnitigOutputs {
     void *symbols, *offsets, *sums, *ends, *flags;
     uint64_t capacity_unitigs, capacity_symbols;
     uint64_t *out_unitigs, *out_symbol_total;
+    UnitigLinkOutputs *links = nullptr;
     uint64_t U = 0, S = 0;
     bool filled = false;
     uint64_t *d_offsets = nullptr, *d_sums = nullptr;
@@ -643,6 +671,7 @@ struct UnitigOutputs {
         if (int rc = f.open(false, checks)) return rc;
         *out_unitigs = 0;
         if (out_symbol_total) *out_symbol_total = 0;
+        if (links && links->out_links) *links->out_links = 0;
         std::fill(f.h->*info, f.h->*info + W, 0ull);
         return MSBWT_OK;
     }
@@ -654,14 +683,32 @@ struct UnitigOutputs {
         S = total;
         *out_unitigs = U;
         if (out_symbol_total) *out_symbol_total = S;
-        if (capacity_unitigs == 0 && capacity_symbols == 0) return MSBWT_OK;
+        if (links) {  // L, before anything is written: the tails' degrees added up
+            uint64_t c[kUnitigLinkEntries + 1] = {};
+            HIP_TRY(h, launch_unitig_link_degrees(g, state, nullptr, uint32_t(f.k), links->canonical, U, nullptr, nullptr, f.stream));
+            if (int rc = read_counters(f, g.counters, c)) return rc;
+            links->L = c[kUnitigLinkEntries];
+            if (links->L > 8 * U || (links->expect != ~0ull && links->L != links->expect))
+                return fail(h, MSBWT_ERR_INTERNAL, f.name + ": the sides hold " + std::to_string(links->L) + " entries, which the graph's counters do not bear out");
+            if (links->out_links) *links->out_links = links->L;
+        }
+        if (capacity_unitigs == 0 && capacity_symbols == 0 && (!links || links->capacity == 0)) return MSBWT_OK;
+        const std::string need = "U = " + std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols";
+        if (links && (capacity_unitigs < U || (symbols && capacity_symbols < S) || (links->targets && links->capacity < links->L)))
+            return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + ", " + std::to_string(capacity_symbols) + " and " + std::to_string(links->capacity) +
+                            " are less than the " + need + " with L = " + std::to_string(links->L) + " links");
         if (capacity_unitigs < U || (symbols && capacity_symbols < S))
-            return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the U = " +
-                            std::to_string(U) + " unitigs of S = " + std::to_string(S) + " symbols");
+            return f.refuse(": the capacities " + std::to_string(capacity_unitigs) + " and " + std::to_string(capacity_symbols) + " are less than the " + need);
         const bool stage_sums = host && sums, stage_symbols = host && symbols, stage_ends = host && ends, stage_flags = host && flags;
         const UnitigOutputLayout at = unitig_output_layout(U, S, stage_sums, stage_symbols, stage_ends, stage_flags);
-        char *block = nullptr;
+        char *block = nullptr, *link_block = nullptr;
         if (int rc = f.take_more(&block, at.bytes, "for the unitigs")) return rc;
+        const UnitigLinkLayout link_at = links ? unitig_link_layout(U, links->L, host && links->targets) : UnitigLinkLayout{};
+        if (links) {
+            if (int rc = f.take_more(&link_block, link_at.bytes, "for the links")) return rc;
+            links->d_offsets = in<uint64_t>(link_block, link_at.offsets);
+            links->d_targets = host && links->targets ? in<uint64_t>(link_block, link_at.targets) : static_cast<uint64_t *>(links->targets);
+        }
         // a device form's outputs are the caller's own; a staged one has its place in the block
         d_offsets = in<uint64_t>(block, at.offsets);
         d_sums = static_cast<uint64_t *>(stage_sums ? block + at.sums : sums);
@@ -671,7 +718,26 @@ struct UnitigOutputs {
         if (d_sums) HIP_TRY(h, hipMemsetAsync(d_sums, 0, 8 * U, f.stream));
         HIP_TRY(h, launch_unitig_number(g, heads, tiles, uint32_t(f.k), U, S, d_offsets, f.stream));
         HIP_TRY(h, launch_unitig_emit(g, state, heads, uint32_t(f.k), U, S, d_symbols, d_sums, d_ends, d_flags, f.stream, skip_marked));
+        if (links) {
+            HIP_TRY(h, launch_unitig_link_degrees(g, state, heads, uint32_t(f.k), links->canonical, U, links->d_offsets, d_flags, f.stream));
+            HIP_TRY(h, launch_unitig_link_scan(U, links->d_offsets, link_block + link_at.tiles, f.stream));
+            if (links->d_targets)
+                HIP_TRY(h, launch_unitig_link_targets(g, state, heads, uint32_t(f.k), links->canonical, uint32_t(ceil_log2(g.n) + 1), U, links->L, links->d_offsets,
+                                                      links->d_targets, f.stream));
+        }
         filled = true;
+        return MSBWT_OK;
+    }
+
+    // a graph call that had capacities and found nothing to fill (an empty index, no node that counts): side 0 of no unitig starts at 0
+    int close(Frame &f, int rc) const {
+        if (rc || filled || !links || !links->offsets || !(capacity_unitigs || capacity_symbols || links->capacity)) return rc;
+        if (f.host) {
+            *static_cast<uint64_t *>(links->offsets) = 0;
+            return MSBWT_OK;
+        }
+        HIP_TRY(f.h, hipMemsetAsync(links->offsets, 0, 8, f.stream));
+        HIP_TRY(f.h, hipStreamSynchronize(f.stream));
         return MSBWT_OK;
     }
 
@@ -684,6 +750,8 @@ struct UnitigOutputs {
             if (f.host && symbols) HIP_TRY(h, hipMemcpyAsync(symbols, d_symbols, S, kind, f.stream));
             if (f.host && ends) HIP_TRY(h, hipMemcpyAsync(ends, d_ends, U, kind, f.stream));
             if (f.host && flags) HIP_TRY(h, hipMemcpyAsync(flags, d_flags, U, kind, f.stream));
+            if (links && links->offsets) HIP_TRY(h, hipMemcpyAsync(links->offsets, links->d_offsets, 8 * unitig_link_sides(U), kind, f.stream));
+            if (links && f.host && links->targets && links->L) HIP_TRY(h, hipMemcpyAsync(links->targets, links->d_targets, 8 * links->L, kind, f.stream));
         }
         if (f.host) return status_of(h, f.stream, f.which);  // synchronises
         HIP_TRY(h, hipStreamSynchronize(f.stream));           // (the scratch is freed on return)
@@ -694,13 +762,14 @@ struct UnitigOutputs {
 // Both forms: the sorted dump's counting walk, the staged walk with the edge pass behind it (into scratch: words, counts, edge bytes
 // and predecessor slots), then links, ranking, cycles, numbering and emission over the slots (unitigs.hpp).
 int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums, void *out_ends,
-            void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total, hipStream_t stream) {
-    Frame f(bwt, "enumerate_unitigs", k, host, stream);
+            void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total, hipStream_t stream,
+            UnitigLinkOutputs *links = nullptr) {
+    Frame f(bwt, links ? "enumerate_unitig_graph" : "enumerate_unitigs", k, host, stream);
     const GraphCut cut(min_count, min_edge);
-    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links};
     if (int rc = out.open(f, cut, &msbwt_rle::unitig_info, [] { return int(MSBWT_OK); })) return rc;
     msbwt_rle *h = f.h;
-    return two_pass(
+    const int rc = two_pass(
         f, ~0ull, nullptr, "k-mers", false, [&](uint64_t *n) { return count_nodes(f, kUnitigShape, cut, n); },
         [&](uint64_t n) -> int {
             const UnitigNodeLayout at = unitig_node_layout(n);
@@ -721,9 +790,11 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
             const uint64_t U = n - c[kUnitigLinks] + c[kUnitigCircular], S = n + U * (k - 1);
             const uint64_t info[MSBWT_UNITIG_INFO_WORDS] = {n, c[kUnitigEdges], c[kUnitigLinks], U, S, c[kUnitigCircular], c[kUnitigLongest], rounds};
             std::copy(info, info + MSBWT_UNITIG_INFO_WORDS, h->unitig_info);
+            if (links) links->expect = 2 * (c[kUnitigEdges] - c[kUnitigLinks] + c[kUnitigCircular]);  // (every edge that is no link, and a closing link, from both its ends)
             return out.emit(f, g, cur, other, block + at.tiles, U, S, false);
         },
         [&](uint64_t) { return out.deliver(f); });
+    return out.close(f, rc);
 }
 
 // ---- canonical unitigs ----
@@ -733,10 +804,10 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
 // slots, with the cuts behind the links and the choice between a unitig and its mirror behind the ranking (canonical_unitigs.hpp).
 int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums,
                       void *out_ends, void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total,
-                      hipStream_t stream) {
-    Frame f(bwt, "enumerate_canonical_unitigs", k, host, stream);
+                      hipStream_t stream, UnitigLinkOutputs *links = nullptr) {
+    Frame f(bwt, links ? "enumerate_canonical_unitig_graph" : "enumerate_canonical_unitigs", k, host, stream);
     const GraphCut cut(min_count, min_edge);
-    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total};
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links};
     if (int rc = out.open(f, cut, &msbwt_rle::canonical_unitig_info,
                           [&] { return k > 31 ? f.refuse(" needs 1 <= k <= 31 (an edge is a packed (k+1)-mer)") : int(MSBWT_OK); }))
         return rc;
@@ -747,7 +818,7 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
     classes.max = ~0ull;
     const uint64_t prune = cut.m / 2 + cut.m % 2;  // (enumerate_canonical: the member that emits a class has at least half of its count)
     uint64_t totals[kCanonicalTotalWords] = {};
-    return two_pass(
+    const int rc = two_pass(
         f, ~0ull, nullptr, "classes", true,
         [&](uint64_t *n) -> int {
             if (int rc = take_scratch(f, kCanonicalUnitigShape)) return rc;
@@ -820,6 +891,7 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
             return out.emit(f, g, cur, other, block + at.tiles, U, S, true);
         },
         [&](uint64_t) { return out.deliver(f); });
+    return out.close(f, rc);
 }
 
 // what a family's last call on the handle left in its info words
@@ -1034,6 +1106,54 @@ int msbwt_rle_enumerate_canonical_unitigs_device(const msbwt_rle *bwt, size_t k,
 }
 
 int msbwt_rle_canonical_unitig_info(const msbwt_rle *bwt, uint64_t *out) { return info_words(bwt, &msbwt_rle::canonical_unitig_info, out); }
+
+// ---- unitig graphs: either unitig call with the link table of the compacted graph behind it ----
+
+int msbwt_rle_enumerate_unitig_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols, uint64_t *out_offsets,
+                                     uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags, uint64_t *out_link_offsets, uint64_t *out_link_targets,
+                                     uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                     uint64_t *out_links) {
+    UnitigLinkOutputs links{out_link_offsets, out_link_targets, capacity_links, out_links, false};
+    return unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs,
+                   out_symbol_total, nullptr, &links);
+}
+
+int msbwt_rle_enumerate_unitig_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols, void *d_out_offsets,
+                                            void *d_out_count_sums, void *d_out_ends, void *d_out_flags, void *d_out_link_offsets, void *d_out_link_targets,
+                                            uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                            uint64_t *out_links, void *hip_stream) {
+    UnitigLinkOutputs links{d_out_link_offsets, d_out_link_targets, capacity_links, out_links, false};
+    return unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs, capacity_symbols,
+                   out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream), &links);
+}
+
+int msbwt_rle_enumerate_canonical_unitig_graph(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols, uint64_t *out_offsets,
+                                               uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags, uint64_t *out_link_offsets, uint64_t *out_link_targets,
+                                               uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs,
+                                               uint64_t *out_symbol_total, uint64_t *out_links) {
+    UnitigLinkOutputs links{out_link_offsets, out_link_targets, capacity_links, out_links, true};
+    return canonical_unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols,
+                             out_unitigs, out_symbol_total, nullptr, &links);
+}
+
+int msbwt_rle_enumerate_canonical_unitig_graph_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols, void *d_out_offsets,
+                                                      void *d_out_count_sums, void *d_out_ends, void *d_out_flags, void *d_out_link_offsets, void *d_out_link_targets,
+                                                      uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs,
+                                                      uint64_t *out_symbol_total, uint64_t *out_links, void *hip_stream) {
+    UnitigLinkOutputs links{d_out_link_offsets, d_out_link_targets, capacity_links, out_links, true};
+    return canonical_unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs,
+                             capacity_symbols, out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream), &links);
+}
+
+// the host call that fills every buffer, the two link arrays included (none of unitigs, symbols and links: the counting call)
+int msbwt_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t links, uint64_t *device_bytes) {
+    return unitig_graph_plan(kUnitigShape, unitig_node_layout(nodes).bytes, total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, device_bytes);
+}
+
+int msbwt_canonical_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t links,
+                                      uint64_t *device_bytes) {
+    return unitig_graph_plan(kCanonicalUnitigShape, canonical_unitig_layout(classes).bytes, total_rows, free_hbm_bytes, classes, unitigs, symbols, links, device_bytes);
+}
 
 // the host call over `classes` classes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)
 int msbwt_canonical_unitigs_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t *device_bytes) {

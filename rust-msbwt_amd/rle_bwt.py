@@ -573,6 +573,60 @@ class RleBWT(BWT):
         return self._info(_lib.lib().msbwt_rle_canonical_unitig_info,
                           ("classes", "edge_classes", "links", "unitigs", "symbols", "circular", "longest", "rounds", "palindromes", "cut_links"))
 
+    # ---- unitig links: either unitig call with the compacted graph's edges behind its columns ----
+    def enumerate_unitig_graph(self, k, min_count=1, min_edge=None, canonical=False, text=False):
+        """msbwt_rle_enumerate_[canonical_]unitig_graph, both calls of the two-call pattern -> what enumerate_unitigs (canonical=True:
+        enumerate_canonical_unitigs) returns, plus (link_offsets, link_targets): side 2u leaves unitig u forwards, side 2u + 1 leaves its
+        reverse complement forwards, and side a holds link_targets[link_offsets[a]:link_offsets[a + 1]], one entry 2v + o per edge in
+        A C G T order of the appended symbol: the edge reaches the first node of v (o = 0) or the reverse complement of its last node
+        (o = 1).  canonical: flags[u] bit 1 = the unitig is its own reverse complement and has one side.  unitig_link_records keeps
+        every edge once, write_gfa writes the graph."""
+        fn = _lib.lib().msbwt_rle_enumerate_canonical_unitig_graph if canonical else _lib.lib().msbwt_rle_enumerate_unitig_graph
+        args = (int(k), int(min_count), int(min_edge or 0))
+        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = fn(self._h, *args, None, None, None, None, None, None, None, 0, 0, 0, C.byref(U), C.byref(S), C.byref(L))
+        if rc:
+            _raise(rc, self._h)
+        symbols, offsets = np.zeros(S.value, dtype=np.uint8), np.zeros(U.value + 1, dtype=np.uint64)
+        sums, ends, flags = np.zeros(U.value, dtype=np.uint64), np.zeros(U.value, dtype=np.uint8), np.zeros(U.value, dtype=np.uint8)
+        link_offsets, link_targets = np.zeros(2 * U.value + 1, dtype=np.uint64), np.zeros(L.value, dtype=np.uint64)
+        if U.value:
+            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in (symbols, offsets, sums, ends, flags, link_offsets, link_targets)], U.value, S.value, L.value,
+                    C.byref(U), C.byref(S), C.byref(L))
+            if rc:
+                _raise(rc, self._h)
+        if not text:
+            return symbols, offsets, sums, ends, flags, link_offsets, link_targets
+        letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
+        return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags, link_offsets, link_targets
+
+    def _unitig_graph_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols,
+                             capacity_links, min_count, min_edge, stream):
+        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets,
+                int(capacity_unitigs), int(capacity_symbols), int(capacity_links), C.byref(U), C.byref(S), C.byref(L), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n, err.symbols, err.links = U.value, S.value, L.value
+                raise
+        return U.value, S.value, L.value
+
+    def enumerate_unitig_graph_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols,
+                                      capacity_links, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_enumerate_unitig_graph_device: device pointers (ints, each may be None; the byte arrays at any alignment) ->
+        (U, S, L); all three capacities 0 only counts, a capacity too small raises (nothing written; the error carries .n = U,
+        .symbols = S and .links = L).  Synchronises `stream`."""
+        return self._unitig_graph_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets,
+                                         d_link_targets, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge, stream)
+
+    def enumerate_canonical_unitig_graph_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs,
+                                                capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_enumerate_canonical_unitig_graph_device: as enumerate_unitig_graph_device."""
+        return self._unitig_graph_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
+                                         d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge, stream)
+
     def spectrum_scratch_bytes(self):
         """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""
         out = C.c_uint64(0)
@@ -1160,6 +1214,46 @@ def graph_predecessors(words, edges, k):
     """(index, neighbours): for every predecessor bit j of edges[i], in the order of i then j, the record i and the 2-bit word of the
     node the edge j.words[i] comes from (j, then words[i] without its last symbol).  Pure host logic."""
     return _graph_neighbours(words, edges, k, False)
+
+
+def unitig_link_records(link_offsets, link_targets, flags):
+    """(side, target): the records of a link table (RleBWT.enumerate_unitig_graph) with every bidirected edge kept once.  The record
+    (a, e) -- side a holds entry e -- has the mirror (c(e ^ 1), c(a ^ 1)), the same edge from its other end, where c clears bit 0 for a
+    unitig that is its own reverse complement (flags bit 1); a record stays when it is not above its mirror, compared as pairs.  In table
+    order.  Pure host logic."""
+    link_offsets, link_targets = np.ascontiguousarray(link_offsets, dtype=np.uint64), np.ascontiguousarray(link_targets, dtype=np.uint64)
+    own_mirror = (np.ascontiguousarray(flags, dtype=np.uint8) & np.uint8(2)) != 0
+    if link_offsets.size != 2 * own_mirror.size + 1 or int(link_offsets[-1]) != link_targets.size:
+        raise ValueError("a link table has 2 U + 1 offsets, the last of which is the number of its targets")
+    sides = np.repeat(np.arange(2 * own_mirror.size, dtype=np.uint64), np.diff(link_offsets).astype(np.int64))
+    one = np.uint64(1)
+
+    def c(x):
+        return np.where(own_mirror[(x >> one).astype(np.int64)], x & ~one, x)
+
+    mirror_side, mirror_target = c(link_targets ^ one), c(sides ^ one)
+    keep = (sides < mirror_side) | ((sides == mirror_side) & (link_targets <= mirror_target))
+    return sides[keep], link_targets[keep]
+
+
+def write_gfa(file, k, symbols, offsets, count_sums, flags, link_offsets, link_targets):
+    """The compacted graph of RleBWT.enumerate_unitig_graph as GFA 1: a header, one `S <u> <sequence> KC:i:<count sum>` line a unitig
+    (named by its number) and one `L <u> <+|-> <v> <+|-> <k-1>M` line per edge, each edge once (unitig_link_records): an odd side leaves
+    the reverse complement (-), an odd entry reaches one.  `file`: a path, or an object with write().  -> (segments, links) written."""
+    k = int(k)
+    letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[np.ascontiguousarray(symbols, dtype=np.uint8)].tobytes().decode()
+    sides, targets = unitig_link_records(link_offsets, link_targets, flags)
+    lines = ["H\tVN:Z:1.0\n"]
+    for u, (a, z) in enumerate(zip(offsets[:-1], offsets[1:])):
+        lines.append("S\t%d\t%s\tKC:i:%d\n" % (u, letters[int(a):int(z)], int(count_sums[u])))
+    for a, e in zip(sides.tolist(), targets.tolist()):
+        lines.append("L\t%d\t%s\t%d\t%s\t%dM\n" % (a >> 1, "-" if a & 1 else "+", e >> 1, "-" if e & 1 else "+", k - 1))
+    if hasattr(file, "write"):
+        file.write("".join(lines))
+    else:
+        with open(file, "w") as out:
+            out.write("".join(lines))
+    return len(offsets) - 1, len(sides)
 
 
 def count_read_kmers_multi(replicas, reads, k, ascii=False, forward=True, revcomp=False):

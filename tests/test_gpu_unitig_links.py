@@ -1,0 +1,311 @@
+"""Unitig links (csrc/unitig_links.hip and its driver in csrc/spectrum.cpp): the link table msbwt_rle_enumerate_unitig_graph and
+msbwt_rle_enumerate_canonical_unitig_graph return behind the five columns of the unitig calls.
+
+Every expected value comes from tests/link_oracle.py over the unitigs of an oracle (the string oracles of test_gpu_unitigs.py and
+test_gpu_canonical_unitigs.py on small sets, tests/graph_oracle.py on large ones); tests/test_link_oracle.py holds that table to a brute
+force over strings on the CPU.  Nothing expected comes from the library; the five shared columns and the info words are ALSO compared
+with what the existing unitig call returns on the same handle.
+
+1. The hand-made sets of link_oracle.HAND_MADE at k = 1 ... 5, 31 and 32, both calls: every edge present (four entries a side), a
+   circular unitig of one node, isolated circles, a hairpin edge, a palindromic node with neighbours on both ends, the header's
+   {"CATG"}, reads of $ and N only, k = 1, a branch at a word whose top bits are set; and the empty index.
+2. The ragged sets of test_gpu_unitigs.test_ragged_sets_at_every_k at its k (the canonical call up to 31) under (1, 0) and (2, 3).
+3. Loop trips.  45 000 random reads of 150 symbols at k = 11 hold three quarters of all 11-mers, more than half of them branching:
+   asserted from the oracle before the library is called, more than 524 288 slots (the second grid-stride trip of the degrees and
+   the targets), more than 2048 unitigs, more than 2 097 152 sides (the second round of k_scan_tile_sums<2>) and more than 4 194 304
+   (the second trip of k_link_tile_sums and k_link_scan).  The plain call runs it: the scan is the same for both calls, and the
+   canonical oracle of this set alone takes 10 s.  The canonical call goes round its slot loops on scale_set() of
+   test_gpu_graph_scale.py at k = 21 under (2, 3) -- 1.2e6 slots, 2e5 unitigs, long chains, circles, next to no edge left -- and under
+   (1, 0), with more than 1000 branching nodes; both calls run both under the automatic frontier and one of 65 536.
+4. The contract: the ladder of each of the three capacities, NULL buffers one by one, tails behind sentinels, the _device forms with
+   byte pointers at odd addresses, another index form, the minimum frontier, msbwt_rle_spectrum_scratch_bytes against the plans for the
+   host, device and counting forms, the existing calls after a new one, msbwt_rle_device_bytes.
+
+There is no case past 2^32 rows: nothing the link kernels add takes a row number -- they work over slots, unitig numbers, sides and
+offsets, all below 2^32 on any index that fits the card -- and the walks before them are those tests/test_gpu_graph_scale.py covers.
+Run with `pytest -m gpu`."""
+import ctypes as C
+import importlib
+import time
+
+import numpy as np
+import pytest
+
+import graph_oracle as G
+import link_oracle as L
+from test_gpu_canonical_unitigs import canonical_unitigs_of_texts
+from test_gpu_graph_scale import FRONTIERS, SCAN_ROUND, TILE_TRIP, TRIP, scale_index, scale_want
+from test_gpu_kmer_graph import FORMS
+from test_gpu_reads_build import ragged_set, read_set
+from test_gpu_spectrum import loaded
+from test_gpu_unitigs import KS, unitigs_of_texts
+
+pytestmark = pytest.mark.gpu
+
+msbwt = importlib.import_module("rust-msbwt_amd")
+_lib = msbwt._lib
+MsbwtError = msbwt.MsbwtError
+U64 = np.uint64
+NAMES = G.NAMES + ("link_offsets", "link_targets")
+
+
+def expected(unitigs, k, canonical):
+    """the seven columns: the oracle's five, the flags with bit 1, and the link table"""
+    offsets, targets, flags = L.link_table(unitigs, k, canonical)
+    want = {x: unitigs[x] for x in G.NAMES}
+    want.update(flags=flags, link_offsets=offsets, link_targets=targets, info=unitigs["info"])
+    return want
+
+
+def check_graph_call(b, k, want, canonical, min_count=1, min_edge=0, where=None):
+    """the new call against the oracle, then against the existing call on the same handle: columns, info words"""
+    where = where or (k, min_count, min_edge, canonical)
+    got = b.enumerate_unitig_graph(k, min_count=min_count, min_edge=min_edge or None, canonical=canonical)
+    for name, g in zip(NAMES, got):
+        assert g.dtype == want[name].dtype and g.shape == want[name].shape, (where, name, g.shape, want[name].shape)
+        bad = np.flatnonzero(g != want[name])
+        assert bad.size == 0, (where, name, bad[:5], g[bad[:5]], want[name][bad[:5]])
+    report = b.canonical_unitig_info if canonical else b.unitig_info
+    info = report()
+    old = (b.enumerate_canonical_unitigs if canonical else b.enumerate_unitigs)(k, min_count=min_count, min_edge=min_edge or None)
+    assert report() == info, where
+    if want["info"]["classes" if canonical else "nodes"]:
+        assert {x: info[x] for x in want["info"]} == want["info"], where
+    else:
+        assert not any(info.values()), where
+    for name, g, o in zip(G.NAMES, got, old):
+        assert (g & 1 if name == "flags" else g).tobytes() == o.tobytes(), (where, name)
+    return got
+
+
+# ---- 1. the hand-made sets ----
+
+_built = {}
+
+
+def built(reads):
+    key = tuple(reads)
+    if key not in _built:
+        b = msbwt.RleBWT(device=0)
+        b.load_reads(list(reads), ascii=True)
+        _built[key] = b
+    return _built[key]
+
+
+@pytest.mark.parametrize("name", sorted(L.HAND_MADE))
+def test_hand_made_sets(name):
+    entries = 0
+    for _, reads, k, min_count, min_edge, canonical in (x for x in L.hand_made_cases() if x[0] == name):
+        unitigs = (canonical_unitigs_of_texts if canonical else unitigs_of_texts)(reads, k, min_count, min_edge)
+        want = expected(unitigs, k, canonical)
+        got = check_graph_call(built(reads), k, want, canonical, min_count, min_edge, where=(name, k, min_count, min_edge, canonical))
+        entries += len(got[6])
+        if name == "every edge present" and not canonical:
+            assert len(got[2]) == 4 ** k and (np.diff(got[5].astype(np.int64)) == 4).all()
+        if name == "a circular unitig of one node":
+            assert got[5].tolist() == [0, 1, 2] and got[6].tolist() == [0, 1] and got[4].tolist() == [1]
+    assert (entries == 0) == (name == "no node at all")
+
+
+def test_the_cases_of_the_header_and_the_empty_index():
+    from test_gpu_merge_many import EMPTY
+    table = lambda got: L.sides_of(got[5], got[6])
+    got = built(["CATG"]).enumerate_unitig_graph(2, min_count=2, canonical=True)
+    assert table(got) == [[], []] and got[4].tolist() == [0]  # AT is no node: ATG is no edge
+    got = built(["AATT"]).enumerate_unitig_graph(3, canonical=True)
+    assert table(got) == [[1], []] and got[4].tolist() == [0]  # the hairpin AAT -> ATT
+    got = built(["GGACGTCC"]).enumerate_unitig_graph(4, canonical=True, text=True)
+    assert got[0] == ["ACGT", "CGTCC"] and got[3].tolist() == [2, 0] and L.sides_of(got[4], got[5]) == [[2], [], [], [0]]
+    got = built(["GGACGTCC"]).enumerate_unitig_graph(4)
+    assert not (got[4] & 2).any()  # the plain call never sets bit 1
+    empty = loaded(EMPTY)
+    lib, u, s, n = _lib.lib(), C.c_uint64(7), C.c_uint64(7), C.c_uint64(7)
+    for canonical in (False, True):
+        for k in (1, 21, 31):
+            got = empty.enumerate_unitig_graph(k, canonical=canonical)
+            assert [len(a) for a in got] == [0, 1, 0, 0, 0, 1, 0] and got[1].tolist() == [0] and got[5].tolist() == [0]
+        fn = lib.msbwt_rle_enumerate_canonical_unitig_graph if canonical else lib.msbwt_rle_enumerate_unitig_graph
+        side = np.full(3, 7, dtype=U64)
+        assert fn(empty._h, 5, 1, 0, None, None, None, None, None, side.ctypes.data_as(C.c_void_p), None, 4, 4, 4, C.byref(u), C.byref(s), C.byref(n)) == 0
+        assert (u.value, s.value, n.value) == (0, 0, 0) and side.tolist() == [0, 7, 7]  # U = S = L = 0 and out_link_offsets[0] = 0
+        assert not any((empty.canonical_unitig_info if canonical else empty.unitig_info)().values())
+
+
+# ---- 2. ragged sets ----
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 5, 11])
+def test_ragged_sets_at_every_k(seed):
+    reads = ragged_set(seed)
+    b = built(reads)
+    entries = 0
+    for k in KS:
+        for min_count, min_edge in L.PAIRS:
+            for canonical in (False, True) if k <= 31 else (False,):
+                unitigs = (canonical_unitigs_of_texts if canonical else unitigs_of_texts)(reads, k, min_count, min_edge)
+                got = check_graph_call(b, k, expected(unitigs, k, canonical), canonical, min_count, min_edge, where=(seed, k, min_count, min_edge, canonical))
+                entries += len(got[6])
+    assert entries > 100
+
+
+# ---- 3. loop trips ----
+
+DENSE_READS, DENSE_READ, DENSE_K = 45000, 150, 11
+_dense = {}
+
+
+def dense_set():
+    """(the oracle's expected columns, a handle), made once; the sizes asserted from the oracle first"""
+    if not _dense:
+        t0 = time.perf_counter()
+        flat = G.SYMBOL[np.random.default_rng(11).integers(0, 4, size=DENSE_READS * DENSE_READ)]
+        reads = list(flat.reshape(DENSE_READS, DENSE_READ))
+        cen = G.census(reads, DENSE_K)
+        plain = G.unitigs_of_census(cen, DENSE_K)
+        U = plain["info"]["unitigs"]
+        assert plain["info"]["nodes"] > TRIP  # the second grid-stride trip of the slot-strided kernels
+        assert U > 2048
+        assert 2 * U + 1 > TILE_TRIP > SCAN_ROUND  # the second trip of k_link_tile_sums and k_link_scan, the second round of k_scan_tile_sums<2>
+        assert plain["branching"] > plain["info"]["nodes"] // 2
+        want = expected(plain, DENSE_K, False)
+        assert len(want["link_targets"]) > 5 * 10 ** 6
+        b = msbwt.RleBWT(device=0)
+        t1 = time.perf_counter()
+        b.load_reads((flat, np.arange(DENSE_READS + 1, dtype=U64) * U64(DENSE_READ)))
+        print("dense set: %d nodes, %d unitigs, %d entries; oracle %.1f s, load_reads %.2f s"
+              % (plain["info"]["nodes"], U, len(want["link_targets"]), t1 - t0, time.perf_counter() - t1))
+        _dense.update(want=want, b=b)
+    return _dense["want"], _dense["b"]
+
+
+def test_links_at_multi_trip_sizes():
+    want, b = dense_set()
+    t0 = time.perf_counter()
+    got = check_graph_call(b, DENSE_K, want, False)
+    print("plain: %d unitigs, %d entries, %.2f s" % (len(got[2]), len(got[6]), time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("frontier", sorted(FRONTIERS))
+def test_links_of_the_scale_set(frontier):
+    k = 21
+    wants = {(pair, canonical): scale_want("canonical" if canonical else "plain", k, pair) for pair in ((2, 3), (1, 0)) for canonical in (False, True)}
+    for unitigs in wants.values():
+        lengths = np.diff(unitigs["offsets"].astype(np.int64)) - (k - 1)
+        assert lengths.max() > 1000 and unitigs["info"]["circular"] >= 1  # chains and circles outlast the thresholds
+    assert wants[(2, 3), False]["info"]["nodes"] > TRIP and wants[(2, 3), True]["slots"] > TRIP and wants[(2, 3), True]["info"]["unitigs"] > 2048
+    assert wants[(1, 0), False]["branching"] >= 1000  # (under (2, 3) next to no edge is left: (1, 0) runs beside it)
+    b = scale_index(False)
+    b.set_spectrum_frontier(FRONTIERS[frontier])
+    try:
+        for (pair, canonical), unitigs in wants.items():
+            t0 = time.perf_counter()
+            got = check_graph_call(b, k, expected(unitigs, k, canonical), canonical, *pair, where=(frontier, pair, canonical))
+            assert b.spectrum_info()["chunks"] >= (2 if FRONTIERS[frontier] else 1) and (pair != (1, 0) or len(got[6]) > 1000)
+            print("scale set, %s, %s, %s: %d unitigs, %d entries, %.2f s"
+                  % (frontier, pair, "canonical" if canonical else "plain", len(got[2]), len(got[6]), time.perf_counter() - t0))
+    finally:
+        b.set_spectrum_frontier(0)
+
+
+# ---- 4. the contract ----
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+_contract = {}
+
+
+def contract_set(canonical):
+    name, k, min_count = "plain_100", 17, 2
+    if canonical not in _contract:
+        (flat, offsets), _ = read_set(name)
+        reads = [flat[int(a):int(z)] for a, z in zip(offsets[:-1], offsets[1:])]
+        unitigs = (G.canonical_unitigs_of_codes if canonical else G.unitigs_of_codes)(reads, k, min_count)
+        _contract[canonical] = expected(unitigs, k, canonical)
+    return read_set(name)[1], k, min_count, _contract[canonical]
+
+
+@pytest.mark.parametrize("canonical", [False, True], ids=["plain", "canonical"])
+def test_capacity_and_null_buffers(canonical):
+    import torch
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rle, k, min_count, want = contract_set(canonical)
+    n, U, S, Ln = want["info"]["classes" if canonical else "nodes"], want["info"]["unitigs"], want["info"]["symbols"], len(want["link_targets"])
+    assert U > 50 and n > 10000 and Ln > 50
+    b = loaded(rle)
+    lib, got_u, got_s, got_l = _lib.lib(), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    host_fn = lib.msbwt_rle_enumerate_canonical_unitig_graph if canonical else lib.msbwt_rle_enumerate_unitig_graph
+    device = b.enumerate_canonical_unitig_graph_device if canonical else b.enumerate_unitig_graph_device
+    total, before, free = b.get_total_size(), b.device_bytes(), torch.cuda.mem_get_info(0)[0]
+    plan = lambda *a: msbwt.unitig_graph_plan(total, free, *a, canonical=canonical)
+    old_plan = lambda *a: (msbwt.canonical_unitigs_plan if canonical else msbwt.unitigs_plan)(total, free, *a)
+    sizes = {"symbols": S, "offsets": U + 1, "count_sums": U, "ends": U, "flags": U, "link_offsets": 2 * U + 1, "link_targets": Ln}
+    staged = {"symbols": 8 * ((S + 7) // 8), "offsets": 0, "count_sums": 8 * U, "ends": 8 * ((U + 7) // 8), "flags": 8 * ((U + 7) // 8), "link_offsets": 0, "link_targets": 8 * Ln}
+    # the plans are the unitig plans and the terms of the header
+    assert plan(n) == plan(n, 0, 0, 0) == old_plan(n)
+    assert plan(n, U, S, Ln) == old_plan(n, U, S) + 16 * U + 256 + 16 * ((2 * U + 1 + 2047) // 2048) + 8 * Ln
+
+    def host(cap_u, cap_s, cap_l, skip=()):
+        bufs = {x: np.full(sizes[x] + 3, 7, dtype=want[x].dtype) for x in NAMES}
+        args = [_ptr(bufs[x]) if x not in skip else None for x in NAMES]
+        return host_fn(b._h, k, min_count, 0, *args, cap_u, cap_s, cap_l, C.byref(got_u), C.byref(got_s), C.byref(got_l)), bufs
+
+    # the counting call reports L; a capacity too small (each of the three) writes nothing and names U, S and L
+    rc, bufs = host(0, 0, 0)
+    assert rc == 0 and (got_u.value, got_s.value, got_l.value) == (U, S, Ln) and all((a == 7).all() for a in bufs.values())
+    assert b.spectrum_scratch_bytes() == plan(n)
+    for caps in ((U - 1, S, Ln), (U, S - 1, Ln), (U, S, Ln - 1), (1, 1, 1), (0, S, Ln), (U, 0, Ln), (U, S, 0), (0, 0, Ln)):
+        got_u.value = got_s.value = got_l.value = 0
+        rc, bufs = host(*caps)
+        message = lib.msbwt_rle_last_error(b._h)
+        assert rc == _lib.ERR_INVALID_ARG and (got_u.value, got_s.value, got_l.value) == (U, S, Ln), caps
+        assert all(str(x).encode() in message for x in (U, S, Ln)) and all((a == 7).all() for a in bufs.values()), caps
+    # every output NULL in turn, and all at once; capacities above need
+    for skip in ((),) + tuple((x,) for x in NAMES) + (NAMES,):
+        rc, bufs = host(U + 2, S + 2, Ln + 2, skip)
+        assert rc == 0 and (got_u.value, got_s.value, got_l.value) == (U, S, Ln), skip
+        for x in NAMES:
+            assert (bufs[x][sizes[x]:] == 7).all() and (np.array_equal(bufs[x][:sizes[x]], want[x]) if x not in skip else (bufs[x] == 7).all()), (skip, x)
+        assert b.spectrum_scratch_bytes() == plan(n, U, S, Ln) - sum(staged[x] for x in skip), skip
+    assert host(U, 0, Ln, ("symbols",))[0] == 0 and host(U, S, 0, ("link_targets",))[0] == 0  # a buffer not wanted: its capacity does not matter
+    # the device form: the same, into buffers of the caller's; the byte arrays at odd addresses
+    assert device(k, None, None, None, None, None, None, None, 0, 0, 0, min_count=min_count, stream=stream) == (U, S, Ln)
+    assert b.spectrum_scratch_bytes() == plan(n)
+    words = ("offsets", "count_sums", "link_offsets", "link_targets")
+    for skip in ((), ("flags",), ("link_offsets",), ("link_targets",)):
+        bufs = {x: torch.full((sizes[x] + 9,), 7, dtype=torch.int64 if x in words else torch.uint8, device=dev) for x in NAMES}
+        ptrs = [None if x in skip else bufs[x].data_ptr() + (0 if x in words else 1) for x in NAMES]
+        for caps in ((U - 1, S, Ln), (U, S - 1, Ln), (U, S, Ln - 1)):
+            if caps[2] < Ln and "link_targets" in skip:
+                continue
+            with pytest.raises(MsbwtError) as err:
+                device(k, *ptrs, *caps, min_count=min_count, stream=stream)
+            assert err.value.code == _lib.ERR_INVALID_ARG and (err.value.n, err.value.symbols, err.value.links) == (U, S, Ln) and str(Ln) in str(err.value)
+            assert all(bool((bufs[x] == 7).all()) for x in NAMES)
+        assert device(k, *ptrs, U + 1, S + 1, Ln + 1, min_count=min_count, stream=stream) == (U, S, Ln)
+        b.device_status(stream)
+        assert b.spectrum_scratch_bytes() == plan(n, U, S, Ln) - sum(staged.values())  # nothing staged
+        for x in NAMES:
+            got, lead = bufs[x].cpu().numpy(), 0 if x in words else 1
+            if x in skip:
+                assert (got == 7).all(), (skip, x)
+            else:
+                assert (got[:lead] == 7).all() and (got[lead + sizes[x]:] == 7).all() and np.array_equal(got[lead:lead + sizes[x]].astype(want[x].dtype), want[x]), (skip, x)
+    assert b.device_bytes() == before
+    # the existing call after the new ones: its bytes, its scratch
+    old = (b.enumerate_canonical_unitigs if canonical else b.enumerate_unitigs)(k, min_count=min_count)
+    assert all(np.array_equal(o, want[x] & 1 if x == "flags" else want[x]) for x, o in zip(G.NAMES, old)) and b.spectrum_scratch_bytes() == old_plan(n, U, S)
+    # the guards behind "nothing loaded", in the order of the unitig calls
+    none = (None,) * 7
+    for bad_k in (0, 32 if canonical else 33, 1000):
+        assert host_fn(b._h, bad_k, 1, 0, *none, 0, 0, 0, C.byref(got_u), C.byref(got_s), C.byref(got_l)) == _lib.ERR_INVALID_ARG
+    assert host_fn(b._h, k, 3, 2, *none, 0, 0, 0, C.byref(got_u), C.byref(got_s), C.byref(got_l)) == _lib.ERR_INVALID_ARG
+    assert host_fn(b._h, k, 1, 0, *none, 0, 0, 0, None, C.byref(got_s), C.byref(got_l)) == _lib.ERR_INVALID_ARG
+    assert host_fn(b._h, k, 0, 0, *none, 0, 0, 0, C.byref(got_u), None, None) == 0  # the two totals are optional
+    # the minimum frontier, and another index form: the same bytes
+    b.set_spectrum_frontier(_lib.SPECTRUM_MIN_FRONTIER)
+    check_graph_call(b, k, want, canonical, min_count, where="minimum frontier")
+    assert b.spectrum_info()["chunks"] > 1
+    b.set_spectrum_frontier(0)
+    check_graph_call(loaded(rle, **FORMS["run blocks"]), k, want, canonical, min_count, where="run blocks")

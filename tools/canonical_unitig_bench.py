@@ -14,7 +14,9 @@ At min_count = 2 (`--check-min-count`) U, S and a fixed sample of 65 536 unitigs
 the canonical dumps at k and at k + 1 (classes and edge classes), single-threaded: both members of every class sorted, the edge bytes
 with the both-ends clause, links with the two cuts, pointer jumping, min-label opening of cycles, the choice by head slots, numbering,
 emission.  A mismatch fails the tool.  One JSON line per (k, min_count) and a closing summary line; no threshold on the times.
-A driver that wants each GPU step under its own time limit runs one (k, min_count) per process: --ks 21 --min-counts 2."""
+A driver that wants each GPU step under its own time limit runs one (k, min_count) per process: --ks 21 --min-counts 2.
+`--links` prints the link lines of tools/unitig_bench.py INSTEAD, for the canonical call: enumerate_canonical_unitig_graph_device beside
+enumerate_canonical_unitigs_device in the same rounds, and the host route (the unitig call to host arrays, then the numpy join)."""
 import argparse
 import json
 import os
@@ -31,7 +33,7 @@ import rust_msbwt_amd as msbwt  # noqa: E402
 from canonical_bench import COMPLEMENT  # noqa: E402
 from kmer_graph_bench import spread, wall  # noqa: E402
 from reads_build_bench import read_set  # noqa: E402
-from unitig_bench import CODE, LOW, POP, rank_by_jumping  # noqa: E402
+from unitig_bench import CODE, LOW, POP, finish_links, link_lines, rank_by_jumping  # noqa: E402
 
 SAMPLE = 1 << 16
 U64 = np.uint64
@@ -138,6 +140,7 @@ def pair_mirrors(symbols, offsets, k):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--links", action="store_true", help="the link lines in place of the others: enumerate_canonical_unitig_graph_device beside the unitig call")
     ap.add_argument("--config", default="c4")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--ks", default="21,31")
@@ -159,6 +162,10 @@ def main():
     (_, load_ms) = wall(lambda: b.load_reads((reads.reshape(-1), np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(length))))
     del reads
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if args.links:
+        lines, same = link_lines(b, args, True, dev, stream)
+        finish_links(args, lines, same, load_ms)
+        return
     lines, same = [], True
     for k in [int(x) for x in args.ks.split(",")]:
         for m in [int(x) for x in args.min_counts.split(",")]:

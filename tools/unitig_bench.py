@@ -12,7 +12,13 @@ within a round (median and spread, wall clock around calls that end in a synchro
              Timed once per window, and only for windows of at most `--host-max-nodes` nodes.
 U and S of (i) and (iii) must agree, and so must the sequences, count sums, ends and flags of a fixed sample of unitigs: a mismatch
 fails the tool.  One JSON line per (k, min_count) with unitig_info and the scratch bytes, and a closing summary line; no threshold on
-the times."""
+the times.
+`--links` prints the link lines INSTEAD (tools/canonical_unitig_bench.py --links: the same for the canonical call), per (k, min_count):
+  graph      enumerate_unitig_graph_device: the five columns and the link table into device buffers
+  unitigs    beside it in the same rounds, enumerate_unitigs_device: what the link table adds is the difference
+  host       the route a caller had before, timed once: the unitig call to host arrays, then a numpy join of the end k-mers against the
+             first k-mers (the successors of every last word looked up among the first words and the mirrored last words)
+The two link tables must be equal, word for word: a mismatch fails the tool."""
 import argparse
 import json
 import os
@@ -113,8 +119,106 @@ def host_compaction(words, counts, edges, k):
     return symbols, offsets, sums, ends, flags, rounds
 
 
+REVERSED = np.array([int("{:04b}".format(x)[::-1], 2) for x in range(16)], dtype=np.uint8)  # a nibble with bit j at 3 - j
+
+
+def words_at(symbols, starts, k):
+    two = np.zeros(6, dtype=U64)
+    two[[1, 2, 3, 5]] = [0, 1, 2, 3]
+    w = np.zeros(len(starts), dtype=U64)
+    for j in range(k):
+        w = (w << U64(2)) | two[symbols[starts + j]]
+    return w
+
+
+def host_join(symbols, offsets, ends, k, canonical):
+    """the link table from a unitig call's host arrays -> (link_offsets, link_targets): side 2u leaves the last word of u along its
+    out-bits, side 2u + 1 the reverse complement of its first word along its in-bits mirrored; the word reached is looked up among the
+    first words (2v) and among the reverse complements of the last words (2v + 1)"""
+    rc2 = msbwt.rle_bwt.reverse_complement_2bit
+    first, last = words_at(symbols, offsets[:-1].astype(np.int64), k), words_at(symbols, offsets[1:].astype(np.int64) - k, k)
+    U = len(first)
+    mirrored_first, mirrored_last = rc2(first, k), rc2(last, k)
+    own_mirror = (first == last) & (mirrored_first == first) if canonical else np.zeros(U, dtype=bool)
+    order = np.argsort(mirrored_last, kind="stable")
+    mirrored_sorted = mirrored_last[order]
+    leaves = np.stack([last, mirrored_first], axis=1).reshape(2 * U)
+    bits = np.stack([ends >> 4, np.where(own_mirror, 0, REVERSED[ends & 15])], axis=1).reshape(2 * U)
+    present = ((bits[:, None] >> np.arange(4, dtype=np.uint8)[None, :]) & 1).astype(bool)
+    side, c = np.nonzero(present)
+    reached = (leaves[side] << U64(2)) | c.astype(U64)
+    if k < 32:
+        reached &= U64((1 << (2 * k)) - 1)
+    at_first = np.minimum(np.searchsorted(first, reached), U - 1)
+    at_last = order[np.minimum(np.searchsorted(mirrored_sorted, reached), U - 1)]
+    to_first = first[at_first] == reached if canonical else side % 2 == 0
+    link_offsets = np.zeros(2 * U + 1, dtype=U64)
+    np.cumsum(present.sum(axis=1), out=link_offsets[1:])
+    return link_offsets, np.where(to_first, 2 * at_first, 2 * at_last + 1).astype(U64)
+
+
+def link_lines(b, args, canonical, dev, stream):
+    """the --links lines of either tool -> (lines, all tables equal)"""
+    graph_device = b.enumerate_canonical_unitig_graph_device if canonical else b.enumerate_unitig_graph_device
+    unitigs_device = b.enumerate_canonical_unitigs_device if canonical else b.enumerate_unitigs_device
+    to_host = b.enumerate_canonical_unitigs if canonical else b.enumerate_unitigs
+    lines, same = [], True
+    for k in [int(x) for x in args.ks.split(",")]:
+        for m in [int(x) for x in args.min_counts.split(",")]:
+            U, S, L = graph_device(k, None, None, None, None, None, None, None, 0, 0, 0, min_count=m, stream=stream)
+            out = {"symbols": torch.empty(S, dtype=torch.uint8, device=dev), "offsets": torch.empty(U + 1, dtype=torch.int64, device=dev),
+                   "sums": torch.empty(U, dtype=torch.int64, device=dev), "ends": torch.empty(U, dtype=torch.uint8, device=dev),
+                   "flags": torch.empty(U, dtype=torch.uint8, device=dev), "link_offsets": torch.empty(2 * U + 1, dtype=torch.int64, device=dev),
+                   "link_targets": torch.empty(L, dtype=torch.int64, device=dev)}
+            ptrs = [x.data_ptr() for x in out.values()]
+            calls = {"graph": lambda: graph_device(k, *ptrs, U, S, L, min_count=m, stream=stream),
+                     "unitigs": lambda: unitigs_device(k, *ptrs[:5], U, S, min_count=m, stream=stream)}
+            for fn in calls.values():  # warm-up
+                fn()
+            ms = {name: [] for name in calls}
+            for _ in range(args.repeats):  # alternating
+                for name, fn in calls.items():
+                    _, t = wall(fn)
+                    ms[name].append(t)
+            b.device_status(stream)
+            assert calls["graph"]() == (U, S, L)
+            scratch = b.spectrum_scratch_bytes()
+            info = (b.canonical_unitig_info if canonical else b.unitig_info)()
+            res = {"links": True, "canonical": canonical, "k": k, "min_count": m, "symbols": int(b.get_total_size()), "info": info, "link_entries": L,
+                   "scratch_bytes": scratch, "graph_ms": spread(ms["graph"]), "unitigs_ms": spread(ms["unitigs"])}
+            res["links_add_ms"] = round(res["graph_ms"]["median"] - res["unitigs_ms"]["median"], 3)
+            res["ns_per_entry"] = round(1e6 * res["links_add_ms"] / max(L, 1), 2)
+            (theirs, dump_ms) = wall(lambda: to_host(k, min_count=m))
+            ((link_offsets, link_targets), join_ms) = wall(lambda: host_join(theirs[0], theirs[1], theirs[3], k, canonical))
+            res["host_ms"] = {"unitigs_to_host": round(dump_ms, 1), "join": round(join_ms, 1), "total": round(dump_ms + join_ms, 1)}
+            res["host_over_graph"] = round(res["host_ms"]["total"] / res["graph_ms"]["median"], 1)
+            ok = np.array_equal(out["link_offsets"].cpu().numpy().view(U64), link_offsets) and np.array_equal(out["link_targets"].cpu().numpy().view(U64), link_targets)
+            res["same_table"] = bool(ok)
+            same = same and bool(ok)
+            del theirs, link_offsets, link_targets, out
+            torch.cuda.empty_cache()
+            print(json.dumps(res), flush=True)
+            lines.append(res)
+    return lines, same
+
+
+def finish_links(args, lines, same, load_ms):
+    """the closing summary line of a --links run, the file, and the verdict"""
+    key = lambda r: "%d/%d" % (r["k"], r["min_count"])
+    summary = {"links": True, "config": args.config, "scale": args.scale, "load_reads_ms": round(load_ms, 1), "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+               "graph_ms": {key(r): r["graph_ms"]["median"] for r in lines}, "unitigs_ms": {key(r): r["unitigs_ms"]["median"] for r in lines},
+               "host_ms": {key(r): r["host_ms"]["total"] for r in lines}, "link_entries": {key(r): r["link_entries"] for r in lines}, "same": same}
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"lines": lines, "summary": summary}, f, indent=1)
+    if not same:
+        sys.exit("the host join and the device link table disagree")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--links", action="store_true", help="the link lines in place of the others: enumerate_unitig_graph_device beside enumerate_unitigs_device")
     ap.add_argument("--config", default="c4")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--ks", default="21,31")
@@ -134,6 +238,10 @@ def main():
     (_, load_ms) = wall(lambda: b.load_reads((reads.reshape(-1), np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(length))))
     del reads
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if args.links:
+        lines, same = link_lines(b, args, False, dev, stream)
+        finish_links(args, lines, same, load_ms)
+        return
     lines, same = [], True
     for k in [int(x) for x in args.ks.split(",")]:
         for m in [int(x) for x in args.min_counts.split(",")]:
