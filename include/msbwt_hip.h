@@ -713,6 +713,74 @@ int msbwt_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64
 int msbwt_canonical_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols,
                                       uint64_t links, uint64_t *device_bytes);
 
+/* ---- unitigs by source ---- the per-input abundance of every unitig: either unitig GRAPH call, on an index with sources attached
+ * (msbwt_rle_load_merged_many_sources, msbwt_rle_set_sources), with ONE MORE COLUMN behind the link table (no reference counterpart).
+ * The arguments are those of the graph call of the same kind in the same order, out_source_sums behind out_link_targets.
+ * S = msbwt_rle_source_count.  Write c_s(q) for the rows of source s in the FM range of the k-mer q, as msbwt_rle_range_sources
+ * defines them: the sum of c_s(q) over s is count_kmer(q).
+ *   out_source_sums   U x S words, row-major; may be NULL
+ * PLAIN CALL: out_source_sums[u S + s] = the sum of c_s(q) over the nodes q of unitig u.
+ * CANONICAL CALL: the same sum over the classes of u, a class {q, rc(q)} counting c_s(q) + c_s(rc(q)); a palindromic class
+ * (q == rc(q)) counts c_s(q) ONCE.  A member that does not occur in the index adds nothing.
+ * ROW SUMS: in both calls row u sums to out_count_sums[u].
+ * THRESHOLDS: min_count and min_edge meet the counts over all inputs together, exactly as in the graph calls: the graph is that of
+ * the union, and only this column looks at sources.
+ * The five columns and the link table are byte for byte what the graph call returns on the same index with the same arguments, and
+ * msbwt_rle_unitig_info / msbwt_rle_canonical_unitig_info are filled exactly as those calls fill them.
+ * Capacity: the graph call's.  The matrix needs capacity_unitigs >= U and has no capacity of its own; a refused call writes NOTHING,
+ * the matrix included, returns MSBWT_ERR_INVALID_ARG and names U, S (symbols) and L; all three capacities 0 only counts; the tail
+ * past U x S words stays untouched.  The _device form takes a device pointer.
+ * Guards, before the first HIP call: a NULL handle; nothing loaded (MSBWT_ERR_NOT_LOADED, "no BWT loaded"); no attachment
+ * (MSBWT_ERR_NOT_LOADED, "no sources attached"); k (1..32, canonical 1..31); the thresholds; *out_unitigs NULL.  An empty index, or
+ * one without a node: U = S = L = 0, and a call with a capacity writes out_link_offsets[0] = 0.  Results depend on no knob and are
+ * the same from run to run.
+ *
+ * How ("Unitigs by source"): behind the links, over the arrays the emission used.  The plain call keeps every node's
+ * range start from its edge walk; the canonical call searches a chunk of slots' words again for their ranges.  One 8-lane group a
+ * slot finds the slot's unitig -- the number at its head, or, where the canonical call did not emit that unitig, at the head of the
+ * slot of the word's reverse complement, one binary search --, counts the range's rows per source as the by-source k-mer calls do
+ * and adds the non-zero counts to the unitig's row with 64-bit integer atomics. */
+int msbwt_rle_enumerate_unitig_graph_by_source(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols,
+                                               uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags,
+                                               uint64_t *out_link_offsets /* 2U + 1 */, uint64_t *out_link_targets /* L */,
+                                               uint64_t *out_source_sums /* U x S */, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                               uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                               uint64_t *out_links);
+int msbwt_rle_enumerate_unitig_graph_by_source_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                                      void *d_out_symbols, void *d_out_offsets, void *d_out_count_sums, void *d_out_ends,
+                                                      void *d_out_flags, void *d_out_link_offsets, void *d_out_link_targets,
+                                                      void *d_out_source_sums, uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                                      uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                                      uint64_t *out_links, void *hip_stream);
+int msbwt_rle_enumerate_canonical_unitig_graph_by_source(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                                         uint8_t *out_symbols, uint64_t *out_offsets, uint64_t *out_count_sums,
+                                                         uint8_t *out_ends, uint8_t *out_flags, uint64_t *out_link_offsets /* 2U + 1 */,
+                                                         uint64_t *out_link_targets /* L */, uint64_t *out_source_sums /* U x S */,
+                                                         uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links,
+                                                         uint64_t *out_unitigs, uint64_t *out_symbol_total, uint64_t *out_links);
+int msbwt_rle_enumerate_canonical_unitig_graph_by_source_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge,
+                                                                void *d_out_symbols, void *d_out_offsets, void *d_out_count_sums,
+                                                                void *d_out_ends, void *d_out_flags, void *d_out_link_offsets,
+                                                                void *d_out_link_targets, void *d_out_source_sums,
+                                                                uint64_t capacity_unitigs, uint64_t capacity_symbols,
+                                                                uint64_t capacity_links, uint64_t *out_unitigs,
+                                                                uint64_t *out_symbol_total, uint64_t *out_links, void *hip_stream);
+/* Pure functions, no device: bytes of HBM a host call that fills all eight buffers allocates and frees again, EXACTLY
+ *     msbwt_unitig_graph_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links)   (msbwt_canonical_unitig_graph_plan for the
+ *                                                                                            canonical call, nodes = classes)
+ *     + ceil(8 R / 256) 256                                   the range words: R = nodes, one range start a node (plain call, taken
+ *                                                             before its edge walk), or R = 2 min(2 classes, 2^20), a pair {l, h}
+ *                                                             a slot of a chunk (canonical call)
+ *     + ceil(8 unitigs n_sources / 256) 256                   the matrix staged for the host
+ * The _device form takes the last line less; a NULL out_source_sums takes neither line: the call is the graph call then.  A counting
+ * call (all three capacities 0) allocates what the graph call's counting call does: unitigs = symbols = links = 0 says so.
+ * n_sources outside 1..MSBWT_MERGE_MAX_INPUTS: MSBWT_ERR_INVALID_ARG.  MSBWT_ERR_TOO_LARGE as for the graph plans; device_bytes may
+ * be NULL. */
+int msbwt_unitig_graph_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols,
+                                      uint64_t links, size_t n_sources, uint64_t *device_bytes);
+int msbwt_canonical_unitig_graph_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs,
+                                                uint64_t symbols, uint64_t links, size_t n_sources, uint64_t *device_bytes);
+
 /* The bytes of scratch the handle's last k-mer walk call (any call of the four sections above that walks) allocated in HBM and freed
  * again before it returned; 0 before the first one and after a call that allocated nothing (an empty index, a refused argument leaves
  * it as it was).  Every allocation counts with its size, 256 bytes at the least.  For the by-source calls this is what

@@ -571,6 +571,55 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, canonical ? "msbwt_canonical_unitig_graph_plan" : "msbwt_unitig_graph_plan");
         return bytes;
     }
+    /// What enumerate_unitig_graph_by_source returns: the unitig graph and, per unitig and per input of the merged index, the rows of
+    /// that input in the ranges of the unitig's nodes (canonical: of both members of its classes, a palindrome once):
+    /// source_sums[u * sources + s]; row u sums to count_sums[u].
+    struct UnitigGraphBySource : UnitigGraph {
+        std::vector<std::uint64_t> source_sums;
+        std::size_t sources = 0;
+    };
+    /// Either unitig graph call with the matrix by source behind the link table, on an index with sources attached.
+    UnitigGraphBySource enumerate_unitig_graph_by_source(std::size_t k, std::uint64_t min_count = 1, std::uint64_t min_edge = 0, bool canonical = false) const {
+        const auto call = canonical ? msbwt_rle_enumerate_canonical_unitig_graph_by_source : msbwt_rle_enumerate_unitig_graph_by_source;
+        std::uint64_t n = 0, s = 0, l = 0;
+        check(call(raw_, k, min_count, min_edge, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, &n, &s, &l));
+        UnitigGraphBySource u;
+        u.sources = std::size_t(msbwt_rle_source_count(raw_));
+        u.symbols.resize(s);
+        u.offsets.resize(n + 1);
+        u.count_sums.resize(n);
+        u.ends.resize(n);
+        u.flags.resize(n);
+        u.link_offsets.resize(2 * n + 1);
+        u.link_targets.resize(l);
+        u.source_sums.resize(n * u.sources);
+        if (n)
+            check(call(raw_, k, min_count, min_edge, u.symbols.data(), u.offsets.data(), u.count_sums.data(), u.ends.data(), u.flags.data(), u.link_offsets.data(),
+                       u.link_targets.data(), u.source_sums.data(), n, s, l, &n, &s, &l));
+        return u;
+    }
+    /// Device buffers (each may be null; d_source_sums: capacity_unitigs x sources words) -> the unitigs, as enumerate_unitig_graph_device.
+    std::uint64_t enumerate_unitig_graph_by_source_device(std::size_t k, std::uint64_t min_count, std::uint64_t min_edge, bool canonical, void *d_symbols, void *d_offsets,
+                                                          void *d_count_sums, void *d_ends, void *d_flags, void *d_link_offsets, void *d_link_targets,
+                                                          void *d_source_sums, std::uint64_t capacity_unitigs, std::uint64_t capacity_symbols,
+                                                          std::uint64_t capacity_links, std::uint64_t *symbol_total, std::uint64_t *links,
+                                                          void *hip_stream = nullptr) const {
+        const auto call = canonical ? msbwt_rle_enumerate_canonical_unitig_graph_by_source_device : msbwt_rle_enumerate_unitig_graph_by_source_device;
+        std::uint64_t n = 0;
+        check(call(raw_, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs,
+                   capacity_symbols, capacity_links, &n, symbol_total, links, hip_stream));
+        return n;
+    }
+    /// HBM bytes a host unitig graph call by source that fills every buffer allocates (and frees again): the graph call's plan, the
+    /// range words and the staged matrix; unitigs = symbols = links = 0: the counting call.
+    static std::uint64_t unitig_graph_by_source_plan(std::uint64_t total_rows, std::uint64_t free_hbm_bytes, std::uint64_t nodes, std::uint64_t unitigs,
+                                                     std::uint64_t symbols, std::uint64_t links, std::size_t n_sources, bool canonical = false) {
+        std::uint64_t bytes = 0;
+        const int rc = (canonical ? msbwt_canonical_unitig_graph_by_source_plan : msbwt_unitig_graph_by_source_plan)(total_rows, free_hbm_bytes, nodes, unitigs, symbols,
+                                                                                                                     links, n_sources, &bytes);
+        if (rc) throw Panic(rc, canonical ? "msbwt_canonical_unitig_graph_by_source_plan" : "msbwt_unitig_graph_by_source_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

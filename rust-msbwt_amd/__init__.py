@@ -17,7 +17,7 @@ from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "unitig_graph_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "unitig_graph_plan", "unitig_graph_by_source_plan", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():
@@ -198,6 +198,19 @@ def unitig_graph_plan(total_rows, free_hbm_bytes, nodes=0, unitigs=0, symbols=0,
     size = ctypes.c_uint64(0)
     name = "msbwt_canonical_unitig_graph_plan" if canonical else "msbwt_unitig_graph_plan"
     rc = getattr(_lib.lib(), name)(int(total_rows), int(free_hbm_bytes), int(nodes), int(unitigs), int(symbols), int(links), ctypes.byref(size))
+    if rc:
+        raise MsbwtError(rc, name)
+    return size.value
+
+
+def unitig_graph_by_source_plan(total_rows, free_hbm_bytes, nodes=0, unitigs=0, symbols=0, links=0, n_sources=1, canonical=False):
+    """HBM bytes a RleBWT.enumerate_unitig_graph_by_source call on an index of `n_sources` inputs allocates and frees again:
+    unitig_graph_plan of the same kind, the range words and the staged matrix (include/msbwt_hip.h writes the terms out); unitigs,
+    symbols and links all 0: the counting call.  The device form stages no matrix.  Pure host logic."""
+    import ctypes
+    size = ctypes.c_uint64(0)
+    name = "msbwt_canonical_unitig_graph_by_source_plan" if canonical else "msbwt_unitig_graph_by_source_plan"
+    rc = getattr(_lib.lib(), name)(int(total_rows), int(free_hbm_bytes), int(nodes), int(unitigs), int(symbols), int(links), int(n_sources), ctypes.byref(size))
     if rc:
         raise MsbwtError(rc, name)
     return size.value

@@ -106,6 +106,12 @@ SIGNATURES = {
     "msbwt_rle_enumerate_canonical_unitig_graph": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64]),
     "msbwt_rle_enumerate_canonical_unitig_graph_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64, _vp]),
     "msbwt_canonical_unitig_graph_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _u64, _pu64]),
+    "msbwt_rle_enumerate_unitig_graph_by_source": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64]),
+    "msbwt_rle_enumerate_unitig_graph_by_source_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64, _vp]),
+    "msbwt_unitig_graph_by_source_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _u64, _sz, _pu64]),
+    "msbwt_rle_enumerate_canonical_unitig_graph_by_source": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64]),
+    "msbwt_rle_enumerate_canonical_unitig_graph_by_source_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64, _vp]),
+    "msbwt_canonical_unitig_graph_by_source_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _u64, _sz, _pu64]),
     "msbwt_rle_spectrum_scratch_bytes": (_int, [_vp, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),

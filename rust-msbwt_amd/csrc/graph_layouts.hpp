@@ -3,7 +3,8 @@
 // starts: a msbwt_*_plan and the hipMalloc take `bytes`, the call carves `base + field`, the memset runs from `zero_from` to `bytes`.
 // A struct lists its arrays in their order in HBM, and its function puts their extents down in that order: the n-th put() is the n-th
 // field.  hipMalloc aligns a block to 256 bytes; what precedes a 16-byte array is a multiple of 16, what precedes a 64-bit one of 8
-// (tests/cpp/graph_layouts.cpp, and link_layouts.cpp for the link table, hold every layout to that, and to no array reaching into the next).
+// (tests/cpp/graph_layouts.cpp, link_layouts.cpp for the link table and colour_layouts.cpp for the block by source hold every layout
+// to that, and to no array reaching into the next).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -94,5 +95,19 @@ inline UnitigLinkLayout unitig_link_layout(uint64_t U, uint64_t L, bool targets)
     LayoutCursor c;
     return {c.put(16 * U + 256), c.put(unitig_tiles(unitig_link_sides(U)) * kUnitigTileBytes), c.put(targets ? 8 * L : 0), c.bytes};
 }
+
+// The block of a unitig graph call by source: the range words -- the plain call's l of every node, or the canonical call's pairs {l, h}
+// of a chunk of slots -- then the U x `sources` matrix where a host form stages it; a device form's is the caller's own and takes no
+// room.  Both extents are whole multiples of 256 bytes, so a block that holds either is no smaller than what hipMalloc hands out.
+struct UnitigSourceLayout {
+    uint64_t ranges, sums, bytes;
+};
+inline UnitigSourceLayout unitig_source_layout(uint64_t range_words, uint64_t U, uint64_t sources, bool sums) {
+    const auto padded = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
+    LayoutCursor c;
+    return {c.put(padded(8 * range_words)), c.put(sums ? padded(8 * U * sources) : 0), c.bytes};
+}
+// the range words of either call: a word a node, or a pair a slot of a chunk of the 2 x `classes` slots
+inline uint64_t unitig_source_range_words(uint64_t nodes, bool canonical) { return canonical ? 2 * std::min(2 * nodes, kCanonicalUnitigChunkSlots) : nodes; }
 
 }  // namespace msbwt

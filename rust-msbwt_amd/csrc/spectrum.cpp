@@ -4,7 +4,8 @@
 // (source_spectrum.hpp) and the k-mer graph (kmer_graph.hpp).  Two of two, a host and a device form: the unitigs that graph compacts
 // into (unitigs.hpp: the graph's walks into scratch, then kernels over its slots) and the canonical unitigs (canonical_unitigs.hpp: the
 // same compaction over both members of every canonical class), each also as a unitig GRAPH call that adds the link table of the
-// compacted graph behind the emission (unitig_links.hpp).  The kernels are behind those headers; this file is the host side, and
+// compacted graph behind the emission (unitig_links.hpp), and that once more by source: the matrix of per-input sums behind the links
+// (unitig_sources.hpp).  The kernels are behind those headers; this file is the host side, and
 // what the calls share is written once:
 //   Frame         a call: the locked handle, the guard ladder (no index, no sources, k, the call's own arguments, the device), the
 //                 stream, the clock, the SpectrumInfo and the scratch -- allocated per call, freed before it returns -- and, built from
@@ -19,6 +20,7 @@
 //   GraphCut / graph_edge_walk   the thresholds of the three graph calls and their staged walk with the edge pass behind it
 //   rank_unitigs / UnitigOutputs   the compaction both unitig calls run over their slots, and their outputs from guard to delivery;
 //                 UnitigLinkOutputs: the link table the unitig graph calls add behind the emission (unitig_links.hpp)
+//                 UnitigSourceOutputs: the matrix by source the by-source graph calls add behind the links (unitig_sources.hpp)
 // A body below is what is left: its argument checks, its sink, and the order of its passes.
 #include <algorithm>
 #include <chrono>
@@ -29,11 +31,13 @@
 #include "graph_layouts.hpp"
 #include "handle.hpp"
 #include "kmer_graph.hpp"
+#include "order.hpp"
 #include "radix_sort.hpp"
 #include "run_encode.hpp"
 #include "source_spectrum.hpp"
 #include "spectrum.hpp"
 #include "unitig_links.hpp"
+#include "unitig_sources.hpp"
 #include "unitigs.hpp"
 
 namespace {
@@ -583,6 +587,19 @@ int unitig_graph_plan(const Shape &p, uint64_t node_bytes, uint64_t total_rows, 
     return plan(p, total_rows, free_bytes, nodes, node_bytes + out, device_bytes);
 }
 
+// a msbwt_[canonical_]unitig_graph_by_source_plan: that plan and, unless it is the counting call, the block by source with the
+// matrix of `n_sources` columns staged
+int unitig_graph_by_source_plan(bool canonical, uint64_t total_rows, uint64_t free_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t links, size_t n_sources,
+                                uint64_t *device_bytes) {
+    if (n_sources < 1 || n_sources > kSourceMax) return MSBWT_ERR_INVALID_ARG;
+    uint64_t graph = 0;
+    const uint64_t node_bytes = canonical ? canonical_unitig_layout(nodes).bytes : unitig_node_layout(nodes).bytes;
+    if (int rc = unitig_graph_plan(canonical ? kCanonicalUnitigShape : kUnitigShape, node_bytes, total_rows, free_bytes, nodes, unitigs, symbols, links, &graph)) return rc;
+    const bool fills = unitigs || symbols || links;
+    if (device_bytes) *device_bytes = graph + (fills ? unitig_source_layout(unitig_source_range_words(nodes, canonical), unitigs, n_sources, true).bytes : 0);
+    return MSBWT_OK;
+}
+
 uint64_t ceil_log2(uint64_t x) {
     uint64_t r = 0;
     while (r < 63 && (1ull << r) < x) ++r;
@@ -655,11 +672,26 @@ struct UnitigLinkOutputs {
     uint64_t *d_offsets = nullptr, *d_targets = nullptr;
 };
 
+// With `by_source` (the unitig graph calls by source) the U x S matrix rides along behind the links: open() asks for the attachment;
+// a call that fills buffers and wants the matrix takes unitig_source_layout -- the plain call its range words before the edge walk,
+// which leaves every node's l there; the rest in emit(), as one more allocation behind the link block -- and runs the sums behind the
+// emission (unitig_sources.hpp), the canonical call a chunk of slots at a time behind a search for their ranges; deliver() copies it.
+struct UnitigSourceOutputs {
+    void *sums;  // the caller's: U x S words, may be nullptr
+    bool canonical;
+    uint64_t *l = nullptr;       // plain: every node's range start, n words
+    uint64_t *chunk = nullptr;   // canonical: 32 bytes a slot of a chunk (the call's own, free behind the fold) ...
+    uint64_t chunk_slots = 0;    // ... and the slots of a chunk
+    uint64_t sources = 0;
+    uint64_t *d_sums = nullptr;
+};
+
 struct UnitigOutputs {
     void *symbols, *offsets, *sums, *ends, *flags;
     uint64_t capacity_unitigs, capacity_symbols;
     uint64_t *out_unitigs, *out_symbol_total;
     UnitigLinkOutputs *links = nullptr;
+    UnitigSourceOutputs *by_source = nullptr;
     uint64_t U = 0, S = 0;
     bool filled = false;
     uint64_t *d_offsets = nullptr, *d_sums = nullptr;
@@ -668,11 +700,24 @@ struct UnitigOutputs {
     template <size_t W, class Args>
     int open(Frame &f, const GraphCut &cut, uint64_t (msbwt_rle::*info)[W], Args &&args) const {
         const auto checks = [&] { const int rc = args(); return rc ? rc : cut.check(f, out_unitigs); };
-        if (int rc = f.open(false, checks)) return rc;
+        if (int rc = f.open(by_source != nullptr, checks)) return rc;
         *out_unitigs = 0;
         if (out_symbol_total) *out_symbol_total = 0;
         if (links && links->out_links) *links->out_links = 0;
         std::fill(f.h->*info, f.h->*info + W, 0ull);
+        return MSBWT_OK;
+    }
+
+    // the matrix is wanted, and the call fills buffers
+    bool colours() const { return by_source && by_source->sums && (capacity_unitigs || capacity_symbols || (links && links->capacity)); }
+
+    // the plain call's range words, before its edge walk: nullptr where the matrix is not wanted
+    int take_ranges(Frame &f, uint64_t n, uint64_t **l) const {
+        *l = nullptr;
+        if (!colours() || by_source->canonical) return MSBWT_OK;
+        char *block = nullptr;
+        if (int rc = f.take_more(&block, unitig_source_layout(unitig_source_range_words(n, false), 0, 0, false).bytes, "for the ranges of the nodes")) return rc;
+        *l = by_source->l = in<uint64_t>(block, 0);
         return MSBWT_OK;
     }
 
@@ -709,6 +754,17 @@ struct UnitigOutputs {
             links->d_offsets = in<uint64_t>(link_block, link_at.offsets);
             links->d_targets = host && links->targets ? in<uint64_t>(link_block, link_at.targets) : static_cast<uint64_t *>(links->targets);
         }
+        uint64_t *pairs = nullptr;
+        if (colours()) {
+            UnitigSourceOutputs &bs = *by_source;
+            bs.sources = h->sources.n_sources;
+            const UnitigSourceLayout source_at = unitig_source_layout(bs.canonical ? 2 * bs.chunk_slots : 0, U, bs.sources, host);
+            char *source_block = nullptr;
+            if (source_at.bytes)
+                if (int rc = f.take_more(&source_block, source_at.bytes, "for the sums by source")) return rc;
+            if (bs.canonical) pairs = in<uint64_t>(source_block, source_at.ranges);
+            bs.d_sums = host ? in<uint64_t>(source_block, source_at.sums) : static_cast<uint64_t *>(bs.sums);
+        }
         // a device form's outputs are the caller's own; a staged one has its place in the block
         d_offsets = in<uint64_t>(block, at.offsets);
         d_sums = static_cast<uint64_t *>(stage_sums ? block + at.sums : sums);
@@ -724,6 +780,27 @@ struct UnitigOutputs {
             if (links->d_targets)
                 HIP_TRY(h, launch_unitig_link_targets(g, state, heads, uint32_t(f.k), links->canonical, uint32_t(ceil_log2(g.n) + 1), U, links->L, links->d_offsets,
                                                       links->d_targets, f.stream));
+        }
+        if (colours()) {
+            const UnitigSourceOutputs &bs = *by_source;
+            const SourceView view = h->sources.view(h->totals.total);
+            const uint32_t probes = uint32_t(ceil_log2(g.n) + 1);
+            HIP_TRY(h, hipMemsetAsync(bs.d_sums, 0, 8 * U * bs.sources, f.stream));
+            if (!bs.canonical) {
+                HIP_TRY(h, launch_unitig_source_sums(g, state, heads, uint32_t(f.k), false, probes, U, view, UnitigSourceRanges{bs.l, nullptr, 0, g.n}, bs.d_sums, f.stream));
+            } else {
+                // the slots hold words and class counts: a chunk's words as symbol bytes, their ranges by the library's search, the sums
+                uint8_t *rows = reinterpret_cast<uint8_t *>(bs.chunk);
+                for (uint64_t first = 0; first < g.n; first += bs.chunk_slots) {
+                    const uint64_t m = std::min(bs.chunk_slots, g.n - first);
+                    HIP_TRY(h, launch_unpack_rows(g.kmers + first, uint32_t(f.k), m, rows, f.stream));
+                    if (int rc = timed_with_tickets(h, f.stream, [&](const IndexView &v) {
+                            return launch_kmer_ranges(v, rows, uint32_t(f.k), m, pairs, pairs + 1, 2u, h->d_flags + f.which, f.stream);
+                        }))
+                        return rc;
+                    HIP_TRY(h, launch_unitig_source_sums(g, state, heads, uint32_t(f.k), true, probes, U, view, UnitigSourceRanges{nullptr, pairs, first, m}, bs.d_sums, f.stream));
+                }
+            }
         }
         filled = true;
         return MSBWT_OK;
@@ -752,6 +829,7 @@ struct UnitigOutputs {
             if (f.host && flags) HIP_TRY(h, hipMemcpyAsync(flags, d_flags, U, kind, f.stream));
             if (links && links->offsets) HIP_TRY(h, hipMemcpyAsync(links->offsets, links->d_offsets, 8 * unitig_link_sides(U), kind, f.stream));
             if (links && f.host && links->targets && links->L) HIP_TRY(h, hipMemcpyAsync(links->targets, links->d_targets, 8 * links->L, kind, f.stream));
+            if (f.host && colours()) HIP_TRY(h, hipMemcpyAsync(by_source->sums, by_source->d_sums, 8 * U * by_source->sources, kind, f.stream));
         }
         if (f.host) return status_of(h, f.stream, f.which);  // synchronises
         HIP_TRY(h, hipStreamSynchronize(f.stream));           // (the scratch is freed on return)
@@ -763,10 +841,10 @@ struct UnitigOutputs {
 // and predecessor slots), then links, ranking, cycles, numbering and emission over the slots (unitigs.hpp).
 int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums, void *out_ends,
             void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total, hipStream_t stream,
-            UnitigLinkOutputs *links = nullptr) {
-    Frame f(bwt, links ? "enumerate_unitig_graph" : "enumerate_unitigs", k, host, stream);
+            UnitigLinkOutputs *links = nullptr, UnitigSourceOutputs *by_source = nullptr) {
+    Frame f(bwt, by_source ? "enumerate_unitig_graph_by_source" : links ? "enumerate_unitig_graph" : "enumerate_unitigs", k, host, stream);
     const GraphCut cut(min_count, min_edge);
-    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links};
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links, by_source};
     if (int rc = out.open(f, cut, &msbwt_rle::unitig_info, [] { return int(MSBWT_OK); })) return rc;
     msbwt_rle *h = f.h;
     const int rc = two_pass(
@@ -780,7 +858,9 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
             uint32_t *edge_words = in<uint32_t>(block, at.edge_words);
             HIP_TRY(h, hipMemsetAsync(block + at.zero_from, 0, at.bytes - at.zero_from, f.stream));
             HIP_TRY(h, hipMemsetAsync(pred, 0xFF, n * 8, f.stream));  // (no slot)
-            if (int rc = graph_edge_walk(f, cut, n, edge_words, kmers, counts, nullptr, pred)) return rc;
+            uint64_t *l = nullptr;
+            if (int rc = out.take_ranges(f, n, &l)) return rc;
+            if (int rc = graph_edge_walk(f, cut, n, edge_words, kmers, counts, l, pred)) return rc;
 
             const UnitigNodes g{n, kmers, counts, pred, edge_words, in<uint32_t>(block, at.link_words), in<unsigned long long>(block, at.counters), h->d_flags + f.which};
             uint64_t c[kUnitigCounterWords] = {}, rounds = 0;
@@ -804,10 +884,10 @@ int unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edg
 // slots, with the cuts behind the links and the choice between a unitig and its mirror behind the ranking (canonical_unitigs.hpp).
 int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, bool host, void *out_symbols, void *out_offsets, void *out_sums,
                       void *out_ends, void *out_flags, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t *out_unitigs, uint64_t *out_symbol_total,
-                      hipStream_t stream, UnitigLinkOutputs *links = nullptr) {
-    Frame f(bwt, links ? "enumerate_canonical_unitig_graph" : "enumerate_canonical_unitigs", k, host, stream);
+                      hipStream_t stream, UnitigLinkOutputs *links = nullptr, UnitigSourceOutputs *by_source = nullptr) {
+    Frame f(bwt, by_source ? "enumerate_canonical_unitig_graph_by_source" : links ? "enumerate_canonical_unitig_graph" : "enumerate_canonical_unitigs", k, host, stream);
     const GraphCut cut(min_count, min_edge);
-    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links};
+    UnitigOutputs out{out_symbols, out_offsets, out_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs, out_symbol_total, links, by_source};
     if (int rc = out.open(f, cut, &msbwt_rle::canonical_unitig_info,
                           [&] { return k > 31 ? f.refuse(" needs 1 <= k <= 31 (an edge is a packed (k+1)-mer)") : int(MSBWT_OK); }))
         return rc;
@@ -888,6 +968,10 @@ int canonical_unitigs(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64
             const uint64_t info[MSBWT_CANONICAL_UNITIG_INFO_WORDS] = {n, (c[kUnitigEdges] + own[kCanonicalUnitigHairpins]) / 2, n + circular - U, U, S, circular, c[kUnitigLongest], rounds,
                                                               2 * n - N, own[kCanonicalUnitigCut]};
             std::copy(info, info + MSBWT_CANONICAL_UNITIG_INFO_WORDS, h->canonical_unitig_info);
+            if (by_source) {
+                by_source->chunk = chunk;
+                by_source->chunk_slots = at.chunk_slots;
+            }
             return out.emit(f, g, cur, other, block + at.tiles, U, S, true);
         },
         [&](uint64_t) { return out.deliver(f); });
@@ -1153,6 +1237,61 @@ int msbwt_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64
 int msbwt_canonical_unitig_graph_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t links,
                                       uint64_t *device_bytes) {
     return unitig_graph_plan(kCanonicalUnitigShape, canonical_unitig_layout(classes).bytes, total_rows, free_hbm_bytes, classes, unitigs, symbols, links, device_bytes);
+}
+
+// ---- unitig graphs by source: either unitig graph call with the U x S matrix of per-input sums behind the link table ----
+
+int msbwt_rle_enumerate_unitig_graph_by_source(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols, uint64_t *out_offsets,
+                                               uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags, uint64_t *out_link_offsets, uint64_t *out_link_targets,
+                                               uint64_t *out_source_sums, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links,
+                                               uint64_t *out_unitigs, uint64_t *out_symbol_total, uint64_t *out_links) {
+    UnitigLinkOutputs links{out_link_offsets, out_link_targets, capacity_links, out_links, false};
+    UnitigSourceOutputs by_source{out_source_sums, false};
+    return unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols, out_unitigs,
+                   out_symbol_total, nullptr, &links, &by_source);
+}
+
+int msbwt_rle_enumerate_unitig_graph_by_source_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols, void *d_out_offsets,
+                                                      void *d_out_count_sums, void *d_out_ends, void *d_out_flags, void *d_out_link_offsets, void *d_out_link_targets,
+                                                      void *d_out_source_sums, uint64_t capacity_unitigs, uint64_t capacity_symbols, uint64_t capacity_links,
+                                                      uint64_t *out_unitigs, uint64_t *out_symbol_total, uint64_t *out_links, void *hip_stream) {
+    UnitigLinkOutputs links{d_out_link_offsets, d_out_link_targets, capacity_links, out_links, false};
+    UnitigSourceOutputs by_source{d_out_source_sums, false};
+    return unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs, capacity_symbols,
+                   out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream), &links, &by_source);
+}
+
+int msbwt_rle_enumerate_canonical_unitig_graph_by_source(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, uint8_t *out_symbols,
+                                                         uint64_t *out_offsets, uint64_t *out_count_sums, uint8_t *out_ends, uint8_t *out_flags,
+                                                         uint64_t *out_link_offsets, uint64_t *out_link_targets, uint64_t *out_source_sums, uint64_t capacity_unitigs,
+                                                         uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                                         uint64_t *out_links) {
+    UnitigLinkOutputs links{out_link_offsets, out_link_targets, capacity_links, out_links, true};
+    UnitigSourceOutputs by_source{out_source_sums, true};
+    return canonical_unitigs(bwt, k, min_count, min_edge, true, out_symbols, out_offsets, out_count_sums, out_ends, out_flags, capacity_unitigs, capacity_symbols,
+                             out_unitigs, out_symbol_total, nullptr, &links, &by_source);
+}
+
+int msbwt_rle_enumerate_canonical_unitig_graph_by_source_device(const msbwt_rle *bwt, size_t k, uint64_t min_count, uint64_t min_edge, void *d_out_symbols,
+                                                                void *d_out_offsets, void *d_out_count_sums, void *d_out_ends, void *d_out_flags,
+                                                                void *d_out_link_offsets, void *d_out_link_targets, void *d_out_source_sums, uint64_t capacity_unitigs,
+                                                                uint64_t capacity_symbols, uint64_t capacity_links, uint64_t *out_unitigs, uint64_t *out_symbol_total,
+                                                                uint64_t *out_links, void *hip_stream) {
+    UnitigLinkOutputs links{d_out_link_offsets, d_out_link_targets, capacity_links, out_links, true};
+    UnitigSourceOutputs by_source{d_out_source_sums, true};
+    return canonical_unitigs(bwt, k, min_count, min_edge, false, d_out_symbols, d_out_offsets, d_out_count_sums, d_out_ends, d_out_flags, capacity_unitigs,
+                             capacity_symbols, out_unitigs, out_symbol_total, static_cast<hipStream_t>(hip_stream), &links, &by_source);
+}
+
+// the graph plan of the same kind and, unless it is the counting call, unitig_source_layout with the matrix staged
+int msbwt_unitig_graph_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t nodes, uint64_t unitigs, uint64_t symbols, uint64_t links, size_t n_sources,
+                                      uint64_t *device_bytes) {
+    return unitig_graph_by_source_plan(false, total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, n_sources, device_bytes);
+}
+
+int msbwt_canonical_unitig_graph_by_source_plan(uint64_t total_rows, uint64_t free_hbm_bytes, uint64_t classes, uint64_t unitigs, uint64_t symbols, uint64_t links,
+                                                size_t n_sources, uint64_t *device_bytes) {
+    return unitig_graph_by_source_plan(true, total_rows, free_hbm_bytes, classes, unitigs, symbols, links, n_sources, device_bytes);
 }
 
 // the host call over `classes` classes that fills every buffer with `unitigs` unitigs of `symbols` symbols (none of either: the counting call)

@@ -14,6 +14,7 @@
 #include "kernels.hpp"
 #include "slot_bytes.hpp"
 #include "unitig_links.hpp"
+#include "unitig_slots.hpp"
 #include "workgroup.hpp"
 
 namespace msbwt {
@@ -23,23 +24,6 @@ constexpr int kThreads = 256;
 constexpr uint32_t kGridCap = 256u * 8u;
 constexpr uint32_t kPerThread = uint32_t(kUnitigTileSlots) / uint32_t(kThreads);
 constexpr uint64_t kNoEntry = ~0ull;
-
-// the slot of w among the n sorted words, or n where w is none of them; `probes` halvings at the most
-__device__ __forceinline__ uint64_t slot_of(const uint64_t *__restrict__ words, uint64_t n, uint32_t probes, uint64_t w) {
-    uint64_t lo = 0, hi = n;
-    for (uint32_t step = 0; step < probes && lo < hi; ++step) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (words[mid] < w) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && words[lo] == w ? lo : n;
-}
-
-// the head of slot i's unitig, or n where the ranking left none (the host ranks until nothing is unfinished)
-__device__ __forceinline__ uint64_t head_of(const UnitigNodes &g, const UnitigState *__restrict__ state, uint64_t i) {
-    const UnitigState s = state[i];
-    return (s.y & kUnitigDone) && s.x < g.n ? uint64_t(s.x) : g.n;
-}
 
 template <bool kCanonical>
 __device__ __forceinline__ bool own_mirror(const UnitigNodes &g, uint32_t k, uint64_t slot) {

@@ -627,6 +627,60 @@ class RleBWT(BWT):
         return self._unitig_graph_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
                                          d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge, stream)
 
+    # ---- unitigs by source: either unitig graph call with the per-input sums of every unitig behind the link table ----
+    def enumerate_unitig_graph_by_source(self, k, min_count=1, min_edge=None, canonical=False, text=False):
+        """msbwt_rle_enumerate_[canonical_]unitig_graph_by_source, both calls of the two-call pattern, on an index with sources attached
+        (load_merged_many(keep_sources=True), set_sources) -> what enumerate_unitig_graph returns with source_sums appended: U x S
+        uint64, source_sums[u, s] = the rows of input s in the ranges of the nodes of unitig u (canonical: of both members of its
+        classes, a palindrome once).  Row u sums to count_sums[u]; the thresholds meet the counts of all inputs together."""
+        fn = _lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_by_source if canonical else _lib.lib().msbwt_rle_enumerate_unitig_graph_by_source
+        args = (int(k), int(min_count), int(min_edge or 0))
+        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = fn(self._h, *args, None, None, None, None, None, None, None, None, 0, 0, 0, C.byref(U), C.byref(S), C.byref(L))
+        if rc:
+            _raise(rc, self._h)
+        symbols, offsets = np.zeros(S.value, dtype=np.uint8), np.zeros(U.value + 1, dtype=np.uint64)
+        sums, ends, flags = np.zeros(U.value, dtype=np.uint64), np.zeros(U.value, dtype=np.uint8), np.zeros(U.value, dtype=np.uint8)
+        link_offsets, link_targets = np.zeros(2 * U.value + 1, dtype=np.uint64), np.zeros(L.value, dtype=np.uint64)
+        source_sums = np.zeros((U.value, self.source_count()), dtype=np.uint64)
+        if U.value:
+            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in (symbols, offsets, sums, ends, flags, link_offsets, link_targets, source_sums)], U.value,
+                    S.value, L.value, C.byref(U), C.byref(S), C.byref(L))
+            if rc:
+                _raise(rc, self._h)
+        if not text:
+            return symbols, offsets, sums, ends, flags, link_offsets, link_targets, source_sums
+        letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
+        return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags, link_offsets, link_targets, source_sums
+
+    def _unitig_graph_by_source_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs,
+                                       capacity_symbols, capacity_links, min_count, min_edge, stream):
+        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
+                int(capacity_unitigs), int(capacity_symbols), int(capacity_links), C.byref(U), C.byref(S), C.byref(L), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as err:
+                err.n, err.symbols, err.links = U.value, S.value, L.value
+                raise
+        return U.value, S.value, L.value
+
+    def enumerate_unitig_graph_by_source_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
+                                                capacity_unitigs, capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_enumerate_unitig_graph_by_source_device: as enumerate_unitig_graph_device with d_source_sums (capacity_unitigs x
+        source_count() u64, may be None) behind d_link_targets -> (U, S, L)."""
+        return self._unitig_graph_by_source_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_by_source_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
+                                                   d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge,
+                                                   stream)
+
+    def enumerate_canonical_unitig_graph_by_source_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
+                                                          capacity_unitigs, capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_enumerate_canonical_unitig_graph_by_source_device: as enumerate_unitig_graph_by_source_device."""
+        return self._unitig_graph_by_source_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_by_source_device, k, d_symbols, d_offsets, d_count_sums, d_ends,
+                                                   d_flags, d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs, capacity_symbols, capacity_links, min_count,
+                                                   min_edge, stream)
+
     def spectrum_scratch_bytes(self):
         """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""
         out = C.c_uint64(0)
@@ -1236,16 +1290,19 @@ def unitig_link_records(link_offsets, link_targets, flags):
     return sides[keep], link_targets[keep]
 
 
-def write_gfa(file, k, symbols, offsets, count_sums, flags, link_offsets, link_targets):
+def write_gfa(file, k, symbols, offsets, count_sums, flags, link_offsets, link_targets, source_sums=None):
     """The compacted graph of RleBWT.enumerate_unitig_graph as GFA 1: a header, one `S <u> <sequence> KC:i:<count sum>` line a unitig
     (named by its number) and one `L <u> <+|-> <v> <+|-> <k-1>M` line per edge, each edge once (unitig_link_records): an odd side leaves
-    the reverse complement (-), an odd entry reaches one.  `file`: a path, or an object with write().  -> (segments, links) written."""
+    the reverse complement (-), an odd entry reaches one.  With `source_sums` (U x S, RleBWT.enumerate_unitig_graph_by_source) every S
+    line carries the tag `sc:Z:c0,c1,...` behind KC:i:, the unitig's sums by input in decimal.  `file`: a path, or an object with
+    write().  -> (segments, links) written."""
     k = int(k)
     letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[np.ascontiguousarray(symbols, dtype=np.uint8)].tobytes().decode()
     sides, targets = unitig_link_records(link_offsets, link_targets, flags)
     lines = ["H\tVN:Z:1.0\n"]
     for u, (a, z) in enumerate(zip(offsets[:-1], offsets[1:])):
-        lines.append("S\t%d\t%s\tKC:i:%d\n" % (u, letters[int(a):int(z)], int(count_sums[u])))
+        colours = "" if source_sums is None else "\tsc:Z:" + ",".join(str(int(c)) for c in source_sums[u])
+        lines.append("S\t%d\t%s\tKC:i:%d%s\n" % (u, letters[int(a):int(z)], int(count_sums[u]), colours))
     for a, e in zip(sides.tolist(), targets.tolist()):
         lines.append("L\t%d\t%s\t%d\t%s\t%dM\n" % (a >> 1, "-" if a & 1 else "+", e >> 1, "-" if e & 1 else "+", k - 1))
     if hasattr(file, "write"):

@@ -143,6 +143,33 @@ extern "C" {
     fn msbwt_unitig_graph_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64, links: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_canonical_unitig_graph_plan(total_rows: u64, free_hbm_bytes: u64, classes: u64, unitigs: u64, symbols: u64, links: u64,
                                          device_bytes: *mut u64) -> c_int;
+    // unitigs by source: either unitig graph call with the U x S matrix of per-input sums behind the link table
+    fn msbwt_rle_enumerate_unitig_graph_by_source(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_symbols: *mut u8,
+                                                  out_offsets: *mut u64, out_count_sums: *mut u64, out_ends: *mut u8, out_flags: *mut u8,
+                                                  out_link_offsets: *mut u64, out_link_targets: *mut u64, out_source_sums: *mut u64,
+                                                  capacity_unitigs: u64, capacity_symbols: u64, capacity_links: u64, out_unitigs: *mut u64,
+                                                  out_symbol_total: *mut u64, out_links: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_unitig_graph_by_source_device(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, d_out_symbols: *mut c_void,
+                                                         d_out_offsets: *mut c_void, d_out_count_sums: *mut c_void, d_out_ends: *mut c_void,
+                                                         d_out_flags: *mut c_void, d_out_link_offsets: *mut c_void, d_out_link_targets: *mut c_void,
+                                                         d_out_source_sums: *mut c_void, capacity_unitigs: u64, capacity_symbols: u64,
+                                                         capacity_links: u64, out_unitigs: *mut u64, out_symbol_total: *mut u64, out_links: *mut u64,
+                                                         hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_enumerate_canonical_unitig_graph_by_source(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64, out_symbols: *mut u8,
+                                                            out_offsets: *mut u64, out_count_sums: *mut u64, out_ends: *mut u8, out_flags: *mut u8,
+                                                            out_link_offsets: *mut u64, out_link_targets: *mut u64, out_source_sums: *mut u64,
+                                                            capacity_unitigs: u64, capacity_symbols: u64, capacity_links: u64, out_unitigs: *mut u64,
+                                                            out_symbol_total: *mut u64, out_links: *mut u64) -> c_int;
+    fn msbwt_rle_enumerate_canonical_unitig_graph_by_source_device(bwt: *const MsbwtRle, k: usize, min_count: u64, min_edge: u64,
+                                                                   d_out_symbols: *mut c_void, d_out_offsets: *mut c_void, d_out_count_sums: *mut c_void,
+                                                                   d_out_ends: *mut c_void, d_out_flags: *mut c_void, d_out_link_offsets: *mut c_void,
+                                                                   d_out_link_targets: *mut c_void, d_out_source_sums: *mut c_void, capacity_unitigs: u64,
+                                                                   capacity_symbols: u64, capacity_links: u64, out_unitigs: *mut u64,
+                                                                   out_symbol_total: *mut u64, out_links: *mut u64, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_unitig_graph_by_source_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64, links: u64, n_sources: usize,
+                                         device_bytes: *mut u64) -> c_int;
+    fn msbwt_canonical_unitig_graph_by_source_plan(total_rows: u64, free_hbm_bytes: u64, classes: u64, unitigs: u64, symbols: u64, links: u64,
+                                                   n_sources: usize, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
@@ -709,6 +736,59 @@ impl GpuRleBWT {
             else { msbwt_unitig_graph_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, &mut bytes) }
         };
         assert_eq!(rc, MSBWT_OK, "unitig_graph_plan: {} rows, {} nodes", total_rows, nodes);
+        bytes
+    }
+
+    /// Either unitig graph call with the matrix by source behind the link table, on an index with sources attached: the arrays of
+    /// `enumerate_unitig_graph`, then source_sums, unitigs x `source_count()` words, row-major: the rows of input s in the ranges of
+    /// the nodes of unitig u (canonical: of both members of its classes, a palindrome once).  Row u sums to count_sums[u].
+    pub fn enumerate_unitig_graph_by_source(&self, k: usize, min_count: u64, min_edge: u64, canonical: bool)
+                                            -> (Vec<u8>, Vec<u64>, Vec<u64>, Vec<u8>, Vec<u8>, Vec<u64>, Vec<u64>, Vec<u64>) {
+        let call = if canonical { msbwt_rle_enumerate_canonical_unitig_graph_by_source } else { msbwt_rle_enumerate_unitig_graph_by_source };
+        let (mut u, mut s, mut l) = (0u64, 0u64, 0u64);
+        let null8 = std::ptr::null_mut::<u8>();
+        let null64 = std::ptr::null_mut::<u64>();
+        let rc = unsafe { call(self.raw, k, min_count, min_edge, null8, null64, null64, null8, null8, null64, null64, null64, 0, 0, 0, &mut u, &mut s, &mut l) };
+        if rc != MSBWT_OK { panic!("enumerate_unitig_graph_by_source: {}", self.last_error()); }
+        let (mut symbols, mut offsets) = (vec![0u8; s as usize], vec![0u64; u as usize + 1]);
+        let (mut sums, mut ends, mut flags) = (vec![0u64; u as usize], vec![0u8; u as usize], vec![0u8; u as usize]);
+        let (mut link_offsets, mut link_targets) = (vec![0u64; 2 * u as usize + 1], vec![0u64; l as usize]);
+        let mut source_sums = vec![0u64; u as usize * self.source_count()];
+        if u > 0 {
+            let rc = unsafe {
+                call(self.raw, k, min_count, min_edge, symbols.as_mut_ptr(), offsets.as_mut_ptr(), sums.as_mut_ptr(), ends.as_mut_ptr(), flags.as_mut_ptr(),
+                     link_offsets.as_mut_ptr(), link_targets.as_mut_ptr(), source_sums.as_mut_ptr(), u, s, l, &mut u, &mut s, &mut l)
+            };
+            if rc != MSBWT_OK { panic!("enumerate_unitig_graph_by_source: {}", self.last_error()); }
+        }
+        (symbols, offsets, sums, ends, flags, link_offsets, link_targets, source_sums)
+    }
+
+    /// The same into device buffers (each may be null; d_source_sums: capacity_unitigs x `source_count()` words) -> (unitigs, symbols,
+    /// links); all three capacities 0 only counts.
+    pub unsafe fn enumerate_unitig_graph_by_source_device(&self, k: usize, min_count: u64, min_edge: u64, canonical: bool, d_symbols: *mut c_void,
+                                                          d_offsets: *mut c_void, d_count_sums: *mut c_void, d_ends: *mut c_void, d_flags: *mut c_void,
+                                                          d_link_offsets: *mut c_void, d_link_targets: *mut c_void, d_source_sums: *mut c_void,
+                                                          capacity_unitigs: u64, capacity_symbols: u64, capacity_links: u64, hip_stream: *mut c_void)
+                                                          -> (u64, u64, u64) {
+        let call = if canonical { msbwt_rle_enumerate_canonical_unitig_graph_by_source_device } else { msbwt_rle_enumerate_unitig_graph_by_source_device };
+        let (mut u, mut s, mut l) = (0u64, 0u64, 0u64);
+        let rc = call(self.raw, k, min_count, min_edge, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
+                      capacity_unitigs, capacity_symbols, capacity_links, &mut u, &mut s, &mut l, hip_stream);
+        if rc != MSBWT_OK { panic!("enumerate_unitig_graph_by_source_device: {}", self.last_error()); }
+        (u, s, l)
+    }
+
+    /// HBM bytes a host unitig graph call by source that fills every buffer allocates and frees again: the graph call's plan, the range
+    /// words and the staged matrix (pure function).
+    pub fn unitig_graph_by_source_plan(total_rows: u64, free_hbm_bytes: u64, nodes: u64, unitigs: u64, symbols: u64, links: u64, n_sources: usize,
+                                       canonical: bool) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe {
+            if canonical { msbwt_canonical_unitig_graph_by_source_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, n_sources, &mut bytes) }
+            else { msbwt_unitig_graph_by_source_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, n_sources, &mut bytes) }
+        };
+        assert_eq!(rc, MSBWT_OK, "unitig_graph_by_source_plan: {} rows, {} nodes, {} sources", total_rows, nodes, n_sources);
         bytes
     }
 
