@@ -789,6 +789,110 @@ int msbwt_canonical_unitig_graph_by_source_plan(uint64_t total_rows, uint64_t fr
  * nothing), plus 8 S n_bins for the spectrum -- the tests hold the two against each other.  NULL handle or pointer: MSBWT_ERR_INVALID_ARG. */
 int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes);
 
+/* ---- traces ---- from each of n seed k-mers, a walk through the k-mer graph, node by node in one direction under one rule, all walks
+ * of a batch advancing together on the device (no reference counterpart).  The calls above answer whole-index questions and take
+ * scratch in proportion to the nodes; a trace is the LOCAL question -- from this k-mer, where does the graph go? -- and its cost
+ * follows the answer, not the index: read correction, bridging between two anchors, local assembly around a k-mer a dump reported.
+ * (A "walk" elsewhere in this header is the frontier walk of the enumerating calls; hence "trace".)
+ *
+ * THE GRAPH is G(k, m, me) exactly as "the k-mer graph" defines it: nodes are the k-mers over ACGT with count_kmer >= m =
+ * max(min_count, 1), edges the (k+1)-mers with count_kmer >= me (min_edge == 0: me = m; 0 < min_edge < m: MSBWT_ERR_INVALID_ARG).
+ * 1 <= k <= 31: an edge is ONE packed (k+1)-mer, the canonical unitig call's limit and its reason.
+ * DIRECTION: MSBWT_TRACE_RIGHT follows successors, MSBWT_TRACE_LEFT predecessors.  The FAN of a node q is the set of edges that leave
+ * it in the walk direction (q.c for RIGHT, c.q for LEFT), its BACK-FAN the set of edges that enter it in the walk direction.  With the
+ * packed words of "compact queries" (first symbol most significant), for a node word w and a symbol c = 0..3 (A C G T):
+ *                 RIGHT                          LEFT
+ *   edge word     (w << 2) | c                   (c << 2k) | w
+ *   next node     that edge's low 2k bits        (c << 2(k-1)) | (w >> 2)
+ * At k = 31 an edge fills all 64 bits.
+ * MODE: MSBWT_TRACE_UNIQUE goes on while the fan has exactly one edge.  MSBWT_TRACE_UNITIG does the same and does not enter a node
+ * whose back-fan has two or more edges: every step is then a LINK of the unitig section, and a trace from a unitig's first node
+ * RIGHT (its last node LEFT) reproduces that unitig of msbwt_rle_enumerate_unitigs.  MSBWT_TRACE_GREEDY takes, at a fan of several
+ * edges, the one with the largest count_kmer, on a tie the smallest symbol (A < C < G < T).
+ * ONE WALK, with seed s (bits beyond 2k ignored; a target's likewise), cur = s, steps = 0:
+ *   0. s is no node: stop NOT_A_NODE with steps = 0.
+ *   1. steps == max_steps: stop MAX_STEPS.
+ *   2. The fan of cur is empty: stop DEAD_END.
+ *   3. The fan has two or more edges and the mode is not GREEDY: stop BRANCH.  Otherwise e is the edge chosen, nxt its other end.
+ *   4. Mode UNITIG and the back-fan of nxt has two or more edges: stop MERGE; nxt is not entered.
+ *   5. nxt == s: stop RETURNED; nxt is not entered.  An isolated cycle of v nodes ends here after v - 1 steps, a node whose only
+ *      edge is its self-loop after 0.
+ *   6. Enter nxt: symbols[steps] = the symbol appended (RIGHT) or prepended (LEFT), in the library's codes 1 2 3 5;
+ *      edge_sum += count_kmer(e); steps += 1; cur = nxt.
+ *   7. Targets were given and cur == target[i]: stop TARGET.  A target is compared with ENTERED nodes only, so a target equal to the
+ *      seed never stops a walk.
+ *   8. Back to 1.
+ * A walk that runs into a cycle that does not hold its seed turns until max_steps: stated, not cured.
+ * The full sequence of walk i is the seed followed by its row of symbols (RIGHT), or the row reversed followed by the seed (LEFT).
+ *
+ * Outputs, every one may be NULL:
+ *   out_symbols     n x max_steps bytes, row-major: row i holds out_steps[i] symbols, the rest of the row is left untouched
+ *   out_steps       n words
+ *   out_stops       n bytes: MSBWT_TRACE_DEAD_END .. MSBWT_TRACE_NOT_A_NODE; 0 is never written
+ *   out_edge_sums   n words: the sum of count_kmer over the (k+1)-mers traversed
+ *   out_last        n words: the node the walk ended on (the seed, masked, for NOT_A_NODE)
+ *   out_fans        n bytes: bit j is set when the edge by symbol j leaves that final node in the walk direction; 0 for NOT_A_NODE.
+ *                   What a caller needs to fork at a BRANCH.
+ * targets2bit: n words, or NULL.  The _device form takes device pointers, runs on hip_stream, synchronises it before it returns (the
+ * scratch is freed then) and reports a device fault through msbwt_rle_device_status, as the enumerating calls do.
+ * Guards, before the first HIP call: a NULL handle (MSBWT_ERR_INVALID_ARG); nothing loaded (MSBWT_ERR_NOT_LOADED, "no BWT loaded"); k
+ * outside 1..31; a bad min_edge, mode or direction; NULL seeds with n > 0 (all MSBWT_ERR_INVALID_ARG); max_steps, or n x max_steps,
+ * from 2^40 on (MSBWT_ERR_TOO_LARGE).  n == 0 and an empty index are MSBWT_OK; on an empty index every stop is NOT_A_NODE.  Results
+ * depend on no knob, no index form and no piece, and are the same from run to run.
+ *
+ * How ("Traces"): the FM index searches in one direction only, so a step cannot reuse the step before it: every edge is
+ * a search of its own, and the searches go, a ROUND at a time for all live walks at once, through the packed search of
+ * msbwt_rle_count_kmers_packed_device.  Round 0 searches the seeds at length k and their fans; a later round searches, for every live
+ * walk, the 4 edges of the fan of the node it is about to enter and, in UNITIG mode, the 4 of its back-fan.  One kernel a round reads
+ * the counts, applies steps 4-7 and 1-3, writes a finished walk's outputs once and moves the survivors to the front with their next
+ * queries.  The host reads the live count after each round and stops at 0: max_steps + 1 rounds at the most.  The n walks are taken
+ * a PIECE at a time (msbwt_rle_set_trace_piece: 0 = automatic, 2^20 walks; results never depend on it), so the scratch does not grow
+ * with n.  Queries searched: 5 a walk in round 0, then 4 (UNITIG: 8) a live walk and round; a walk of s steps is live in s later
+ * rounds, and in one more where a MERGE or, in UNITIG mode, a RETURNED stops it.  A finished walk is never searched again.
+ *
+ * msbwt_rle_trace_info: out[MSBWT_TRACE_INFO_WORDS] of the handle's last trace call = [0] walks, [1] rounds run, [2] queries handed to
+ * the packed search, [3] steps taken in all, [4] the longest walk, [5] pieces, [6] scratch bytes allocated, [7] walks that were no node.
+ * The scratch is per call and freed on return (msbwt_rle_device_bytes unchanged); an empty index and n == 0 allocate nothing.
+ * msbwt_trace_plan: pure, no device: [6] of a call on an index that holds something, EXACTLY, with P = min(n, piece), piece 0 = 2^20,
+ * and pad(x) = ceil(x / 256) 256:
+ *     256                                   the counters
+ *     + 2 pad(64 P)                         the walks' states, two buffers
+ *     + 2 pad(8 w P)                        the queries and their counts, w = 8 in UNITIG mode, else 5 (round 0 asks 1 + 4 a walk)
+ *   and, host != 0 (the _device form's arrays are the caller's own):
+ *     + pad(8 P)                            a piece's seeds
+ *     + pad(8 P)                            its targets, targets != 0
+ *     + pad(P max_steps)                    its rows of symbols
+ *     + 3 pad(8 P) + 2 pad(P)               its steps, edge sums and last nodes; its stops and fans
+ * A host call stages all six outputs whichever are NULL.  n == 0: 0 bytes.  A bad mode: MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE as
+ * the call; device_bytes may be NULL.
+ *
+ * Out of scope here: the strand-merged (canonical) graph; k from 32 on, which needs two words a query; branching exploration (all
+ * paths between two anchors: out_fans and out_last let a caller fork on the host meanwhile); per-source thresholds. */
+#define MSBWT_TRACE_RIGHT 0
+#define MSBWT_TRACE_LEFT 1
+#define MSBWT_TRACE_UNIQUE 0
+#define MSBWT_TRACE_UNITIG 1
+#define MSBWT_TRACE_GREEDY 2
+#define MSBWT_TRACE_DEAD_END 1
+#define MSBWT_TRACE_BRANCH 2
+#define MSBWT_TRACE_MERGE 3
+#define MSBWT_TRACE_RETURNED 4
+#define MSBWT_TRACE_TARGET 5
+#define MSBWT_TRACE_MAX_STEPS 6
+#define MSBWT_TRACE_NOT_A_NODE 7
+#define MSBWT_TRACE_INFO_WORDS 8
+int msbwt_rle_trace_kmers(const msbwt_rle *bwt, const uint64_t *seeds2bit, const uint64_t *targets2bit /* or NULL */, size_t k, size_t n,
+                          uint64_t min_count, uint64_t min_edge, int mode, int direction, uint64_t max_steps,
+                          uint8_t *out_symbols /* n x max_steps */, uint64_t *out_steps, uint8_t *out_stops, uint64_t *out_edge_sums,
+                          uint64_t *out_last, uint8_t *out_fans);
+int msbwt_rle_trace_kmers_device(const msbwt_rle *bwt, const void *d_seeds2bit, const void *d_targets2bit /* or NULL */, size_t k, size_t n,
+                                 uint64_t min_count, uint64_t min_edge, int mode, int direction, uint64_t max_steps,
+                                 void *d_out_symbols, void *d_out_steps, void *d_out_stops, void *d_out_edge_sums, void *d_out_last,
+                                 void *d_out_fans, void *hip_stream);
+int msbwt_rle_trace_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_TRACE_INFO_WORDS */);
+int msbwt_rle_set_trace_piece(msbwt_rle *bwt, uint64_t walks);
+int msbwt_trace_plan(uint64_t n, uint64_t max_steps, int mode, int targets, int host, uint64_t piece, uint64_t *device_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

@@ -620,6 +620,65 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, canonical ? "msbwt_canonical_unitig_graph_by_source_plan" : "msbwt_unitig_graph_by_source_plan");
         return bytes;
     }
+    /// What trace_kmers returns: row i of symbols (n rows of max_steps bytes) holds steps[i] symbol codes (A C G T = 1 2 3 5) and zeros
+    /// behind them; stops[i] is MSBWT_TRACE_DEAD_END .. MSBWT_TRACE_NOT_A_NODE; last[i] the node the walk ended on; bit j of fans[i] = the
+    /// edge by symbol j leaves that node in the walk direction.
+    struct Traces {
+        std::vector<std::uint8_t> symbols;
+        std::vector<std::uint64_t> steps;
+        std::vector<std::uint8_t> stops;
+        std::vector<std::uint64_t> edge_sums, last;
+        std::vector<std::uint8_t> fans;
+        std::uint64_t max_steps = 0;
+        std::size_t size() const { return steps.size(); }
+    };
+    /// Traces (msbwt_hip.h, "traces"): from each packed seed k-mer (1 <= k <= 31) a walk through the k-mer graph, node by node, under
+    /// `mode` (MSBWT_TRACE_UNIQUE, _UNITIG, _GREEDY) in `direction` (MSBWT_TRACE_RIGHT, _LEFT), max_steps steps at the most; targets:
+    /// one a seed, or empty.
+    Traces trace_kmers(const std::vector<std::uint64_t> &seeds, std::size_t k, std::uint64_t max_steps, int mode = MSBWT_TRACE_UNIQUE, int direction = MSBWT_TRACE_RIGHT,
+                       std::uint64_t min_count = 1, std::uint64_t min_edge = 0, const std::vector<std::uint64_t> &targets = {}) const {
+        if (!targets.empty() && targets.size() != seeds.size()) throw Panic(MSBWT_ERR_INVALID_ARG, "trace_kmers: one target a seed");
+        const std::size_t n = seeds.size();
+        Traces t;
+        t.max_steps = max_steps;
+        t.symbols.resize(n * max_steps);
+        t.steps.resize(n);
+        t.stops.resize(n);
+        t.edge_sums.resize(n);
+        t.last.resize(n);
+        t.fans.resize(n);
+        check(msbwt_rle_trace_kmers(raw_, seeds.data(), targets.empty() ? nullptr : targets.data(), k, n, min_count, min_edge, mode, direction, max_steps, t.symbols.data(),
+                                    t.steps.data(), t.stops.data(), t.edge_sums.data(), t.last.data(), t.fans.data()));
+        return t;
+    }
+    /// Device buffers (every output and d_targets may be null; the byte arrays at any alignment); synchronises hip_stream.
+    void trace_kmers_device(const void *d_seeds, const void *d_targets, std::size_t k, std::size_t n, std::uint64_t min_count, std::uint64_t min_edge, int mode,
+                            int direction, std::uint64_t max_steps, void *d_symbols, void *d_steps, void *d_stops, void *d_edge_sums, void *d_last, void *d_fans,
+                            void *hip_stream = nullptr) const {
+        check(msbwt_rle_trace_kmers_device(raw_, d_seeds, d_targets, k, n, min_count, min_edge, mode, direction, max_steps, d_symbols, d_steps, d_stops, d_edge_sums, d_last,
+                                           d_fans, hip_stream));
+    }
+    /// The last trace call.
+    struct TraceInfo {
+        std::uint64_t walks = 0, rounds = 0, queries = 0, steps = 0, longest = 0, pieces = 0, scratch_bytes = 0, not_nodes = 0;
+    };
+    TraceInfo trace_info() const {
+        std::uint64_t w[MSBWT_TRACE_INFO_WORDS] = {};
+        check(msbwt_rle_trace_info(raw_, w));
+        TraceInfo i;
+        i.walks = w[0], i.rounds = w[1], i.queries = w[2], i.steps = w[3], i.longest = w[4], i.pieces = w[5], i.scratch_bytes = w[6], i.not_nodes = w[7];
+        return i;
+    }
+    /// Most walks a trace call advances at once (0 = automatic, 2^20); results never depend on it.
+    void set_trace_piece(std::uint64_t walks) { check(msbwt_rle_set_trace_piece(raw_, walks)); }
+    /// HBM bytes of scratch a trace call of n walks allocates (and frees again) on an index that holds something.
+    static std::uint64_t trace_plan(std::uint64_t n, std::uint64_t max_steps, int mode = MSBWT_TRACE_UNIQUE, bool targets = false, bool host = true,
+                                    std::uint64_t piece = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_trace_plan(n, max_steps, mode, targets ? 1 : 0, host ? 1 : 0, piece, &bytes);
+        if (rc) throw Panic(rc, "msbwt_trace_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

@@ -18,6 +18,10 @@ SOURCE_INDEX_SLACK = 1024  # MSBWT_SOURCE_INDEX_SLACK
 SPECTRUM_INFO_WORDS = 40  # MSBWT_SPECTRUM_INFO_WORDS
 UNITIG_INFO_WORDS = 8  # MSBWT_UNITIG_INFO_WORDS
 CANONICAL_UNITIG_INFO_WORDS = 10  # MSBWT_CANONICAL_UNITIG_INFO_WORDS
+TRACE_INFO_WORDS = 8  # MSBWT_TRACE_INFO_WORDS
+TRACE_DIRECTIONS = {"right": 0, "left": 1}  # MSBWT_TRACE_RIGHT, _LEFT
+TRACE_MODES = {"unique": 0, "unitig": 1, "greedy": 2}  # MSBWT_TRACE_UNIQUE, _UNITIG, _GREEDY
+TRACE_STOPS = ("", "DEAD_END", "BRANCH", "MERGE", "RETURNED", "TARGET", "MAX_STEPS", "NOT_A_NODE")  # MSBWT_TRACE_DEAD_END = 1 ..
 SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
@@ -113,6 +117,11 @@ SIGNATURES = {
     "msbwt_rle_enumerate_canonical_unitig_graph_by_source_device": (_int, [_vp, _sz, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _pu64, _pu64, _pu64, _vp]),
     "msbwt_canonical_unitig_graph_by_source_plan": (_int, [_u64, _u64, _u64, _u64, _u64, _u64, _sz, _pu64]),
     "msbwt_rle_spectrum_scratch_bytes": (_int, [_vp, _pu64]),
+    "msbwt_rle_trace_kmers": (_int, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_trace_kmers_device": (_int, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_trace_info": (_int, [_vp, _vp]),
+    "msbwt_rle_set_trace_piece": (_int, [_vp, _u64]),
+    "msbwt_trace_plan": (_int, [_u64, _u64, _int, _int, _int, _u64, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

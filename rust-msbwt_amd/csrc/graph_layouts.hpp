@@ -12,6 +12,7 @@
 #include "canonical_unitigs.hpp"
 #include "kmer_graph.hpp"
 #include "radix_sort.hpp"
+#include "trace.hpp"
 #include "unitig_links.hpp"
 #include "unitigs.hpp"
 
@@ -109,5 +110,19 @@ inline UnitigSourceLayout unitig_source_layout(uint64_t range_words, uint64_t U,
 }
 // the range words of either call: a word a node, or a pair a slot of a chunk of the 2 x `classes` slots
 inline uint64_t unitig_source_range_words(uint64_t nodes, bool canonical) { return canonical ? 2 * std::min(2 * nodes, kCanonicalUnitigChunkSlots) : nodes; }
+
+// The one block of a trace call, P walks a piece: the counters, padded, the two state buffers, the queries and their counts -- 1 + 4
+// words a walk in round 0, 4 or 8 in a later round -- and, where a host form stages them, a piece's seeds, targets and six outputs.  A
+// device form's are the caller's own and take no room.  Every extent is a whole multiple of 256 bytes.
+struct TraceLayout {
+    uint64_t counters, states[2], queries, counts, seeds, targets, symbols, steps, stops, edge_sums, last, fans, bytes;
+};
+inline TraceLayout trace_layout(uint64_t P, uint64_t max_steps, int mode, bool targets, bool host) {
+    const auto padded = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
+    const uint64_t words = padded(8 * trace_query_words(P, mode)), column = host ? padded(8 * P) : 0, bytes = host ? padded(P) : 0;
+    LayoutCursor c;
+    return {c.put(kTraceCounterBytes), {c.put(padded(sizeof(TraceWalk) * P)), c.put(padded(sizeof(TraceWalk) * P))}, c.put(words), c.put(words), c.put(column),
+            c.put(targets ? column : 0), c.put(host ? padded(P * max_steps) : 0), c.put(column), c.put(bytes), c.put(column), c.put(column), c.put(bytes), c.bytes};
+}
 
 }  // namespace msbwt

@@ -689,6 +689,67 @@ class RleBWT(BWT):
             _raise(rc, self._h)
         return out.value
 
+    # ---- traces: from seed k-mers through the k-mer graph, node by node, in batches ----
+    def trace_kmers(self, seeds, k, max_steps, mode="unique", direction="right", min_count=1, min_edge=None, targets=None, symbols=None):
+        """msbwt_rle_trace_kmers -> (symbols, steps, stops, edge_sums, last, fans).  seeds (and targets, optional): n packed k-mer words
+        (pack_2bit), 1 <= k <= 31.  mode "unique" | "unitig" | "greedy", direction "right" | "left" (include/msbwt_hip.h, "traces", has
+        the walk step by step).  symbols: (n, max_steps) uint8, row i holding steps[i] symbol codes (A C G T = 1 2 3 5) and zeros -- or
+        what the `symbols` array passed in held -- behind them; stops: _lib.TRACE_STOPS names the codes; last: the node a walk ended
+        on; fans: bit j = the edge by symbol j leaves it.  trace_sequences turns rows into sequences.
+        numpy arrays go through the host form.  torch tensors on this handle's device (int64 or uint64 words) go through the _device
+        form on torch's current stream, and torch tensors come back (words as int64)."""
+        mode, direction = _lib.TRACE_MODES[mode], _lib.TRACE_DIRECTIONS[direction]
+        if hasattr(seeds, "data_ptr"):
+            import torch
+            n, dev = int(seeds.numel()), seeds.device
+            if not seeds.is_contiguous() or seeds.element_size() != 8 or (targets is not None and (not targets.is_contiguous() or targets.element_size() != 8 or targets.numel() != n)):
+                raise ValueError("seeds and targets are contiguous tensors of n 64-bit words")
+            if symbols is None:
+                symbols = torch.zeros((n, int(max_steps)), dtype=torch.uint8, device=dev)
+            steps, edge_sums, last = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
+            stops, fans = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
+            self.trace_kmers_device(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in (symbols, steps, stops, edge_sums, last, fans)], mode=mode,
+                                    direction=direction, min_count=min_count, min_edge=min_edge, d_targets=None if targets is None else targets.data_ptr(),
+                                    stream=torch.cuda.current_stream(dev).cuda_stream)
+            return symbols, steps, stops, edge_sums, last, fans
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        n = len(seeds)
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, dtype=np.uint64).reshape(-1)
+            if len(targets) != n:
+                raise ValueError("one target a seed")
+        if symbols is None:
+            symbols = np.zeros((n, int(max_steps)), dtype=np.uint8)
+        elif symbols.dtype != np.uint8 or symbols.shape != (n, int(max_steps)) or not symbols.flags.c_contiguous:
+            raise ValueError("symbols is a C-contiguous (n, max_steps) uint8 array")
+        steps, edge_sums, last = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        stops, fans = (np.zeros(n, dtype=np.uint8) for _ in range(2))
+        rc = _lib.lib().msbwt_rle_trace_kmers(self._h, seeds.ctypes.data_as(C.c_void_p), None if targets is None else targets.ctypes.data_as(C.c_void_p), int(k), n,
+                                              int(min_count), int(min_edge or 0), mode, direction, int(max_steps),
+                                              *[a.ctypes.data_as(C.c_void_p) for a in (symbols, steps, stops, edge_sums, last, fans)])
+        if rc:
+            _raise(rc, self._h)
+        return symbols, steps, stops, edge_sums, last, fans
+
+    def trace_kmers_device(self, d_seeds, k, n, max_steps, d_symbols, d_steps, d_stops, d_edge_sums, d_last, d_fans, mode=0, direction=0, min_count=1, min_edge=None,
+                           d_targets=None, stream=0):
+        """msbwt_rle_trace_kmers_device: device pointers (ints; every output and d_targets may be None; the byte arrays at any
+        alignment), mode and direction as the header's numbers.  Synchronises `stream`; a device fault shows in device_status."""
+        rc = _lib.lib().msbwt_rle_trace_kmers_device(self._h, d_seeds, d_targets, int(k), int(n), int(min_count), int(min_edge or 0), int(mode), int(direction),
+                                                     int(max_steps), d_symbols, d_steps, d_stops, d_edge_sums, d_last, d_fans, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def trace_info(self):
+        """What the last trace call did: {"walks", "rounds", "queries", "steps", "longest", "pieces", "scratch_bytes", "not_nodes"}."""
+        return self._info(_lib.lib().msbwt_rle_trace_info, ("walks", "rounds", "queries", "steps", "longest", "pieces", "scratch_bytes", "not_nodes"))
+
+    def set_trace_piece(self, walks):
+        """Most walks a trace call advances at once (0 = automatic, 2^20): results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_trace_piece(self._h, int(walks))
+        if rc:
+            _raise(rc, self._h)
+
     def set_spectrum_frontier(self, nodes):
         """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""
         rc = _lib.lib().msbwt_rle_set_spectrum_frontier(self._h, int(nodes))
@@ -1227,6 +1288,34 @@ def unpack_2bit(words, k):
     w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
     shifts = (2 * np.arange(k - 1, -1, -1)).astype(np.uint64)
     return np.array([1, 2, 3, 5], dtype=np.uint8)[((w[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.intp)]
+
+
+def trace_sequences(seeds, k, symbols, steps, direction="right", text=False):
+    """The full sequence of every walk of RleBWT.trace_kmers, in reading order: the seed followed by its steps[i] symbols ("right"), or
+    those symbols reversed followed by the seed ("left") -> a list of uint8 arrays of symbol codes, or (text=True) of str."""
+    if direction not in _lib.TRACE_DIRECTIONS:
+        raise ValueError("direction is 'right' or 'left'")
+    heads = unpack_2bit(np.asarray(seeds, dtype=np.uint64) & np.uint64((1 << (2 * int(k))) - 1), int(k))
+    symbols, steps = np.asarray(symbols, dtype=np.uint8), np.asarray(steps, dtype=np.uint64).reshape(-1)
+    if symbols.ndim != 2 or len(symbols) != len(heads) or len(steps) != len(heads) or (len(steps) and int(steps.max()) > symbols.shape[1]):
+        raise ValueError("symbols is (n, max_steps) and steps[i] <= max_steps")
+    out = []
+    for head, row, s in zip(heads, symbols, steps):
+        row = row[:int(s)]
+        out.append(np.concatenate([head, row]) if direction == "right" else np.concatenate([row[::-1], head]))
+    if not text:
+        return out
+    letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)
+    return [letters[a].tobytes().decode() for a in out]
+
+
+def trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):
+    """msbwt_trace_plan: the bytes of HBM scratch a trace call of n walks allocates (and frees again) on an index that holds something."""
+    out = C.c_uint64(0)
+    rc = _lib.lib().msbwt_trace_plan(int(n), int(max_steps), _lib.TRACE_MODES[mode], int(bool(targets)), int(bool(host)), int(piece), C.byref(out))
+    if rc:
+        raise MsbwtError(rc, "msbwt_trace_plan: max_steps and n x max_steps must stay below 2^40")
+    return out.value
 
 
 def reverse_complement_2bit(words, k):

@@ -171,6 +171,17 @@ extern "C" {
     fn msbwt_canonical_unitig_graph_by_source_plan(total_rows: u64, free_hbm_bytes: u64, classes: u64, unitigs: u64, symbols: u64, links: u64,
                                                    n_sources: usize, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_spectrum_scratch_bytes(bwt: *const MsbwtRle, out_bytes: *mut u64) -> c_int;
+    // traces: from seed k-mers through the k-mer graph, node by node, in batches
+    fn msbwt_rle_trace_kmers(bwt: *const MsbwtRle, seeds2bit: *const u64, targets2bit: *const u64, k: usize, n: usize, min_count: u64, min_edge: u64,
+                             mode: c_int, direction: c_int, max_steps: u64, out_symbols: *mut u8, out_steps: *mut u64, out_stops: *mut u8,
+                             out_edge_sums: *mut u64, out_last: *mut u64, out_fans: *mut u8) -> c_int;
+    fn msbwt_rle_trace_kmers_device(bwt: *const MsbwtRle, d_seeds2bit: *const c_void, d_targets2bit: *const c_void, k: usize, n: usize, min_count: u64,
+                                    min_edge: u64, mode: c_int, direction: c_int, max_steps: u64, d_out_symbols: *mut c_void, d_out_steps: *mut c_void,
+                                    d_out_stops: *mut c_void, d_out_edge_sums: *mut c_void, d_out_last: *mut c_void, d_out_fans: *mut c_void,
+                                    hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_trace_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_rle_set_trace_piece(bwt: *mut MsbwtRle, walks: u64) -> c_int;
+    fn msbwt_trace_plan(n: u64, max_steps: u64, mode: c_int, targets: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -789,6 +800,55 @@ impl GpuRleBWT {
             else { msbwt_unitig_graph_by_source_plan(total_rows, free_hbm_bytes, nodes, unitigs, symbols, links, n_sources, &mut bytes) }
         };
         assert_eq!(rc, MSBWT_OK, "unitig_graph_by_source_plan: {} rows, {} nodes, {} sources", total_rows, nodes, n_sources);
+        bytes
+    }
+
+    /// Traces (include/msbwt_hip.h, "traces"): from each packed seed k-mer (1 <= k <= 31) a walk through the k-mer graph, `mode` 0 unique,
+    /// 1 unitig, 2 greedy, `direction` 0 right, 1 left, `max_steps` steps at the most; one target a seed, or none.
+    /// -> (symbols: n rows of max_steps, row i holding steps[i] symbol codes and zeros behind them; steps; stops; edge sums; last nodes; fans).
+    pub fn trace_kmers(&self, seeds: &[u64], targets: Option<&[u64]>, k: usize, min_count: u64, min_edge: u64, mode: c_int, direction: c_int, max_steps: u64)
+                       -> (Vec<u8>, Vec<u64>, Vec<u8>, Vec<u64>, Vec<u64>, Vec<u8>) {
+        let n = seeds.len();
+        if let Some(t) = targets { assert_eq!(t.len(), n, "trace_kmers: one target a seed"); }
+        let mut symbols = vec![0u8; n * max_steps as usize];
+        let (mut steps, mut sums, mut last) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        let (mut stops, mut fans) = (vec![0u8; n], vec![0u8; n]);
+        let rc = unsafe {
+            msbwt_rle_trace_kmers(self.raw, seeds.as_ptr(), targets.map_or(std::ptr::null(), |t| t.as_ptr()), k, n, min_count, min_edge, mode, direction, max_steps,
+                                  symbols.as_mut_ptr(), steps.as_mut_ptr(), stops.as_mut_ptr(), sums.as_mut_ptr(), last.as_mut_ptr(), fans.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("trace_kmers: {}", self.last_error()); }
+        (symbols, steps, stops, sums, last, fans)
+    }
+
+    /// The same over device buffers (every output and d_targets may be null) on `hip_stream`, which it synchronises.
+    pub unsafe fn trace_kmers_device(&self, d_seeds: *const c_void, d_targets: *const c_void, k: usize, n: usize, min_count: u64, min_edge: u64, mode: c_int,
+                                     direction: c_int, max_steps: u64, d_symbols: *mut c_void, d_steps: *mut c_void, d_stops: *mut c_void,
+                                     d_edge_sums: *mut c_void, d_last: *mut c_void, d_fans: *mut c_void, hip_stream: *mut c_void) {
+        let rc = msbwt_rle_trace_kmers_device(self.raw, d_seeds, d_targets, k, n, min_count, min_edge, mode, direction, max_steps, d_symbols, d_steps, d_stops,
+                                              d_edge_sums, d_last, d_fans, hip_stream);
+        if rc != MSBWT_OK { panic!("trace_kmers_device: {}", self.last_error()); }
+    }
+
+    /// The last trace call: walks, rounds, queries searched, steps in all, the longest walk, pieces, scratch bytes, walks that were no node.
+    pub fn trace_info(&self) -> [u64; 8] {
+        let mut words = [0u64; 8];
+        let rc = unsafe { msbwt_rle_trace_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("trace_info: {}", self.last_error()); }
+        words
+    }
+
+    /// Most walks a trace call advances at once (0 = automatic, 2^20); results never depend on it.
+    pub fn set_trace_piece(&mut self, walks: u64) {
+        let rc = unsafe { msbwt_rle_set_trace_piece(self.raw, walks) };
+        if rc != MSBWT_OK { panic!("set_trace_piece: {}", self.last_error()); }
+    }
+
+    /// HBM bytes of scratch a trace call of n walks allocates and frees again on an index that holds something (pure function).
+    pub fn trace_plan(n: u64, max_steps: u64, mode: c_int, targets: bool, host: bool, piece: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_trace_plan(n, max_steps, mode, targets as c_int, host as c_int, piece, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "trace_plan: {} walks of {} steps", n, max_steps);
         bytes
     }
 
