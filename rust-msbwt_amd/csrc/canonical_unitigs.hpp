@@ -3,7 +3,7 @@
 // what the kernels do between the canonical walk (canonical.hpp), which leaves the n classes (canonical word, own, other) in walk
 // order, and the compaction of unitigs.hpp, which works over slots whatever they came from:
 //   doubling   both member words of every class into one array of N = 2n - palindromes keys, the class count as the payload
-//   order      the stable 8-bit radix passes of radix_sort.hpp over the low ceil(2k / 8) bytes of the keys (spectrum.cpp calls them): slot
+//   order      the stable 8-bit radix passes of radix_sort.hpp over the low ceil(2k / 8) bytes of the keys (unitig_calls.cpp calls them): slot
 //              order is word order from here on.  WORD -> SLOT is a binary search over the sorted keys, ceil(log2 N) + 1 probes at the
 //              most; a word that is no node comes back as N, never as a slot.
 //   edges      the four (k+1)-mers q.c of every node are written as packed words chunk by chunk, counted by the library's packed

@@ -1,4 +1,4 @@
-// Where the arrays of a graph or unitig call lie in its HBM blocks (spectrum.cpp, and nothing else, includes this).  One function per
+// Where the arrays of a graph or unitig call lie in its HBM blocks (graph_calls.cpp, unitig_calls.cpp and trace_calls.cpp include this).  One function per
 // block returns the byte offset of every array, the block's bytes and -- where the kernels want a tail of it zeroed -- where that tail
 // starts: a msbwt_*_plan and the hipMalloc take `bytes`, the call carves `base + field`, the memset runs from `zero_from` to `bytes`.
 // A struct lists its arrays in their order in HBM, and its function puts their extents down in that order: the n-th put() is the n-th

@@ -104,7 +104,7 @@ int launch_count(msbwt_rle *h, const uint8_t *d_kmers, size_t k, size_t n, uint6
     });
 }
 
-// the same for queries handed over as 2-bit words (include/msbwt_hip.h, msbwt_rle_count_kmers_packed_device; the canonical k-mer calls of spectrum.cpp)
+// the same for queries handed over as 2-bit words (include/msbwt_hip.h, msbwt_rle_count_kmers_packed_device; the canonical walk of walk_call.cpp, the canonical unitigs and the traces)
 int launch_count_2bit(msbwt_rle *h, const uint64_t *d_packed, size_t k, size_t n, uint64_t *d_out, hipStream_t stream, int which) {
     if (k < 1 || k > 64) return fail(h, MSBWT_ERR_INVALID_ARG, "packed queries need 1 <= k <= 64");
     if (reinterpret_cast<uintptr_t>(d_packed) & 7u) return fail(h, MSBWT_ERR_INVALID_ARG, "packed queries must be 8-byte aligned");

@@ -1,7 +1,7 @@
 // The device sort of the builders (radix_sort.hip): stable least-significant-digit passes of 8 bits over (64-bit key, payload) pairs
 // -- per tile of 4096 keys a digit histogram, the exclusive scan of run_encode.hpp over digits x tiles, a scatter.  The builder from
 // reads sorts suffix positions by gathered key words with it (reads_build.hip: 32- or 64-bit positions), the canonical unitigs their
-// nodes by k-mer word (spectrum.cpp: the class count as the payload).  All pointers are device pointers; integer only.
+// nodes by k-mer word (unitig_calls.cpp: the class count as the payload).  All pointers are device pointers; integer only.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

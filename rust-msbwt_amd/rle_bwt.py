@@ -105,6 +105,15 @@ def _call_growing(call, cap):
     return rc, out[:length.value]
 
 
+_LETTERS = np.frombuffer(b"$ACGNT", dtype=np.uint8)  # a symbol code as text
+
+
+def _sequences(symbols, offsets):
+    """The ragged rows symbols[offsets[u]:offsets[u + 1]] of symbol codes as a list of str."""
+    letters = _LETTERS[symbols].tobytes().decode()
+    return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
 class RleBWT(BWT):
     def __init__(self, bin_power=8, device=-1):
         """RleBWT::new() / with_bin_power (rle_bwt.rs:297-322). `device` = HIP ordinal."""
@@ -496,36 +505,41 @@ class RleBWT(BWT):
         return table, nodes.value, edges.value
 
     # ---- unitigs: the non-branching paths of the k-mer graph as ragged sequences ----
-    def _unitigs(self, fn, k, min_count, min_edge, text):
-        """Both calls of the two-call pattern of a unitig entry point -> (symbols, offsets, count_sums, ends, flags), or with text=True
-        (sequences, count_sums, ends, flags)."""
+    def _unitigs(self, fn, k, min_count, min_edge, text, links=False, by_source=False):
+        """Both calls of the two-call pattern of a unitig entry point -> (symbols, offsets, count_sums, ends, flags) and, as the entry
+        point has them, (link_offsets, link_targets) and source_sums behind; with text=True the sequences in place of (symbols, offsets)."""
         args = (int(k), int(min_count), int(min_edge or 0))
-        U, S = C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, *args, None, None, None, None, None, 0, 0, C.byref(U), C.byref(S))
+        totals = [C.c_uint64(0) for _ in range(3 if links else 2)]  # U, S and, of a graph call, L
+        refs = [C.byref(t) for t in totals]
+        rc = fn(self._h, *args, *[None] * (5 + 2 * links + by_source), *[0] * len(totals), *refs)
         if rc:
             _raise(rc, self._h)
-        symbols, offsets = np.zeros(S.value, dtype=np.uint8), np.zeros(U.value + 1, dtype=np.uint64)
-        sums, ends, flags = np.zeros(U.value, dtype=np.uint64), np.zeros(U.value, dtype=np.uint8), np.zeros(U.value, dtype=np.uint8)
-        if U.value:
-            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in (symbols, offsets, sums, ends, flags)], U.value, S.value, C.byref(U), C.byref(S))
+        U, S = totals[0].value, totals[1].value
+        arrays = [np.zeros(S, dtype=np.uint8), np.zeros(U + 1, dtype=np.uint64), np.zeros(U, dtype=np.uint64), np.zeros(U, dtype=np.uint8), np.zeros(U, dtype=np.uint8)]
+        if links:
+            arrays += [np.zeros(2 * U + 1, dtype=np.uint64), np.zeros(totals[2].value, dtype=np.uint64)]
+        if by_source:
+            arrays.append(np.zeros((U, self.source_count()), dtype=np.uint64))
+        if U:
+            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in arrays], *[t.value for t in totals], *refs)
             if rc:
                 _raise(rc, self._h)
-        if not text:
-            return symbols, offsets, sums, ends, flags
-        letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
-        return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags
+        if text:
+            arrays[:2] = [_sequences(arrays[0], arrays[1])]
+        return tuple(arrays)
 
-    def _unitigs_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count, min_edge, stream):
-        U, S = C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, int(capacity_unitigs), int(capacity_symbols),
-                C.byref(U), C.byref(S), stream)
+    def _unitigs_device(self, fn, k, pointers, capacities, min_count, min_edge, stream):
+        """A device form of a unitig entry point: its device pointers, and a total per capacity -> (U, S) or (U, S, L)."""
+        totals = [C.c_uint64(0) for _ in capacities]
+        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), *pointers, *[int(c) for c in capacities], *[C.byref(t) for t in totals], stream)
         if rc:
             try:
                 _raise(rc, self._h)
             except MsbwtError as err:
-                err.n, err.symbols = U.value, S.value
+                for name, t in zip(("n", "symbols", "links"), totals):
+                    setattr(err, name, t.value)
                 raise
-        return U.value, S.value
+        return tuple(t.value for t in totals)
 
     def _info(self, fn, names):
         w = np.zeros(len(names), dtype=np.uint64)
@@ -547,8 +561,8 @@ class RleBWT(BWT):
         """msbwt_rle_enumerate_unitigs_device: device pointers (ints, each may be None; the byte arrays at any alignment) -> (U, S);
         both capacities 0 only counts, a capacity too small raises (nothing written; the error carries .n = U and .symbols = S).
         Synchronises `stream`."""
-        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_unitigs_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs,
-                                    capacity_symbols, min_count, min_edge, stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_unitigs_device, k, (d_symbols, d_offsets, d_count_sums, d_ends, d_flags),
+                                    (capacity_unitigs, capacity_symbols), min_count, min_edge, stream)
 
     def unitig_info(self):
         """What the last unitig call found: {"nodes", "edges", "links", "unitigs", "symbols", "circular", "longest", "rounds"}."""
@@ -564,8 +578,8 @@ class RleBWT(BWT):
     def enumerate_canonical_unitigs_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs, capacity_symbols, min_count=1,
                                            min_edge=None, stream=0):
         """msbwt_rle_enumerate_canonical_unitigs_device: as enumerate_unitigs_device."""
-        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_canonical_unitigs_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, capacity_unitigs,
-                                    capacity_symbols, min_count, min_edge, stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_canonical_unitigs_device, k, (d_symbols, d_offsets, d_count_sums, d_ends, d_flags),
+                                    (capacity_unitigs, capacity_symbols), min_count, min_edge, stream)
 
     def canonical_unitig_info(self):
         """What the last canonical unitig call found, for the emitted set: {"classes", "edge_classes", "links", "unitigs", "symbols",
@@ -582,50 +596,22 @@ class RleBWT(BWT):
         (o = 1).  canonical: flags[u] bit 1 = the unitig is its own reverse complement and has one side.  unitig_link_records keeps
         every edge once, write_gfa writes the graph."""
         fn = _lib.lib().msbwt_rle_enumerate_canonical_unitig_graph if canonical else _lib.lib().msbwt_rle_enumerate_unitig_graph
-        args = (int(k), int(min_count), int(min_edge or 0))
-        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, *args, None, None, None, None, None, None, None, 0, 0, 0, C.byref(U), C.byref(S), C.byref(L))
-        if rc:
-            _raise(rc, self._h)
-        symbols, offsets = np.zeros(S.value, dtype=np.uint8), np.zeros(U.value + 1, dtype=np.uint64)
-        sums, ends, flags = np.zeros(U.value, dtype=np.uint64), np.zeros(U.value, dtype=np.uint8), np.zeros(U.value, dtype=np.uint8)
-        link_offsets, link_targets = np.zeros(2 * U.value + 1, dtype=np.uint64), np.zeros(L.value, dtype=np.uint64)
-        if U.value:
-            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in (symbols, offsets, sums, ends, flags, link_offsets, link_targets)], U.value, S.value, L.value,
-                    C.byref(U), C.byref(S), C.byref(L))
-            if rc:
-                _raise(rc, self._h)
-        if not text:
-            return symbols, offsets, sums, ends, flags, link_offsets, link_targets
-        letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
-        return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags, link_offsets, link_targets
-
-    def _unitig_graph_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols,
-                             capacity_links, min_count, min_edge, stream):
-        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets,
-                int(capacity_unitigs), int(capacity_symbols), int(capacity_links), C.byref(U), C.byref(S), C.byref(L), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n, err.symbols, err.links = U.value, S.value, L.value
-                raise
-        return U.value, S.value, L.value
+        return self._unitigs(fn, k, min_count, min_edge, text, links=True)
 
     def enumerate_unitig_graph_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols,
                                       capacity_links, min_count=1, min_edge=None, stream=0):
         """msbwt_rle_enumerate_unitig_graph_device: device pointers (ints, each may be None; the byte arrays at any alignment) ->
         (U, S, L); all three capacities 0 only counts, a capacity too small raises (nothing written; the error carries .n = U,
         .symbols = S and .links = L).  Synchronises `stream`."""
-        return self._unitig_graph_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets,
-                                         d_link_targets, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge, stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_device, k, (d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets),
+                                    (capacity_unitigs, capacity_symbols, capacity_links), min_count, min_edge, stream)
 
     def enumerate_canonical_unitig_graph_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, capacity_unitigs,
                                                 capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
         """msbwt_rle_enumerate_canonical_unitig_graph_device: as enumerate_unitig_graph_device."""
-        return self._unitig_graph_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
-                                         d_link_offsets, d_link_targets, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge, stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_device, k,
+                                    (d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets),
+                                    (capacity_unitigs, capacity_symbols, capacity_links), min_count, min_edge, stream)
 
     # ---- unitigs by source: either unitig graph call with the per-input sums of every unitig behind the link table ----
     def enumerate_unitig_graph_by_source(self, k, min_count=1, min_edge=None, canonical=False, text=False):
@@ -634,52 +620,22 @@ class RleBWT(BWT):
         uint64, source_sums[u, s] = the rows of input s in the ranges of the nodes of unitig u (canonical: of both members of its
         classes, a palindrome once).  Row u sums to count_sums[u]; the thresholds meet the counts of all inputs together."""
         fn = _lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_by_source if canonical else _lib.lib().msbwt_rle_enumerate_unitig_graph_by_source
-        args = (int(k), int(min_count), int(min_edge or 0))
-        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, *args, None, None, None, None, None, None, None, None, 0, 0, 0, C.byref(U), C.byref(S), C.byref(L))
-        if rc:
-            _raise(rc, self._h)
-        symbols, offsets = np.zeros(S.value, dtype=np.uint8), np.zeros(U.value + 1, dtype=np.uint64)
-        sums, ends, flags = np.zeros(U.value, dtype=np.uint64), np.zeros(U.value, dtype=np.uint8), np.zeros(U.value, dtype=np.uint8)
-        link_offsets, link_targets = np.zeros(2 * U.value + 1, dtype=np.uint64), np.zeros(L.value, dtype=np.uint64)
-        source_sums = np.zeros((U.value, self.source_count()), dtype=np.uint64)
-        if U.value:
-            rc = fn(self._h, *args, *[a.ctypes.data_as(C.c_void_p) for a in (symbols, offsets, sums, ends, flags, link_offsets, link_targets, source_sums)], U.value,
-                    S.value, L.value, C.byref(U), C.byref(S), C.byref(L))
-            if rc:
-                _raise(rc, self._h)
-        if not text:
-            return symbols, offsets, sums, ends, flags, link_offsets, link_targets, source_sums
-        letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[symbols].tobytes().decode()
-        return [letters[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], sums, ends, flags, link_offsets, link_targets, source_sums
-
-    def _unitig_graph_by_source_device(self, fn, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs,
-                                       capacity_symbols, capacity_links, min_count, min_edge, stream):
-        U, S, L = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._h, int(k), int(min_count), int(min_edge or 0), d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
-                int(capacity_unitigs), int(capacity_symbols), int(capacity_links), C.byref(U), C.byref(S), C.byref(L), stream)
-        if rc:
-            try:
-                _raise(rc, self._h)
-            except MsbwtError as err:
-                err.n, err.symbols, err.links = U.value, S.value, L.value
-                raise
-        return U.value, S.value, L.value
+        return self._unitigs(fn, k, min_count, min_edge, text, links=True, by_source=True)
 
     def enumerate_unitig_graph_by_source_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
                                                 capacity_unitigs, capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
         """msbwt_rle_enumerate_unitig_graph_by_source_device: as enumerate_unitig_graph_device with d_source_sums (capacity_unitigs x
         source_count() u64, may be None) behind d_link_targets -> (U, S, L)."""
-        return self._unitig_graph_by_source_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_by_source_device, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags,
-                                                   d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs, capacity_symbols, capacity_links, min_count, min_edge,
-                                                   stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_unitig_graph_by_source_device, k,
+                                    (d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums),
+                                    (capacity_unitigs, capacity_symbols, capacity_links), min_count, min_edge, stream)
 
     def enumerate_canonical_unitig_graph_by_source_device(self, k, d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums,
                                                           capacity_unitigs, capacity_symbols, capacity_links, min_count=1, min_edge=None, stream=0):
         """msbwt_rle_enumerate_canonical_unitig_graph_by_source_device: as enumerate_unitig_graph_by_source_device."""
-        return self._unitig_graph_by_source_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_by_source_device, k, d_symbols, d_offsets, d_count_sums, d_ends,
-                                                   d_flags, d_link_offsets, d_link_targets, d_source_sums, capacity_unitigs, capacity_symbols, capacity_links, min_count,
-                                                   min_edge, stream)
+        return self._unitigs_device(_lib.lib().msbwt_rle_enumerate_canonical_unitig_graph_by_source_device, k,
+                                    (d_symbols, d_offsets, d_count_sums, d_ends, d_flags, d_link_offsets, d_link_targets, d_source_sums),
+                                    (capacity_unitigs, capacity_symbols, capacity_links), min_count, min_edge, stream)
 
     def spectrum_scratch_bytes(self):
         """Bytes of HBM scratch the last k-mer walk call of this handle allocated (and freed again before it returned)."""
@@ -1305,8 +1261,7 @@ def trace_sequences(seeds, k, symbols, steps, direction="right", text=False):
         out.append(np.concatenate([head, row]) if direction == "right" else np.concatenate([row[::-1], head]))
     if not text:
         return out
-    letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)
-    return [letters[a].tobytes().decode() for a in out]
+    return [_LETTERS[a].tobytes().decode() for a in out]
 
 
 def trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):
@@ -1386,12 +1341,11 @@ def write_gfa(file, k, symbols, offsets, count_sums, flags, link_offsets, link_t
     line carries the tag `sc:Z:c0,c1,...` behind KC:i:, the unitig's sums by input in decimal.  `file`: a path, or an object with
     write().  -> (segments, links) written."""
     k = int(k)
-    letters = np.frombuffer(b"$ACGNT", dtype=np.uint8)[np.ascontiguousarray(symbols, dtype=np.uint8)].tobytes().decode()
     sides, targets = unitig_link_records(link_offsets, link_targets, flags)
     lines = ["H\tVN:Z:1.0\n"]
-    for u, (a, z) in enumerate(zip(offsets[:-1], offsets[1:])):
+    for u, sequence in enumerate(_sequences(np.ascontiguousarray(symbols, dtype=np.uint8), offsets)):
         colours = "" if source_sums is None else "\tsc:Z:" + ",".join(str(int(c)) for c in source_sums[u])
-        lines.append("S\t%d\t%s\tKC:i:%d%s\n" % (u, letters[int(a):int(z)], int(count_sums[u]), colours))
+        lines.append("S\t%d\t%s\tKC:i:%d%s\n" % (u, sequence, int(count_sums[u]), colours))
     for a, e in zip(sides.tolist(), targets.tolist()):
         lines.append("L\t%d\t%s\t%d\t%s\t%dM\n" % (a >> 1, "-" if a & 1 else "+", e >> 1, "-" if e & 1 else "+", k - 1))
     if hasattr(file, "write"):

@@ -1,4 +1,4 @@
-"""Canonical unitigs (csrc/canonical_unitigs.hip, csrc/spectrum.cpp): the strand-merged k-mer graph compacted into its non-branching
+"""Canonical unitigs (csrc/canonical_unitigs.hip, csrc/unitig_calls.cpp): the strand-merged k-mer graph compacted into its non-branching
 paths on the device, every class of a k-mer and its reverse complement in exactly one unitig exactly once.
 
 Expected values never come from the code under test.  The oracle is Python over the reads as strings, in the style of

@@ -1,5 +1,5 @@
 """The k-mer graph, the unitigs and the canonical unitigs (csrc/kmer_graph.hip, csrc/unitigs.hip, csrc/canonical_unitigs.hip and their
-driver in csrc/spectrum.cpp) at the sizes where their loops go round, and on an index of more than 2^32 rows whose k-mer ranges lie
+drivers in csrc/graph_calls.cpp and csrc/unitig_calls.cpp) at the sizes where their loops go round, and on an index of more than 2^32 rows whose k-mer ranges lie
 on both sides of row 2^32.  Every column is compared for equality with tests/graph_oracle.py, the numpy oracle that
 tests/test_graph_oracle.py holds to the string oracles of the neighbouring files on the CPU; nothing expected comes from the library.
 

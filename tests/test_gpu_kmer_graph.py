@@ -1,4 +1,4 @@
-"""The k-mer graph (csrc/kmer_graph.hip, csrc/spectrum.cpp): the sorted dump with an edge byte per k-mer, and the degree table.
+"""The k-mer graph (csrc/kmer_graph.hip, csrc/graph_calls.cpp): the sorted dump with an edge byte per k-mer, and the degree table.
 
 Expected values never come from the code under test: a census of the reads' ACGT-only windows at k and at k + 1 -- a Counter over
 strings for the small sets (and for k = 32, where k + 1 does not fit a word), numpy for the 4000-read sets --, the CPU oracle's ranges

@@ -1,4 +1,4 @@
-"""Traces (csrc/trace.hip, csrc/spectrum.cpp: msbwt_rle_trace_kmers[_device]): from seed k-mers through the k-mer graph, node by node.
+"""Traces (csrc/trace.hip, csrc/trace_calls.cpp: msbwt_rle_trace_kmers[_device]): from seed k-mers through the k-mer graph, node by node.
 
 Expected values never come from the code under test: tests/trace_oracle.py is the header's definition over strings (checked against
 the unitig oracle in tests/test_trace_oracle.py), closed forms for a random chain, and -- where the issue asks for exactly that -- the

@@ -1,4 +1,4 @@
-"""Unitig links (csrc/unitig_links.hip and its driver in csrc/spectrum.cpp): the link table msbwt_rle_enumerate_unitig_graph and
+"""Unitig links (csrc/unitig_links.hip and its driver in csrc/unitig_calls.cpp): the link table msbwt_rle_enumerate_unitig_graph and
 msbwt_rle_enumerate_canonical_unitig_graph return behind the five columns of the unitig calls.
 
 Every expected value comes from tests/link_oracle.py over the unitigs of an oracle (the string oracles of test_gpu_unitigs.py and

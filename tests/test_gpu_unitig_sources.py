@@ -1,4 +1,4 @@
-"""Unitigs by source (csrc/unitig_sources.hip and its driver in csrc/spectrum.cpp): the U x S matrix
+"""Unitigs by source (csrc/unitig_sources.hip and its driver in csrc/unitig_calls.cpp): the U x S matrix
 msbwt_rle_enumerate_unitig_graph_by_source and msbwt_rle_enumerate_canonical_unitig_graph_by_source return behind the link table.
 
 Every expected matrix comes from tests/colour_oracle.py -- Counters of the k-windows per source over the unitigs of the string oracles,

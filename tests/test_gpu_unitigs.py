@@ -1,4 +1,4 @@
-"""Unitigs (csrc/unitigs.hip, csrc/spectrum.cpp): the k-mer graph compacted into its non-branching paths on the device.
+"""Unitigs (csrc/unitigs.hip, csrc/unitig_calls.cpp): the k-mer graph compacted into its non-branching paths on the device.
 
 Expected values never come from the code under test.  The oracle is a few lines of Python over the reads as strings: Counters of the
 ACGT-only windows at k and at k + 1 (test_gpu_kmer_graph.windows) give the nodes and the edges, the links follow from the definition

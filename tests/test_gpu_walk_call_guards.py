@@ -1,4 +1,4 @@
-"""The guards of the k-mer walk calls (csrc/spectrum.cpp) -- the spectra, the dumps in both forms and the degree table of the plain,
+"""The guards of the k-mer walk calls (csrc/walk_call.hpp, csrc/spectrum.cpp, csrc/graph_calls.cpp) -- the spectra, the dumps in both forms and the degree table of the plain,
 canonical, by-source and graph families -- as their callers see them: the return code AND the whole text msbwt_rle_last_error gives,
 for a k out of range, limits the wrong way round, a histogram too short, a NULL out_n and a capacity between 0 and n; the order the
 checks fire in (no index before any argument, no sources before k, k before the limits); and the scratch a plain or a canonical call
