@@ -866,7 +866,7 @@ int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes);
  * A host call stages all six outputs whichever are NULL.  n == 0: 0 bytes.  A bad mode: MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE as
  * the call; device_bytes may be NULL.
  *
- * Out of scope here: the strand-merged (canonical) graph; k from 32 on, which needs two words a query; branching exploration (all
+ * Out of scope here: the strand-merged graph, which "canonical traces" below walks; k from 32 on, which needs two words a query; branching exploration (all
  * paths between two anchors: out_fans and out_last let a caller fork on the host meanwhile); per-source thresholds. */
 #define MSBWT_TRACE_RIGHT 0
 #define MSBWT_TRACE_LEFT 1
@@ -892,6 +892,72 @@ int msbwt_rle_trace_kmers_device(const msbwt_rle *bwt, const void *d_seeds2bit, 
 int msbwt_rle_trace_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_TRACE_INFO_WORDS */);
 int msbwt_rle_set_trace_piece(msbwt_rle *bwt, uint64_t walks);
 int msbwt_trace_plan(uint64_t n, uint64_t max_steps, int mode, int targets, int host, uint64_t piece, uint64_t *device_bytes);
+
+/* ---- canonical traces ---- the traces above through the strand-merged graph: from each of n seed k-mers a walk through D, on the
+ * device (no reference counterpart).  Reads come from both strands, and G sees half the coverage on each: a path seen once per strand
+ * is no path of G at min_count = 2, a branch on the other strand goes unseen, and a trace through G does not reproduce the unitigs of
+ * msbwt_rle_enumerate_canonical_unitigs.  These calls take the arguments of msbwt_rle_trace_kmers[_device] type for type and return
+ * its six outputs; modes, directions and the stops 1-7 are the MSBWT_TRACE_* values, and 1 <= k <= 31.
+ *
+ * THE GRAPH is D(k, m, me) exactly as "canonical unitigs" defines it.  cc(x) = count_kmer(x) + count_kmer(rc(x)), and cc(x) =
+ * count_kmer(x) for a palindrome.  NODES: every k-mer q with cc(q) >= m = max(min_count, 1) -- both members of a class, a member the
+ * index does not hold included, so a seed may be a k-mer the index holds only as its reverse complement.  EDGES: q -> q' by symbol c
+ * (q.c for RIGHT, c.q for LEFT) when cc of that (k+1)-mer is >= me AND q' is a node; the second clause can fail only at a palindromic
+ * q', with k even and m >= 2 (reads {"CATG"}, k = 2, m = 2: cc(CAT) = 2 and cc(AT) = 1, so the fan of CA is empty).  min_edge as above.
+ * The FAN, the BACK-FAN, the edge word and the next node are the traces' table, unchanged.
+ * ONE WALK: steps 0-8 of "traces" with these changes and no others.
+ *   0.  s is no node when cc(s) < m.
+ *   2, 3, 4 and out_fans read fans of D: the count is cc, the far end must be a node.
+ *   3.  GREEDY takes the edge with the largest cc, on a tie the smallest symbol.
+ *   3b. Mode UNITIG only, once e and nxt are chosen: stop MSBWT_CANONICAL_TRACE_MIRROR when cur is a palindrome, nxt is a palindrome, or
+ *       e is its own reverse complement; nxt is not entered.  These are exactly the two cuts of the canonical unitigs' LINKS.  The step
+ *       comes BEFORE 4: a cut link into a node with two predecessors reports MIRROR, not MERGE.
+ *   6.  edge_sum += cc(e).
+ *   5, 7 compare words as they are: nxt == s, cur == target.  rc(s) and rc(target) stop nothing.
+ * out_last is the word in the walk's orientation; out_edge_sums sums cc.
+ * UNIQUE and GREEDY follow D as it is: through palindromic nodes and across hairpin edges q -> rc(q).  After a hairpin the walk runs
+ * down the mirror of its own path, until a stop of its own or max_steps: stated, not cured.
+ * A UNITIG trace RIGHT from the first node of a unitig of msbwt_rle_enumerate_canonical_unitigs reproduces that unitig, and so does a
+ * UNITIG trace LEFT from its last node: steps = nodes - 1, it stops RETURNED exactly on the circular unitigs, and out_fans equals
+ * out_ends >> 4 (RIGHT) and out_ends & 15 (LEFT).  For UNIQUE and UNITIG the trace of rc(s) in the other direction is the mirror of the
+ * trace of s (symbols complemented, last reverse-complemented, fan bit j <-> 3 - j); GREEDY's tie rule is not symmetric.  An index of
+ * the same reads with any of them reverse-complemented returns the same bytes.
+ *
+ * Guards and their order, the empty index (every stop NOT_A_NODE, seeds masked, nothing allocated), n == 0, NULL outputs, untouched
+ * row tails, the _device form and its stream, the scratch (per call, freed on return) and faults through msbwt_rle_device_status are
+ * those of msbwt_rle_trace_kmers[_device].  msbwt_rle_set_trace_piece governs both calls.  Results depend on no knob, no index form
+ * and no piece.
+ *
+ * How ("Canonical traces"): the rounds of the traces, with every query searched on both strands.  Round 0 searches the
+ * seed and its reverse complement at length k and the 4 edges of the seed's fan with their 4 reverse complements; a later round the
+ * same 8 for the candidate's fan and, in UNITIG mode, 8 for its back-fan.  One kernel a round folds the counts to cc (a word that is
+ * its own reverse complement counts once), applies the steps, writes a finished walk's outputs once and compacts the survivors with
+ * their next queries.  THE NODE CLAUSE: of the four far ends of a fan at most one can be a palindrome -- the one by the complement of
+ * the node's second symbol (RIGHT; its last but one for LEFT).  Only with k even and m >= 2 does its count matter; then (E = 1, else
+ * E = 0) each walk and fan side asks ONE more query of length k, that far end, searched as a batch of its own; its count is used only
+ * where the word is a palindrome.  Queries searched, exactly: (10 + E) n in round 0, then 8 + E (UNITIG: 16 + 2 E) a live walk and
+ * round; a walk of s steps is live in s later rounds, and in one more where a MERGE or, in UNITIG mode, a RETURNED stops it.  MIRROR
+ * and the RETURNED of the other modes are seen on words and cost no round.
+ *
+ * msbwt_rle_canonical_trace_info: out[MSBWT_CANONICAL_TRACE_INFO_WORDS] of the handle's last canonical trace call, with the eight
+ * meanings of msbwt_rle_trace_info (which a canonical call leaves as it was, and the other way round).
+ * msbwt_canonical_trace_plan: pure, no device: msbwt_trace_plan with w = 18 in UNITIG mode, else 11, in its term 2 pad(8 w P) -- [6] of
+ * a call on an index that holds something, EXACTLY, whatever k and m are.
+ *
+ * Out of scope here: k from 32 on; forking at branches; per-source thresholds; a target or the seed matched by its reverse
+ * complement; both strands in one extension-count search (that call takes a byte a symbol). */
+#define MSBWT_CANONICAL_TRACE_MIRROR 8
+#define MSBWT_CANONICAL_TRACE_INFO_WORDS 8
+int msbwt_rle_trace_canonical_kmers(const msbwt_rle *bwt, const uint64_t *seeds2bit, const uint64_t *targets2bit /* or NULL */, size_t k,
+                                    size_t n, uint64_t min_count, uint64_t min_edge, int mode, int direction, uint64_t max_steps,
+                                    uint8_t *out_symbols /* n x max_steps */, uint64_t *out_steps, uint8_t *out_stops,
+                                    uint64_t *out_edge_sums, uint64_t *out_last, uint8_t *out_fans);
+int msbwt_rle_trace_canonical_kmers_device(const msbwt_rle *bwt, const void *d_seeds2bit, const void *d_targets2bit /* or NULL */, size_t k,
+                                           size_t n, uint64_t min_count, uint64_t min_edge, int mode, int direction, uint64_t max_steps,
+                                           void *d_out_symbols, void *d_out_steps, void *d_out_stops, void *d_out_edge_sums,
+                                           void *d_out_last, void *d_out_fans, void *hip_stream);
+int msbwt_rle_canonical_trace_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_CANONICAL_TRACE_INFO_WORDS */);
+int msbwt_canonical_trace_plan(uint64_t n, uint64_t max_steps, int mode, int targets, int host, uint64_t piece, uint64_t *device_bytes);
 
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path

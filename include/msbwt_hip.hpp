@@ -679,6 +679,49 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_trace_plan");
         return bytes;
     }
+    /// Canonical traces (msbwt_hip.h, "canonical traces"): trace_kmers through the strand-merged graph of the canonical unitigs -- a k-mer
+    /// counts with its reverse complement, edge_sums sums class counts, last is the word in the walk's orientation, and MSBWT_TRACE_UNITIG
+    /// stops MSBWT_CANONICAL_TRACE_MIRROR where the link chosen is one of the canonical unitigs' cuts.
+    Traces trace_canonical_kmers(const std::vector<std::uint64_t> &seeds, std::size_t k, std::uint64_t max_steps, int mode = MSBWT_TRACE_UNIQUE,
+                                 int direction = MSBWT_TRACE_RIGHT, std::uint64_t min_count = 1, std::uint64_t min_edge = 0,
+                                 const std::vector<std::uint64_t> &targets = {}) const {
+        if (!targets.empty() && targets.size() != seeds.size()) throw Panic(MSBWT_ERR_INVALID_ARG, "trace_canonical_kmers: one target a seed");
+        const std::size_t n = seeds.size();
+        Traces t;
+        t.max_steps = max_steps;
+        t.symbols.resize(n * max_steps);
+        t.steps.resize(n);
+        t.stops.resize(n);
+        t.edge_sums.resize(n);
+        t.last.resize(n);
+        t.fans.resize(n);
+        check(msbwt_rle_trace_canonical_kmers(raw_, seeds.data(), targets.empty() ? nullptr : targets.data(), k, n, min_count, min_edge, mode, direction, max_steps,
+                                              t.symbols.data(), t.steps.data(), t.stops.data(), t.edge_sums.data(), t.last.data(), t.fans.data()));
+        return t;
+    }
+    /// Device buffers, as trace_kmers_device.
+    void trace_canonical_kmers_device(const void *d_seeds, const void *d_targets, std::size_t k, std::size_t n, std::uint64_t min_count, std::uint64_t min_edge, int mode,
+                                      int direction, std::uint64_t max_steps, void *d_symbols, void *d_steps, void *d_stops, void *d_edge_sums, void *d_last, void *d_fans,
+                                      void *hip_stream = nullptr) const {
+        check(msbwt_rle_trace_canonical_kmers_device(raw_, d_seeds, d_targets, k, n, min_count, min_edge, mode, direction, max_steps, d_symbols, d_steps, d_stops,
+                                                     d_edge_sums, d_last, d_fans, hip_stream));
+    }
+    /// The last canonical trace call.
+    TraceInfo canonical_trace_info() const {
+        std::uint64_t w[MSBWT_CANONICAL_TRACE_INFO_WORDS] = {};
+        check(msbwt_rle_canonical_trace_info(raw_, w));
+        TraceInfo i;
+        i.walks = w[0], i.rounds = w[1], i.queries = w[2], i.steps = w[3], i.longest = w[4], i.pieces = w[5], i.scratch_bytes = w[6], i.not_nodes = w[7];
+        return i;
+    }
+    /// HBM bytes of scratch a canonical trace call of n walks allocates (and frees again) on an index that holds something.
+    static std::uint64_t canonical_trace_plan(std::uint64_t n, std::uint64_t max_steps, int mode = MSBWT_TRACE_UNIQUE, bool targets = false, bool host = true,
+                                              std::uint64_t piece = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_canonical_trace_plan(n, max_steps, mode, targets ? 1 : 0, host ? 1 : 0, piece, &bytes);
+        if (rc) throw Panic(rc, "msbwt_canonical_trace_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

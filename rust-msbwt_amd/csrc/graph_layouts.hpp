@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "canonical_trace.hpp"
 #include "canonical_unitigs.hpp"
 #include "kmer_graph.hpp"
 #include "radix_sort.hpp"
@@ -117,12 +118,20 @@ inline uint64_t unitig_source_range_words(uint64_t nodes, bool canonical) { retu
 struct TraceLayout {
     uint64_t counters, states[2], queries, counts, seeds, targets, symbols, steps, stops, edge_sums, last, fans, bytes;
 };
-inline TraceLayout trace_layout(uint64_t P, uint64_t max_steps, int mode, bool targets, bool host) {
+inline TraceLayout trace_layout_of(uint64_t P, uint64_t max_steps, uint64_t query_words, bool targets, bool host) {
     const auto padded = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
-    const uint64_t words = padded(8 * trace_query_words(P, mode)), column = host ? padded(8 * P) : 0, bytes = host ? padded(P) : 0;
+    const uint64_t words = padded(8 * query_words), column = host ? padded(8 * P) : 0, bytes = host ? padded(P) : 0;
     LayoutCursor c;
     return {c.put(kTraceCounterBytes), {c.put(padded(sizeof(TraceWalk) * P)), c.put(padded(sizeof(TraceWalk) * P))}, c.put(words), c.put(words), c.put(column),
             c.put(targets ? column : 0), c.put(host ? padded(P * max_steps) : 0), c.put(column), c.put(bytes), c.put(column), c.put(column), c.put(bytes), c.bytes};
+}
+inline TraceLayout trace_layout(uint64_t P, uint64_t max_steps, int mode, bool targets, bool host) {
+    return trace_layout_of(P, max_steps, trace_query_words(P, mode), targets, host);
+}
+// The one block of a canonical trace call: the same, with the queries of both strands and of the node clause -- 2 + 8 + 1 words a walk in
+// round 0, 8 + 1 or 16 + 2 in a later round (canonical_trace.hpp has where each lies).
+inline TraceLayout canonical_trace_layout(uint64_t P, uint64_t max_steps, int mode, bool targets, bool host) {
+    return trace_layout_of(P, max_steps, canonical_trace_query_words(P, mode), targets, host);
 }
 
 }  // namespace msbwt

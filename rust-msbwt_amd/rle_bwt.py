@@ -654,7 +654,13 @@ class RleBWT(BWT):
         on; fans: bit j = the edge by symbol j leaves it.  trace_sequences turns rows into sequences.
         numpy arrays go through the host form.  torch tensors on this handle's device (int64 or uint64 words) go through the _device
         form on torch's current stream, and torch tensors come back (words as int64)."""
+        return self._trace_kmers(False, seeds, k, max_steps, mode, direction, min_count, min_edge, targets, symbols)
+
+    def _trace_kmers(self, canonical, seeds, k, max_steps, mode, direction, min_count, min_edge, targets, symbols):
+        """trace_kmers and trace_canonical_kmers: the arrays of either call"""
         mode, direction = _lib.TRACE_MODES[mode], _lib.TRACE_DIRECTIONS[direction]
+        host_call = _lib.lib().msbwt_rle_trace_canonical_kmers if canonical else _lib.lib().msbwt_rle_trace_kmers
+        device_call = self.trace_canonical_kmers_device if canonical else self.trace_kmers_device
         if hasattr(seeds, "data_ptr"):
             import torch
             n, dev = int(seeds.numel()), seeds.device
@@ -664,9 +670,8 @@ class RleBWT(BWT):
                 symbols = torch.zeros((n, int(max_steps)), dtype=torch.uint8, device=dev)
             steps, edge_sums, last = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
             stops, fans = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
-            self.trace_kmers_device(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in (symbols, steps, stops, edge_sums, last, fans)], mode=mode,
-                                    direction=direction, min_count=min_count, min_edge=min_edge, d_targets=None if targets is None else targets.data_ptr(),
-                                    stream=torch.cuda.current_stream(dev).cuda_stream)
+            device_call(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in (symbols, steps, stops, edge_sums, last, fans)], mode=mode, direction=direction,
+                        min_count=min_count, min_edge=min_edge, d_targets=None if targets is None else targets.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
             return symbols, steps, stops, edge_sums, last, fans
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
         n = len(seeds)
@@ -680,9 +685,8 @@ class RleBWT(BWT):
             raise ValueError("symbols is a C-contiguous (n, max_steps) uint8 array")
         steps, edge_sums, last = (np.zeros(n, dtype=np.uint64) for _ in range(3))
         stops, fans = (np.zeros(n, dtype=np.uint8) for _ in range(2))
-        rc = _lib.lib().msbwt_rle_trace_kmers(self._h, seeds.ctypes.data_as(C.c_void_p), None if targets is None else targets.ctypes.data_as(C.c_void_p), int(k), n,
-                                              int(min_count), int(min_edge or 0), mode, direction, int(max_steps),
-                                              *[a.ctypes.data_as(C.c_void_p) for a in (symbols, steps, stops, edge_sums, last, fans)])
+        rc = host_call(self._h, seeds.ctypes.data_as(C.c_void_p), None if targets is None else targets.ctypes.data_as(C.c_void_p), int(k), n, int(min_count),
+                       int(min_edge or 0), mode, direction, int(max_steps), *[a.ctypes.data_as(C.c_void_p) for a in (symbols, steps, stops, edge_sums, last, fans)])
         if rc:
             _raise(rc, self._h)
         return symbols, steps, stops, edge_sums, last, fans
@@ -700,8 +704,29 @@ class RleBWT(BWT):
         """What the last trace call did: {"walks", "rounds", "queries", "steps", "longest", "pieces", "scratch_bytes", "not_nodes"}."""
         return self._info(_lib.lib().msbwt_rle_trace_info, ("walks", "rounds", "queries", "steps", "longest", "pieces", "scratch_bytes", "not_nodes"))
 
+    # ---- canonical traces: the same through the strand-merged graph ----
+    def trace_canonical_kmers(self, seeds, k, max_steps, mode="unique", direction="right", min_count=1, min_edge=None, targets=None, symbols=None):
+        """msbwt_rle_trace_canonical_kmers -> (symbols, steps, stops, edge_sums, last, fans): trace_kmers through the strand-merged graph
+        of the canonical unitigs (include/msbwt_hip.h, "canonical traces").  A k-mer counts with its reverse complement, so a seed may
+        be a k-mer the index holds only on the other strand; edge_sums sums class counts; last is the word in the walk's orientation.
+        stops: _lib.CANONICAL_TRACE_STOPS names the codes -- "unitig" mode has MIRROR, where the link chosen is a cut of the canonical
+        unitigs.  Arguments, arrays and tensors as trace_kmers; trace_sequences serves both."""
+        return self._trace_kmers(True, seeds, k, max_steps, mode, direction, min_count, min_edge, targets, symbols)
+
+    def trace_canonical_kmers_device(self, d_seeds, k, n, max_steps, d_symbols, d_steps, d_stops, d_edge_sums, d_last, d_fans, mode=0, direction=0, min_count=1,
+                                     min_edge=None, d_targets=None, stream=0):
+        """msbwt_rle_trace_canonical_kmers_device: as trace_kmers_device."""
+        rc = _lib.lib().msbwt_rle_trace_canonical_kmers_device(self._h, d_seeds, d_targets, int(k), int(n), int(min_count), int(min_edge or 0), int(mode), int(direction),
+                                                               int(max_steps), d_symbols, d_steps, d_stops, d_edge_sums, d_last, d_fans, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def canonical_trace_info(self):
+        """What the last canonical trace call did: the words of trace_info."""
+        return self._info(_lib.lib().msbwt_rle_canonical_trace_info, ("walks", "rounds", "queries", "steps", "longest", "pieces", "scratch_bytes", "not_nodes"))
+
     def set_trace_piece(self, walks):
-        """Most walks a trace call advances at once (0 = automatic, 2^20): results never depend on it."""
+        """Most walks a trace call of either kind advances at once (0 = automatic, 2^20): results never depend on it."""
         rc = _lib.lib().msbwt_rle_set_trace_piece(self._h, int(walks))
         if rc:
             _raise(rc, self._h)
@@ -1262,6 +1287,15 @@ def trace_sequences(seeds, k, symbols, steps, direction="right", text=False):
     if not text:
         return out
     return [_LETTERS[a].tobytes().decode() for a in out]
+
+
+def canonical_trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):
+    """msbwt_canonical_trace_plan: the bytes of HBM scratch a canonical trace call of n walks allocates (and frees again) on an index that holds something."""
+    out = C.c_uint64(0)
+    rc = _lib.lib().msbwt_canonical_trace_plan(int(n), int(max_steps), _lib.TRACE_MODES[mode], int(bool(targets)), int(bool(host)), int(piece), C.byref(out))
+    if rc:
+        raise MsbwtError(rc, "msbwt_canonical_trace_plan: max_steps and n x max_steps must stay below 2^40")
+    return out.value
 
 
 def trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):

@@ -182,6 +182,16 @@ extern "C" {
     fn msbwt_rle_trace_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
     fn msbwt_rle_set_trace_piece(bwt: *mut MsbwtRle, walks: u64) -> c_int;
     fn msbwt_trace_plan(n: u64, max_steps: u64, mode: c_int, targets: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
+    // canonical traces: the same through the strand-merged graph
+    fn msbwt_rle_trace_canonical_kmers(bwt: *const MsbwtRle, seeds2bit: *const u64, targets2bit: *const u64, k: usize, n: usize, min_count: u64, min_edge: u64,
+                                       mode: c_int, direction: c_int, max_steps: u64, out_symbols: *mut u8, out_steps: *mut u64, out_stops: *mut u8,
+                                       out_edge_sums: *mut u64, out_last: *mut u64, out_fans: *mut u8) -> c_int;
+    fn msbwt_rle_trace_canonical_kmers_device(bwt: *const MsbwtRle, d_seeds2bit: *const c_void, d_targets2bit: *const c_void, k: usize, n: usize, min_count: u64,
+                                              min_edge: u64, mode: c_int, direction: c_int, max_steps: u64, d_out_symbols: *mut c_void, d_out_steps: *mut c_void,
+                                              d_out_stops: *mut c_void, d_out_edge_sums: *mut c_void, d_out_last: *mut c_void, d_out_fans: *mut c_void,
+                                              hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_canonical_trace_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_canonical_trace_plan(n: u64, max_steps: u64, mode: c_int, targets: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -849,6 +859,50 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_trace_plan(n, max_steps, mode, targets as c_int, host as c_int, piece, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "trace_plan: {} walks of {} steps", n, max_steps);
+        bytes
+    }
+
+    /// Canonical traces (include/msbwt_hip.h, "canonical traces"): trace_kmers through the strand-merged graph of the canonical unitigs.  A
+    /// k-mer counts with its reverse complement; the edge sums are sums of class counts; stop 8 (MIRROR, unitig mode) is a cut of the
+    /// canonical unitigs' links.  Arguments and the six arrays as trace_kmers.
+    pub fn trace_canonical_kmers(&self, seeds: &[u64], targets: Option<&[u64]>, k: usize, min_count: u64, min_edge: u64, mode: c_int, direction: c_int,
+                                 max_steps: u64) -> (Vec<u8>, Vec<u64>, Vec<u8>, Vec<u64>, Vec<u64>, Vec<u8>) {
+        let n = seeds.len();
+        if let Some(t) = targets { assert_eq!(t.len(), n, "trace_canonical_kmers: one target a seed"); }
+        let mut symbols = vec![0u8; n * max_steps as usize];
+        let (mut steps, mut sums, mut last) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        let (mut stops, mut fans) = (vec![0u8; n], vec![0u8; n]);
+        let rc = unsafe {
+            msbwt_rle_trace_canonical_kmers(self.raw, seeds.as_ptr(), targets.map_or(std::ptr::null(), |t| t.as_ptr()), k, n, min_count, min_edge, mode, direction,
+                                            max_steps, symbols.as_mut_ptr(), steps.as_mut_ptr(), stops.as_mut_ptr(), sums.as_mut_ptr(), last.as_mut_ptr(),
+                                            fans.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("trace_canonical_kmers: {}", self.last_error()); }
+        (symbols, steps, stops, sums, last, fans)
+    }
+
+    /// The same over device buffers (every output and d_targets may be null) on `hip_stream`, which it synchronises.
+    pub unsafe fn trace_canonical_kmers_device(&self, d_seeds: *const c_void, d_targets: *const c_void, k: usize, n: usize, min_count: u64, min_edge: u64,
+                                               mode: c_int, direction: c_int, max_steps: u64, d_symbols: *mut c_void, d_steps: *mut c_void, d_stops: *mut c_void,
+                                               d_edge_sums: *mut c_void, d_last: *mut c_void, d_fans: *mut c_void, hip_stream: *mut c_void) {
+        let rc = msbwt_rle_trace_canonical_kmers_device(self.raw, d_seeds, d_targets, k, n, min_count, min_edge, mode, direction, max_steps, d_symbols, d_steps,
+                                                        d_stops, d_edge_sums, d_last, d_fans, hip_stream);
+        if rc != MSBWT_OK { panic!("trace_canonical_kmers_device: {}", self.last_error()); }
+    }
+
+    /// The last canonical trace call: the words of trace_info.
+    pub fn canonical_trace_info(&self) -> [u64; 8] {
+        let mut words = [0u64; 8];
+        let rc = unsafe { msbwt_rle_canonical_trace_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("canonical_trace_info: {}", self.last_error()); }
+        words
+    }
+
+    /// HBM bytes of scratch a canonical trace call of n walks allocates and frees again on an index that holds something (pure function).
+    pub fn canonical_trace_plan(n: u64, max_steps: u64, mode: c_int, targets: bool, host: bool, piece: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_canonical_trace_plan(n, max_steps, mode, targets as c_int, host as c_int, piece, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "canonical_trace_plan: {} walks of {} steps", n, max_steps);
         bytes
     }
 

@@ -9,7 +9,13 @@ spread, wall clock around calls that end in a synchronise):
              edges of every live walk's candidate and, in unitig mode, the 4 of its back-fan --, the decision in torch on the device,
              and the live walks picked out with a boolean mask, whose size the host reads: the same rounds, written by a caller
 All six outputs of the two routes must be equal, word for word: a mismatch fails the tool.  One JSON line per setting with trace_info
-and the queries per second of the search inside the rounds, and a closing summary line; no threshold on the times."""
+and the queries per second of the search inside the rounds, and a closing summary line; no threshold on the times.
+
+--canonical: the same for trace_canonical_kmers_device, on the read set with every second read reverse-complemented.  The seed sets are
+the first k-mers of enumerate_canonical_unitigs(k, min_count=2) and 10^6 k-mers of enumerate_canonical_kmers(k); the host loop searches
+every query and its reverse complement -- TWO count_kmers_packed_device calls a step, folded in torch (a third for the far ends where k
+is even and min_count >= 2) -- and a third route, `plain`, is trace_kmers_device on the same index and seeds: the strand-specific
+walk, which answers another question with half the searches a live walk, for the ratio of the two calls' times."""
 import argparse
 import json
 import os
@@ -28,7 +34,7 @@ from reads_build_bench import read_set  # noqa: E402
 
 MODES = {"unique": 0, "unitig": 1, "greedy": 2}
 DIRECTIONS = {"right": 0, "left": 1}
-DEAD_END, BRANCH, MERGE, RETURNED, TARGET, MAX_STEPS, NOT_A_NODE = range(1, 8)
+DEAD_END, BRANCH, MERGE, RETURNED, TARGET, MAX_STEPS, NOT_A_NODE, MIRROR = range(1, 9)
 
 
 def edge_words(w, k, left):
@@ -37,8 +43,22 @@ def edge_words(w, k, left):
     return (c << (2 * k)) | w[:, None] if left else (w[:, None] << 2) | c
 
 
-def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream):
-    """the six outputs by one packed count call a step and torch ops between them"""
+def next_nodes(w, k, left):
+    """(m, 4) int64: the nodes at the other end of edge_words"""
+    c = torch.arange(4, dtype=torch.int64, device=w.device)[None, :]
+    return (c << (2 * (k - 1))) | (w[:, None] >> 2) if left else ((w[:, None] << 2) | c) & ((1 << (2 * k)) - 1)
+
+
+def reverse_complement(w, length):
+    """packed reverse complements of words of `length` symbols (int64 holds the bit pattern: every shift right is masked)"""
+    for shift, mask in ((2, 0x3333333333333333), (4, 0x0F0F0F0F0F0F0F0F), (8, 0x00FF00FF00FF00FF), (16, 0x0000FFFF0000FFFF), (32, 0x00000000FFFFFFFF)):
+        w = ((w >> shift) & mask) | ((w & mask) << shift)
+    w = ~w
+    return w if length == 32 else (w >> (64 - 2 * length)) & ((1 << (2 * length)) - 1)
+
+
+def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream, canonical=False):
+    """the six outputs by one packed count call a step (canonical: two, a word and its reverse complement) and torch ops between them"""
     dev, n = seeds.device, seeds.numel()
     left, unitig, greedy = direction == "left", mode == "unitig", mode == "greedy"
     mask = (1 << (2 * k)) - 1
@@ -52,6 +72,19 @@ def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream):
         b.count_kmers_packed_device(words.data_ptr(), kk, words.numel(), out.data_ptr(), stream)
         return out.view(words.shape)
 
+    if canonical:  # the class count: both strands, a palindrome once
+        count_one = count
+
+        def count(words, kk):
+            other = reverse_complement(words, kk)
+            return torch.where(other == words, count_one(words, kk), count_one(words, kk) + count_one(other, kk))
+
+    def missing_far_end(w, lft):
+        """(m, 4) bool: the edges of a fan whose far end is a palindrome below the node threshold (even k and m >= 2 only)"""
+        far = next_nodes(w, k, lft)
+        return (far == reverse_complement(far, k)) & (count_one(far, k) < m)
+
+    node_clause = canonical and k % 2 == 0 and m >= 2
     symbols = torch.zeros((n, max_steps), dtype=torch.uint8, device=dev)
     steps, sums, last = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
     stops, fans = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
@@ -66,9 +99,12 @@ def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream):
     idx = torch.nonzero(node).flatten()
     cur, esum = seed[idx], torch.zeros(idx.numel(), dtype=torch.int64, device=dev)
     fc = count(edge_words(cur, k, left), k + 1)
+    lacking = missing_far_end(cur, left) if node_clause else None
     r = 0
     while idx.numel():  # (the host reads the live count: one decision a step)
         solid = fc >= me
+        if node_clause:
+            solid = solid & ~lacking
         width, fanbits = solid.sum(1), (solid * bit).sum(1)
         stop = torch.zeros_like(idx)
         if r == max_steps:
@@ -79,6 +115,10 @@ def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream):
         best = torch.where(solid, fc * 4 + (3 - symbol), torch.full_like(fc, -1)).argmax(1)  # the largest count, on a tie the smallest symbol
         bcount = fc.gather(1, best[:, None]).flatten()
         cand = (best << (2 * (k - 1))) | (cur >> 2) if left else ((cur << 2) | best) & mask
+        if canonical and unitig:  # a cut of the canonical unitigs' links
+            edge = edge_words(cur, k, left).gather(1, best[:, None]).flatten()
+            cut = (cur == reverse_complement(cur, k)) | (cand == reverse_complement(cand, k)) | (edge == reverse_complement(edge, k + 1))
+            stop = torch.where((stop == 0) & cut, torch.full_like(idx, MIRROR), stop)
         if not unitig:
             stop = torch.where((stop == 0) & (cand == seed[idx]), torch.full_like(idx, RETURNED), stop)
         done = stop != 0
@@ -91,12 +131,19 @@ def host_loop(b, seeds, k, max_steps, mode, direction, m, me, stream):
         if unitig:
             queries = torch.cat([queries, edge_words(cand, k, not left)], dim=1)
         c = count(queries, k + 1)
+        if node_clause:
+            lacking = missing_far_end(cand, left)
         if unitig:
-            merge = (c[:, 4:] >= me).sum(1) >= 2
+            back = c[:, 4:] >= me
+            if node_clause:
+                back = back & ~missing_far_end(cand, not left)
+            merge = back.sum(1) >= 2
             done = merge | (cand == seed[idx])
             finish(idx[done], torch.where(merge, torch.full_like(idx, MERGE), torch.full_like(idx, RETURNED))[done], r, esum[done], cur[done], fanbits[done])
             keep = ~done
             idx, esum, cand, best, bcount, c = (x[keep] for x in (idx, esum, cand, best, bcount, c))
+            if node_clause:
+                lacking = lacking[keep]
         symbols[idx, r] = code[best]
         esum, cur, fc = esum + bcount, cand, c[:, :4]
         r += 1
@@ -112,15 +159,21 @@ def first_words(symbols, offsets, k):
     return w
 
 
-def seed_sets(b, k, cap, dev, stream):
-    U, S = b.enumerate_unitigs_device(k, None, None, None, None, None, 0, 0, min_count=2, stream=stream)
+def seed_sets(b, k, cap, dev, stream, canonical=False):
+    unitigs = b.enumerate_canonical_unitigs_device if canonical else b.enumerate_unitigs_device
+    U, S = unitigs(k, None, None, None, None, None, 0, 0, min_count=2, stream=stream)
     symbols, offsets = torch.empty(S, dtype=torch.uint8, device=dev), torch.empty(U + 1, dtype=torch.int64, device=dev)
-    b.enumerate_unitigs_device(k, symbols.data_ptr(), offsets.data_ptr(), None, None, None, U, S, min_count=2, stream=stream)
+    unitigs(k, symbols.data_ptr(), offsets.data_ptr(), None, None, None, U, S, min_count=2, stream=stream)
     unitig_firsts = first_words(symbols, offsets, k)
     del symbols, offsets
-    n = b.enumerate_kmers_device(k, None, None, None, 0, stream=stream)
-    words = torch.empty(n, dtype=torch.int64, device=dev)
-    b.enumerate_kmers_device(k, words.data_ptr(), None, None, n, stream=stream)
+    if canonical:
+        n = b.enumerate_canonical_kmers_device(k, None, None, None, 0, stream=stream)
+        words = torch.empty(n, dtype=torch.int64, device=dev)
+        b.enumerate_canonical_kmers_device(k, words.data_ptr(), None, None, n, stream=stream)
+    else:
+        n = b.enumerate_kmers_device(k, None, None, None, 0, stream=stream)
+        words = torch.empty(n, dtype=torch.int64, device=dev)
+        b.enumerate_kmers_device(k, words.data_ptr(), None, None, n, stream=stream)
     pick = torch.linspace(0, n - 1, min(n, 10 ** 6), dtype=torch.float64, device=dev).long()
     sets = {"unitig_firsts": unitig_firsts, "kmers": words[pick].clone()}
     del words
@@ -139,6 +192,7 @@ def main():
     ap.add_argument("--max-seeds", type=int, default=10 ** 6, help="seeds a set at the most, taken evenly (the rows of symbols take n x max_steps bytes)")
     ap.add_argument("--min-count", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--canonical", action="store_true", help="trace_canonical_kmers_device on the read set with every second read reverse-complemented")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -148,22 +202,30 @@ def main():
     dev = torch.device("cuda:0")
     reads = read_set(args.config, args.scale)
     n_reads, length = reads.shape
+    if args.canonical:  # reads from both strands ($ A C G N T -> $ T G C N A, reversed)
+        reads = reads.copy()
+        reads[1::2] = np.array([0, 5, 3, 2, 4, 1], dtype=np.uint8)[reads[1::2, ::-1]]
     b = msbwt.RleBWT(device=0)
     (_, load_ms) = wall(lambda: b.load_reads((reads.reshape(-1), np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(length))))
     del reads
     stream = torch.cuda.current_stream(dev).cuda_stream
     lines, same = [], True
     for k in [int(x) for x in args.ks.split(",")]:
-        for name, seeds in seed_sets(b, k, args.max_seeds, dev, stream).items():
+        for name, seeds in seed_sets(b, k, args.max_seeds, dev, stream, args.canonical).items():
             n = seeds.numel()
             for max_steps in [int(x) for x in args.max_steps.split(",")]:
                 for mode in args.modes.split(","):
                     for direction in args.directions.split(","):
                         ours = [torch.zeros((n, max_steps), dtype=torch.uint8, device=dev)] + [torch.zeros(n, dtype=t, device=dev) for t in
                                                                                               (torch.int64, torch.uint8, torch.int64, torch.int64, torch.uint8)]
-                        calls = {"trace": lambda: b.trace_kmers_device(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in ours], mode=MODES[mode],
-                                                                       direction=DIRECTIONS[direction], min_count=args.min_count, stream=stream),
-                                 "host_loop": lambda: host_loop(b, seeds, k, max_steps, mode, direction, args.min_count, args.min_count, stream)}
+                        trace = b.trace_canonical_kmers_device if args.canonical else b.trace_kmers_device
+                        calls = {"trace": lambda: trace(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in ours], mode=MODES[mode], direction=DIRECTIONS[direction],
+                                                        min_count=args.min_count, stream=stream),
+                                 "host_loop": lambda: host_loop(b, seeds, k, max_steps, mode, direction, args.min_count, args.min_count, stream, args.canonical)}
+                        if args.canonical:  # the strand-specific call on the same index and seeds, into buffers of its own
+                            plain = [torch.zeros_like(t) for t in ours]
+                            calls["plain"] = lambda: b.trace_kmers_device(seeds.data_ptr(), k, n, max_steps, *[t.data_ptr() for t in plain], mode=MODES[mode],
+                                                                          direction=DIRECTIONS[direction], min_count=args.min_count, stream=stream)
                         theirs = calls["host_loop"]()  # warm-up, and the comparison
                         calls["trace"]()
                         b.device_status(stream)
@@ -175,19 +237,26 @@ def main():
                                 _, t = wall(fn)
                                 ms[route].append(t)
                         calls["trace"]()
-                        info = b.trace_info()
-                        res = {"k": k, "seeds": name, "n": n, "max_steps": max_steps, "mode": mode, "direction": direction, "min_count": args.min_count,
+                        info = b.canonical_trace_info() if args.canonical else b.trace_info()
+                        res = {"canonical": args.canonical, "k": k, "seeds": name, "n": n, "max_steps": max_steps, "mode": mode, "direction": direction, "min_count": args.min_count,
                                "symbols": int(b.get_total_size()), "info": info, "trace_ms": spread(ms["trace"]), "host_loop_ms": spread(ms["host_loop"]), "same": bool(ok)}
                         res["host_loop_over_trace"] = round(res["host_loop_ms"]["median"] / res["trace_ms"]["median"], 2)
                         res["queries_per_s"] = round(info["queries"] / (res["trace_ms"]["median"] * 1e-3), 0)
+                        if args.canonical:
+                            calls["plain"]()
+                            res.update(plain_ms=spread(ms["plain"]), plain_info=b.trace_info(), stops=torch.bincount(ours[2], minlength=9).tolist())
+                            res["trace_over_plain"] = round(res["trace_ms"]["median"] / res["plain_ms"]["median"], 2)
+                            del plain
                         same = same and bool(ok)
                         print(json.dumps(res), flush=True)
                         lines.append(res)
                         del ours
                         torch.cuda.empty_cache()
     key = lambda r: "%d/%s/%d/%s/%s" % (r["k"], r["seeds"], r["max_steps"], r["mode"], r["direction"])
-    summary = {"config": args.config, "scale": args.scale, "load_reads_ms": round(load_ms, 1), "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+    summary = {"canonical": args.canonical, "config": args.config, "scale": args.scale, "load_reads_ms": round(load_ms, 1), "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
                "trace_ms": {key(r): r["trace_ms"]["median"] for r in lines}, "host_loop_ms": {key(r): r["host_loop_ms"]["median"] for r in lines}, "same": same}
+    if args.canonical:
+        summary["plain_ms"] = {key(r): r["plain_ms"]["median"] for r in lines}
     print(json.dumps(summary), flush=True)
     if args.out:
         with open(args.out, "w") as f:
