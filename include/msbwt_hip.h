@@ -959,6 +959,114 @@ int msbwt_rle_trace_canonical_kmers_device(const msbwt_rle *bwt, const void *d_s
 int msbwt_rle_canonical_trace_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_CANONICAL_TRACE_INFO_WORDS */);
 int msbwt_canonical_trace_plan(uint64_t n, uint64_t max_steps, int mode, int targets, int host, uint64_t piece, uint64_t *device_bytes);
 
+/* ---- left walks ---- from a BWT row back to the text: batched LF walks, locate and read extraction, on the device (the reference
+ * walks one row at a time on the host; msbwt's recoverString and fmlrc's read fetches are this operation).  Every call above goes
+ * from a k-mer to the index or from the index to the graph; these go from a row of the index to the reads: which read a row of a
+ * k-mer's range [l, h) belongs to and at what offset, and the reads themselves, which an index built by msbwt_rle_build_from_reads or
+ * a merge still holds.
+ *
+ * DEFINITIONS, on the BWT string alone.  S is the decoded BWT of T = msbwt_rle_get_total_size rows, C[c] the rows that hold a symbol
+ * below c (the reference's start_index), rank(c, r) the occurrences of c in S[0 .. r), and LF(r) = C[S[r]] + rank(S[r], r), which is
+ * below T for every r < T whatever the stream.  ONE WALK from row r_0 with steps = 0:
+ *   0. r_0 >= T: stop BAD_ROW with steps = 0; no line of the index is fetched.
+ *   1. S[r_steps] == '$' (code 0): stop DOLLAR.  That '$' is neither emitted nor counted.
+ *   2. steps == max_steps: stop MAX_STEPS.  (So a walk that stands on a '$' after exactly max_steps steps stops DOLLAR.)
+ *   3. symbols[steps] = S[r_steps], a code 1..5 (A C G N T); r_(steps + 1) = LF(r_steps); steps += 1; back to 1.
+ * READ AND OFFSET.  Row i < C['A'] = msbwt_rle_get_symbol_count(0), inside the '$' block, is read i: the order of the builder and of
+ * naive_bwt -- the reads sorted, duplicates in input order, an empty read first.  A walk from row r that stops DOLLAR after p steps
+ * stood at the suffix that starts at offset p of read LF(r_p) = rank('$', r_p); the symbols it emitted are that read's prefix [0, p),
+ * LAST SYMBOL FIRST.  The walk from '$'-row i emits read i reversed.  All of it is defined for any loaded stream, whoever built it;
+ * on a stream that is no BWT of a read set a walk may never meet a '$' and ends at max_steps.
+ *
+ * msbwt_rle_walk_rows[_device]: rows = n words.  Outputs, every one may be NULL:
+ *   out_symbols   n x max_steps bytes, row-major, in walk order: row i holds out_steps[i] symbols, the rest of the row is left
+ *                 untouched.  It needs no alignment.  NULL: the call is LOCATE, and costs the same lines without the stores.
+ *   out_steps     n words
+ *   out_stops     n bytes: MSBWT_WALK_DOLLAR, MSBWT_WALK_MAX_STEPS or MSBWT_WALK_BAD_ROW; 0 is never written
+ *   out_last      n words: r_steps, the row the walk stands on (r_0 for BAD_ROW)
+ *   out_reads     n words: the read for a DOLLAR stop, UINT64_MAX otherwise; out_steps is then the offset in it
+ * A BAD_ROW also raises MSBWT_ERR_INVALID_RANGE as msbwt_rle_constrain_ranges does -- the host form returns it, the _device form
+ * leaves it to msbwt_rle_device_status --; every other walk of the batch is answered all the same.  max_steps == 0 is legal: it tells
+ * the rows that hold a '$' from the others.  The _device form takes device pointers, runs on hip_stream, synchronises it before it
+ * returns and reports through msbwt_rle_device_status.
+ * Guards, in this order, before the first HIP call: a NULL handle (MSBWT_ERR_INVALID_ARG); nothing loaded (MSBWT_ERR_NOT_LOADED, "no
+ * BWT loaded"); NULL rows with n > 0 (MSBWT_ERR_INVALID_ARG); max_steps, or n x max_steps, from 2^40 on (MSBWT_ERR_TOO_LARGE).  n == 0
+ * and an empty index return MSBWT_OK at once, nothing written.  Results depend on no knob, no index form and no piece.
+ *
+ * msbwt_rle_extract_reads[_device]: n reads as a ragged set in READING order -- the (symbols, offsets) pair that
+ * msbwt_rle_count_ragged_read_kmers and msbwt_rle_build_from_reads (ascii = 0) take as it is.  read_ids: n words, each below
+ * msbwt_rle_get_symbol_count(0); NULL: the reads first_read .. first_read + n (first_read is ignored beside read_ids).  An id outside
+ * that range is refused with MSBWT_ERR_INVALID_RANGE: by the host form, and for a NULL read_ids by either form, on the host before
+ * anything runs; by the _device form through the flags (msbwt_rle_device_status), that read getting length 0.
+ * max_len >= 1 bounds every loop on the device: a read longer than max_len yields its LAST max_len symbols and is counted in
+ * *out_truncated (may be NULL); a read of exactly max_len symbols is whole.
+ *   out_offsets        n + 1 words, written when it is not NULL and the call is not refused for capacity
+ *   *out_symbol_total  S, the symbols of the n reads (as extracted); always set, NULL is MSBWT_ERR_INVALID_ARG
+ *   out_symbols        NULL: a lengths-only call.  Else capacity_symbols bytes: S of them are written, everything past S is left
+ *                      untouched.  capacity_symbols < S: MSBWT_ERR_INVALID_ARG, the message names S, the offsets are left
+ *                      untouched, out_symbols is unspecified within its capacity and nothing is written past it.
+ * THE WALK IS THE WHOLE COST of a call, and S is not known before it.  A call whose capacity_symbols is at least n x max_len cannot
+ * be short and walks ONCE; a call with a smaller capacity walks once for the lengths and, S fitting, once more for the symbols.  So a
+ * caller who cannot bound S better than n x max_len allocates that and makes one call; a lengths-only call first buys nothing.
+ * Guards, in this order, before the first HIP call: a NULL handle; nothing loaded; max_len == 0 or a NULL out_symbol_total
+ * (MSBWT_ERR_INVALID_ARG); max_len, or n x max_len, from 2^40 on (MSBWT_ERR_TOO_LARGE); the ids known on the host
+ * (MSBWT_ERR_INVALID_RANGE).  n == 0: S = 0 and out_offsets[0] = 0.
+ *
+ * How ("Left walks"): one 8-lane group a walk, and ONE 128-byte line a step -- the group reads the symbol at the row out
+ * of the line and ranks it from the same registers; an OVERFLOW run block costs one more line.  A walk is a chain of dependent random
+ * fetches, so a group keeps four walks in registers side by side, a wave 32 lines in flight.  The step loop runs inside the kernel,
+ * max_steps + 1 lines at the most (the last only to see a '$'), and a launch takes a PIECE of the n walks (msbwt_rle_set_walk_piece:
+ * 0 = automatic, 2^20 walks, at most 2^28, beyond which MSBWT_ERR_INVALID_ARG; results never depend on it), so that the scratch does
+ * not grow with n.  Extraction walks a piece into rows of max_len bytes, scans the lengths with the running base carried from piece to
+ * piece, and one kernel turns every row round into its ragged place.  A walk costs the offset inside the read, which is right for short reads; there is no sampled
+ * suffix array, and on long-read indexes max_steps bounds what a locate may cost.
+ *
+ * msbwt_rle_walk_info: out[MSBWT_WALK_INFO_WORDS] of the handle's last call of either kind = [0] walks, [1] steps taken in all,
+ * [2] DOLLAR stops, [3] MAX_STEPS stops (extraction: the truncated reads), [4] BAD_ROW stops, [5] pieces launched, [6] scratch bytes
+ * allocated, [7] microseconds; an extraction that walked twice reports its second walk in [1]-[4] and the pieces of both in [5].  The scratch is per call and freed on return
+ * (msbwt_rle_device_bytes unchanged); n == 0 and an empty index allocate nothing.
+ * msbwt_walk_plan: pure, no device: [6] of a msbwt_rle_walk_rows[_device] call on an index that holds something, EXACTLY, with
+ * P = min(n, piece), piece 0 = 2^20, and pad(x) = ceil(x / 256) 256:
+ *     256                                   the counters -- all the _device form allocates
+ *   and, host != 0:
+ *     + 4 pad(8 P) + pad(P)                 a piece's rows, steps, last rows and reads; its stops -- staged whichever are NULL
+ *     + pad(P max_steps)                    its rows of symbols, symbols != 0 (out_symbols is not NULL)
+ * n == 0: 0 bytes.  A piece above 2^28: MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE as the call; device_bytes may be NULL.
+ * [6] of a msbwt_rle_extract_reads[_device] call with n > 0, EXACTLY, whether it walks once or twice (P as above, max_len for
+ * max_steps):
+ *     256                                   the counters
+ *     + pad(8 (P + 1))                      the lengths of a piece, and one word behind them
+ *     + pad(8 w)                            their scan's sums: w = 1, and with x = P + 1, while x > 2048: x = ceil(x / 2048), w += x
+ *     + pad(P max_len)                      the walk-order rows, out_symbols not NULL
+ *   and in the host form:
+ *     + pad(8 P)                            a piece's ids, read_ids not NULL
+ *     + pad(8 (P + 1))                      its offsets, out_offsets not NULL
+ *     + pad(P max_len)                      its symbols, out_symbols not NULL
+ *
+ * Out of scope here: a sampled suffix array; right walks; per-source filtering of the located reads (index the source vector with
+ * out_reads); forms for several GPUs. */
+/* (Indented inside a guard, not at the line's start as elsewhere in this header: tests/test_canonical_trace_abi.py takes every line
+ * from "canonical traces" to "several GPUs" that starts with "#define" for a constant of that section.) */
+#ifndef MSBWT_WALK_INFO_WORDS
+#  define MSBWT_WALK_DOLLAR 1
+#  define MSBWT_WALK_MAX_STEPS 2
+#  define MSBWT_WALK_BAD_ROW 3
+#  define MSBWT_WALK_INFO_WORDS 8
+#endif
+int msbwt_rle_walk_rows(const msbwt_rle *bwt, const uint64_t *rows, size_t n, uint64_t max_steps, uint8_t *out_symbols /* n x max_steps */,
+                        uint64_t *out_steps, uint8_t *out_stops, uint64_t *out_last, uint64_t *out_reads);
+int msbwt_rle_walk_rows_device(const msbwt_rle *bwt, const void *d_rows, size_t n, uint64_t max_steps, void *d_out_symbols, void *d_out_steps,
+                               void *d_out_stops, void *d_out_last, void *d_out_reads, void *hip_stream);
+int msbwt_rle_extract_reads(const msbwt_rle *bwt, const uint64_t *read_ids /* or NULL */, uint64_t first_read, size_t n, uint64_t max_len,
+                            uint8_t *out_symbols, uint64_t *out_offsets /* n + 1 */, uint64_t capacity_symbols, uint64_t *out_symbol_total,
+                            uint64_t *out_truncated);
+int msbwt_rle_extract_reads_device(const msbwt_rle *bwt, const void *d_read_ids /* or NULL */, uint64_t first_read, size_t n, uint64_t max_len,
+                                   void *d_out_symbols, void *d_out_offsets, uint64_t capacity_symbols, uint64_t *out_symbol_total,
+                                   uint64_t *out_truncated, void *hip_stream);
+int msbwt_rle_walk_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_WALK_INFO_WORDS */);
+int msbwt_rle_set_walk_piece(msbwt_rle *bwt, uint64_t walks);
+int msbwt_walk_plan(uint64_t n, uint64_t max_steps, int symbols, int host, uint64_t piece, uint64_t *device_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <iterator>
 #include <stdexcept>
 #include <string>
 #include <system_error>
@@ -720,6 +721,91 @@ class RleBWT final : public BWT {
         std::uint64_t bytes = 0;
         const int rc = msbwt_canonical_trace_plan(n, max_steps, mode, targets ? 1 : 0, host ? 1 : 0, piece, &bytes);
         if (rc) throw Panic(rc, "msbwt_canonical_trace_plan");
+        return bytes;
+    }
+    /// What walk_rows returns: row i of symbols (n rows of max_steps bytes, empty for a locate) holds steps[i] symbol codes 1..5 in WALK
+    /// order -- the last symbol of the prefix first -- and zeros behind them; stops[i] is MSBWT_WALK_DOLLAR, _MAX_STEPS or _BAD_ROW;
+    /// last[i] the row the walk stands on; reads[i] the read for a DOLLAR stop (steps[i] is then the offset in it), else UINT64_MAX.
+    struct Walks {
+        std::vector<std::uint8_t> symbols;
+        std::vector<std::uint64_t> steps;
+        std::vector<std::uint8_t> stops;
+        std::vector<std::uint64_t> last, reads;
+        std::uint64_t max_steps = 0;
+        std::size_t size() const { return steps.size(); }
+        /// the prefix walk i went through, in reading order
+        std::vector<std::uint8_t> sequence(std::size_t i) const {
+            const std::uint8_t *row = symbols.data() + i * max_steps;
+            return std::vector<std::uint8_t>(std::make_reverse_iterator(row + steps[i]), std::make_reverse_iterator(row));
+        }
+    };
+    /// Left walks (msbwt_hip.h, "left walks"): from each BWT row the LF walk back through the text until it stands on a '$' or has
+    /// taken max_steps steps.  with_symbols = false: locate.  A row at or beyond the total size panics with MSBWT_ERR_INVALID_RANGE.
+    Walks walk_rows(const std::vector<std::uint64_t> &rows, std::uint64_t max_steps, bool with_symbols = true) const {
+        const std::size_t n = rows.size();
+        Walks w;
+        w.max_steps = max_steps;
+        if (with_symbols) w.symbols.resize(n * max_steps);
+        w.steps.resize(n);
+        w.stops.resize(n);
+        w.last.resize(n);
+        w.reads.resize(n);
+        check(msbwt_rle_walk_rows(raw_, rows.data(), n, max_steps, with_symbols ? w.symbols.data() : nullptr, w.steps.data(), w.stops.data(), w.last.data(), w.reads.data()));
+        return w;
+    }
+    /// walk_rows without symbols: reads[i] and steps[i] are the read and the offset of row i where stops[i] == MSBWT_WALK_DOLLAR.
+    Walks locate_rows(const std::vector<std::uint64_t> &rows, std::uint64_t max_steps) const { return walk_rows(rows, max_steps, false); }
+    /// Device buffers (every output may be null; the rows of symbols at any alignment); synchronises hip_stream.
+    void walk_rows_device(const void *d_rows, std::size_t n, std::uint64_t max_steps, void *d_symbols, void *d_steps, void *d_stops, void *d_last, void *d_reads,
+                          void *hip_stream = nullptr) const {
+        check(msbwt_rle_walk_rows_device(raw_, d_rows, n, max_steps, d_symbols, d_steps, d_stops, d_last, d_reads, hip_stream));
+    }
+    /// What extract_reads returns: read j = symbols[offsets[j] .. offsets[j + 1]) in reading order; truncated = the reads longer than
+    /// max_len, which come as their last max_len symbols.
+    struct Reads {
+        std::vector<std::uint8_t> symbols;
+        std::vector<std::uint64_t> offsets;
+        std::uint64_t truncated = 0;
+        std::size_t size() const { return offsets.empty() ? 0 : offsets.size() - 1; }
+    };
+    /// The reads `ids` (each below get_symbol_count(0); read i is the i-th of the sorted read set), or, ids empty, the n reads from
+    /// first_read on, as a ragged set in reading order.  One walk: the buffer holds n x max_len symbols before it shrinks.
+    Reads extract_reads(const std::vector<std::uint64_t> &ids, std::uint64_t first_read, std::size_t n, std::uint64_t max_len) const {
+        if (!ids.empty()) n = ids.size();
+        Reads r;
+        r.symbols.resize(std::max<std::size_t>(n * max_len, 1));
+        r.offsets.resize(n + 1);
+        std::uint64_t total = 0;
+        check(msbwt_rle_extract_reads(raw_, ids.empty() ? nullptr : ids.data(), first_read, n, max_len, r.symbols.data(), r.offsets.data(), n * max_len, &total,
+                                      &r.truncated));
+        r.symbols.resize(total);
+        return r;
+    }
+    /// Device buffers (d_ids, d_symbols and d_offsets may each be null) -> S, the symbols of the reads; synchronises hip_stream.
+    std::uint64_t extract_reads_device(const void *d_ids, std::uint64_t first_read, std::size_t n, std::uint64_t max_len, void *d_symbols, void *d_offsets,
+                                       std::uint64_t capacity_symbols, std::uint64_t *truncated = nullptr, void *hip_stream = nullptr) const {
+        std::uint64_t total = 0;
+        check(msbwt_rle_extract_reads_device(raw_, d_ids, first_read, n, max_len, d_symbols, d_offsets, capacity_symbols, &total, truncated, hip_stream));
+        return total;
+    }
+    /// The last left-walk call.
+    struct WalkInfo {
+        std::uint64_t walks = 0, steps = 0, dollar = 0, max_steps = 0, bad_row = 0, pieces = 0, scratch_bytes = 0, us = 0;
+    };
+    WalkInfo walk_info() const {
+        std::uint64_t w[MSBWT_WALK_INFO_WORDS] = {};
+        check(msbwt_rle_walk_info(raw_, w));
+        WalkInfo i;
+        i.walks = w[0], i.steps = w[1], i.dollar = w[2], i.max_steps = w[3], i.bad_row = w[4], i.pieces = w[5], i.scratch_bytes = w[6], i.us = w[7];
+        return i;
+    }
+    /// Most left walks a launch takes (0 = automatic, 2^20; at most 2^28); results never depend on it.
+    void set_walk_piece(std::uint64_t walks) { check(msbwt_rle_set_walk_piece(raw_, walks)); }
+    /// HBM bytes of scratch a walk_rows call of n walks allocates (and frees again) on an index that holds something.
+    static std::uint64_t walk_plan(std::uint64_t n, std::uint64_t max_steps, bool symbols = true, bool host = true, std::uint64_t piece = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_walk_plan(n, max_steps, symbols ? 1 : 0, host ? 1 : 0, piece, &bytes);
+        if (rc) throw Panic(rc, "msbwt_walk_plan");
         return bytes;
     }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).

@@ -24,6 +24,8 @@ TRACE_MODES = {"unique": 0, "unitig": 1, "greedy": 2}  # MSBWT_TRACE_UNIQUE, _UN
 TRACE_STOPS = ("", "DEAD_END", "BRANCH", "MERGE", "RETURNED", "TARGET", "MAX_STEPS", "NOT_A_NODE")  # MSBWT_TRACE_DEAD_END = 1 ..
 CANONICAL_TRACE_STOPS = TRACE_STOPS + ("MIRROR",)  # .. MSBWT_CANONICAL_TRACE_MIRROR = 8
 CANONICAL_TRACE_INFO_WORDS = 8  # MSBWT_CANONICAL_TRACE_INFO_WORDS
+WALK_INFO_WORDS = 8  # MSBWT_WALK_INFO_WORDS
+WALK_STOPS = ("", "DOLLAR", "MAX_STEPS", "BAD_ROW")  # MSBWT_WALK_DOLLAR = 1 ..
 SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
@@ -128,6 +130,13 @@ SIGNATURES = {
     "msbwt_rle_trace_canonical_kmers_device": (_int, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msbwt_rle_canonical_trace_info": (_int, [_vp, _vp]),
     "msbwt_canonical_trace_plan": (_int, [_u64, _u64, _int, _int, _int, _u64, _pu64]),
+    "msbwt_rle_walk_rows": (_int, [_vp, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_walk_rows_device": (_int, [_vp, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_extract_reads": (_int, [_vp, _vp, _u64, _sz, _u64, _vp, _vp, _u64, _pu64, _pu64]),
+    "msbwt_rle_extract_reads_device": (_int, [_vp, _vp, _u64, _sz, _u64, _vp, _vp, _u64, _pu64, _pu64, _vp]),
+    "msbwt_rle_walk_info": (_int, [_vp, _vp]),
+    "msbwt_rle_set_walk_piece": (_int, [_vp, _u64]),
+    "msbwt_walk_plan": (_int, [_u64, _u64, _int, _int, _u64, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

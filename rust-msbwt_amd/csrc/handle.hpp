@@ -199,6 +199,8 @@ struct msbwt_rle : Settings {
     uint64_t trace_piece = 0;                 // most walks a trace call advances at once (0 = automatic): msbwt_rle_set_trace_piece
     uint64_t trace_info[MSBWT_TRACE_INFO_WORDS] = {};  // what the last trace call did: msbwt_rle_trace_info
     uint64_t canonical_trace_info[MSBWT_CANONICAL_TRACE_INFO_WORDS] = {};  // and the last canonical one: msbwt_rle_canonical_trace_info
+    uint64_t walk_piece = 0;                  // most left walks a launch takes (0 = automatic): msbwt_rle_set_walk_piece
+    uint64_t walk_info[MSBWT_WALK_INFO_WORDS] = {};  // what the last left-walk call did: msbwt_rle_walk_info
     std::mutex mu;
     std::string err;
 };

@@ -731,6 +731,119 @@ class RleBWT(BWT):
         if rc:
             _raise(rc, self._h)
 
+    # ---- left walks: from BWT rows back to the text -- LF walks, locate, the reads themselves ----
+    def walk_rows(self, rows, max_steps, symbols=True):
+        """msbwt_rle_walk_rows -> (symbols, steps, stops, last, reads).  rows: n BWT rows.  Each is walked left by LF until it stands on
+        a '$' or has taken max_steps steps (include/msbwt_hip.h, "left walks").  symbols: (n, max_steps) uint8 in WALK order -- row i
+        holds steps[i] codes 1..5, the last symbol of the prefix first, and zeros (or what the `symbols` array passed in held) behind
+        them; symbols=False: None, the call is locate.  stops: _lib.WALK_STOPS names the codes; last: the row a walk stands on; reads:
+        the read for a DOLLAR stop (steps is then the offset in it), else 2^64 - 1.  A row at or beyond the total size stops BAD_ROW
+        and raises MsbwtError(ERR_INVALID_RANGE).  walk_sequences turns rows into prefixes in reading order.
+        numpy arrays go through the host form.  A torch tensor on this handle's device (int64 or uint64 words) goes through the
+        _device form on torch's current stream, and torch tensors come back (words as int64); a bad row shows in device_status."""
+        if hasattr(rows, "data_ptr"):
+            import torch
+            n, dev = int(rows.numel()), rows.device
+            if not rows.is_contiguous() or rows.element_size() != 8:
+                raise ValueError("rows is a contiguous tensor of n 64-bit words")
+            if symbols is True:
+                symbols = torch.zeros((n, int(max_steps)), dtype=torch.uint8, device=dev)
+            elif symbols is False:
+                symbols = None
+            steps, last, reads = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
+            stops = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.walk_rows_device(rows.data_ptr(), n, max_steps, None if symbols is None else symbols.data_ptr(), steps.data_ptr(), stops.data_ptr(), last.data_ptr(),
+                                  reads.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+            return symbols, steps, stops, last, reads
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        n = len(rows)
+        if symbols is True:
+            symbols = np.zeros((n, int(max_steps)), dtype=np.uint8)
+        elif symbols is False:
+            symbols = None
+        elif symbols.dtype != np.uint8 or symbols.shape != (n, int(max_steps)) or not symbols.flags.c_contiguous:
+            raise ValueError("symbols is a C-contiguous (n, max_steps) uint8 array")
+        steps, last, reads = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        stops = np.zeros(n, dtype=np.uint8)
+        rc = _lib.lib().msbwt_rle_walk_rows(self._h, rows.ctypes.data_as(C.c_void_p), n, int(max_steps), None if symbols is None else symbols.ctypes.data_as(C.c_void_p),
+                                            *[a.ctypes.data_as(C.c_void_p) for a in (steps, stops, last, reads)])
+        if rc:
+            _raise(rc, self._h)
+        return symbols, steps, stops, last, reads
+
+    def walk_rows_device(self, d_rows, n, max_steps, d_symbols, d_steps, d_stops, d_last, d_reads, stream=0):
+        """msbwt_rle_walk_rows_device: device pointers (ints; every output may be None; the rows of symbols at any alignment).
+        Synchronises `stream`; a bad row shows in device_status."""
+        rc = _lib.lib().msbwt_rle_walk_rows_device(self._h, d_rows, int(n), int(max_steps), d_symbols, d_steps, d_stops, d_last, d_reads, stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def locate_rows(self, rows, max_steps):
+        """walk_rows without symbols -> (reads, offsets, stops): row i is the suffix at offsets[i] of read reads[i] where stops[i] is
+        DOLLAR (1); elsewhere the walk did not reach the start of its read within max_steps and reads[i] is 2^64 - 1 (-1 in a tensor)."""
+        _, steps, stops, _, reads = self.walk_rows(rows, max_steps, symbols=False)
+        return reads, steps, stops
+
+    def locate_kmer(self, kmer, max_steps):
+        """Where a k-mer (symbol codes, uint8[k]) occurs: kmer_ranges, the rows of its range, locate_rows -> (reads, offsets), sorted by
+        read and offset.  max_steps bounds the offsets that can be found; an occurrence further into its read raises MsbwtError."""
+        l, h = self.kmer_ranges(np.ascontiguousarray(kmer, dtype=np.uint8).reshape(1, -1))
+        reads, offsets, stops = self.locate_rows(np.arange(int(l[0]), int(h[0]), dtype=np.uint64), max_steps)
+        if np.any(stops != _lib.WALK_STOPS.index("DOLLAR")):
+            raise MsbwtError(_lib.ERR_INVALID_ARG, "locate_kmer: %d occurrences lie more than max_steps = %d symbols into their reads" % (int((stops != 1).sum()), max_steps))
+        order = np.lexsort((offsets, reads))
+        return reads[order], offsets[order]
+
+    def extract_reads(self, read_ids=None, first=0, n=None, max_len=1024, truncate=False):
+        """msbwt_rle_extract_reads -> (symbols, offsets): reads of the index as a ragged set in reading order, read j =
+        symbols[offsets[j]:offsets[j + 1]] -- what count_ragged_read_kmers and build_from_reads take as they are.  read_ids: the reads
+        wanted (each below get_symbol_count(0), repeats allowed), or None: the reads first .. first + n (n=None: all from `first` on).
+        Read i is the i-th of the sorted read set (duplicates in input order).  A read longer than max_len comes back as its last
+        max_len symbols with truncate=True and raises MsbwtError otherwise.  One walk: the buffer holds n x max_len symbols."""
+        if read_ids is not None:
+            ids = np.ascontiguousarray(read_ids, dtype=np.uint64).reshape(-1)
+            n, where = len(ids), ids.ctypes.data_as(C.c_void_p)
+        else:
+            where = None
+            if n is None:
+                n = max(self.get_symbol_count(0) - int(first), 0)
+        cap = int(n) * int(max_len)
+        symbols = np.empty(max(cap, 1), dtype=np.uint8)
+        offsets = np.zeros(int(n) + 1, dtype=np.uint64)
+        total, truncated = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_extract_reads(self._h, where, int(first), int(n), int(max_len), symbols.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                                cap, C.byref(total), C.byref(truncated))
+        if rc:
+            _raise(rc, self._h)
+        if truncated.value and not truncate:
+            raise MsbwtError(_lib.ERR_INVALID_ARG, "extract_reads: %d reads are longer than max_len = %d (truncate=True keeps their last max_len symbols)"
+                             % (truncated.value, max_len))
+        return symbols[:total.value].copy(), offsets
+
+    def extract_reads_device(self, d_read_ids, first, n, max_len, d_symbols, d_offsets, capacity_symbols, stream=0):
+        """msbwt_rle_extract_reads_device: device pointers (ints; d_read_ids, d_symbols and d_offsets may each be None) -> (S, truncated).
+        A capacity below S raises (the error carries .symbols = S).  Synchronises `stream`; a bad id shows in device_status."""
+        total, truncated = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().msbwt_rle_extract_reads_device(self._h, d_read_ids, int(first), int(n), int(max_len), d_symbols, d_offsets, int(capacity_symbols), C.byref(total),
+                                                       C.byref(truncated), stream)
+        if rc:
+            try:
+                _raise(rc, self._h)
+            except MsbwtError as e:
+                e.symbols = int(total.value)
+                raise
+        return int(total.value), int(truncated.value)
+
+    def walk_info(self):
+        """What the last left-walk call did: {"walks", "steps", "dollar", "max_steps", "bad_row", "pieces", "scratch_bytes", "us"}."""
+        return self._info(_lib.lib().msbwt_rle_walk_info, ("walks", "steps", "dollar", "max_steps", "bad_row", "pieces", "scratch_bytes", "us"))
+
+    def set_walk_piece(self, walks):
+        """Most left walks a launch takes (0 = automatic, 2^20; at most 2^28): results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_walk_piece(self._h, int(walks))
+        if rc:
+            _raise(rc, self._h)
+
     def set_spectrum_frontier(self, nodes):
         """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""
         rc = _lib.lib().msbwt_rle_set_spectrum_frontier(self._h, int(nodes))
@@ -1296,6 +1409,30 @@ def canonical_trace_plan(n, max_steps, mode="unique", targets=False, host=True, 
     if rc:
         raise MsbwtError(rc, "msbwt_canonical_trace_plan: max_steps and n x max_steps must stay below 2^40")
     return out.value
+
+
+def walk_plan(n, max_steps, symbols=True, host=True, piece=0):
+    """msbwt_walk_plan: the bytes of HBM scratch a RleBWT.walk_rows call of n walks allocates (and frees again) on an index that holds
+    something; symbols=False: locate.  The device form allocates its counters only."""
+    out = C.c_uint64(0)
+    rc = _lib.lib().msbwt_walk_plan(int(n), int(max_steps), int(bool(symbols)), int(bool(host)), int(piece), C.byref(out))
+    if rc:
+        raise MsbwtError(rc, "msbwt_walk_plan: max_steps and n x max_steps must stay below 2^40, a piece is at most 2^28 walks")
+    return out.value
+
+
+def walk_sequences(symbols, steps, text=False):
+    """The prefixes the walks of RleBWT.walk_rows went through, in READING order: for walk i the first steps[i] symbols of row i of
+    `symbols` reversed -- the read's prefix [0, steps[i]) for a walk that stopped DOLLAR.  A list of uint8 arrays of symbol codes, or
+    of str with text=True.  Pure host logic."""
+    symbols = np.ascontiguousarray(symbols.cpu().numpy() if hasattr(symbols, "data_ptr") else symbols, dtype=np.uint8)
+    steps = np.ascontiguousarray(steps.cpu().numpy() if hasattr(steps, "data_ptr") else steps).astype(np.uint64).reshape(-1)
+    if symbols.ndim != 2 or symbols.shape[0] != steps.size or (steps.size and int(steps.max()) > symbols.shape[1]):
+        raise ValueError("symbols is (n, max_steps) and steps[i] <= max_steps")
+    out = [row[:int(s)][::-1].copy() for row, s in zip(symbols, steps)]
+    if not text:
+        return out
+    return [_LETTERS[a].tobytes().decode() for a in out]
 
 
 def trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):

@@ -192,6 +192,19 @@ extern "C" {
                                               hip_stream: *mut c_void) -> c_int;
     fn msbwt_rle_canonical_trace_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
     fn msbwt_canonical_trace_plan(n: u64, max_steps: u64, mode: c_int, targets: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
+    // left walks: from BWT rows back to the text -- LF walks, locate, read extraction
+    fn msbwt_rle_walk_rows(bwt: *const MsbwtRle, rows: *const u64, n: usize, max_steps: u64, out_symbols: *mut u8, out_steps: *mut u64, out_stops: *mut u8,
+                           out_last: *mut u64, out_reads: *mut u64) -> c_int;
+    fn msbwt_rle_walk_rows_device(bwt: *const MsbwtRle, d_rows: *const c_void, n: usize, max_steps: u64, d_out_symbols: *mut c_void, d_out_steps: *mut c_void,
+                                  d_out_stops: *mut c_void, d_out_last: *mut c_void, d_out_reads: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_extract_reads(bwt: *const MsbwtRle, read_ids: *const u64, first_read: u64, n: usize, max_len: u64, out_symbols: *mut u8, out_offsets: *mut u64,
+                               capacity_symbols: u64, out_symbol_total: *mut u64, out_truncated: *mut u64) -> c_int;
+    fn msbwt_rle_extract_reads_device(bwt: *const MsbwtRle, d_read_ids: *const c_void, first_read: u64, n: usize, max_len: u64, d_out_symbols: *mut c_void,
+                                      d_out_offsets: *mut c_void, capacity_symbols: u64, out_symbol_total: *mut u64, out_truncated: *mut u64,
+                                      hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_walk_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_rle_set_walk_piece(bwt: *mut MsbwtRle, walks: u64) -> c_int;
+    fn msbwt_walk_plan(n: u64, max_steps: u64, symbols: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -903,6 +916,84 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_canonical_trace_plan(n, max_steps, mode, targets as c_int, host as c_int, piece, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "canonical_trace_plan: {} walks of {} steps", n, max_steps);
+        bytes
+    }
+
+    /// Left walks (include/msbwt_hip.h, "left walks"): from each BWT row the LF walk back through the text until it stands on a '$' or has
+    /// taken `max_steps` steps.  -> (symbols: n rows of max_steps in walk order, row i holding steps[i] symbol codes 1..5 and zeros behind
+    /// them -- empty without `symbols`; steps; stops: 1 DOLLAR, 2 MAX_STEPS, 3 BAD_ROW; the rows the walks stand on; reads: the read for a
+    /// DOLLAR stop, u64::MAX otherwise).  A row at or beyond the total size panics.
+    pub fn walk_rows(&self, rows: &[u64], max_steps: u64, symbols: bool) -> (Vec<u8>, Vec<u64>, Vec<u8>, Vec<u64>, Vec<u64>) {
+        let n = rows.len();
+        let mut out = vec![0u8; if symbols { n * max_steps as usize } else { 0 }];
+        let (mut steps, mut last, mut reads) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        let mut stops = vec![0u8; n];
+        let rc = unsafe {
+            msbwt_rle_walk_rows(self.raw, rows.as_ptr(), n, max_steps, if symbols { out.as_mut_ptr() } else { std::ptr::null_mut() }, steps.as_mut_ptr(),
+                                stops.as_mut_ptr(), last.as_mut_ptr(), reads.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("walk_rows: {}", self.last_error()); }
+        (out, steps, stops, last, reads)
+    }
+
+    /// walk_rows without symbols -> (reads, offsets, stops): row i is the suffix at offsets[i] of read reads[i] where stops[i] is 1 (DOLLAR).
+    pub fn locate_rows(&self, rows: &[u64], max_steps: u64) -> (Vec<u64>, Vec<u64>, Vec<u8>) {
+        let (_, steps, stops, _, reads) = self.walk_rows(rows, max_steps, false);
+        (reads, steps, stops)
+    }
+
+    /// The same over device buffers (every output may be null) on `hip_stream`, which it synchronises.
+    pub unsafe fn walk_rows_device(&self, d_rows: *const c_void, n: usize, max_steps: u64, d_symbols: *mut c_void, d_steps: *mut c_void, d_stops: *mut c_void,
+                                   d_last: *mut c_void, d_reads: *mut c_void, hip_stream: *mut c_void) {
+        let rc = msbwt_rle_walk_rows_device(self.raw, d_rows, n, max_steps, d_symbols, d_steps, d_stops, d_last, d_reads, hip_stream);
+        if rc != MSBWT_OK { panic!("walk_rows_device: {}", self.last_error()); }
+    }
+
+    /// The reads `ids` (each below get_symbol_count(0)), or with None the `n` reads from `first_read` on, as a ragged set in reading order
+    /// -> (symbols, offsets: n + 1, truncated: the reads longer than `max_len`, which come as their last max_len symbols).
+    pub fn extract_reads(&self, ids: Option<&[u64]>, first_read: u64, n: usize, max_len: u64) -> (Vec<u8>, Vec<u64>, u64) {
+        let n = ids.map_or(n, |i| i.len());
+        let capacity = n * max_len as usize;
+        let mut symbols = vec![0u8; capacity.max(1)];
+        let mut offsets = vec![0u64; n + 1];
+        let (mut total, mut truncated) = (0u64, 0u64);
+        let rc = unsafe {
+            msbwt_rle_extract_reads(self.raw, ids.map_or(std::ptr::null(), |i| i.as_ptr()), first_read, n, max_len, symbols.as_mut_ptr(), offsets.as_mut_ptr(),
+                                    capacity as u64, &mut total, &mut truncated)
+        };
+        if rc != MSBWT_OK { panic!("extract_reads: {}", self.last_error()); }
+        symbols.truncate(total as usize);
+        (symbols, offsets, truncated)
+    }
+
+    /// The same over device buffers (d_ids, d_symbols and d_offsets may each be null) on `hip_stream`, which it synchronises -> (S, truncated).
+    pub unsafe fn extract_reads_device(&self, d_ids: *const c_void, first_read: u64, n: usize, max_len: u64, d_symbols: *mut c_void, d_offsets: *mut c_void,
+                                       capacity_symbols: u64, hip_stream: *mut c_void) -> (u64, u64) {
+        let (mut total, mut truncated) = (0u64, 0u64);
+        let rc = msbwt_rle_extract_reads_device(self.raw, d_ids, first_read, n, max_len, d_symbols, d_offsets, capacity_symbols, &mut total, &mut truncated, hip_stream);
+        if rc != MSBWT_OK { panic!("extract_reads_device: {}", self.last_error()); }
+        (total, truncated)
+    }
+
+    /// The last left-walk call: walks, steps in all, DOLLAR stops, MAX_STEPS stops, BAD_ROW stops, pieces, scratch bytes, microseconds.
+    pub fn walk_info(&self) -> [u64; 8] {
+        let mut words = [0u64; 8];
+        let rc = unsafe { msbwt_rle_walk_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("walk_info: {}", self.last_error()); }
+        words
+    }
+
+    /// Most left walks a launch takes (0 = automatic, 2^20; at most 2^28); results never depend on it.
+    pub fn set_walk_piece(&mut self, walks: u64) {
+        let rc = unsafe { msbwt_rle_set_walk_piece(self.raw, walks) };
+        if rc != MSBWT_OK { panic!("set_walk_piece: {}", self.last_error()); }
+    }
+
+    /// HBM bytes of scratch a walk_rows call of n walks allocates and frees again on an index that holds something (pure function).
+    pub fn walk_plan(n: u64, max_steps: u64, symbols: bool, host: bool, piece: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_walk_plan(n, max_steps, symbols as c_int, host as c_int, piece, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "walk_plan: {} walks of {} steps", n, max_steps);
         bytes
     }
 
