@@ -1067,6 +1067,97 @@ int msbwt_rle_walk_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_WALK_INFO_W
 int msbwt_rle_set_walk_piece(msbwt_rle *bwt, uint64_t walks);
 int msbwt_walk_plan(uint64_t n, uint64_t max_steps, int symbols, int host, uint64_t piece, uint64_t *device_bytes);
 
+/* ---- read overlaps ---- the suffix-prefix overlaps of queries with the reads of the index, every length from ONE backward search,
+ * batched on the device (the reference has no counterpart: it answers one constrain_range at a time on the host).  Suffix-prefix
+ * overlaps between reads are the edges of a string graph (Simpson and Durbin's FM-index overlapper), the seeds of read-to-read
+ * correction, and the test for "does this contig end continue into a read".  msbwt_rle_extract_reads -> msbwt_rle_read_overlaps is an
+ * all-against-all overlap of an index whose reads are gone.
+ *
+ * DEFINITIONS, on the BWT string alone; they hold on any loaded stream, whoever built it.  S, T, C[c] and rank(c, r) are as in the
+ * "left walks" section, and constrain(c, [l, h)) = [C[c] + rank(c, l), C[c] + rank(c, h)).  A query is a string Q of L >= 0 symbol
+ * codes.  The call takes min_overlap = m >= 1, max_overlap = M (0 means no limit) and strand (0: Q as given; 1: its reverse
+ * complement, COMPLEMENT_INT = [0,5,3,2,4,1], N stays N).  Let Q' be the string actually searched and E = min(L, M) (E = L when M is
+ * 0).  Set R_0 = [0, T) and j = 0.
+ *   1. If j >= m and D_j = [rank('$', l_j), rank('$', h_j)) is not empty, emit the record (j, D_j.l, D_j.h - D_j.l).
+ *   2. If j == E, stop END.
+ *   3. Let c = Q'[L - 1 - j].  If c is 0 or above 5, stop BAD_SYMBOL.  The records emitted so far stand.
+ *   4. Set R_(j+1) = constrain(c, R_j).  If it is empty, stop EMPTY.  Otherwise set j += 1 and go back to 1.
+ * After j symbols [l_j, h_j) holds the suffixes that start with the last j symbols of Q'; the rows among them whose BWT symbol is '$'
+ * are the reads that BEGIN with those j symbols, and row i of the '$' block is read i of the sorted read set: D_j is a contiguous
+ * interval of read ids, every read whose prefix equals that suffix of Q'.  Per query the call returns its records, in ascending j;
+ * `matched`, the final j: the longest suffix of Q', up to E symbols, that occurs in the index; `edges`, the sum of the counts of its
+ * records; and the stop code.  A record of length j == L names the reads that start with all of Q: Q itself and its duplicates when
+ * they are in the index, and every read that contains Q as a prefix.  The call reports them; dropping self, duplicate and containment
+ * edges is the caller's policy.  An index of T = 0 rows answers before any search: every query stops EMPTY with matched = 0 and no
+ * records, and nothing is allocated.
+ *
+ * msbwt_rle_read_overlaps[_device]: the n queries are symbol codes as a ragged set, the (reads, read_offsets) pair of
+ * msbwt_rle_extract_reads; they need no alignment.  Outputs, every one may be NULL unless stated:
+ *   out_offsets          n + 1 words: the records of query i are [out_offsets[i], out_offsets[i + 1]) of the three columns
+ *   out_lengths, out_first, out_counts   the record columns, capacity_records words each: all three, or none
+ *   *out_record_total    R, the records of all queries; always set, NULL is MSBWT_ERR_INVALID_ARG
+ *   out_matched, out_edges   n words each;  out_stops  n bytes: MSBWT_OVERLAP_END, _EMPTY or _BAD_SYMBOL; 0 is never written
+ * All three columns NULL is a COUNTING call: one search, and every per-query output is written.  A FILLING call costs TWO searches:
+ * pass A writes the per-query outputs and counts the records, a scan places them, pass B searches again and writes each record at
+ * its place; everything past R is left untouched.  (A single pass through a fixed-stride staging area is a follow-up.)
+ * capacity_records < R: MSBWT_ERR_INVALID_ARG, the message names R; the per-query outputs are written all the same, the columns are
+ * unspecified within their capacity and nothing is written past it.  A BAD_SYMBOL also raises MSBWT_ERR_INVALID_SYMBOL as a BAD_ROW
+ * raises its error in msbwt_rle_walk_rows -- the host form returns it, the _device form leaves it to msbwt_rle_device_status --;
+ * every other query is answered all the same.  The _device form takes device pointers (out_record_total a host pointer), runs on
+ * hip_stream, synchronises it before it returns and reports through msbwt_rle_device_status; read_offsets that decrease show there as
+ * MSBWT_ERR_INVALID_RANGE, that query searched as an empty one.
+ * Guards, in this order, before the first HIP call: a NULL handle (MSBWT_ERR_INVALID_ARG); nothing loaded (MSBWT_ERR_NOT_LOADED, "no
+ * BWT loaded"); NULL reads or read_offsets with n > 0, a NULL out_record_total, min_overlap == 0, a strand that is not 0 or 1, or only
+ * some of the three columns given (MSBWT_ERR_INVALID_ARG); n from 2^40 on (MSBWT_ERR_TOO_LARGE: before an offset is read); host form
+ * only: offsets that decrease (MSBWT_ERR_INVALID_RANGE), then symbols from 2^40 on (MSBWT_ERR_TOO_LARGE).  n == 0 returns MSBWT_OK
+ * with R = 0 and out_offsets[0] = 0.  Results depend on no knob, no index form and no piece.
+ *
+ * How ("Read overlaps"): one 8-lane group a query, four queries a group side by side, because a search is a chain of
+ * dependent random fetches.  A step fetches the line of l_j and the line of h_j -- ONE line when both bounds lie in the same block,
+ * none for a bound that is T -- and takes from those registers the ranks of the next symbol AND of '$': both ranks sit in the same
+ * 128-byte lines the search step fetches anyway.  Step 0 needs no line.  A search fetches at most 2 matched + 2 lines, plus at most
+ * one more per bound that lies in an OVERFLOW run block.  The step loop runs inside the kernel, and a launch takes a PIECE of the n
+ * queries (msbwt_rle_set_overlap_piece: 0 = automatic, 2^20 queries, at most 2^28, beyond which MSBWT_ERR_INVALID_ARG).  Pair blocks
+ * and the direct and sparse tables are left out of this version.
+ *
+ * msbwt_rle_overlap_info: out[MSBWT_OVERLAP_INFO_WORDS] of the handle's last call = [0] queries, [1] symbols consumed in all (the sum
+ * of matched), [2] records, [3] edges, [4] END stops, [5] EMPTY stops, [6] BAD_SYMBOL stops, [7] index lines fetched (both passes),
+ * [8] pieces, [9] scratch bytes at their peak, [10] microseconds, [11] the most symbols a piece staged, [12] the most records a piece
+ * staged ([11], [12]: host form, else 0).  The scratch is per call and freed on return (msbwt_rle_device_bytes unchanged).
+ * msbwt_overlap_plan: pure, no device: [9] of a call with n > 0 on an index that holds something, EXACTLY, with P = min(n, piece),
+ * piece 0 = 2^20, pad(x) = ceil(x / 256) 256, piece_symbols = [11] and piece_records = [12] of that call (the most symbols the queries
+ * of one piece hold; the most records one piece emits, 0 for a counting call):
+ *     256                                   the counters
+ *     + pad(8 (P + 1))                      the record counts of a piece, and one word behind them
+ *     + pad(8 w)                            their scan's sums: w = 1, and with x = P + 1, while x > 2048: x = ceil(x / 2048), w += x
+ *   and, host != 0 (piece_symbols and piece_records are ignored otherwise):
+ *     + 2 pad(8 (P + 1))                    a piece's query offsets and record offsets
+ *     + 2 pad(8 P) + pad(P)                 its matched and edges; its stops -- staged whichever are NULL
+ *     + pad(piece_symbols)                  its symbols
+ *     + 3 pad(8 piece_records)              its record columns, piece_records > 0
+ * n == 0: 0 bytes.  A piece above 2^28: MSBWT_ERR_INVALID_ARG; n, piece_symbols or piece_records from 2^40 on: MSBWT_ERR_TOO_LARGE;
+ * device_bytes may be NULL.
+ *
+ * Out of scope here: the pair blocks and tables under the first symbols of a search; a single-pass filling call; forms for several
+ * GPUs. */
+#ifndef MSBWT_OVERLAP_INFO_WORDS
+#  define MSBWT_OVERLAP_END 1
+#  define MSBWT_OVERLAP_EMPTY 2
+#  define MSBWT_OVERLAP_BAD_SYMBOL 3
+#  define MSBWT_OVERLAP_INFO_WORDS 13
+#endif
+int msbwt_rle_read_overlaps(const msbwt_rle *bwt, const uint8_t *reads, const uint64_t *read_offsets /* n + 1 */, size_t n, uint64_t min_overlap,
+                            uint64_t max_overlap, int strand, uint64_t *out_offsets /* n + 1 */, uint64_t *out_lengths, uint64_t *out_first,
+                            uint64_t *out_counts, uint64_t capacity_records, uint64_t *out_record_total, uint64_t *out_matched, uint64_t *out_edges,
+                            uint8_t *out_stops);
+int msbwt_rle_read_overlaps_device(const msbwt_rle *bwt, const void *d_reads, const void *d_read_offsets, size_t n, uint64_t min_overlap,
+                                   uint64_t max_overlap, int strand, void *d_out_offsets, void *d_out_lengths, void *d_out_first, void *d_out_counts,
+                                   uint64_t capacity_records, uint64_t *out_record_total, void *d_out_matched, void *d_out_edges, void *d_out_stops,
+                                   void *hip_stream);
+int msbwt_rle_overlap_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_OVERLAP_INFO_WORDS */);
+int msbwt_rle_set_overlap_piece(msbwt_rle *bwt, uint64_t queries);
+int msbwt_overlap_plan(uint64_t n, int host, uint64_t piece, uint64_t piece_symbols, uint64_t piece_records, uint64_t *device_bytes);
+
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path
  * shards over queries: every device holds a replica of the index, a batch is cut into contiguous

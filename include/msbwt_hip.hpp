@@ -808,6 +808,71 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_walk_plan");
         return bytes;
     }
+    /// What read_overlaps returns: the records of query i are [offsets[i], offsets[i + 1]) of lengths / first / counts, in ascending
+    /// length -- the reads first[r] .. first[r] + counts[r] begin with the last lengths[r] symbols of the query searched --; matched,
+    /// edges and stops (MSBWT_OVERLAP_END, _EMPTY, _BAD_SYMBOL) hold one entry a query.  A counting call leaves the columns empty.
+    struct Overlaps {
+        std::vector<std::uint64_t> offsets, lengths, first, counts, matched, edges;
+        std::vector<std::uint8_t> stops;
+        std::size_t size() const { return matched.size(); }
+        std::uint64_t records() const { return offsets.empty() ? 0 : offsets.back(); }
+    };
+    /// The suffix-prefix overlaps of n queries (symbol codes as a ragged set: query i = symbols[offsets[i] .. offsets[i + 1])) with
+    /// the reads of the index, at least min_overlap and, max_overlap not 0, at most max_overlap symbols long; strand 1 searches the
+    /// reverse complements.  records = false: a counting call, one search instead of two.
+    Overlaps read_overlaps(const std::vector<std::uint8_t> &symbols, const std::vector<std::uint64_t> &offsets, std::uint64_t min_overlap,
+                           std::uint64_t max_overlap = 0, int strand = 0, bool records = true) const {
+        const std::size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        const std::uint8_t none = 0;
+        Overlaps o;
+        o.offsets.resize(n + 1);
+        o.matched.resize(n);
+        o.edges.resize(n);
+        o.stops.resize(n);
+        std::uint64_t total = 0;
+        const std::uint8_t *where = symbols.empty() ? &none : symbols.data();
+        check(msbwt_rle_read_overlaps(raw_, where, offsets.data(), n, min_overlap, max_overlap, strand, o.offsets.data(), nullptr, nullptr, nullptr, 0, &total,
+                                      o.matched.data(), o.edges.data(), o.stops.data()));
+        if (!records || total == 0) return o;
+        o.lengths.resize(total);
+        o.first.resize(total);
+        o.counts.resize(total);
+        check(msbwt_rle_read_overlaps(raw_, where, offsets.data(), n, min_overlap, max_overlap, strand, o.offsets.data(), o.lengths.data(), o.first.data(), o.counts.data(),
+                                      total, &total, o.matched.data(), o.edges.data(), o.stops.data()));
+        return o;
+    }
+    /// Device buffers (every output may be null; the three columns come together or not at all) -> R, the records of all queries;
+    /// synchronises hip_stream.
+    std::uint64_t read_overlaps_device(const void *d_symbols, const void *d_offsets, std::size_t n, std::uint64_t min_overlap, std::uint64_t max_overlap, int strand,
+                                       void *d_out_offsets, void *d_lengths, void *d_first, void *d_counts, std::uint64_t capacity_records, void *d_matched,
+                                       void *d_edges, void *d_stops, void *hip_stream = nullptr) const {
+        std::uint64_t total = 0;
+        check(msbwt_rle_read_overlaps_device(raw_, d_symbols, d_offsets, n, min_overlap, max_overlap, strand, d_out_offsets, d_lengths, d_first, d_counts, capacity_records,
+                                             &total, d_matched, d_edges, d_stops, hip_stream));
+        return total;
+    }
+    /// The last read-overlap call.
+    struct OverlapInfo {
+        std::uint64_t queries = 0, symbols = 0, records = 0, edges = 0, end = 0, empty = 0, bad_symbol = 0, lines = 0, pieces = 0, scratch_bytes = 0, us = 0,
+                      piece_symbols = 0, piece_records = 0;
+    };
+    OverlapInfo overlap_info() const {
+        std::uint64_t w[MSBWT_OVERLAP_INFO_WORDS] = {};
+        check(msbwt_rle_overlap_info(raw_, w));
+        OverlapInfo i;
+        i.queries = w[0], i.symbols = w[1], i.records = w[2], i.edges = w[3], i.end = w[4], i.empty = w[5], i.bad_symbol = w[6], i.lines = w[7], i.pieces = w[8];
+        i.scratch_bytes = w[9], i.us = w[10], i.piece_symbols = w[11], i.piece_records = w[12];
+        return i;
+    }
+    /// Most overlap queries a launch takes (0 = automatic, 2^20; at most 2^28); results never depend on it.
+    void set_overlap_piece(std::uint64_t queries) { check(msbwt_rle_set_overlap_piece(raw_, queries)); }
+    /// Peak HBM bytes of scratch a read_overlaps call of n queries allocates (and frees again) on an index that holds something.
+    static std::uint64_t overlap_plan(std::uint64_t n, bool host = true, std::uint64_t piece = 0, std::uint64_t piece_symbols = 0, std::uint64_t piece_records = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_overlap_plan(n, host ? 1 : 0, piece, piece_symbols, piece_records, &bytes);
+        if (rc) throw Panic(rc, "msbwt_overlap_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

@@ -26,6 +26,8 @@ CANONICAL_TRACE_STOPS = TRACE_STOPS + ("MIRROR",)  # .. MSBWT_CANONICAL_TRACE_MI
 CANONICAL_TRACE_INFO_WORDS = 8  # MSBWT_CANONICAL_TRACE_INFO_WORDS
 WALK_INFO_WORDS = 8  # MSBWT_WALK_INFO_WORDS
 WALK_STOPS = ("", "DOLLAR", "MAX_STEPS", "BAD_ROW")  # MSBWT_WALK_DOLLAR = 1 ..
+OVERLAP_INFO_WORDS = 13  # MSBWT_OVERLAP_INFO_WORDS
+OVERLAP_STOPS = ("", "END", "EMPTY", "BAD_SYMBOL")  # MSBWT_OVERLAP_END = 1 ..
 SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
@@ -137,6 +139,11 @@ SIGNATURES = {
     "msbwt_rle_walk_info": (_int, [_vp, _vp]),
     "msbwt_rle_set_walk_piece": (_int, [_vp, _u64]),
     "msbwt_walk_plan": (_int, [_u64, _u64, _int, _int, _u64, _pu64]),
+    "msbwt_rle_read_overlaps": (_int, [_vp, _vp, _vp, _sz, _u64, _u64, _int, _vp, _vp, _vp, _vp, _u64, _pu64, _vp, _vp, _vp]),
+    "msbwt_rle_read_overlaps_device": (_int, [_vp, _vp, _vp, _sz, _u64, _u64, _int, _vp, _vp, _vp, _vp, _u64, _pu64, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_overlap_info": (_int, [_vp, _vp]),
+    "msbwt_rle_set_overlap_piece": (_int, [_vp, _u64]),
+    "msbwt_overlap_plan": (_int, [_u64, _int, _u64, _u64, _u64, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

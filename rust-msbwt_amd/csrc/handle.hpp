@@ -201,6 +201,8 @@ struct msbwt_rle : Settings {
     uint64_t canonical_trace_info[MSBWT_CANONICAL_TRACE_INFO_WORDS] = {};  // and the last canonical one: msbwt_rle_canonical_trace_info
     uint64_t walk_piece = 0;                  // most left walks a launch takes (0 = automatic): msbwt_rle_set_walk_piece
     uint64_t walk_info[MSBWT_WALK_INFO_WORDS] = {};  // what the last left-walk call did: msbwt_rle_walk_info
+    uint64_t overlap_piece = 0;               // most overlap queries a launch takes (0 = automatic): msbwt_rle_set_overlap_piece
+    uint64_t overlap_info[MSBWT_OVERLAP_INFO_WORDS] = {};  // what the last read-overlap call did: msbwt_rle_overlap_info
     std::mutex mu;
     std::string err;
 };

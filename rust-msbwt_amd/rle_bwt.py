@@ -844,6 +844,91 @@ class RleBWT(BWT):
         if rc:
             _raise(rc, self._h)
 
+    # ---- read overlaps: the reads that begin with a suffix of a query, every length from one backward search ----
+    def read_overlaps(self, reads, min_overlap, max_overlap=0, strand=0, records=True, ascii=False):
+        """msbwt_rle_read_overlaps -> OverlapResult.  reads: the queries, as pack_reads takes them -- a list of strings (ascii=True) or of
+        arrays of symbol codes, or a (symbols, offsets) pair of codes such as extract_reads returns.  Each is searched backwards
+        (strand=1: its reverse complement), and for every length j >= min_overlap (and <= max_overlap, 0 = no limit) at which reads of
+        the index begin with the query's last j symbols the result holds one record (length, first read, count): the records of query
+        i are [offsets[i], offsets[i + 1]) of lengths / first / counts, in ascending length (include/msbwt_hip.h, "read overlaps").
+        matched: the longest suffix found; edges: the sum of the query's counts; stops: _lib.OVERLAP_STOPS names the codes.
+        records=False: a counting call, one search instead of two; lengths, first and counts are None.  A symbol that is no code 1..5
+        stops its query BAD_SYMBOL and raises MsbwtError(ERR_INVALID_SYMBOL).  overlap_edges expands the result to edges."""
+        flat, offsets = pack_reads(reads, ascii=ascii)
+        if ascii:
+            codes = np.empty_like(flat)
+            _lib.lib().msbwt_convert_stoi(flat.ctypes.data_as(C.c_void_p), flat.size, codes.ctypes.data_as(C.c_void_p))
+            flat = codes
+        n = len(offsets) - 1
+        out = OverlapResult(n, np.diff(offsets.astype(np.int64)).astype(np.uint64))
+        total = C.c_uint64(0)
+
+        def call(columns, capacity):
+            return _lib.lib().msbwt_rle_read_overlaps(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n, int(min_overlap), int(max_overlap),
+                                                      int(strand), out.offsets.ctypes.data_as(C.c_void_p), *columns, capacity, C.byref(total),
+                                                      out.matched.ctypes.data_as(C.c_void_p), out.edges.ctypes.data_as(C.c_void_p), out.stops.ctypes.data_as(C.c_void_p))
+
+        rc = call((None, None, None), 0)
+        if rc:
+            _raise(rc, self._h)
+        if records:
+            R = int(total.value)
+            out.lengths, out.first, out.counts = (np.zeros(R, dtype=np.uint64) for _ in range(3))
+            if R:
+                rc = call([a.ctypes.data_as(C.c_void_p) for a in (out.lengths, out.first, out.counts)], R)
+                if rc:
+                    _raise(rc, self._h)
+        return out
+
+    def read_overlaps_device(self, reads, offsets, min_overlap, max_overlap=0, strand=0, records=True, capacity=None):
+        """msbwt_rle_read_overlaps_device on torch tensors of this handle's device, on torch's current stream -> OverlapResult of tensors
+        (words as int64).  reads: uint8 symbol codes; offsets: n + 1 words (int64 or uint64), contiguous.  records=True counts first
+        and fills tensors of exactly R records -- three searches in all -- unless `capacity` says how many records the columns are to
+        hold: then one filling call, and MsbwtError (with .records = R) if R exceeds it.  A bad symbol shows in device_status."""
+        import torch
+        if not (reads.is_contiguous() and offsets.is_contiguous()) or reads.element_size() != 1 or offsets.element_size() != 8:
+            raise ValueError("reads is a contiguous uint8 tensor, offsets a contiguous tensor of n + 1 64-bit words")
+        n, dev = int(offsets.numel()) - 1, offsets.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        out = OverlapResult(n, None, torch=torch, device=dev)
+        total = C.c_uint64(0)
+
+        def call(columns, cap):
+            rc = _lib.lib().msbwt_rle_read_overlaps_device(self._h, reads.data_ptr() if reads.numel() else offsets.data_ptr(), offsets.data_ptr(), n, int(min_overlap),
+                                                           int(max_overlap), int(strand), out.offsets.data_ptr(), *columns, cap, C.byref(total), out.matched.data_ptr(),
+                                                           out.edges.data_ptr(), out.stops.data_ptr(), stream)
+            if rc:
+                try:
+                    _raise(rc, self._h)
+                except MsbwtError as e:
+                    e.records = int(total.value)
+                    raise
+
+        if not records:
+            call((None, None, None), 0)
+        else:
+            if capacity is None:
+                call((None, None, None), 0)
+                capacity = int(total.value)
+            out.lengths, out.first, out.counts = (torch.zeros(max(int(capacity), 1), dtype=torch.int64, device=dev) for _ in range(3))
+            call([a.data_ptr() for a in (out.lengths, out.first, out.counts)], int(capacity))
+            R = int(total.value)
+            out.lengths, out.first, out.counts = out.lengths[:R], out.first[:R], out.counts[:R]
+        out.query_lengths = (offsets[1:] - offsets[:-1]) if n else offsets[:0]
+        return out
+
+    def overlap_info(self):
+        """What the last read-overlap call did: {"queries", "symbols", "records", "edges", "end", "empty", "bad_symbol", "lines", "pieces",
+        "scratch_bytes", "us", "piece_symbols", "piece_records"}."""
+        return self._info(_lib.lib().msbwt_rle_overlap_info, ("queries", "symbols", "records", "edges", "end", "empty", "bad_symbol", "lines", "pieces", "scratch_bytes",
+                                                              "us", "piece_symbols", "piece_records"))
+
+    def set_overlap_piece(self, queries):
+        """Most overlap queries a launch takes (0 = automatic, 2^20; at most 2^28): results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_overlap_piece(self._h, int(queries))
+        if rc:
+            _raise(rc, self._h)
+
     def set_spectrum_frontier(self, nodes):
         """Most nodes per frontier buffer of the k-mer walks (0 = automatic, else at least _lib.SPECTRUM_MIN_FRONTIER): results never depend on it."""
         rc = _lib.lib().msbwt_rle_set_spectrum_frontier(self._h, int(nodes))
@@ -1433,6 +1518,63 @@ def walk_sequences(symbols, steps, text=False):
     if not text:
         return out
     return [_LETTERS[a].tobytes().decode() for a in out]
+
+
+class OverlapResult:
+    """What RleBWT.read_overlaps returns: offsets (n + 1), the record columns lengths / first / counts (None for a counting call),
+    matched, edges, stops (n each) and query_lengths.  numpy arrays from the host form, torch tensors (words as int64) from the
+    device form."""
+
+    def __init__(self, n, query_lengths, torch=None, device=None):
+        self.query_lengths = query_lengths
+        self.lengths = self.first = self.counts = None
+        if torch is None:
+            self.offsets = np.zeros(n + 1, dtype=np.uint64)
+            self.matched, self.edges = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+            self.stops = np.zeros(n, dtype=np.uint8)
+        else:
+            self.offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
+            self.matched, self.edges = torch.zeros(n, dtype=torch.int64, device=device), torch.zeros(n, dtype=torch.int64, device=device)
+            self.stops = torch.zeros(n, dtype=torch.uint8, device=device)
+
+
+def overlap_edges(result, query_ids=None, drop_self=True, drop_contained=False):
+    """The records of an OverlapResult expanded to edges: an (E, 3) uint64 array of (query, read, length) rows, by query, then length,
+    then read.  query_ids: the read id of each query where the queries are reads of the index (extract_reads order: the ids
+    themselves); with it, drop_self removes (i, query_ids[i], L_i), the query found as itself.  drop_contained removes every edge
+    whose length equals its query's length: the reads that hold the whole query as a prefix, duplicates and self included.  Pure
+    host logic in numpy."""
+    def host(a):
+        return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "data_ptr") else a).astype(np.uint64).reshape(-1)
+
+    if result.lengths is None:
+        raise ValueError("overlap_edges needs the records: read_overlaps(..., records=True)")
+    offsets, lengths, first, counts, qlen = host(result.offsets), host(result.lengths), host(result.first), host(result.counts), host(result.query_lengths)
+    per_query = np.diff(offsets.astype(np.int64))
+    rec_query = np.repeat(np.arange(per_query.size, dtype=np.uint64), per_query)
+    c = counts.astype(np.int64)
+    query = np.repeat(rec_query, c)
+    length = np.repeat(lengths, c)
+    starts = np.cumsum(c) - c
+    read = np.repeat(first, c) + (np.arange(int(c.sum()), dtype=np.int64) - np.repeat(starts, c)).astype(np.uint64)
+    keep = np.ones(query.size, dtype=bool)
+    whole = length == qlen[query.astype(np.int64)] if query.size else keep
+    if drop_contained:
+        keep &= ~whole
+    elif drop_self and query_ids is not None:
+        ids = host(query_ids)
+        keep &= ~(whole & (read == ids[query.astype(np.int64)]))
+    return np.stack([query[keep], read[keep], length[keep]], axis=1) if query.size else np.zeros((0, 3), dtype=np.uint64)
+
+
+def overlap_plan(n, host=True, piece=0, piece_symbols=0, piece_records=0):
+    """msbwt_overlap_plan: the peak bytes of HBM scratch a RleBWT.read_overlaps call of n queries allocates (and frees again) on an
+    index that holds something; piece_symbols / piece_records: overlap_info's words of the same names (host form)."""
+    out = C.c_uint64(0)
+    rc = _lib.lib().msbwt_overlap_plan(int(n), int(bool(host)), int(piece), int(piece_symbols), int(piece_records), C.byref(out))
+    if rc:
+        raise MsbwtError(rc, "msbwt_overlap_plan: n, the symbols and the records of a piece must stay below 2^40, a piece is at most 2^28 queries")
+    return out.value
 
 
 def trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):

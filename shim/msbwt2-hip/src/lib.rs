@@ -205,6 +205,17 @@ extern "C" {
     fn msbwt_rle_walk_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
     fn msbwt_rle_set_walk_piece(bwt: *mut MsbwtRle, walks: u64) -> c_int;
     fn msbwt_walk_plan(n: u64, max_steps: u64, symbols: c_int, host: c_int, piece: u64, device_bytes: *mut u64) -> c_int;
+    // read overlaps: the reads that begin with a suffix of a query, every length from one backward search
+    fn msbwt_rle_read_overlaps(bwt: *const MsbwtRle, reads: *const u8, read_offsets: *const u64, n: usize, min_overlap: u64, max_overlap: u64, strand: c_int,
+                               out_offsets: *mut u64, out_lengths: *mut u64, out_first: *mut u64, out_counts: *mut u64, capacity_records: u64,
+                               out_record_total: *mut u64, out_matched: *mut u64, out_edges: *mut u64, out_stops: *mut u8) -> c_int;
+    fn msbwt_rle_read_overlaps_device(bwt: *const MsbwtRle, d_reads: *const c_void, d_read_offsets: *const c_void, n: usize, min_overlap: u64, max_overlap: u64,
+                                      strand: c_int, d_out_offsets: *mut c_void, d_out_lengths: *mut c_void, d_out_first: *mut c_void, d_out_counts: *mut c_void,
+                                      capacity_records: u64, out_record_total: *mut u64, d_out_matched: *mut c_void, d_out_edges: *mut c_void,
+                                      d_out_stops: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_overlap_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_rle_set_overlap_piece(bwt: *mut MsbwtRle, queries: u64) -> c_int;
+    fn msbwt_overlap_plan(n: u64, host: c_int, piece: u64, piece_symbols: u64, piece_records: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -994,6 +1005,71 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_walk_plan(n, max_steps, symbols as c_int, host as c_int, piece, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "walk_plan: {} walks of {} steps", n, max_steps);
+        bytes
+    }
+
+    /// Read overlaps (include/msbwt_hip.h, "read overlaps"): each of the n queries (symbol codes, query i = symbols[offsets[i] .. offsets[i + 1]))
+    /// searched backwards -- strand 1: its reverse complement --, and for every length j >= min_overlap (and <= max_overlap, 0 = no limit) at
+    /// which reads of the index begin with the query's last j symbols one record (length, first read, count)
+    /// -> (record offsets: n + 1, lengths, first, counts, matched, edges, stops).  records = false: a counting call, one search, the columns empty.
+    pub fn read_overlaps(&self, symbols: &[u8], offsets: &[u64], min_overlap: u64, max_overlap: u64, strand: i32, records: bool)
+                         -> (Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u8>) {
+        let n = offsets.len().saturating_sub(1);
+        let none = [0u8];
+        let reads = if symbols.is_empty() { none.as_ptr() } else { symbols.as_ptr() };
+        let mut out_offsets = vec![0u64; n + 1];
+        let (mut matched, mut edges, mut stops) = (vec![0u64; n], vec![0u64; n], vec![0u8; n]);
+        let mut total = 0u64;
+        let null = std::ptr::null_mut::<u64>();
+        let rc = unsafe {
+            msbwt_rle_read_overlaps(self.raw, reads, offsets.as_ptr(), n, min_overlap, max_overlap, strand as c_int, out_offsets.as_mut_ptr(), null, null, null, 0,
+                                    &mut total, matched.as_mut_ptr(), edges.as_mut_ptr(), stops.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("read_overlaps: {}", self.last_error()); }
+        let filled = if records { total as usize } else { 0 };
+        let (mut lengths, mut first, mut counts) = (vec![0u64; filled], vec![0u64; filled], vec![0u64; filled]);
+        if filled > 0 {
+            let rc = unsafe {
+                msbwt_rle_read_overlaps(self.raw, reads, offsets.as_ptr(), n, min_overlap, max_overlap, strand as c_int, out_offsets.as_mut_ptr(), lengths.as_mut_ptr(),
+                                        first.as_mut_ptr(), counts.as_mut_ptr(), total, &mut total, matched.as_mut_ptr(), edges.as_mut_ptr(), stops.as_mut_ptr())
+            };
+            if rc != MSBWT_OK { panic!("read_overlaps: {}", self.last_error()); }
+        }
+        (out_offsets, lengths, first, counts, matched, edges, stops)
+    }
+
+    /// The same over device buffers (every output may be null; the three columns together or not at all) on `hip_stream`, which it
+    /// synchronises -> R, the records of all queries.
+    pub unsafe fn read_overlaps_device(&self, d_symbols: *const c_void, d_offsets: *const c_void, n: usize, min_overlap: u64, max_overlap: u64, strand: i32,
+                                       d_out_offsets: *mut c_void, d_lengths: *mut c_void, d_first: *mut c_void, d_counts: *mut c_void, capacity_records: u64,
+                                       d_matched: *mut c_void, d_edges: *mut c_void, d_stops: *mut c_void, hip_stream: *mut c_void) -> u64 {
+        let mut total = 0u64;
+        let rc = msbwt_rle_read_overlaps_device(self.raw, d_symbols, d_offsets, n, min_overlap, max_overlap, strand as c_int, d_out_offsets, d_lengths, d_first, d_counts,
+                                                capacity_records, &mut total, d_matched, d_edges, d_stops, hip_stream);
+        if rc != MSBWT_OK { panic!("read_overlaps_device: {}", self.last_error()); }
+        total
+    }
+
+    /// The last read-overlap call: queries, symbols consumed, records, edges, END / EMPTY / BAD_SYMBOL stops, index lines fetched, pieces,
+    /// scratch bytes, microseconds, the most symbols and the most records a piece staged.
+    pub fn overlap_info(&self) -> [u64; 13] {
+        let mut words = [0u64; 13];
+        let rc = unsafe { msbwt_rle_overlap_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("overlap_info: {}", self.last_error()); }
+        words
+    }
+
+    /// Most overlap queries a launch takes (0 = automatic, 2^20; at most 2^28); results never depend on it.
+    pub fn set_overlap_piece(&mut self, queries: u64) {
+        let rc = unsafe { msbwt_rle_set_overlap_piece(self.raw, queries) };
+        if rc != MSBWT_OK { panic!("set_overlap_piece: {}", self.last_error()); }
+    }
+
+    /// Peak HBM bytes of scratch a read_overlaps call of n queries allocates and frees again on an index that holds something (pure function).
+    pub fn overlap_plan(n: u64, host: bool, piece: u64, piece_symbols: u64, piece_records: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_overlap_plan(n, host as c_int, piece, piece_symbols, piece_records, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "overlap_plan: {} queries", n);
         bytes
     }
 
