@@ -866,8 +866,8 @@ int msbwt_rle_spectrum_scratch_bytes(const msbwt_rle *bwt, uint64_t *out_bytes);
  * A host call stages all six outputs whichever are NULL.  n == 0: 0 bytes.  A bad mode: MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE as
  * the call; device_bytes may be NULL.
  *
- * Out of scope here: the strand-merged graph, which "canonical traces" below walks; k from 32 on, which needs two words a query; branching exploration (all
- * paths between two anchors: out_fans and out_last let a caller fork on the host meanwhile); per-source thresholds. */
+ * Out of scope here: the strand-merged graph, which "canonical traces" below walks; k from 32 on, which needs two words a query; per-source thresholds.
+ * All walks between two anchors, forks included, are the "bridges" section's. */
 #define MSBWT_TRACE_RIGHT 0
 #define MSBWT_TRACE_LEFT 1
 #define MSBWT_TRACE_UNIQUE 0
@@ -1157,6 +1157,108 @@ int msbwt_rle_read_overlaps_device(const msbwt_rle *bwt, const void *d_reads, co
 int msbwt_rle_overlap_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_OVERLAP_INFO_WORDS */);
 int msbwt_rle_set_overlap_piece(msbwt_rle *bwt, uint64_t queries);
 int msbwt_overlap_plan(uint64_t n, int host, uint64_t piece, uint64_t piece_symbols, uint64_t piece_records, uint64_t *device_bytes);
+
+/* ---- bridges ---- all bounded walks of the k-mer graph between two anchor k-mers, for n pairs (seed, target) at once, on the device
+ * (no reference counterpart).  This is what an fmlrc-style corrector does for every weak stretch of a read: two solid k-mers flank the
+ * stretch, and every walk of the graph that leads from one into the other within a window of lengths and a branching budget is a
+ * candidate for what the read should say there.  A trace follows one rule along one path and stops at the first BRANCH; a bridge call
+ * explores the branches, level by level.
+ *
+ * THE GRAPH G(k, m, me), the thresholds (min_count, min_edge), the packed words, the edge word, the next node and the two directions
+ * are exactly those of "traces", 1 <= k <= 31; MSBWT_BRIDGE_RIGHT and MSBWT_BRIDGE_LEFT have the numbers of the traces' directions.
+ * As there me >= m, so the far end of an edge is always a node.  A WALK may repeat nodes, the seed included.
+ * ONE PAIR i, with seed s and target t (bits beyond 2k ignored in both), lo = max(min_steps, 1), found = 0:
+ *   0. s is no node: stop NO_SEED.  Else t is no node: stop NO_TARGET.  In both cases found = 0 and depth = 0.
+ *   1. W(0) = {the empty walk standing on s}.  For r = 1, 2, ...:
+ *      EXPAND.   max_steps == 0: stop MAX_STEPS with depth 0.  Otherwise E(r) is every extension of every walk of W(r-1) by one edge
+ *                of its last node's fan.  E(r) keeps the order of W(r-1) and, within one parent, the order A < C < G < T: every level
+ *                is in lexicographic order of its rows of symbols.
+ *      COLLECT.  B(r) is the members of E(r) whose new node equals t, when r >= lo: the bridges of length r.  They are numbered found,
+ *                found + 1, ... in that order, and those numbered below max_paths are written.  Then found += |B(r)|,
+ *                W(r) = E(r) \ B(r), and depth = r.  An entry into t with r < lo does not end the walk.
+ *      STOP, in this precedence: found >= max_paths: FULL.  W(r) is empty: EXHAUSTED.  r == max_steps: MAX_STEPS.
+ *                |W(r)| > max_live: TOO_WIDE.  Otherwise go on.
+ * Whatever the stop, THE BRIDGES OF LENGTH <= out_depths[i] ARE ALL COUNTED IN out_found[i], and the first min(found, max_paths) of
+ * them, in the order (length, then symbols), are the ones written.  EXHAUSTED says in addition that no longer bridge exists.  A walk
+ * that enters t at r >= lo ends there: a bridge is never extended through its target.
+ * The full sequence of bridge (i, j) is the seed followed by its row of symbols (RIGHT), or the row reversed followed by the seed (LEFT).
+ *
+ * Outputs, every one may be NULL; with out_symbols NULL the call is a COUNTING call:
+ *   out_symbols     n x max_paths x max_steps bytes: row (i, j) holds out_lengths[i max_paths + j] symbols in walk order, in the
+ *                   library's codes 1 2 3 5; the rest of the row, and every unused row, is left untouched
+ *   out_lengths     n x max_paths words: the length of bridge (i, j); unused entries are written 0
+ *   out_edge_sums   n x max_paths words: the sum of count_kmer over the (k+1)-mers of bridge (i, j); unused entries are written 0
+ *   out_found       n words;  out_depths  n words: the last level collected;  out_live  n words: |W(depth)| at the stop (0 for NO_SEED
+ *                   and NO_TARGET, 1 for max_steps == 0)
+ *   out_stops       n bytes: MSBWT_BRIDGE_EXHAUSTED .. MSBWT_BRIDGE_NO_TARGET; 0 is never written
+ * The _device form takes device pointers, runs on hip_stream, synchronises it before it returns (the scratch is freed then) and
+ * reports a device fault through msbwt_rle_device_status, as the trace calls do.
+ * Guards, before the first HIP call: those of the traces (a NULL handle; nothing loaded, MSBWT_ERR_NOT_LOADED; k outside 1..31; a bad
+ * min_edge or direction; NULL seeds with n > 0); NULL targets with n > 0, max_paths == 0, max_live == 0, min_steps > max_steps (all
+ * MSBWT_ERR_INVALID_ARG); max_steps above MSBWT_BRIDGE_MAX_STEPS_CAP, max_live above MSBWT_BRIDGE_MAX_LIVE_CAP, n x max_paths or
+ * n x max_paths x max_steps from 2^40 on (MSBWT_ERR_TOO_LARGE).  n == 0 and an empty index are MSBWT_OK; on an empty index every
+ * stop is NO_SEED.  Results depend on no knob, no index form and no piece size, and are the same from run to run -- which bridges are
+ * written, and in which row, included.
+ *
+ * How ("Bridges"): rounds of the packed search of msbwt_rle_count_kmers_packed_device, as the traces'.  Round 0 searches
+ * every pair's seed and target at length k and the seed's fan at k + 1.  The FRONTIER is one array of fixed-size states in the order
+ * (pair, walk order): pair, node, steps, edge sum and the walk's symbols at 2 bits, 64 + 8 ceil(max_steps / 32) bytes.  A round
+ * searches the 4 edges of every state's fan, then: a kernel forms every state's child and bridge masks and adds them up per pair (64-bit
+ * atomic adds: order-free sums), a kernel applies the four stops per pair, a STABLE exclusive scan over the states' child and bridge
+ * counts gives every child its slot and every bridge its number, and a kernel writes the children -- with their 4 next queries -- to the
+ * other buffer and the bridges to their rows.  No atomic ticket decides an order, so run-to-run sameness needs no sort.  The host
+ * reads the size of the next level once a round.  The n pairs are taken a PIECE at a time: P = max(1, slots / max_live) pairs, slots
+ * from msbwt_rle_set_bridge_slots (0 = automatic: 2^20; max_live where that is larger; at most 2^28, beyond which
+ * MSBWT_ERR_INVALID_ARG) -- a pair that goes on holds at most max_live states, so a piece's frontier never outgrows its P max_live slots.
+ * Queries searched, EXACTLY: 6 a pair in round 0, then 4 a state of every W(r) that goes on.
+ *
+ * msbwt_rle_bridge_info: out[MSBWT_BRIDGE_INFO_WORDS] of the handle's last bridge call = [0] pairs, [1] rounds run (round 0 and every
+ * expansion, summed over the pieces), [2] queries handed to the packed search, [3] walk-steps expanded (the sum of |E(r)|), [4] bridges
+ * found, [5] pieces, [6] scratch bytes allocated, [7] the widest frontier of a piece (its pairs in round 0, else the states of a
+ * level).  The scratch is per call and freed on return (msbwt_rle_device_bytes unchanged); an empty index and n == 0 allocate nothing.
+ * msbwt_bridge_plan: pure, no device: [6] of a call on an index that holds something, EXACTLY, with s = max(slots, max_live) (slots 0 =
+ * 2^20), P = min(n, s / max_live), S = P max_live, W = 8 + ceil(max_steps / 32) and pad(x) = ceil(x / 256) 256:
+ *     256                                   the counters
+ *     + pad(48 P)                           the pairs' table
+ *     + 2 pad(8 W S)                        the states, two buffers
+ *     + pad(8 S)                            a scan word a state
+ *     + pad(8 w)                            the scan's sums: w = 1, and with x = S, while x > 2048: x = ceil(x / 2048), w += x
+ *     + 2 pad(8 max(4 S, 6 P))              the queries and their counts
+ *   and, host != 0 (the _device form's arrays are the caller's own):
+ *     + 2 pad(8 P)                          a piece's seeds and targets
+ *     + pad(P max_paths max_steps)          its rows of symbols
+ *     + 2 pad(8 P max_paths)                its lengths and edge sums
+ *     + 3 pad(8 P) + pad(P)                 its found, depths and live; its stops
+ * A host call has room for all seven outputs whichever are NULL.  n == 0: 0 bytes.  max_paths == 0, max_live == 0 or slots above 2^28:
+ * MSBWT_ERR_INVALID_ARG; MSBWT_ERR_TOO_LARGE as the call; device_bytes may be NULL.
+ *
+ * Out of scope here: the strand-merged graph; k from 32 on; choosing among bridges by edit distance to the read; per-source
+ * thresholds; forms for several GPUs. */
+#ifndef MSBWT_BRIDGE_INFO_WORDS
+#  define MSBWT_BRIDGE_RIGHT 0
+#  define MSBWT_BRIDGE_LEFT 1
+#  define MSBWT_BRIDGE_EXHAUSTED 1
+#  define MSBWT_BRIDGE_FULL 2
+#  define MSBWT_BRIDGE_MAX_STEPS 3
+#  define MSBWT_BRIDGE_TOO_WIDE 4
+#  define MSBWT_BRIDGE_NO_SEED 5
+#  define MSBWT_BRIDGE_NO_TARGET 6
+#  define MSBWT_BRIDGE_MAX_STEPS_CAP 4096
+#  define MSBWT_BRIDGE_MAX_LIVE_CAP 16777216
+#  define MSBWT_BRIDGE_INFO_WORDS 8
+#endif
+int msbwt_rle_bridge_kmers(const msbwt_rle *bwt, const uint64_t *seeds2bit, const uint64_t *targets2bit, size_t k, size_t n, uint64_t min_count,
+                           uint64_t min_edge, int direction, uint64_t min_steps, uint64_t max_steps, uint64_t max_paths, uint64_t max_live,
+                           uint8_t *out_symbols /* n x max_paths x max_steps */, uint64_t *out_lengths /* n x max_paths */,
+                           uint64_t *out_edge_sums /* n x max_paths */, uint64_t *out_found, uint8_t *out_stops, uint64_t *out_depths,
+                           uint64_t *out_live);
+int msbwt_rle_bridge_kmers_device(const msbwt_rle *bwt, const void *d_seeds2bit, const void *d_targets2bit, size_t k, size_t n, uint64_t min_count,
+                                  uint64_t min_edge, int direction, uint64_t min_steps, uint64_t max_steps, uint64_t max_paths, uint64_t max_live,
+                                  void *d_out_symbols, void *d_out_lengths, void *d_out_edge_sums, void *d_out_found, void *d_out_stops,
+                                  void *d_out_depths, void *d_out_live, void *hip_stream);
+int msbwt_rle_bridge_info(const msbwt_rle *bwt, uint64_t *out /* MSBWT_BRIDGE_INFO_WORDS */);
+int msbwt_rle_set_bridge_slots(msbwt_rle *bwt, uint64_t slots);
+int msbwt_bridge_plan(uint64_t n, uint64_t max_steps, uint64_t max_paths, uint64_t max_live, int host, uint64_t slots, uint64_t *device_bytes);
 
 /* ---- several GPUs of one node (no reference counterpart: the crate is single-threaded) ----
  * count_kmer calls are independent and read-only (`&self`, src/msbwt_core.rs:125), so the path

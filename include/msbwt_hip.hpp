@@ -873,6 +873,72 @@ class RleBWT final : public BWT {
         if (rc) throw Panic(rc, "msbwt_overlap_plan");
         return bytes;
     }
+    /// What bridge_kmers returns: row (i, j) of symbols (n x max_paths rows of max_steps bytes) holds lengths[i max_paths + j] symbol codes
+    /// (A C G T = 1 2 3 5) in walk order and zeros behind them; an unused row has length 0.  stops[i] is MSBWT_BRIDGE_EXHAUSTED ..
+    /// MSBWT_BRIDGE_NO_TARGET; the bridges of at most depths[i] edges are all counted in found[i]; live[i] walks were live at the stop.
+    struct Bridges {
+        std::vector<std::uint8_t> symbols;
+        std::vector<std::uint64_t> lengths, edge_sums, found;
+        std::vector<std::uint8_t> stops;
+        std::vector<std::uint64_t> depths, live;
+        std::uint64_t max_steps = 0, max_paths = 0;
+        std::size_t size() const { return found.size(); }
+        /// the symbols of bridge j of pair i, in walk order
+        std::vector<std::uint8_t> row(std::size_t i, std::size_t j) const {
+            const std::uint8_t *at = symbols.data() + (i * max_paths + j) * max_steps;
+            return std::vector<std::uint8_t>(at, at + lengths[i * max_paths + j]);
+        }
+    };
+    /// Bridges (msbwt_hip.h, "bridges"): for each pair of packed k-mers (seed, target), 1 <= k <= 31, every walk of the k-mer graph from
+    /// the seed into the target of min_steps .. max_steps edges in `direction` (MSBWT_BRIDGE_RIGHT, _LEFT); at most max_paths are written
+    /// a pair, and a pair whose level holds more than max_live walks stops TOO_WIDE.
+    Bridges bridge_kmers(const std::vector<std::uint64_t> &seeds, const std::vector<std::uint64_t> &targets, std::size_t k, std::uint64_t max_steps,
+                         std::uint64_t min_steps = 0, std::uint64_t max_paths = 4, std::uint64_t max_live = 64, int direction = MSBWT_BRIDGE_RIGHT,
+                         std::uint64_t min_count = 1, std::uint64_t min_edge = 0) const {
+        if (targets.size() != seeds.size()) throw Panic(MSBWT_ERR_INVALID_ARG, "bridge_kmers: one target a seed");
+        const std::size_t n = seeds.size();
+        Bridges b;
+        b.max_steps = max_steps;
+        b.max_paths = max_paths;
+        b.symbols.resize(n * max_paths * max_steps);
+        b.lengths.resize(n * max_paths);
+        b.edge_sums.resize(n * max_paths);
+        b.found.resize(n);
+        b.stops.resize(n);
+        b.depths.resize(n);
+        b.live.resize(n);
+        check(msbwt_rle_bridge_kmers(raw_, seeds.data(), targets.data(), k, n, min_count, min_edge, direction, min_steps, max_steps, max_paths, max_live, b.symbols.data(),
+                                     b.lengths.data(), b.edge_sums.data(), b.found.data(), b.stops.data(), b.depths.data(), b.live.data()));
+        return b;
+    }
+    /// Device buffers (every output may be null; the byte arrays at any alignment); synchronises hip_stream.
+    void bridge_kmers_device(const void *d_seeds, const void *d_targets, std::size_t k, std::size_t n, std::uint64_t min_count, std::uint64_t min_edge, int direction,
+                             std::uint64_t min_steps, std::uint64_t max_steps, std::uint64_t max_paths, std::uint64_t max_live, void *d_symbols, void *d_lengths,
+                             void *d_edge_sums, void *d_found, void *d_stops, void *d_depths, void *d_live, void *hip_stream = nullptr) const {
+        check(msbwt_rle_bridge_kmers_device(raw_, d_seeds, d_targets, k, n, min_count, min_edge, direction, min_steps, max_steps, max_paths, max_live, d_symbols, d_lengths,
+                                            d_edge_sums, d_found, d_stops, d_depths, d_live, hip_stream));
+    }
+    /// The last bridge call.
+    struct BridgeInfo {
+        std::uint64_t pairs = 0, rounds = 0, queries = 0, expanded = 0, found = 0, pieces = 0, scratch_bytes = 0, widest = 0;
+    };
+    BridgeInfo bridge_info() const {
+        std::uint64_t w[MSBWT_BRIDGE_INFO_WORDS] = {};
+        check(msbwt_rle_bridge_info(raw_, w));
+        BridgeInfo i;
+        i.pairs = w[0], i.rounds = w[1], i.queries = w[2], i.expanded = w[3], i.found = w[4], i.pieces = w[5], i.scratch_bytes = w[6], i.widest = w[7];
+        return i;
+    }
+    /// The frontier slots of a bridge call's piece (0 = automatic, 2^20; max_live where that is larger; at most 2^28); results never depend on it.
+    void set_bridge_slots(std::uint64_t slots) { check(msbwt_rle_set_bridge_slots(raw_, slots)); }
+    /// HBM bytes of scratch a bridge call of n pairs allocates (and frees again) on an index that holds something.
+    static std::uint64_t bridge_plan(std::uint64_t n, std::uint64_t max_steps, std::uint64_t max_paths = 4, std::uint64_t max_live = 64, bool host = true,
+                                     std::uint64_t slots = 0) {
+        std::uint64_t bytes = 0;
+        const int rc = msbwt_bridge_plan(n, max_steps, max_paths, max_live, host ? 1 : 0, slots, &bytes);
+        if (rc) throw Panic(rc, "msbwt_bridge_plan");
+        return bytes;
+    }
     /// HBM bytes of scratch the last k-mer walk call allocated (and freed again before it returned).
     std::uint64_t spectrum_scratch_bytes() const {
         std::uint64_t bytes = 0;

@@ -12,12 +12,12 @@ string_util, bwt_converter, dynamic_bwt (create_from_fastx), bwt_util (pairwise_
 from . import _lib
 from ._lib import MERGE_MAX_INPUTS
 from .msbwt_core import BWT, BWTRange, VC_LEN, LETTER_BITS, NUMBER_BITS, NUM_POWER, MASK, COUNT_MASK
-from .rle_bwt import RleBWT, MsbwtError, RankComm, trace_plan, canonical_trace_plan, trace_sequences, walk_plan, walk_sequences, overlap_plan, overlap_edges, OverlapResult
+from .rle_bwt import RleBWT, MsbwtError, RankComm, trace_plan, canonical_trace_plan, trace_sequences, walk_plan, walk_sequences, overlap_plan, overlap_edges, OverlapResult, bridge_plan, bridge_sequences
 from . import string_util, bwt_converter, msbwt_core, rle_bwt, sharded, dynamic_bwt, bwt_util
 from .dynamic_bwt import create_from_fastx
 
 __all__ = ["BWT", "BWTRange", "RleBWT", "MsbwtError", "RankComm", "string_util", "bwt_converter", "msbwt_core",
-           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "unitig_graph_plan", "unitig_graph_by_source_plan", "trace_plan", "canonical_trace_plan", "trace_sequences", "walk_plan", "walk_sequences", "overlap_plan", "overlap_edges", "OverlapResult", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
+           "rle_bwt", "sharded", "dynamic_bwt", "create_from_fastx", "build_reads_plan", "build_reads_sort_tile", "bwt_util", "merge_plan", "merge_many_plan", "merge_tile", "source_index_plan", "source_block_rows", "source_narrow_rows", "spectrum_plan", "canonical_plan", "kmers_by_source_plan", "kmer_graph_plan", "unitigs_plan", "canonical_unitigs_plan", "unitig_graph_plan", "unitig_graph_by_source_plan", "trace_plan", "canonical_trace_plan", "trace_sequences", "walk_plan", "walk_sequences", "overlap_plan", "overlap_edges", "OverlapResult", "bridge_plan", "bridge_sequences", "MERGE_MAX_INPUTS", "VC_LEN", "LETTER_BITS", "NUMBER_BITS", "NUM_POWER", "MASK", "COUNT_MASK"]
 
 
 def version():

@@ -6,8 +6,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmsbwt_hip.so")
-SOURCES = ["capi.cpp", "index_build.cpp", "query.cpp", "sources.cpp", "walk_call.cpp", "spectrum.cpp", "graph_calls.cpp", "unitig_calls.cpp", "trace_calls.cpp", "left_walk_calls.cpp", "overlap_calls.cpp", "produce.cpp", "multi_device.cpp", "kernels.hip", "lanes.hip", "lanes_tier.hip", "lanes_wide.hip", "lanes_xwide.hip", "lookup_kernel.hip", "extend.hip", "sparse_table.hip", "device_build.hip", "pair_index.hip", "gather.hip", "order.hip", "run_build.hip", "reads_build.hip", "radix_sort.hip", "run_encode.hip", "merge.hip", "merge_many.hip", "source_index.hip", "spectrum.hip", "canonical.hip", "source_spectrum.hip", "kmer_graph.hip", "unitigs.hip", "canonical_unitigs.hip", "unitig_links.hip", "unitig_sources.hip", "trace.hip", "canonical_trace.hip", "left_walk.hip", "overlaps.hip", "plane_index.cpp", "run_index.cpp", "npy_io.cpp", "rle_codec.cpp"]
-HEADERS = ["handle.hpp", "walk_call.hpp", "index_build.hpp", "kernels.hpp", "lanes_kernel.hpp", "lookup_kernel.hpp", "sparse_table.hpp", "sparse_build.hpp", "sparse_policy.hpp", "device_build.hpp", "pair_index.hpp", "gather.hpp", "order.hpp", "run_build.hpp", "reads_build.hpp", "radix_sort.hpp", "run_encode.hpp", "workgroup.hpp", "slot_bytes.hpp", "rle_subruns.hpp", "merge.hpp", "merge_common.hpp", "source_index.hpp", "source_count.hpp", "source_spectrum.hpp", "kmer_graph.hpp", "unitigs.hpp", "canonical_unitigs.hpp", "unitig_links.hpp", "unitig_slots.hpp", "unitig_sources.hpp", "trace.hpp", "canonical_trace.hpp", "left_walk.hpp", "overlaps.hpp", "graph_layouts.hpp", "frontier.hpp", "frontier_walk.hpp", "spectrum.hpp", "canonical.hpp", "rank_ops.hpp", "search_common.hpp", "host_pipeline.hpp", "plane_index.hpp", "run_index.hpp", "table_policy.hpp", "npy_io.hpp", "rle_codec.hpp", os.path.join("..", "..", "include", "msbwt_hip.h")]
+SOURCES = ["capi.cpp", "index_build.cpp", "query.cpp", "sources.cpp", "walk_call.cpp", "spectrum.cpp", "graph_calls.cpp", "unitig_calls.cpp", "trace_calls.cpp", "left_walk_calls.cpp", "overlap_calls.cpp", "bridge_calls.cpp", "produce.cpp", "multi_device.cpp", "kernels.hip", "lanes.hip", "lanes_tier.hip", "lanes_wide.hip", "lanes_xwide.hip", "lookup_kernel.hip", "extend.hip", "sparse_table.hip", "device_build.hip", "pair_index.hip", "gather.hip", "order.hip", "run_build.hip", "reads_build.hip", "radix_sort.hip", "run_encode.hip", "merge.hip", "merge_many.hip", "source_index.hip", "spectrum.hip", "canonical.hip", "source_spectrum.hip", "kmer_graph.hip", "unitigs.hip", "canonical_unitigs.hip", "unitig_links.hip", "unitig_sources.hip", "trace.hip", "canonical_trace.hip", "left_walk.hip", "overlaps.hip", "bridges.hip", "plane_index.cpp", "run_index.cpp", "npy_io.cpp", "rle_codec.cpp"]
+HEADERS = ["handle.hpp", "walk_call.hpp", "index_build.hpp", "kernels.hpp", "lanes_kernel.hpp", "lookup_kernel.hpp", "sparse_table.hpp", "sparse_build.hpp", "sparse_policy.hpp", "device_build.hpp", "pair_index.hpp", "gather.hpp", "order.hpp", "run_build.hpp", "reads_build.hpp", "radix_sort.hpp", "run_encode.hpp", "workgroup.hpp", "slot_bytes.hpp", "rle_subruns.hpp", "merge.hpp", "merge_common.hpp", "source_index.hpp", "source_count.hpp", "source_spectrum.hpp", "kmer_graph.hpp", "unitigs.hpp", "canonical_unitigs.hpp", "unitig_links.hpp", "unitig_slots.hpp", "unitig_sources.hpp", "trace.hpp", "canonical_trace.hpp", "left_walk.hpp", "overlaps.hpp", "bridges.hpp", "graph_layouts.hpp", "frontier.hpp", "frontier_walk.hpp", "spectrum.hpp", "canonical.hpp", "rank_ops.hpp", "search_common.hpp", "host_pipeline.hpp", "plane_index.hpp", "run_index.hpp", "table_policy.hpp", "npy_io.hpp", "rle_codec.hpp", os.path.join("..", "..", "include", "msbwt_hip.h")]
 
 
 def hipcc():

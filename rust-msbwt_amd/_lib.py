@@ -28,6 +28,10 @@ WALK_INFO_WORDS = 8  # MSBWT_WALK_INFO_WORDS
 WALK_STOPS = ("", "DOLLAR", "MAX_STEPS", "BAD_ROW")  # MSBWT_WALK_DOLLAR = 1 ..
 OVERLAP_INFO_WORDS = 13  # MSBWT_OVERLAP_INFO_WORDS
 OVERLAP_STOPS = ("", "END", "EMPTY", "BAD_SYMBOL")  # MSBWT_OVERLAP_END = 1 ..
+BRIDGE_INFO_WORDS = 8  # MSBWT_BRIDGE_INFO_WORDS
+BRIDGE_STOPS = ("", "EXHAUSTED", "FULL", "MAX_STEPS", "TOO_WIDE", "NO_SEED", "NO_TARGET")  # MSBWT_BRIDGE_EXHAUSTED = 1 ..
+BRIDGE_MAX_STEPS_CAP = 4096  # MSBWT_BRIDGE_MAX_STEPS_CAP
+BRIDGE_MAX_LIVE_CAP = 1 << 24  # MSBWT_BRIDGE_MAX_LIVE_CAP
 SPECTRUM_MIN_FRONTIER = 64  # MSBWT_SPECTRUM_MIN_FRONTIER
 MERGE_STAGES = ("copy_in", "decode", "iterate", "emit", "encode", "copy_out")  # MSBWT_MERGE_STAGES
 
@@ -144,6 +148,11 @@ SIGNATURES = {
     "msbwt_rle_overlap_info": (_int, [_vp, _vp]),
     "msbwt_rle_set_overlap_piece": (_int, [_vp, _u64]),
     "msbwt_overlap_plan": (_int, [_u64, _int, _u64, _u64, _u64, _pu64]),
+    "msbwt_rle_bridge_kmers": (_int, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _int, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_bridge_kmers_device": (_int, [_vp, _vp, _vp, _sz, _sz, _u64, _u64, _int, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msbwt_rle_bridge_info": (_int, [_vp, _vp]),
+    "msbwt_rle_set_bridge_slots": (_int, [_vp, _u64]),
+    "msbwt_bridge_plan": (_int, [_u64, _u64, _u64, _u64, _int, _u64, _pu64]),
     "msbwt_rle_replicate": (_vp, [_vp, _int]),
     "msbwt_rle_count_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _vp]),
     "msbwt_rle_count_read_kmers_multi": (_int, [_vp, _sz, _vp, _sz, _sz, _sz, _int, _vp, _vp]),

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "bridges.hpp"
 #include "canonical_trace.hpp"
 #include "canonical_unitigs.hpp"
 #include "kmer_graph.hpp"
@@ -132,6 +133,23 @@ inline TraceLayout trace_layout(uint64_t P, uint64_t max_steps, int mode, bool t
 // round 0, 8 + 1 or 16 + 2 in a later round (canonical_trace.hpp has where each lies).
 inline TraceLayout canonical_trace_layout(uint64_t P, uint64_t max_steps, int mode, bool targets, bool host) {
     return trace_layout_of(P, max_steps, canonical_trace_query_words(P, mode), targets, host);
+}
+
+// The one block of a bridge call, P pairs a piece with a frontier of S = P max_live slots: the counters, padded, the pairs' table, the
+// two buffers of states, a scan word a slot and the scan's sums (scan_words = scan_scratch_words(S)), the queries and their counts --
+// 2 + 4 words a pair in round 0, 4 a state in a later round -- and, where a host form stages them, a piece's seeds, targets and seven
+// outputs.  A device form's are the caller's own and take no room.  Every extent is a whole multiple of 256 bytes.
+struct BridgeLayout {
+    uint64_t counters, table, states[2], weights, scan, queries, counts, seeds, targets, symbols, lengths, edge_sums, found, stops, depths, live, bytes;
+};
+inline BridgeLayout bridge_layout(uint64_t P, uint64_t max_steps, uint64_t max_paths, uint64_t max_live, bool host, uint64_t scan_words) {
+    const auto padded = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
+    const uint64_t S = bridge_piece_slots(P, max_live), state = padded(8 * bridge_state_words(max_steps) * S), words = padded(8 * bridge_query_words(P, S));
+    const uint64_t column = host ? padded(8 * P) : 0, rows = host ? padded(8 * P * max_paths) : 0;
+    LayoutCursor c;
+    return {c.put(kBridgeCounterBytes), c.put(padded(8 * kBridgePairWords * P)), {c.put(state), c.put(state)}, c.put(padded(8 * S)), c.put(padded(8 * scan_words)),
+            c.put(words), c.put(words), c.put(column), c.put(column), c.put(host ? padded(P * max_paths * max_steps) : 0), c.put(rows), c.put(rows), c.put(column),
+            c.put(host ? padded(P) : 0), c.put(column), c.put(column), c.bytes};
 }
 
 }  // namespace msbwt

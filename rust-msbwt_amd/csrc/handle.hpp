@@ -203,6 +203,8 @@ struct msbwt_rle : Settings {
     uint64_t walk_info[MSBWT_WALK_INFO_WORDS] = {};  // what the last left-walk call did: msbwt_rle_walk_info
     uint64_t overlap_piece = 0;               // most overlap queries a launch takes (0 = automatic): msbwt_rle_set_overlap_piece
     uint64_t overlap_info[MSBWT_OVERLAP_INFO_WORDS] = {};  // what the last read-overlap call did: msbwt_rle_overlap_info
+    uint64_t bridge_slots = 0;                // the frontier slots of a bridge call's piece (0 = automatic): msbwt_rle_set_bridge_slots
+    uint64_t bridge_info[MSBWT_BRIDGE_INFO_WORDS] = {};  // what the last bridge call did: msbwt_rle_bridge_info
     std::mutex mu;
     std::string err;
 };

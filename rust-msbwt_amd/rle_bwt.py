@@ -731,6 +731,74 @@ class RleBWT(BWT):
         if rc:
             _raise(rc, self._h)
 
+    # ---- bridges: all bounded walks of the k-mer graph between two anchor k-mers ----
+    def bridge_kmers(self, seeds, targets, k, max_steps, min_steps=0, max_paths=4, max_live=64, direction="right", min_count=1, min_edge=None, symbols=True):
+        """msbwt_rle_bridge_kmers -> (symbols, lengths, edge_sums, found, stops, depths, live).  seeds and targets: n packed k-mer words
+        each (pack_2bit), 1 <= k <= 31; include/msbwt_hip.h, "bridges", has the exploration level by level.  symbols: (n, max_paths,
+        max_steps) uint8, row (i, j) holding lengths[i, j] symbol codes (A C G T = 1 2 3 5) in walk order and zeros -- or what the
+        `symbols` array passed in held -- behind them; symbols=False is a counting call and returns None there.  lengths, edge_sums:
+        (n, max_paths); found, depths, live: n words; stops: _lib.BRIDGE_STOPS names the codes.  bridge_sequences turns rows into
+        sequences.
+        numpy arrays go through the host form.  torch tensors on this handle's device (int64 or uint64 words) go through the _device
+        form on torch's current stream, and torch tensors come back (words as int64)."""
+        direction = _lib.TRACE_DIRECTIONS[direction]
+        n_steps, n_paths = int(max_steps), int(max_paths)
+        if hasattr(seeds, "data_ptr"):
+            import torch
+            n, dev = int(seeds.numel()), seeds.device
+            if not hasattr(targets, "data_ptr") or any(not t.is_contiguous() or t.element_size() != 8 for t in (seeds, targets)) or targets.numel() != n:
+                raise ValueError("seeds and targets are contiguous tensors of n 64-bit words")
+            if symbols is True:
+                symbols = torch.zeros((n, n_paths, n_steps), dtype=torch.uint8, device=dev)
+            elif symbols is False:
+                symbols = None
+            lengths, edge_sums = (torch.zeros((n, n_paths), dtype=torch.int64, device=dev) for _ in range(2))
+            found, depths, live = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
+            stops = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.bridge_kmers_device(seeds.data_ptr(), targets.data_ptr(), k, n, max_steps, None if symbols is None else symbols.data_ptr(),
+                                     *[t.data_ptr() for t in (lengths, edge_sums, found, stops, depths, live)], min_steps=min_steps, max_paths=max_paths, max_live=max_live,
+                                     direction=direction, min_count=min_count, min_edge=min_edge, stream=torch.cuda.current_stream(dev).cuda_stream)
+            return symbols, lengths, edge_sums, found, stops, depths, live
+        seeds, targets = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (seeds, targets))
+        n = len(seeds)
+        if len(targets) != n:
+            raise ValueError("one target a seed")
+        if symbols is True:
+            symbols = np.zeros((n, n_paths, n_steps), dtype=np.uint8)
+        elif symbols is False:
+            symbols = None
+        elif symbols.dtype != np.uint8 or symbols.shape != (n, n_paths, n_steps) or not symbols.flags.c_contiguous:
+            raise ValueError("symbols is a C-contiguous (n, max_paths, max_steps) uint8 array")
+        lengths, edge_sums = (np.zeros((n, n_paths), dtype=np.uint64) for _ in range(2))
+        found, depths, live = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        stops = np.zeros(n, dtype=np.uint8)
+        rc = _lib.lib().msbwt_rle_bridge_kmers(self._h, seeds.ctypes.data_as(C.c_void_p), targets.ctypes.data_as(C.c_void_p), int(k), n, int(min_count), int(min_edge or 0),
+                                               direction, int(min_steps), n_steps, n_paths, int(max_live), None if symbols is None else symbols.ctypes.data_as(C.c_void_p),
+                                               *[a.ctypes.data_as(C.c_void_p) for a in (lengths, edge_sums, found, stops, depths, live)])
+        if rc:
+            _raise(rc, self._h)
+        return symbols, lengths, edge_sums, found, stops, depths, live
+
+    def bridge_kmers_device(self, d_seeds, d_targets, k, n, max_steps, d_symbols, d_lengths, d_edge_sums, d_found, d_stops, d_depths, d_live, min_steps=0, max_paths=4,
+                            max_live=64, direction=0, min_count=1, min_edge=None, stream=0):
+        """msbwt_rle_bridge_kmers_device: device pointers (ints; every output may be None; the byte arrays at any alignment), direction
+        as the header's number.  Synchronises `stream`; a device fault shows in device_status."""
+        rc = _lib.lib().msbwt_rle_bridge_kmers_device(self._h, d_seeds, d_targets, int(k), int(n), int(min_count), int(min_edge or 0), int(direction), int(min_steps),
+                                                      int(max_steps), int(max_paths), int(max_live), d_symbols, d_lengths, d_edge_sums, d_found, d_stops, d_depths, d_live,
+                                                      stream)
+        if rc:
+            _raise(rc, self._h)
+
+    def bridge_info(self):
+        """What the last bridge call did: {"pairs", "rounds", "queries", "expanded", "found", "pieces", "scratch_bytes", "widest"}."""
+        return self._info(_lib.lib().msbwt_rle_bridge_info, ("pairs", "rounds", "queries", "expanded", "found", "pieces", "scratch_bytes", "widest"))
+
+    def set_bridge_slots(self, slots):
+        """The frontier slots of a bridge call's piece (0 = automatic, 2^20; max_live where that is larger): results never depend on it."""
+        rc = _lib.lib().msbwt_rle_set_bridge_slots(self._h, int(slots))
+        if rc:
+            _raise(rc, self._h)
+
     # ---- left walks: from BWT rows back to the text -- LF walks, locate, the reads themselves ----
     def walk_rows(self, rows, max_steps, symbols=True):
         """msbwt_rle_walk_rows -> (symbols, steps, stops, last, reads).  rows: n BWT rows.  Each is walked left by LF until it stands on
@@ -1485,6 +1553,35 @@ def trace_sequences(seeds, k, symbols, steps, direction="right", text=False):
     if not text:
         return out
     return [_LETTERS[a].tobytes().decode() for a in out]
+
+
+def bridge_sequences(seeds, k, symbols, lengths, direction="right", text=False):
+    """The full sequence of every written bridge of RleBWT.bridge_kmers, in reading order: per pair a list with, for each row j of
+    lengths[i, j] > 0 symbols, the seed followed by them ("right") or those symbols reversed followed by the seed ("left") -> lists of
+    uint8 arrays of symbol codes, or (text=True) of str.  (A bridge has at least one symbol, so a length of 0 is an unused row.)"""
+    if direction not in _lib.TRACE_DIRECTIONS:
+        raise ValueError("direction is 'right' or 'left'")
+    heads = unpack_2bit(np.asarray(seeds, dtype=np.uint64) & np.uint64((1 << (2 * int(k))) - 1), int(k))
+    symbols, lengths = np.asarray(symbols, dtype=np.uint8), np.asarray(lengths, dtype=np.uint64)
+    if symbols.ndim != 3 or lengths.shape != symbols.shape[:2] or len(symbols) != len(heads) or (lengths.size and int(lengths.max()) > symbols.shape[2]):
+        raise ValueError("symbols is (n, max_paths, max_steps), lengths (n, max_paths) and lengths[i, j] <= max_steps")
+    out = []
+    for head, rows, lens in zip(heads, symbols, lengths):
+        found = [row[:int(s)] for row, s in zip(rows, lens) if s]
+        out.append([np.concatenate([head, row]) if direction == "right" else np.concatenate([row[::-1], head]) for row in found])
+    if not text:
+        return out
+    return [[_LETTERS[a].tobytes().decode() for a in rows] for rows in out]
+
+
+def bridge_plan(n, max_steps, max_paths=4, max_live=64, host=True, slots=0):
+    """msbwt_bridge_plan: the bytes of HBM scratch a bridge call of n pairs allocates (and frees again) on an index that holds something."""
+    out = C.c_uint64(0)
+    rc = _lib.lib().msbwt_bridge_plan(int(n), int(max_steps), int(max_paths), int(max_live), int(bool(host)), int(slots), C.byref(out))
+    if rc:
+        raise MsbwtError(rc, "msbwt_bridge_plan: max_paths and max_live are at least 1, slots at most 2^28, max_steps at most 4096, max_live at most 2^24, "
+                             "and n x max_paths x max_steps must stay below 2^40")
+    return out.value
 
 
 def canonical_trace_plan(n, max_steps, mode="unique", targets=False, host=True, piece=0):

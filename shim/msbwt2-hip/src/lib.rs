@@ -216,6 +216,17 @@ extern "C" {
     fn msbwt_rle_overlap_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
     fn msbwt_rle_set_overlap_piece(bwt: *mut MsbwtRle, queries: u64) -> c_int;
     fn msbwt_overlap_plan(n: u64, host: c_int, piece: u64, piece_symbols: u64, piece_records: u64, device_bytes: *mut u64) -> c_int;
+    // bridges: all bounded walks of the k-mer graph between two anchor k-mers
+    fn msbwt_rle_bridge_kmers(bwt: *const MsbwtRle, seeds2bit: *const u64, targets2bit: *const u64, k: usize, n: usize, min_count: u64, min_edge: u64,
+                              direction: c_int, min_steps: u64, max_steps: u64, max_paths: u64, max_live: u64, out_symbols: *mut u8, out_lengths: *mut u64,
+                              out_edge_sums: *mut u64, out_found: *mut u64, out_stops: *mut u8, out_depths: *mut u64, out_live: *mut u64) -> c_int;
+    fn msbwt_rle_bridge_kmers_device(bwt: *const MsbwtRle, d_seeds2bit: *const c_void, d_targets2bit: *const c_void, k: usize, n: usize, min_count: u64,
+                                     min_edge: u64, direction: c_int, min_steps: u64, max_steps: u64, max_paths: u64, max_live: u64,
+                                     d_out_symbols: *mut c_void, d_out_lengths: *mut c_void, d_out_edge_sums: *mut c_void, d_out_found: *mut c_void,
+                                     d_out_stops: *mut c_void, d_out_depths: *mut c_void, d_out_live: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    fn msbwt_rle_bridge_info(bwt: *const MsbwtRle, out: *mut u64) -> c_int;
+    fn msbwt_rle_set_bridge_slots(bwt: *mut MsbwtRle, slots: u64) -> c_int;
+    fn msbwt_bridge_plan(n: u64, max_steps: u64, max_paths: u64, max_live: u64, host: c_int, slots: u64, device_bytes: *mut u64) -> c_int;
     fn msbwt_rle_set_table_depth(bwt: *mut MsbwtRle, depth: c_int) -> c_int;
     fn msbwt_rle_last_error(bwt: *const MsbwtRle) -> *const c_char;
     // several GPUs of one node
@@ -1070,6 +1081,61 @@ impl GpuRleBWT {
         let mut bytes = 0u64;
         let rc = unsafe { msbwt_overlap_plan(n, host as c_int, piece, piece_symbols, piece_records, &mut bytes) };
         assert_eq!(rc, MSBWT_OK, "overlap_plan: {} queries", n);
+        bytes
+    }
+
+    /// Bridges (include/msbwt_hip.h, "bridges"): for each pair of packed k-mers (seed, target), 1 <= k <= 31, every walk of the k-mer graph
+    /// from the seed into the target of min_steps ..= max_steps edges, `direction` 0 right, 1 left; at most max_paths of them are written a
+    /// pair, and a pair whose level holds more than max_live walks stops TOO_WIDE.
+    /// -> (symbols: n x max_paths rows of max_steps, row (i, j) holding lengths[i max_paths + j] symbol codes and zeros behind them;
+    /// lengths; edge sums; found; stops; depths; live).
+    pub fn bridge_kmers(&self, seeds: &[u64], targets: &[u64], k: usize, min_count: u64, min_edge: u64, direction: c_int, min_steps: u64, max_steps: u64,
+                        max_paths: u64, max_live: u64) -> (Vec<u8>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u8>, Vec<u64>, Vec<u64>) {
+        let n = seeds.len();
+        assert_eq!(targets.len(), n, "bridge_kmers: one target a seed");
+        let rows = n * max_paths as usize;
+        let mut symbols = vec![0u8; rows * max_steps as usize];
+        let (mut lengths, mut sums) = (vec![0u64; rows], vec![0u64; rows]);
+        let (mut found, mut depths, mut live) = (vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        let mut stops = vec![0u8; n];
+        let rc = unsafe {
+            msbwt_rle_bridge_kmers(self.raw, seeds.as_ptr(), targets.as_ptr(), k, n, min_count, min_edge, direction, min_steps, max_steps, max_paths, max_live,
+                                   symbols.as_mut_ptr(), lengths.as_mut_ptr(), sums.as_mut_ptr(), found.as_mut_ptr(), stops.as_mut_ptr(), depths.as_mut_ptr(),
+                                   live.as_mut_ptr())
+        };
+        if rc != MSBWT_OK { panic!("bridge_kmers: {}", self.last_error()); }
+        (symbols, lengths, sums, found, stops, depths, live)
+    }
+
+    /// The same over device buffers (every output may be null) on `hip_stream`, which it synchronises.
+    pub unsafe fn bridge_kmers_device(&self, d_seeds: *const c_void, d_targets: *const c_void, k: usize, n: usize, min_count: u64, min_edge: u64, direction: c_int,
+                                      min_steps: u64, max_steps: u64, max_paths: u64, max_live: u64, d_symbols: *mut c_void, d_lengths: *mut c_void,
+                                      d_edge_sums: *mut c_void, d_found: *mut c_void, d_stops: *mut c_void, d_depths: *mut c_void, d_live: *mut c_void,
+                                      hip_stream: *mut c_void) {
+        let rc = msbwt_rle_bridge_kmers_device(self.raw, d_seeds, d_targets, k, n, min_count, min_edge, direction, min_steps, max_steps, max_paths, max_live, d_symbols,
+                                               d_lengths, d_edge_sums, d_found, d_stops, d_depths, d_live, hip_stream);
+        if rc != MSBWT_OK { panic!("bridge_kmers_device: {}", self.last_error()); }
+    }
+
+    /// The last bridge call: pairs, rounds, queries searched, walk-steps expanded, bridges found, pieces, scratch bytes, the widest frontier.
+    pub fn bridge_info(&self) -> [u64; 8] {
+        let mut words = [0u64; 8];
+        let rc = unsafe { msbwt_rle_bridge_info(self.raw, words.as_mut_ptr()) };
+        if rc != MSBWT_OK { panic!("bridge_info: {}", self.last_error()); }
+        words
+    }
+
+    /// The frontier slots of a bridge call's piece (0 = automatic, 2^20; max_live where that is larger); results never depend on it.
+    pub fn set_bridge_slots(&mut self, slots: u64) {
+        let rc = unsafe { msbwt_rle_set_bridge_slots(self.raw, slots) };
+        if rc != MSBWT_OK { panic!("set_bridge_slots: {}", self.last_error()); }
+    }
+
+    /// HBM bytes of scratch a bridge call of n pairs allocates and frees again on an index that holds something (pure function).
+    pub fn bridge_plan(n: u64, max_steps: u64, max_paths: u64, max_live: u64, host: bool, slots: u64) -> u64 {
+        let mut bytes = 0u64;
+        let rc = unsafe { msbwt_bridge_plan(n, max_steps, max_paths, max_live, host as c_int, slots, &mut bytes) };
+        assert_eq!(rc, MSBWT_OK, "bridge_plan: {} pairs of {} steps, {} paths, {} live", n, max_steps, max_paths, max_live);
         bytes
     }
 
